@@ -11,6 +11,10 @@ are already resident in HBM:
 Nothing is skipped or cached between steps. Multi-GPU: one process per GPU, each rank codes its own batch (weak
 scaling, no data-path collective); one RCCL all-reduce sums the rate / PSNR statistics at the end of the timed region.
 
+A plain run times exactly --steps steps after --warmup untimed ones and prints the headline; --full adds every side
+measurement (roofline legs, other shapes and modes, CPU baseline, ...). --dump-outputs DIR writes what the last timed step
+returned to its caller.
+
 Prints ONE JSON line on rank 0 (see DESIGN.md section 6 for the fields).
 """
 import argparse
@@ -31,11 +35,11 @@ def parse_args(argv=None):
                         help='ranks = GPUs of this node. N > 1 without a launcher (no WORLD_SIZE in the environment): this '
                              'process starts N rank processes itself and waits for them; under torch.distributed.run it must '
                              'equal WORLD_SIZE. configs[3] of BASELINE.json is `--gpus 8 --height 256 --width 256 --batch 64`')
-    parser.add_argument('--steps', type=int, default=100)
+    parser.add_argument('--steps', type=int, default=100, help='timed steps of the headline (one block, unless --min-seconds asks for more)')
     parser.add_argument('--warmup', type=int, default=10)
-    parser.add_argument('--min-seconds', type=float, default=1.0,
-                        help='the block of --steps timed steps is repeated until this much time has been timed in total '
-                             '(every block bracketed by barrier + synchronize); the MEDIAN block is reported')
+    parser.add_argument('--min-seconds', type=float, default=0.,
+                        help='repeat the block of --steps timed steps until this much time has been timed in total (every block '
+                             'bracketed by barrier + synchronize; at most --max-blocks) and report the MEDIAN block. 0 (default): one block')
     parser.add_argument('--max-blocks', type=int, default=25)
     parser.add_argument('--batch', type=int, default=24, help='images per GPU per step (default: the Kodak set)')
     parser.add_argument('--height', type=int, default=512, help='image height (default 512: Kodak)')
@@ -57,6 +61,14 @@ def parse_args(argv=None):
                         help='the coder\'s statistics instead of ones computed from the first batch: a directory with `map_mean.npy`, '
                              '`idx_map_exception.pkl` and `binary_probabilities_<multiplier>.npy` (lossless/stats.py:243-320; e.g. the '
                              'reference\'s lossless/results/1_10000/training_index_10/)')
+    parser.add_argument('--full', action='store_true',
+                        help='after the headline, every side measurement as well: `one_stream_leg` / `roofline`, and on rank 0 of a '
+                             'one-GPU run `library_user`, `single_image`, `other_shapes`, `authors_statistics`, `pcie_inclusive`, '
+                             '`host_coder`, `realistic_entropy`, `dropin_surface`, `cpu_baseline`, `order_sensitivity` (the --no-* '
+                             'flags below leave some of them out). Without it the run is the headline alone')
+    parser.add_argument('--dump-outputs', default=None, metavar='DIR',
+                        help='after the timed steps, write what the last timed step returned to its caller (`Ticket.result()` of '
+                             'rank 0: nb_bits, coder_bits, exception_bits, sse, nb_deads, one value per image) as DIR/<name>.npy, float64')
     parser.add_argument('--no-cpu-baseline', action='store_true')
     parser.add_argument('--no-transforms-alone', action='store_true',
                         help='skip the second launch-by-launch leg (the transforms without the coder: `roofline.transforms_alone`); the profile commands of '
@@ -346,7 +358,7 @@ def run_pipeline(ctx, batch, steps, warmup, variables, h, w, coder='device', cod
     runs `warmup` untimed steps, then BLOCKS of exactly `steps` timed steps -- each block bracketed by barrier + synchronize
     on both sides, its wall time the MAX over ranks -- until `min_seconds` have been timed (at most `max_blocks` blocks; the
     count is the same on every rank because it is decided from the all-reduced times). Everything up to the first barrier
-    is outside the timed region.
+    is outside the timed region. `last_result`: what `Ticket.result()` returned for the last timed step.
     record: HIP events around every named launch of the step (launch-by-launch path, one transform stream: a launch then has
     the GPU to itself apart from the coder's side streams). pcie: the images of every step come from pinned host memory (uint8,
     one async copy on a copy stream) and the uint8 reconstructions go back to pinned host memory (the feed / fetch of the
@@ -453,7 +465,7 @@ def run_pipeline(ctx, batch, steps, warmup, variables, h, w, coder='device', cod
     cpu_ms = torch.zeros(max(world, 1), dtype=torch.float64, device=device)
     cpu_ms[rank] = block_cpu[mid]/steps*1e3
     ctx.all_reduce(cpu_ms, 'SUM')
-    return {'elapsed': block_seconds[mid], 'block_seconds': block_seconds, 'stats': stats, 'events': events,
+    return {'elapsed': block_seconds[mid], 'block_seconds': block_seconds, 'stats': stats, 'events': events, 'last_result': results[-1],
             'probabilities': probabilities, 'map_mean_host': map_mean_host, 'idx_map_exception': idx_map_exception, 'host_coder': coder_mode == 'host',
             'coder_threads': coder_threads, 'coder_ms': coder_ms, 'host_cpu_ms_per_step': [round(float(v), 4) for v in cpu_ms.tolist()]}
 
@@ -546,7 +558,8 @@ def children_alone_on_the_gpu(args, h_in, w_in):
     try:
         env = {k: v for (k, v) in os.environ.items() if k != 'GPU_MAX_HW_QUEUES'}
         child = subprocess.run([sys.executable, os.path.abspath(__file__), '--only-library-user', '--no-cpu-baseline', '--steps', str(args.steps),
-                                '--warmup', str(args.warmup), '--batch', str(args.batch), '--height', str(h_in), '--width', str(w_in)] + same_model,
+                                '--warmup', str(args.warmup), '--min-seconds', repr(args.min_seconds), '--max-blocks', str(args.max_blocks),
+                                '--batch', str(args.batch), '--height', str(h_in), '--width', str(w_in)] + same_model,
                                stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, check=True, text=True, env=env)
         out['library_user'] = json.loads([ln for ln in child.stdout.splitlines() if ln.startswith('{')][-1])['library_user']
     except Exception as exc:      # a side figure must never cost the run its headline
@@ -593,7 +606,7 @@ def main(args):
         dist.destroy_process_group()
         return
     early = {}
-    if (rank == 0 and world == 1 and not args.no_single_image and not (args.only_single_image_pipelined or args.only_library_user or args.only_dropin_surface)
+    if (args.full and rank == 0 and world == 1 and not args.no_single_image and not (args.only_single_image_pipelined or args.only_library_user or args.only_dropin_surface)
             and args.batch != 1 and (h_in, w_in) == (512, 768) and torch.cuda.device_count() > 0):
         early = children_alone_on_the_gpu(args, h_in, w_in)      # BEFORE this process initialises the GPU (counting devices does not)
     if not torch.cuda.is_available():
@@ -650,15 +663,17 @@ def main(args):
         del y0, encoder
         print(json.dumps({'dropin_surface': dropin_surface_leg(ctx, variables, probabilities, map_mean_host, idx_map_exception, h_in, w_in)}))
         return
-    # ---- the roofline leg first, while the process has no other streams: the same steps launched kernel by kernel on ONE
+    # ---- (--full) the roofline leg first, while the process has no other streams: the same steps launched kernel by kernel on ONE
     # transform stream (the default stream), HIP events around every launch (on the stream it goes to), so that a duration is
     # that kernel's own next to nothing but the coder's side streams ------------------------------------------------------
-    roof = run_pipeline(ctx, args.batch, min(args.steps, 30), min(args.warmup, 5), variables, h_in, w_in, coder=args.coder,
-                        coder_streams=min(coder_streams, 3), transform_streams=1, use_graphs=False, min_seconds=0.3, max_blocks=5, record=True)
+    roof = None
+    if args.full:
+        roof = run_pipeline(ctx, args.batch, min(args.steps, 30), min(args.warmup, 5), variables, h_in, w_in, coder=args.coder,
+                            coder_streams=min(coder_streams, 3), transform_streams=1, use_graphs=False, min_seconds=0.3, max_blocks=5, record=True)
     # (the same leg with the transforms ALONE, rank 0 of a one-GPU run: what each kernel reaches of its roof without the coder's
     # long-lived waves beside it -- `roofline.transforms_alone`; `roofline` itself stays the path as it runs)
     roof_alone = None
-    if world == 1 and not args.no_transforms_alone and not os.environ.get('EAE_BENCH_NO_CODER'):
+    if args.full and world == 1 and not args.no_transforms_alone and not os.environ.get('EAE_BENCH_NO_CODER'):
         os.environ['EAE_BENCH_NO_CODER'] = '1'
         try:
             roof_alone = run_pipeline(ctx, args.batch, min(args.steps, 30), min(args.warmup, 5), variables, h_in, w_in, coder=args.coder,
@@ -671,38 +686,17 @@ def main(args):
                        max_blocks=args.max_blocks)
     (elapsed, stats, probabilities, map_mean_host) = (run['elapsed'], run['stats'], run['probabilities'], run['map_mean_host'])
     (host_coder, coder_threads, idx_map_exception) = (run['host_coder'], run['coder_threads'], run['idx_map_exception'])
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path received for the last timed step: per-image integers, exact in float64
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for (name, values) in run['last_result'].items():
+            numpy.save(os.path.join(args.dump_outputs, name + '.npy'), numpy.asarray(values, dtype=numpy.float64))
     # ---- derived figures (outside the timed region) ------------------------------------------------------------------
     pixels_per_step = args.batch*h_in*w_in
     value = pixels_per_step*args.steps*world/elapsed/1e6
     nb_images_total = stats[3].item()
     (bpp, mean_psnr) = rate_and_psnr(stats, h_in, w_in)
-    (per_kernel, per_launch_ms, flops) = launch_rooflines(roof['events'], pixels_per_step, args.fuse_latent, args.batch*128*(h_in//16)*(w_in//16))
-    gemm = {k: v for (k, v) in per_launch_ms.items() if k in GEMM_LAUNCHES}
-    gemm_ms = sum(sum(v) for v in gemm.values())
-    gemm_launches = sum(len(v) for v in gemm.values())
-    gemm_flop = sum(flops[name]*pixels_per_step*len(v) for (name, v) in gemm.items())
-    achieved = gemm_flop/(gemm_ms*1e-3)/1e12 if gemm_ms > 0 else 0.
-    (traffic, traffic_source) = (None, None)
-    traffic_file = os.path.join(ROOT, 'profiles', 'traffic_conv_gemm.json')
-    if os.path.isfile(traffic_file):
-        with open(traffic_file) as f:
-            traffic = json.load(f).get('hbm_bytes_per_launch')
-        traffic_source = ('profiles/traffic_conv_gemm.json: rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE, separate runs) of this '
-                          'command at the default shape, committed with the profile summaries -- a constant of the build, not measured by this run')
     blocks = run['block_seconds']
-    roof_ms = roof['elapsed']/min(args.steps, 30)*1e3
-    transforms_alone = None
-    if roof_alone is not None:
-        (pk_a, ms_a, fl_a) = launch_rooflines(roof_alone['events'], pixels_per_step, args.fuse_latent, args.batch*128*(h_in//16)*(w_in//16))
-        g_a = {k: v for (k, v) in ms_a.items() if k in GEMM_LAUNCHES}
-        g_a_ms = sum(sum(v) for v in g_a.values())
-        g_a_flop = sum(fl_a[k]*pixels_per_step*len(v) for (k, v) in g_a.items())
-        transforms_alone = {'note': 'the same launch-by-launch leg with no coder launched (EAE_BENCH_NO_CODER=1): each kernel without the coder\'s waves beside it',
-                            'achieved': round(g_a_flop/(g_a_ms*1e-3)/1e12, 3) if g_a_ms > 0 else 0.,
-                            'frac': round(g_a_flop/(g_a_ms*1e-3)/1e12/PEAK_F32_MFMA_TFLOPS, 4) if g_a_ms > 0 else 0.,
-                            'one_stream_ms_per_step': round(roof_alone['elapsed']/min(args.steps, 30)*1e3, 4),
-                            'per_kernel': {k: {'avg_ms': v['avg_ms'], 'frac': v.get('frac')} for (k, v) in pk_a.items() if not k.startswith('coder')}}
-        del roof_alone
     line = {
         'metric': 'Mpixels/s encode+decode ({0} {1}x{2} luma), bitstream bit-exact'.format(
             'Kodak' if (h_in, w_in) == (512, 768) else 'synthetic', w_in, h_in),
@@ -730,19 +724,46 @@ def main(args):
         # summed over ranks by the path's one all-reduce, over all timed blocks: exact integers (tests compare them across world sizes)
         'totals': {'bits': int(stats[0].item()), 'sse': int(stats[1].item()), 'dead_maps': int(stats[2].item()), 'images': int(nb_images_total)},
         'rate_bpp': round(bpp, 5), 'psnr_db_pooled': round(mean_psnr, 4), 'dead_maps_per_image': round(stats[2].item()/nb_images_total, 3),
-        'one_stream_leg': {'ms_per_step': round(roof_ms, 4), 'value': round(pixels_per_step*world/roof_ms/1e3, 3), 'unit': 'Mpixels/s',
-                           'flags': '--transform-streams 1 --no-graphs', 'host_cpu_ms_per_step': roof['host_cpu_ms_per_step'],
-                           'note': 'source of `roofline`: every launch bracketed by HIP events on its own stream'},
-        'roofline': {'bound': 'mfma', 'kernel': 'conv_gemm_split_kernel (conv2+GDN2, conv3, tconv1+IGDN5, tconv2+IGDN6)',
-                     'achieved': round(achieved, 3), 'peak': PEAK_F32_MFMA_TFLOPS, 'unit': 'TFLOP/s',
-                     'frac': round(achieved/PEAK_F32_MFMA_TFLOPS, 4), 'traffic': traffic, 'traffic_source': traffic_source,
-                     'avg_launch_ms': round(gemm_ms/max(gemm_launches, 1), 4),
-                     'per_launch_ms': {k: round(sum(v)/len(v), 4) for (k, v) in gemm.items()},
-                     'per_launch_frac': {k: round(flops[k]*pixels_per_step/(sum(v)/len(v)*1e-3)/1e12/PEAK_F32_MFMA_TFLOPS, 4)
-                                         for (k, v) in gemm.items()},
-                     'algorithmic_flop_per_launch': {k: flops[k]*pixels_per_step for k in GEMM_LAUNCHES},
-                     'per_kernel': per_kernel, 'peak_hbm_tbytes_per_s': PEAK_HBM_TBS, 'transforms_alone': transforms_alone},
     }
+    if roof is not None:
+        (per_kernel, per_launch_ms, flops) = launch_rooflines(roof['events'], pixels_per_step, args.fuse_latent, args.batch*128*(h_in//16)*(w_in//16))
+        gemm = {k: v for (k, v) in per_launch_ms.items() if k in GEMM_LAUNCHES}
+        gemm_ms = sum(sum(v) for v in gemm.values())
+        gemm_launches = sum(len(v) for v in gemm.values())
+        gemm_flop = sum(flops[name]*pixels_per_step*len(v) for (name, v) in gemm.items())
+        achieved = gemm_flop/(gemm_ms*1e-3)/1e12 if gemm_ms > 0 else 0.
+        (traffic, traffic_source) = (None, None)
+        traffic_file = os.path.join(ROOT, 'profiles', 'traffic_conv_gemm.json')
+        if os.path.isfile(traffic_file):
+            with open(traffic_file) as f:
+                traffic = json.load(f).get('hbm_bytes_per_launch')
+            traffic_source = ('profiles/traffic_conv_gemm.json: rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE, separate runs) of this '
+                              'command at the default shape, committed with the profile summaries -- a constant of the build, not measured by this run')
+        roof_ms = roof['elapsed']/min(args.steps, 30)*1e3
+        transforms_alone = None
+        if roof_alone is not None:
+            (pk_a, ms_a, fl_a) = launch_rooflines(roof_alone['events'], pixels_per_step, args.fuse_latent, args.batch*128*(h_in//16)*(w_in//16))
+            g_a = {k: v for (k, v) in ms_a.items() if k in GEMM_LAUNCHES}
+            g_a_ms = sum(sum(v) for v in g_a.values())
+            g_a_flop = sum(fl_a[k]*pixels_per_step*len(v) for (k, v) in g_a.items())
+            transforms_alone = {'note': 'the same launch-by-launch leg with no coder launched (EAE_BENCH_NO_CODER=1): each kernel without the coder\'s waves beside it',
+                                'achieved': round(g_a_flop/(g_a_ms*1e-3)/1e12, 3) if g_a_ms > 0 else 0.,
+                                'frac': round(g_a_flop/(g_a_ms*1e-3)/1e12/PEAK_F32_MFMA_TFLOPS, 4) if g_a_ms > 0 else 0.,
+                                'one_stream_ms_per_step': round(roof_alone['elapsed']/min(args.steps, 30)*1e3, 4),
+                                'per_kernel': {k: {'avg_ms': v['avg_ms'], 'frac': v.get('frac')} for (k, v) in pk_a.items() if not k.startswith('coder')}}
+            del roof_alone
+        line['one_stream_leg'] = {'ms_per_step': round(roof_ms, 4), 'value': round(pixels_per_step*world/roof_ms/1e3, 3), 'unit': 'Mpixels/s',
+                                  'flags': '--transform-streams 1 --no-graphs', 'host_cpu_ms_per_step': roof['host_cpu_ms_per_step'],
+                                  'note': 'source of `roofline`: every launch bracketed by HIP events on its own stream'}
+        line['roofline'] = {'bound': 'mfma', 'kernel': 'conv_gemm_split_kernel (conv2+GDN2, conv3, tconv1+IGDN5, tconv2+IGDN6)',
+                            'achieved': round(achieved, 3), 'peak': PEAK_F32_MFMA_TFLOPS, 'unit': 'TFLOP/s',
+                            'frac': round(achieved/PEAK_F32_MFMA_TFLOPS, 4), 'traffic': traffic, 'traffic_source': traffic_source,
+                            'avg_launch_ms': round(gemm_ms/max(gemm_launches, 1), 4),
+                            'per_launch_ms': {k: round(sum(v)/len(v), 4) for (k, v) in gemm.items()},
+                            'per_launch_frac': {k: round(flops[k]*pixels_per_step/(sum(v)/len(v)*1e-3)/1e12/PEAK_F32_MFMA_TFLOPS, 4)
+                                                for (k, v) in gemm.items()},
+                            'algorithmic_flop_per_launch': {k: flops[k]*pixels_per_step for k in GEMM_LAUNCHES},
+                            'per_kernel': per_kernel, 'peak_hbm_tbytes_per_s': PEAK_HBM_TBS, 'transforms_alone': transforms_alone}
     line['exchange'] = args.exchange
     # a scaling curve needs one GPU per rank: ranks sharing a GPU (EAE_BENCH_SHARE_GPU) or a single rank measure none
     line['scaling_measured'] = bool(world > 1 and not share_gpu)
@@ -755,7 +776,7 @@ def main(args):
         line['process_group'] = {'backend': dist.get_backend(), 'world_size': world, 'collectives': ctx.collectives,
                                  'forced_single_rank': bool(world == 1)}
     del run, roof
-    side = rank == 0 and world == 1 and not args.no_single_image
+    side = args.full and rank == 0 and world == 1 and not args.no_single_image
     if side and args.batch != 1 and (h_in, w_in) == (512, 768):
         # BASELINE.json configs[1] is ONE Kodak image: the same path with one image per step (launch-bound, not the headline)
         line['single_image'] = {'ms_per_image': None, 'mpixels_per_s': None, 'steps': 1000, 'warmup': 30, 'host_cpu_ms_per_image': None,      # filled in below
@@ -851,7 +872,7 @@ def main(args):
                 # `ms_step` in the product mode: an indication, not an identity -- the step ratio above is the measurement
                 'coder_span_measured_in': 'launch-by-launch schedule, one transform stream',
                 'coder_on_critical_path': bool(in_pipe > coder_streams*ms_step*0.95)})
-    if rank == 0 and world == 1 and not args.no_dropin_surface and (h_in, w_in) == (512, 768):
+    if args.full and rank == 0 and world == 1 and not args.no_dropin_surface and (h_in, w_in) == (512, 768):
         try:
             line['dropin_surface'] = dropin_surface_leg(ctx, variables, probabilities, map_mean_host, idx_map_exception, h_in, w_in)
         except Exception as exc:      # a side figure must never cost the run its headline
@@ -864,7 +885,7 @@ def main(args):
         if 'value' in line['library_user']:
             line['library_user']['over_headline'] = round(line['library_user']['value']/line['value'], 4)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the one leg of this file that runs checker code (oracle/): the CPU baseline and, with the same CPU transforms, what
             # the transforms' summation order does to symbols, bits and PSNR end to end
             (line['cpu_baseline'], line['order_sensitivity']) = cpu_baseline_leg(variables, probabilities, map_mean_host, cores, h_in, w_in, device)

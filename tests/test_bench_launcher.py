@@ -99,7 +99,7 @@ def test_four_ranks_share_the_gpu_and_the_host_cpu_budget_is_reported():
     step inside the container's CPU quota -- the line reports every rank's `host_cpu_ms_per_step` and `usable_cpus`, and the
     all-reduced totals cover four ranks."""
     common = ['--steps', '3', '--warmup', '1', '--batch', '2', '--no-cpu-baseline', '--no-side', '--min-seconds', '0']
-    (proc, lines) = run_bench(['--gpus', '4'] + common, {'EAE_BENCH_SHARE_GPU': '1'})
+    (proc, lines) = run_bench(['--gpus', '4', '--full'] + common, {'EAE_BENCH_SHARE_GPU': '1'})      # --full: the roofline leg of every rank
     assert proc.returncode == 0, proc.stderr[-2000:]
     assert len(lines) == 1
     four = lines[0]
