@@ -68,12 +68,14 @@ def _raise_for_statuses(results):
         interface_cython.raise_for_status(int(results[2, bad[0]]), int(results[3, bad[0]]))
 
 
-def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_probabilities, idx_map_exception=-1):
+def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_probabilities, idx_map_exception=-1, tile=None):
     """uint8 (N, H, W) or (N, H, W, 1) luminance images -> (blob bytes, info dict).
 
     encoder: pipeline.DeviceEncoder of the model; bin_widths_test float32 (128,) (the trained bin widths times the
     multiplier of the rate point); map_mean float32 (128,); binary_probabilities float64 (128, L) (stats.py:13-68).
     info: 'nb_bits' uint32 (N, 128) (arithmetic-coded + bypass bits of every map), 'payload_bytes', 'header_bytes'.
+    tile=(th, tw): run the analysis transform through windows (pipeline.DeviceEncoder.__call__): the latents, hence the blob
+    bytes, are those of tile=None, and images beyond the untiled path's size limit can be written.
     """
     images = numpy.ascontiguousarray(luminances_uint8)
     if images.dtype != numpy.uint8:
@@ -90,7 +92,7 @@ def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_p
     if bin_widths.shape != (nb_maps,) or mean.shape != (nb_maps,):
         raise ValueError('`bin_widths_test` and `map_mean` must have one element per map.')
     device = encoder.device
-    y = encoder(torch.from_numpy(images).to(device))
+    y = encoder(torch.from_numpy(images).to(device), tile=tile)
     map_size = y.shape[1]*y.shape[2]
     q = dev.quantize_maps(y, torch.from_numpy(bin_widths).to(device), torch.from_numpy(mean).to(device), want_symbols=True)
     if int(q['checks'][0].item()) != 0:
@@ -202,8 +204,9 @@ def decode_symbols(blob, device='cuda'):
     return (header, symbols.view(nb_images, nb_maps, map_size))
 
 
-def decode_images(blob, decoder):
-    """blob + pipeline.DeviceDecoder of the model -> uint8 (N, H, W) reconstructions (BT.601 range, tools.py:61-93)."""
+def decode_images(blob, decoder, tile=None):
+    """blob + pipeline.DeviceDecoder of the model -> uint8 (N, H, W) reconstructions (BT.601 range, tools.py:61-93).
+    tile=(th, tw): run the synthesis transform through windows (pipeline.DeviceDecoder.__call__): same reconstruction."""
     (header, symbols) = decode_symbols(blob, decoder.device)
     if header['are_bin_widths_learned'] != decoder.are_bin_widths_learned:
         raise ValueError('The container was written by the other kind of model (learned / fixed bin widths).')
@@ -211,5 +214,5 @@ def decode_images(blob, decoder):
     shifted = dev.dequantize_maps(symbols, torch.from_numpy(header['bin_widths']).to(device),
                                   torch.from_numpy(header['map_mean']).to(device))['shifted']
     (h_map, w_map) = (header['height']//16, header['width']//16)
-    (_, reconstruction_uint8, _) = decoder(shifted.view(header['nb_images'], h_map, w_map, header['nb_maps']))
+    (_, reconstruction_uint8, _) = decoder(shifted.view(header['nb_images'], h_map, w_map, header['nb_maps']), tile=tile)
     return reconstruction_uint8.cpu().numpy()

@@ -478,6 +478,60 @@ def sse_u8(a, b):
     return sse
 
 
+# ---- tiled encode / decode (include/eae_hip.h, "tiled encode / decode"; the plan comes from pipeline.tile_plan) ----------
+
+TILE_PLAN_COLS = 9
+
+
+def _plan_pointers(plan_device, plan_host):
+    """(device pointer, host pointer, rows) of one plan slice; both copies must hold the same int32 rows."""
+    if plan_host.dtype.name != 'int32' or plan_host.ndim != 2 or plan_host.shape[1] != TILE_PLAN_COLS or not plan_host.flags.c_contiguous:
+        raise HipError('the host plan must be a C-contiguous int32 array of {} columns'.format(TILE_PLAN_COLS))
+    if plan_device.dtype != torch.int32 or tuple(plan_device.shape) != plan_host.shape:
+        raise HipError('the device plan must be int32 of the host plan\'s shape')
+    return _p(plan_device), plan_host.ctypes.data, plan_host.shape[0]
+
+
+def tile_copy(plane, windows, plan_device, plan_host, unit, to_windows):
+    """Rectangles between a full plane [N, h*unit, w*unit, ...] and a batch of windows [G, wh*unit, ww*unit, ...] of the same
+    element type: to_windows=True gathers every whole window, False stitches every interior into the plane. h, w, wh, ww in
+    latents; one plan row per window (G rows)."""
+    if plane.dtype != windows.dtype:
+        raise HipError('plane and windows must have the same dtype')
+    (n, hp, wp) = plane.shape[:3]
+    (g, hw_, ww_) = windows.shape[:3]
+    if hp % unit or wp % unit or hw_ % unit or ww_ % unit:
+        raise HipError('plane and window sides must be multiples of `unit`')
+    elem_bytes = plane.element_size()*(plane[0, 0, 0].numel() if plane.dim() > 3 else 1)
+    if windows.element_size()*(windows[0, 0, 0].numel() if windows.dim() > 3 else 1) != elem_bytes:
+        raise HipError('plane and windows must have the same element size')
+    (plan_p, host_p, rows) = _plan_pointers(plan_device, plan_host)
+    if rows != g:
+        raise HipError('one plan row per window')
+    _check(_native.hip().eae_hip_tile_copy(_p(plane), n, hp//unit, wp//unit, _p(windows), hw_//unit, ww_//unit, unit, elem_bytes, plan_p,
+                                           host_p, rows, 1 if to_windows else 0, _stream(plane)), 'eae_hip_tile_copy')
+
+
+def tile_stitch_u8(windows, plan_device, plan_host, image=None, ref_u8=None, sse=None):
+    """uint8 reconstruction windows [G, 16wh, 16ww] -> their interiors into image [N, 16h, 16w] (optional) and, with ref_u8, the
+    squared error of exactly those pixels added into sse int64 [N] (zeroed here when not given). Returns sse or None."""
+    plane = image if image is not None else ref_u8
+    if plane is None:
+        raise HipError('tile_stitch_u8 needs an image or a reference')
+    (n, hp, wp) = plane.shape[:3]
+    (g, hw_, ww_) = windows.shape[:3]
+    if ref_u8 is not None and sse is None:
+        sse = torch.zeros(n, dtype=torch.int64, device=plane.device)
+    if image is not None and ref_u8 is not None and image.shape != ref_u8.shape:
+        raise HipError('image and reference must have the same shape')
+    (plan_p, host_p, rows) = _plan_pointers(plan_device, plan_host)
+    if rows != g or hp % 16 or wp % 16 or hw_ % 16 or ww_ % 16:
+        raise HipError('one plan row per window, sides multiples of 16')
+    _check(_native.hip().eae_hip_tile_stitch_u8(_p(windows), hw_//16, ww_//16, _p(image), _p(ref_u8), _p(sse), n, hp//16, wp//16,
+                                                plan_p, host_p, rows, _stream(windows)), 'eae_hip_tile_stitch_u8')
+    return sse
+
+
 # ---- lossless coder on the device (include/eae_hip.h, "lossless coder on the device") ---------------------------------
 
 CODER_ROUNDTRIP, CODER_ENCODE_ONLY, CODER_ROUNDTRIP_VERIFY = 0, 1, 2

@@ -113,6 +113,28 @@ int eae_hip_decode(const eae_hip_model* model, const float* quantized_latents, i
                    float* out_f32, uint8_t* out_u8, const uint8_t* ref_u8, uint64_t* sse, void* scratch,
                    uint64_t scratch_bytes, void* stream);
 
+/* ---- tiled encode / decode (csrc/hip/tile.hip) -------------------------------------------------
+ * An image of any size goes through eae_hip_encode / eae_hip_decode as a batch of equally shaped windows; each window keeps only
+ * its interior, the part whose receptive field it holds, so the stitched result is bit-identical to the untiled one. The plan
+ * (pipeline.tile_plan) is int32 [n_windows][EAE_TILE_PLAN_COLS], all coordinates in latents: image, window origin (row, col),
+ * interior origin in the window (row, col), interior origin in the image (row, col), interior extent (rows, cols). `plan` is the
+ * device copy the kernel reads, `host_plan` the same rows in host memory, which the argument checks read before any launch.
+ * Both functions: NULL pointer or a non-positive size -> EAE_HIP_BAD_ARGUMENT; a window larger than the plane, a row of a latent
+ * (unit * elem_bytes) that is not a multiple of 16 bytes, a base pointer not aligned to 16 bytes, or a plan row outside the plane
+ * or its window (or whose two interior origins disagree) -> EAE_HIP_BAD_SHAPE; nothing is launched then. The full plane is
+ * addressed with 64-bit offsets (no size limit); a window's bytes / 16 stay below 2^31, n_windows <= 65535. One launch per call.
+ * tile_copy: plane [n][h * unit][w * unit][elem_bytes] and windows [n_windows][window_h * unit][window_w * unit][elem_bytes];
+ *   to_windows != 0 copies every whole window out of the plane (gather), to_windows == 0 copies every interior into it (stitch).
+ *   uint8 images: unit 16, elem 1; latents: unit 1, elem 512; float reconstruction: unit 16, elem 4.
+ * tile_stitch_u8: uint8 reconstruction windows (unit 16) -> their interiors into image [n][16 h][16 w] (nullable) and, with ref_u8
+ *   (same shape as image), sse[i] += the exact squared error over the interior pixels of image i (caller zeroes; eae_hip_decode's
+ *   own sse would count the halos). At least one of image and ref_u8. */
+#define EAE_TILE_PLAN_COLS 9
+int eae_hip_tile_copy(void* plane, int n, int h, int w, void* windows, int window_h, int window_w, int unit, int elem_bytes,
+                      const int32_t* plan, const int32_t* host_plan, int n_windows, int to_windows, void* stream);
+int eae_hip_tile_stitch_u8(const uint8_t* windows, int window_h, int window_w, uint8_t* image, const uint8_t* ref_u8, uint64_t* sse,
+                           int n, int h, int w, const int32_t* plan, const int32_t* host_plan, int n_windows, void* stream);
+
 /* ---- analysis transform (eae/graph/components.py:86-142) ---------------------------------------------------------*/
 
 /* conv_1 + bias_add + gdn_1  (components.py:119-125; tf.nn.conv2d 9x9, 1->128, stride 4, 'SAME' = pad 2/3;
@@ -126,8 +148,9 @@ int eae_hip_conv9x9s4_u8(const uint8_t* x, const float* w_packed, const float* b
 /* conv_2 / conv_3 + bias_add (+ gdn_2 / gdn_3)  (components.py:126-142; tf.nn.conv2d 5x5, 128->128, stride 2,
  * 'SAME' = pad 1/2). x: f32 [N][H][W][128]; w_packed: from eae_hip_pack_conv_weights (HWIO [5][5][128][128] with the
  * output channels in packed order); out: [N][H/2][W/2][128]. H, W even, and H * W * 512 bytes (one image's input plane; the
- * kernels address inside an image with 32-bit byte offsets) below 2 GB: EAE_HIP_BAD_SHAPE otherwise. For the whole path that is
- * an image of at most 67 megapixels (conv_2's input is the 1/16-size plane: 8192 x 8176 passes, 8192 x 8192 does not).
+ * kernels address inside an image with 32-bit byte offsets) below 2 GB: EAE_HIP_BAD_SHAPE otherwise. For the untiled whole path
+ * that is an image of at most 67 megapixels (conv_2's input is the 1/16-size plane: 8192 x 8176 passes, 8192 x 8192 does not);
+ * the tiled path (eae_hip_tile_copy above) is bounded by the window, not the image.
  * norm: EAE_NORM_NONE (learned-bin-width model, components.py:137-138) or EAE_NORM_GDN (gamma_packed, beta). */
 int eae_hip_conv5x5s2(const float* x, const float* w_packed, const float* bias, int norm, const float* gamma_packed,
                       const float* beta, float* out, int n, int h, int w_in, void* stream);
