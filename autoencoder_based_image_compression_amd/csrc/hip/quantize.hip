@@ -215,6 +215,8 @@ extern "C" int eae_hip_nonzero_flags(const float* x, uint32_t* nonzero_flags, in
 
 // ---- statistics for lossless/stats.py:197-241 (find_index_map_exception) ---------------------------------------------
 // Per-map minimum / maximum (numpy.amin / amax of stats.py:103-104) through order-preserving uint keys and integer atomics.
+// numpy.amin and numpy.amax both return NaN for a map that holds a NaN (of either sign): a NaN takes the smallest key for the
+// minimum and the largest for the maximum, both of which decode to a NaN.
 __device__ __forceinline__ unsigned int float_key(float f) {
     const unsigned int b = __float_as_uint(f);
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
@@ -234,9 +236,11 @@ __global__ __launch_bounds__(256) void map_minmax_kernel(const float* __restrict
     if (sub >= lanes_per_c) return;
     unsigned int lo = 0xFFFFFFFFu, hi = 0u;
     for (long r = (long)blockIdx.x * lanes_per_c + sub; r < rows; r += (long)gridDim.x * lanes_per_c) {
-        const unsigned int k = float_key(y[r * c_count + c]);
-        lo = k < lo ? k : lo;
-        hi = k > hi ? k : hi;
+        const float v = y[r * c_count + c];
+        const unsigned int k = float_key(v);
+        const bool nan = v != v;
+        lo = nan ? 0u : (k < lo ? k : lo);
+        hi = nan ? 0xFFFFFFFFu : (k > hi ? k : hi);
     }
     atomicMin(&keys[c], lo);
     atomicMax(&keys[c_count + c], hi);

@@ -61,7 +61,9 @@ __global__ void preprocess_kernel(const uint8_t* __restrict__ u8, const double* 
 }
 
 // q = bw * round_half_even(y / bw) (tools.py:1095); symbol = round(q / bw) for the histogram behind discrete_entropy;
-// checks[0] += |symbol| >= 2^31 (outside this build's domain), checks[1] += |quantization(y) - y| >= 1.5e-10.
+// checks[0] += |symbol| >= 2^31 or not a number (outside this build's domain), checks[1] += the elements that fail
+// tools.py:214-217, numpy.testing.assert_almost_equal(quantization(y), y, decimal=10): |q - y| >= 1.5e-10, except NaN and
+// +-inf, which numpy compares by position (quantization keeps both where they are) and so never fail that assertion.
 __global__ void quantize_f64_kernel(const double* __restrict__ y, double bw, double* __restrict__ q,
                                     int* __restrict__ symbols, unsigned int* checks, long total) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -69,8 +71,9 @@ __global__ void quantize_f64_kernel(const double* __restrict__ y, double bw, dou
         if (q) q[i] = qq;
         const double s = rint(qq / bw);
         if (!(fabs(s) < 2147483648.0)) atomicAdd(&checks[0], 1u);
-        // tools.py:214-217 when y is passed as already quantised: |quantization(y) - y| < 1.5e-10
-        if (!(fabs(qq - y[i]) < 1.5e-10)) atomicAdd(&checks[1], 1u);
+        // tools.py:214-217 when y is passed as already quantised: |quantization(y) - y| < 1.5e-10, NaN and +-inf exempt
+        const double yi = y[i];
+        if (!(fabs(qq - yi) < 1.5e-10 || qq == yi || yi != yi)) atomicAdd(&checks[1], 1u);
         if (symbols) symbols[i] = (int)s;
     }
 }

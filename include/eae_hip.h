@@ -271,7 +271,8 @@ int eae_hip_map_means(const float* y, float* means, int64_t rows, int c, void* s
 /* The two device passes of lossless/stats.py:197-241 (find_index_map_exception), whose per-map loop calls
  * compute_probabilities_intervals(map, 1.) (stats.py:70-134): numpy.amin / amax per map, then a histogram over the
  * unit-width intervals [floor(min), ceil(max)].
- *   map_minmax: minmax[0][c] = min, minmax[1][c] = max over rows of y[row][c]; scratch_keys: 2*c uint32 of scratch.
+ *   map_minmax: minmax[0][c] = min, minmax[1][c] = max over rows of y[row][c] (both NaN when the map holds a NaN, like
+ *   numpy); scratch_keys: 2*c uint32 of scratch.
  *   floor_histograms: hist[c][floor(y) + radius] += 1 for |floor(y)| <= radius, else overflow[c] += 1 (caller zeroes both;
  *   hist is [c][2*radius+1]). The closed last interval of numpy.histogram (values equal to the right edge) is folded in
  *   by the host, which also forms the probabilities and the Jensen-Shannon divergences in float64 like the reference. */
@@ -464,8 +465,9 @@ int eae_hip_svhn_preprocess(const uint8_t* images, const double* mean, double st
                             void* stream);
 /* tls.quantization (svhn/tools/tools.py:1095): q = bw * round_half_even(y / bw) with ONE scalar bin width, plus the
  * int32 symbols round(q / bw) behind tls.count_symbols / discrete_entropy (:214-231, :289-). q and symbols nullable.
- * checks[2] (caller zeroes): [0] symbols outside int32, [1] |q - y| >= 1.5e-10 ("The quantization was omitted.",
- * tools.py:214-217, when y is passed as already quantised). */
+ * checks[2] (caller zeroes): [0] symbols outside int32 (NaN and +-inf included), [1] |q - y| >= 1.5e-10 ("The quantization
+ * was omitted.", tools.py:214-217, when y is passed as already quantised; NaN and +-inf pass that numpy assertion and are not
+ * counted). */
 int eae_hip_svhn_quantize_f64(const double* y, double bin_width, double* q, int32_t* symbols, uint32_t* checks,
                               int64_t count, void* stream);
 /* minmax[0] = min(minmax[0], min symbols), minmax[1] = max(...): caller initialises to (INT32_MAX, INT32_MIN). */
