@@ -22,6 +22,8 @@ HIP_SYMBOLS = {
     'eae_hip_decode': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp]),
     'eae_hip_tile_copy': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     'eae_hip_tile_stitch_u8': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
+    'eae_hip_tile_symbols_gather': (_i, [_vp, _i, _i, _i, _vp, _i64, _vp, _vp, _i, _vp]),
+    'eae_hip_tile_symbols_dequantize': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'eae_hip_conv9x9s4_u8': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'eae_hip_conv5x5s2': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'eae_hip_gdn': (_i, [_vp, _vp, _vp, _i, _vp, _i64, _vp]),

@@ -19,13 +19,30 @@ Layout (little endian):
 The exception map. The reference does not code it: it charges ceil(h*w*entropy) bits for it (compression.py:68-75), the
 cost of an ideal adaptive coder. A decodable file has to carry it, so it goes through the same UEG0 + arithmetic coder
 with a probability row measured on that very map (stats.py:181-195 applied to its histogram), stored per image.
+
+The tile-indexed format EAT1 (`encode_images(..., coding_tile=(th, tw))`). The latent plane of every
+map is cut into a plain grid of coding tiles of th x tw latents (edge tiles smaller; `coding_tile_grid`), and every (image,
+tile, map) is coded as its own pair of streams, the symbols of the tile in raster order. The probabilities are static, so a
+tile's stream costs its share of the whole map's bits plus its own termination and byte padding. The exception map keeps one
+probability row per image, measured on the whole map. Layout (little endian):
+    magic 'EAT1' | version u16 (= 1) | flags u16 | nb_images u32 | height u32 | width u32 | nb_maps u16 | L u8 | reserved u8 |
+    idx_map_exception i32 | coding_tile_h u16 | coding_tile_w u16                       (tile sides in latents)
+    bin_widths f32[nb_maps] | map_mean f32[nb_maps] | binary_probabilities f64[nb_maps][L]
+    exception_probabilities f64[nb_images][L]              (only when idx_map_exception >= 0)
+    bit counts u32[nb_images][nb_tiles][nb_maps][2]        (arithmetic-coded stream, bypass stream)
+    payload: for every image, every tile (row-major), every map: arithmetic-coded bytes, then bypass bytes (each rounded up
+    to a byte)
+The streams of one (image, tile) are contiguous, so a region of the image needs one byte range per (image, tile) it touches
+(`region_plan`), and `decode_region` reads only those from a file. With one tile per map the payload is EAE1's, byte for byte.
 """
+import numbers
 import struct
 
 import numpy
 import torch
 
 from . import device as dev
+from . import pipeline
 from .kodak.eae.graph import constants as csts
 from .kodak.lossless import interface_cython
 from .kodak.lossless import stats as lossless_stats
@@ -34,6 +51,9 @@ from .kodak.tools import tools as tls
 MAGIC = b'EAE1'
 VERSION = 1
 _HEADER = struct.Struct('<4sHHIIIHBBi')
+TILE_MAGIC = b'EAT1'
+TILE_VERSION = 1
+_TILE_HEADER = struct.Struct('<4sHHIIIHBBiHH')
 
 
 def _exception_rows(symbols_planar, idx_map_exception, truncated_unary_length):
@@ -68,7 +88,8 @@ def _raise_for_statuses(results):
         interface_cython.raise_for_status(int(results[2, bad[0]]), int(results[3, bad[0]]))
 
 
-def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_probabilities, idx_map_exception=-1, tile=None):
+def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_probabilities, idx_map_exception=-1, tile=None,
+                  coding_tile=None, tiles_per_call=64):
     """uint8 (N, H, W) or (N, H, W, 1) luminance images -> (blob bytes, info dict).
 
     encoder: pipeline.DeviceEncoder of the model; bin_widths_test float32 (128,) (the trained bin widths times the
@@ -76,6 +97,9 @@ def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_p
     info: 'nb_bits' uint32 (N, 128) (arithmetic-coded + bypass bits of every map), 'payload_bytes', 'header_bytes'.
     tile=(th, tw): run the analysis transform through windows (pipeline.DeviceEncoder.__call__): the latents, hence the blob
     bytes, are those of tile=None, and images beyond the untiled path's size limit can be written.
+    coding_tile=(th, tw) latents: write the tile-indexed format EAT1 (module docstring) instead of EAE1. The coder runs on groups
+    of `tiles_per_call` (image, tile) pairs, so its streams and workspace are bounded by one group whatever the image size.
+    info then also holds 'tile_bits' uint32 (N, nb_tiles, 128, 2).
     """
     images = numpy.ascontiguousarray(luminances_uint8)
     if images.dtype != numpy.uint8:
@@ -91,6 +115,9 @@ def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_p
     mean = numpy.ascontiguousarray(map_mean, dtype=numpy.float32)
     if bin_widths.shape != (nb_maps,) or mean.shape != (nb_maps,):
         raise ValueError('`bin_widths_test` and `map_mean` must have one element per map.')
+    if coding_tile is not None:
+        coding_tile = _positive_pair(coding_tile, '`coding_tile`')
+        tiles_per_call = _positive_int(tiles_per_call, '`tiles_per_call`')
     device = encoder.device
     y = encoder(torch.from_numpy(images).to(device), tile=tile)
     map_size = y.shape[1]*y.shape[2]
@@ -107,6 +134,9 @@ def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_p
         prob_row[idx_map_exception::nb_maps] = nb_maps + numpy.arange(nb_images, dtype=numpy.int32)
     else:
         idx_map_exception = -1
+    if coding_tile is not None:
+        return _encode_tiles(symbols, (y.shape[1], y.shape[2]), coding_tile, tiles_per_call, table, idx_map_exception, probabilities,
+                             exception_rows, bin_widths, mean, 1 if encoder.are_bin_widths_learned else 0, (height, width))
     n_maps = nb_images*nb_maps
     streams = dev.coder_encode_batch(symbols.view(n_maps, map_size), torch.from_numpy(table).to(device),
                                      torch.from_numpy(prob_row).to(device), truncated_unary_length)
@@ -128,7 +158,11 @@ def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_p
 
 
 def read_header(blob):
-    """Parses everything in front of the payload. Raises ValueError on a malformed or truncated blob."""
+    """Parses everything in front of the payload. Raises ValueError on a malformed or truncated blob.
+    An EAT1 blob gives the same keys, with 'bits' uint32 [nb_images, nb_tiles, nb_maps, 2], plus 'format' ('EAT1') and
+    'coding_tile' (th, tw)."""
+    if bytes(blob[:4]) == TILE_MAGIC:
+        return _read_tile_header(blob, len(blob))
     if len(blob) < _HEADER.size:
         raise ValueError('The container is truncated.')
     (magic, version, flags, nb_images, height, width, nb_maps, truncated_unary_length, _, idx_map_exception) = _HEADER.unpack_from(blob, 0)
@@ -180,6 +214,8 @@ def read_header(blob):
 def decode_symbols(blob, device='cuda'):
     """blob -> (header, int16 symbols [N, 128, map_size] on the device), arithmetic decoding only."""
     header = read_header(blob)
+    if header.get('format') == 'EAT1':
+        raise ValueError('An EAT1 container codes tiles, not whole maps: use decode_tile_symbols.')
     (nb_images, nb_maps) = (header['nb_images'], header['nb_maps'])
     if header['height'] % 16 != 0 or header['width'] % 16 != 0:
         raise ValueError('The image size in the container is not divisible by 16.')
@@ -204,9 +240,13 @@ def decode_symbols(blob, device='cuda'):
     return (header, symbols.view(nb_images, nb_maps, map_size))
 
 
-def decode_images(blob, decoder, tile=None):
+def decode_images(blob, decoder, tile=None, tiles_per_call=64):
     """blob + pipeline.DeviceDecoder of the model -> uint8 (N, H, W) reconstructions (BT.601 range, tools.py:61-93).
-    tile=(th, tw): run the synthesis transform through windows (pipeline.DeviceDecoder.__call__): same reconstruction."""
+    tile=(th, tw): run the synthesis transform through windows (pipeline.DeviceDecoder.__call__): same reconstruction.
+    EAT1 blobs are decoded in groups of `tiles_per_call` coding tiles, scattered and dequantised into the latent plane."""
+    if bytes(blob[:4]) == TILE_MAGIC:
+        header = read_header(blob)
+        return decode_region(blob, decoder, (0, 0, header['height'], header['width']), tile=tile, tiles_per_call=tiles_per_call)
     (header, symbols) = decode_symbols(blob, decoder.device)
     if header['are_bin_widths_learned'] != decoder.are_bin_widths_learned:
         raise ValueError('The container was written by the other kind of model (learned / fixed bin widths).')
@@ -216,3 +256,408 @@ def decode_images(blob, decoder, tile=None):
     (h_map, w_map) = (header['height']//16, header['width']//16)
     (_, reconstruction_uint8, _) = decoder(shifted.view(header['nb_images'], h_map, w_map, header['nb_maps']), tile=tile)
     return reconstruction_uint8.cpu().numpy()
+
+
+# ---- the tile-indexed format EAT1 --------------------------------------------------------------------------------------------
+
+def _positive_int(x, what):
+    if not isinstance(x, numbers.Integral) or isinstance(x, bool) or x < 1:
+        raise ValueError('{} must be a positive integer.'.format(what))
+    return int(x)
+
+
+def _positive_pair(x, what):
+    if not isinstance(x, (tuple, list)) or len(x) != 2:
+        raise ValueError('{} must be a pair of positive integers.'.format(what))
+    return (_positive_int(x[0], what), _positive_int(x[1], what))
+
+
+def _nb_tiles(h, w, coding_tile):
+    return (-(-h//coding_tile[0]))*(-(-w//coding_tile[1]))
+
+
+def coding_tile_grid(h, w, coding_tile):
+    """The coding tiles of an h x w latent plane: (tiles, classes). tiles int64 [nb_tiles, 5], row-major: origin row, origin col,
+    rows, cols, shape class; classes: the distinct (rows, cols), at most 4 (interior, last row, last column, corner)."""
+    (th, tw) = _positive_pair(coding_tile, '`coding_tile`')
+    (h, w) = (_positive_int(h, '`h`'), _positive_int(w, '`w`'))
+    rows = [(r0, min(th, h - r0)) for r0 in range(0, h, th)]
+    cols = [(c0, min(tw, w - c0)) for c0 in range(0, w, tw)]
+    classes = []
+    for shape in ((rows[0][1], cols[0][1]), (rows[-1][1], cols[0][1]), (rows[0][1], cols[-1][1]), (rows[-1][1], cols[-1][1])):
+        if shape not in classes:
+            classes.append(shape)
+    tiles = numpy.empty((len(rows)*len(cols), 5), dtype=numpy.int64)
+    k = 0
+    for (r0, nr) in rows:
+        for (c0, nc) in cols:
+            tiles[k] = (r0, c0, nr, nc, classes.index((nr, nc)))
+            k += 1
+    return tiles, classes
+
+
+def _tile_header_length(fixed, total_length):
+    """Checks the fixed EAT1 header (bytes-like of at least _TILE_HEADER.size bytes) -> (fields, length of the whole header).
+    Everything that sizes a read or an allocation is checked here, against `total_length` (the blob's or the file's)."""
+    if len(fixed) < _TILE_HEADER.size:
+        raise ValueError('The container is truncated.')
+    (magic, version, flags, nb_images, height, width, nb_maps, length, _, idx_map_exception, th, tw) = _TILE_HEADER.unpack_from(fixed, 0)
+    if magic != TILE_MAGIC:
+        raise ValueError('The container does not start with the magic bytes.')
+    if version != TILE_VERSION:
+        raise ValueError('The container version {} is not supported.'.format(version))
+    if nb_maps != csts.NB_MAPS_3:
+        raise ValueError('The container does not hold {} maps per image.'.format(csts.NB_MAPS_3))
+    if length < 1:
+        raise ValueError('The truncated unary length does not belong to [1, 255].')
+    if nb_images < 1 or height < 1 or width < 1 or height % csts.STRIDE_PROD != 0 or width % csts.STRIDE_PROD != 0:
+        raise ValueError('The image sizes in the container are not positive multiples of {}.'.format(csts.STRIDE_PROD))
+    if not -1 <= idx_map_exception < nb_maps:
+        raise ValueError('The index of the exception map in the container is out of range.')
+    if th < 1 or tw < 1:
+        raise ValueError('The coding tile sizes in the container are not positive.')
+    fields = {'nb_images': nb_images, 'height': height, 'width': width, 'nb_maps': nb_maps, 'truncated_unary_length': length,
+              'idx_map_exception': idx_map_exception, 'are_bin_widths_learned': bool(flags & 1), 'format': 'EAT1',
+              'coding_tile': (th, tw)}
+    nb_tiles = _nb_tiles(height//csts.STRIDE_PROD, width//csts.STRIDE_PROD, (th, tw))
+    nb_rows = nb_images if idx_map_exception >= 0 else 0
+    header_length = (_TILE_HEADER.size + 8*nb_maps + 8*nb_maps*length + 8*nb_rows*length + 8*nb_images*nb_tiles*nb_maps)
+    if header_length > total_length:
+        raise ValueError('The container is truncated.')
+    return fields, header_length
+
+
+def _read_tile_header(blob, total_length):
+    """read_header for EAT1: `blob` holds at least the whole header; `total_length` is the blob's (or the file's) length."""
+    (header, header_length) = _tile_header_length(blob, total_length)
+    if len(blob) < header_length:
+        raise ValueError('The container is truncated.')
+    (nb_images, nb_maps, length) = (header['nb_images'], header['nb_maps'], header['truncated_unary_length'])
+    (h, w) = (header['height']//csts.STRIDE_PROD, header['width']//csts.STRIDE_PROD)
+    nb_tiles = _nb_tiles(h, w, header['coding_tile'])
+    pos = _TILE_HEADER.size
+
+    def take(count, dtype):
+        nonlocal pos
+        out = numpy.frombuffer(blob, dtype=dtype, count=count, offset=pos).copy()
+        pos += count*numpy.dtype(dtype).itemsize
+        return out
+
+    header['bin_widths'] = take(nb_maps, numpy.float32)
+    header['map_mean'] = take(nb_maps, numpy.float32)
+    header['binary_probabilities'] = take(nb_maps*length, numpy.float64).reshape(nb_maps, length)
+    nb_rows = nb_images if header['idx_map_exception'] >= 0 else 0
+    header['exception_probabilities'] = take(nb_rows*length, numpy.float64).reshape(nb_rows, length)
+    header['bits'] = take(nb_images*nb_tiles*nb_maps*2, numpy.uint32).reshape(nb_images, nb_tiles, nb_maps, 2)
+    header['payload_offset'] = pos
+    # per tile, as EAE1 per map: no count above the capacity of that tile's stream (the unpacking would write past its region)
+    (tiles, _) = coding_tile_grid(h, w, header['coding_tile'])
+    capacity = numpy.array([stream_capacity_bits(int(r*c), length) for (r, c) in tiles[:, 2:4].tolist()], dtype=numpy.int64)
+    if nb_tiles and (header['bits'].max(axis=(0, 2, 3)).astype(numpy.int64) > capacity).any():
+        raise ValueError('A bit count of the header exceeds the capacity of a stream.')
+    payload_bytes = int(((header['bits'].astype(numpy.int64) + 7)//8).sum())
+    if pos + payload_bytes != total_length:
+        raise ValueError('The payload size does not match the bit counts of the header.')
+    return header
+
+
+def _tile_layout(header):
+    """(coding tile, bits [N, nb_tiles, 128, 2]) of either format: an EAE1 blob is one tile per map."""
+    if header.get('format') == 'EAT1':
+        return header['coding_tile'], header['bits']
+    (h, w) = (header['height']//csts.STRIDE_PROD, header['width']//csts.STRIDE_PROD)
+    return (h, w), header['bits'].reshape(header['nb_images'], 1, header['nb_maps'], 2)
+
+
+def _entry_bytes(bits):
+    """bits [..., 128, 2] -> payload bytes of every (image, tile): its streams rounded up to bytes."""
+    return ((bits.astype(numpy.int64) + 7)//8).sum(axis=(-1, -2))
+
+
+def _stream_offsets(bits):
+    """bits [E, 128, 2] of entries laid out one after the other -> byte offset of every stream, int64 [E, 128, 2]."""
+    nbytes = (bits.astype(numpy.int64) + 7)//8
+    return (numpy.cumsum(nbytes.reshape(-1)) - nbytes.reshape(-1)).reshape(nbytes.shape)
+
+
+def region_plan(header, region, images=None):
+    """What decoding the pixel rectangle region = (y0, x0, height, width) of `images` (indices, default all) needs.
+
+    The region's latents, extended by pipeline.DECODER_HALO and clamped to the image, are the sub-plane whose synthesis gives
+    the region's pixels exactly. Returns a dict: 'sub_plane' (row0, row1, col0, col1) in latents,
+    'images', 'tiles' (indices of the coding tiles that intersect the sub-plane, row-major), 'entries' [(image, tile)],
+    'ranges' [(start, stop)] byte range of every entry in the blob, 'crop' (y, x, height, width) of the region in the
+    sub-plane's reconstruction, and 'header_bytes'. An EAE1 header is one tile per map."""
+    (nb_images, height, width) = (header['nb_images'], header['height'], header['width'])
+    if not isinstance(region, (tuple, list)) or len(region) != 4:
+        raise ValueError('`region` must be (y0, x0, height, width).')
+    for x in region:
+        if not isinstance(x, numbers.Integral) or isinstance(x, bool):
+            raise ValueError('`region` must be (y0, x0, height, width) in integers.')
+    (y0, x0, rh, rw) = (int(x) for x in region)
+    if rh < 1 or rw < 1 or y0 < 0 or x0 < 0 or y0 + rh > height or x0 + rw > width:
+        raise ValueError('The region {} is empty or leaves the {} x {} image.'.format(tuple(region), height, width))
+    if images is None:
+        images = list(range(nb_images))
+    else:
+        images = [int(i) for i in images]
+        if not images or len(set(images)) != len(images) or min(images) < 0 or max(images) >= nb_images:
+            raise ValueError('`images` must be distinct indices of images of the container.')
+    (h, w) = (height//csts.STRIDE_PROD, width//csts.STRIDE_PROD)
+    (before, after) = pipeline.DECODER_HALO
+    (r0, r1) = (max(y0//16 - before, 0), min(-(-(y0 + rh)//16) + after, h))
+    (c0, c1) = (max(x0//16 - before, 0), min(-(-(x0 + rw)//16) + after, w))
+    ((th, tw), bits) = _tile_layout(header)
+    tiles_per_row = -(-w//tw)
+    tiles = [i*tiles_per_row + j for i in range(r0//th, (r1 - 1)//th + 1) for j in range(c0//tw, (c1 - 1)//tw + 1)]
+    nbytes = _entry_bytes(bits).reshape(-1)
+    starts = header['payload_offset'] + numpy.cumsum(nbytes) - nbytes
+    nb_tiles = bits.shape[1]
+    entries = [(i, t) for i in images for t in tiles]
+    ranges = [(int(starts[i*nb_tiles + t]), int(starts[i*nb_tiles + t] + nbytes[i*nb_tiles + t])) for (i, t) in entries]
+    return {'sub_plane': (r0, r1, c0, c1), 'images': images, 'tiles': tiles, 'entries': entries, 'ranges': ranges,
+            'crop': (y0 - 16*r0, x0 - 16*c0, rh, rw), 'header_bytes': header['payload_offset']}
+
+
+def _read_at(f, start, count):
+    f.seek(start)
+    data = f.read(count)
+    if len(data) != count:
+        raise ValueError('The container is truncated.')
+    return data
+
+
+def fetch_region(source, region, images=None):
+    """Host side of decode_region: (header, region_plan, one bytes-like chunk per plan entry). `source`: a bytes-like blob, or a
+    seekable binary file object, from which only the fixed header, then the rest of the header, then the plan's byte ranges
+    (adjacent ranges in one read) are read. An EAE1 file is read whole: its maps are coded whole."""
+    if not hasattr(source, 'read'):
+        blob = memoryview(source).cast('B')
+        header = read_header(blob)
+        plan = region_plan(header, region, images)
+        return header, plan, [blob[a:b] for (a, b) in plan['ranges']]
+    source.seek(0, 2)
+    total = source.tell()
+    fixed = _read_at(source, 0, min(_TILE_HEADER.size, total))
+    if fixed[:4] != TILE_MAGIC:
+        blob = memoryview(fixed + _read_at(source, len(fixed), total - len(fixed)))
+        header = read_header(blob)
+        plan = region_plan(header, region, images)
+        return header, plan, [blob[a:b] for (a, b) in plan['ranges']]
+    (_, header_length) = _tile_header_length(fixed, total)
+    header = _read_tile_header(fixed + _read_at(source, len(fixed), header_length - len(fixed)), total)
+    plan = region_plan(header, region, images)
+    chunks = [None]*len(plan['ranges'])
+    order = sorted(range(len(chunks)), key=lambda k: plan['ranges'][k])
+    k = 0
+    while k < len(order):                       # runs of adjacent ranges in one read
+        run = [order[k]]
+        while k + len(run) < len(order) and plan['ranges'][order[k + len(run)]][0] == plan['ranges'][run[-1]][1]:
+            run.append(order[k + len(run)])
+        start = plan['ranges'][run[0]][0]
+        data = memoryview(_read_at(source, start, plan['ranges'][run[-1]][1] - start))
+        for e in run:
+            (a, b) = plan['ranges'][e]
+            chunks[e] = data[a - start:b - start]
+        k += len(run)
+    return header, plan, chunks
+
+
+def _group_layout(entries, tiles, classes):
+    """Device layout of a group of (image, tile) entries: the entries of one shape class side by side, so that the coder codes
+    every class as one batch of maps of one size. -> (runs [(class, entry positions, first element)], element offset of every
+    entry's map 0, elements of the buffer). Class runs start on 256-byte boundaries."""
+    by_class = {}
+    for (k, (_, t)) in enumerate(entries):
+        by_class.setdefault(int(tiles[t, 4]), []).append(k)
+    (runs, offsets, pos) = ([], numpy.zeros(len(entries), dtype=numpy.int64), 0)
+    for cls in sorted(by_class):
+        ks = by_class[cls]
+        size = classes[cls][0]*classes[cls][1]
+        runs.append((cls, ks, pos))
+        offsets[ks] = pos + numpy.arange(len(ks), dtype=numpy.int64)*(dev.NB_MAPS*size)
+        pos = (pos + len(ks)*dev.NB_MAPS*size + 127)//128*128
+    return runs, offsets, max(pos, 128)
+
+
+def _prob_rows(entries, ks, idx_map_exception):
+    rows = numpy.tile(numpy.arange(dev.NB_MAPS, dtype=numpy.int32), len(ks)).reshape(len(ks), dev.NB_MAPS)
+    if idx_map_exception >= 0:
+        rows[:, idx_map_exception] = dev.NB_MAPS + numpy.array([entries[k][0] for k in ks], dtype=numpy.int32)
+    return rows.reshape(-1)
+
+
+def _symbols_plan(entries, tiles, offsets, image_index=None, origin=(0, 0)):
+    """Plan rows (device.TILE_SYMBOLS_PLAN_COLS) of a group: image (or its index in the output), origin relative to `origin`,
+    extent, offset in the group buffer."""
+    plan = numpy.empty((len(entries), dev.TILE_SYMBOLS_PLAN_COLS), dtype=numpy.int64)
+    for (k, (i, t)) in enumerate(entries):
+        plan[k] = (i if image_index is None else image_index[i], tiles[t, 0] - origin[0], tiles[t, 1] - origin[1], tiles[t, 2],
+                   tiles[t, 3], offsets[k])
+    return plan
+
+
+class _Workspace(object):
+    """One coder workspace per call, grown to the largest class batch of a group (the batches run one after the other)."""
+
+    def __init__(self, device, length):
+        (self.device, self.length, self.tensor) = (device, length, None)
+
+    def get(self, n_maps, map_size):
+        from . import _native
+        need = int(_native.hip().eae_hip_coder_workspace_bytes(n_maps, map_size, self.length))
+        if self.tensor is None or self.tensor.numel() < need:
+            self.tensor = None
+            self.tensor = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self.tensor
+
+
+def _encode_tiles(symbols, shape, coding_tile, per_call, table, idx_map_exception, probabilities, exception_rows, bin_widths, mean,
+                  flags, image_size):
+    """encode_images' EAT1 half: symbols [N, 128, h*w] (device) -> (blob, info). Per group of `per_call` (image, tile) entries in
+    payload order: one gather launch, one coder batch per shape class, one pack launch per class into the group's payload."""
+    (nb_images, nb_maps, _) = symbols.shape
+    (h, w) = shape
+    coding_tile = (min(coding_tile[0], h), min(coding_tile[1], w))
+    if max(coding_tile) > 0xFFFF:
+        raise ValueError('A coding tile side does not fit the container (65535 latents at most).')
+    (tiles, classes) = coding_tile_grid(h, w, coding_tile)
+    nb_tiles = tiles.shape[0]
+    length = table.shape[1]
+    device = symbols.device
+    table_device = torch.from_numpy(table).to(device)
+    workspace = _Workspace(device, length)
+    bits = numpy.zeros((nb_images, nb_tiles, nb_maps, 2), dtype=numpy.uint32)
+    all_entries = [(i, t) for i in range(nb_images) for t in range(nb_tiles)]
+    pieces = []
+    for g0 in range(0, len(all_entries), per_call):
+        entries = all_entries[g0:g0 + per_call]
+        (runs, offsets, total) = _group_layout(entries, tiles, classes)
+        plan = _symbols_plan(entries, tiles, offsets)
+        gathered = torch.empty(total, dtype=torch.int16, device=device)
+        dev.tile_symbols_gather(symbols, gathered, torch.from_numpy(plan).to(device), plan, h, w)
+        coded = []
+        for (cls, ks, start) in runs:
+            size = classes[cls][0]*classes[cls][1]
+            n_maps = len(ks)*nb_maps
+            prob_row = torch.from_numpy(_prob_rows(entries, ks, idx_map_exception)).to(device)
+            coded.append(dev.coder_encode_batch(gathered[start:start + n_maps*size].view(n_maps, size), table_device, prob_row, length,
+                                                workspace=workspace.get(n_maps, size)))
+        group_bits = numpy.zeros((len(entries), nb_maps, 2), dtype=numpy.uint32)
+        for ((_, ks, _), streams) in zip(runs, coded):
+            results = streams.results.cpu().numpy()
+            _raise_for_statuses(results)
+            group_bits[ks] = numpy.stack([results[0], results[1]], axis=1).reshape(len(ks), nb_maps, 2)
+        stream_offsets = _stream_offsets(group_bits)
+        group_bytes = int(_entry_bytes(group_bits).sum())
+        payload = torch.empty(max(group_bytes, 1), dtype=torch.uint8, device=device)
+        for ((_, ks, _), streams) in zip(runs, coded):
+            dev.coder_pack_streams(streams, torch.from_numpy(stream_offsets[ks].reshape(-1, 2)).to(device), group_bytes, payload=payload)
+        pieces.append(payload[:group_bytes].cpu().numpy().tobytes())
+        for (k, (i, t)) in enumerate(entries):
+            bits[i, t] = group_bits[k]
+        del gathered, coded, streams, payload       # before the next group allocates its own
+    (height, width) = image_size
+    head = _TILE_HEADER.pack(TILE_MAGIC, TILE_VERSION, flags, nb_images, height, width, nb_maps, length, 0, idx_map_exception,
+                             coding_tile[0], coding_tile[1])
+    parts = [head, bin_widths.tobytes(), mean.tobytes(), probabilities.tobytes(), exception_rows.tobytes(), bits.tobytes()]
+    header_bytes = sum(len(part) for part in parts)
+    payload = b''.join(pieces)
+    info = {'nb_bits': (bits[..., 0].astype(numpy.int64) + bits[..., 1]).sum(axis=1).astype(numpy.uint32), 'payload_bytes': len(payload),
+            'header_bytes': header_bytes, 'tile_bits': bits}
+    return b''.join(parts) + payload, info
+
+
+def _decode_entries(header, entries, chunks, device, per_call, consume):
+    """Entropy-decodes (image, tile) entries whose payload bytes are `chunks`, in groups of `per_call`: one upload, then per shape
+    class one unpack and one coder batch into the group's tile-major buffer. consume(entries, buffer, offsets, tiles) gets every
+    group (offsets: element offset of every entry's map 0). Raises the coder's error after the group that met it."""
+    (h, w) = (header['height']//csts.STRIDE_PROD, header['width']//csts.STRIDE_PROD)
+    (coding_tile, bits) = _tile_layout(header)
+    (tiles, classes) = coding_tile_grid(h, w, coding_tile)
+    length = header['truncated_unary_length']
+    table = numpy.concatenate([header['binary_probabilities'], header['exception_probabilities']])
+    table_device = torch.from_numpy(table).to(device)
+    workspace = _Workspace(device, length)
+    nb_maps = header['nb_maps']
+    for g0 in range(0, len(entries), per_call):
+        group = entries[g0:g0 + per_call]
+        group_bits = numpy.stack([bits[i, t] for (i, t) in group])
+        stream_offsets = _stream_offsets(group_bits)
+        sizes = _entry_bytes(group_bits)
+        payload = numpy.zeros(int(sizes.sum()) + 8, dtype=numpy.uint8)
+        pos = 0
+        for (k, chunk) in enumerate(chunks[g0:g0 + per_call]):
+            if len(chunk) != sizes[k]:
+                raise ValueError('A payload range does not match the bit counts of the header.')
+            payload[pos:pos + sizes[k]] = numpy.frombuffer(chunk, dtype=numpy.uint8)
+            pos += int(sizes[k])
+        payload_device = torch.from_numpy(payload).to(device)
+        (runs, offsets, total) = _group_layout(group, tiles, classes)
+        decoded = torch.empty(total, dtype=torch.int16, device=device)
+        results = []
+        for (cls, ks, start) in runs:
+            size = classes[cls][0]*classes[cls][1]
+            n_maps = len(ks)*nb_maps
+            run_bits = group_bits[ks].reshape(-1, 2)
+            streams = dev.coder_unpack_streams(payload_device, torch.from_numpy(stream_offsets[ks].reshape(-1, 2)).to(device),
+                                               torch.from_numpy(run_bits[:, 0].astype(numpy.int32)).to(device),
+                                               torch.from_numpy(run_bits[:, 1].astype(numpy.int32)).to(device), size, length)
+            prob_row = torch.from_numpy(_prob_rows(group, ks, header['idx_map_exception'])).to(device)
+            dev.coder_decode_batch(streams, table_device, prob_row, workspace=workspace.get(n_maps, size),
+                                   out=decoded[start:start + n_maps*size].view(n_maps, size))
+            results.append(streams.results)
+        consume(group, decoded, offsets, tiles)
+        for r in results:
+            _raise_for_statuses(r.cpu().numpy())
+        del payload_device, decoded, streams, results
+
+
+def decode_tile_symbols(blob, device='cuda', tiles_per_call=64):
+    """An EAT1 (or EAE1) blob -> (header, symbols): symbols[i][t] = int16 [128, rows, cols] (device) of image i, coding tile t
+    (row-major; an EAE1 blob has one tile per map), arithmetic decoding only."""
+    header = read_header(blob)
+    (coding_tile, bits) = _tile_layout(header)
+    (nb_images, nb_tiles) = bits.shape[:2]
+    plan = region_plan(header, (0, 0, header['height'], header['width']))
+    entries = [(i, t) for i in range(nb_images) for t in range(nb_tiles)]
+    view = memoryview(blob).cast('B')
+    out = [[None]*nb_tiles for _ in range(nb_images)]
+
+    def consume(group, decoded, offsets, tiles):
+        for (k, (i, t)) in enumerate(group):
+            (rows, cols) = (int(tiles[t, 2]), int(tiles[t, 3]))
+            start = int(offsets[k])
+            out[i][t] = decoded[start:start + dev.NB_MAPS*rows*cols].view(dev.NB_MAPS, rows, cols)
+
+    ranges = dict(zip(plan['entries'], plan['ranges']))
+    _decode_entries(header, entries, [view[slice(*ranges[e])] for e in entries], torch.device(device),
+                    _positive_int(tiles_per_call, '`tiles_per_call`'), consume)
+    return header, out
+
+
+def decode_region(source, decoder, region, images=None, tile=None, tiles_per_call=64):
+    """The pixels region = (y0, x0, height, width) of `images` (indices, default all) -> uint8 [N_sel, height, width], equal to
+    decode_images(...)[images, y0:y0 + height, x0:x0 + width]. `source`: a bytes-like blob or a seekable binary file object, of
+    which only the header and the byte ranges region_plan names are read (fetch_region). Only the coding tiles that meet the
+    region's sub-plane are entropy-decoded (for an EAE1 source: the whole maps), and only the sub-plane is synthesised.
+    tile=(th, tw): synthesise the sub-plane through windows (pipeline.DeviceDecoder.__call__)."""
+    tiles_per_call = _positive_int(tiles_per_call, '`tiles_per_call`')
+    (header, plan, chunks) = fetch_region(source, region, images)
+    if header['are_bin_widths_learned'] != decoder.are_bin_widths_learned:
+        raise ValueError('The container was written by the other kind of model (learned / fixed bin widths).')
+    device = decoder.device
+    (r0, r1, c0, c1) = plan['sub_plane']
+    shifted = torch.empty((len(plan['images']), r1 - r0, c1 - c0, header['nb_maps']), dtype=torch.float32, device=device)
+    bin_widths = torch.from_numpy(header['bin_widths']).to(device)
+    map_mean = torch.from_numpy(header['map_mean']).to(device)
+    image_index = {i: k for (k, i) in enumerate(plan['images'])}
+
+    def consume(group, decoded, offsets, tiles):
+        rows = _symbols_plan(group, tiles, offsets, image_index, (r0, c0))
+        dev.tile_symbols_dequantize(decoded, torch.from_numpy(rows).to(device), rows, bin_widths, map_mean, shifted)
+
+    _decode_entries(header, plan['entries'], chunks, device, tiles_per_call, consume)
+    (_, reconstruction, _) = decoder(shifted, tile=tile)
+    (y, x, rh, rw) = plan['crop']
+    return reconstruction[:, y:y + rh, x:x + rw].cpu().numpy()

@@ -532,6 +532,49 @@ def tile_stitch_u8(windows, plan_device, plan_host, image=None, ref_u8=None, sse
     return sse
 
 
+# ---- coding tiles of the EAT1 container (include/eae_hip.h, "coding tiles"; the plan comes from container.py) ---------------
+
+TILE_SYMBOLS_PLAN_COLS = 6
+
+
+def _symbols_plan_pointers(plan_device, plan_host):
+    """(device pointer, host pointer, rows) of a coding-tile plan; both copies must hold the same int64 rows."""
+    if plan_host.dtype.name != 'int64' or plan_host.ndim != 2 or plan_host.shape[1] != TILE_SYMBOLS_PLAN_COLS or not plan_host.flags.c_contiguous:
+        raise HipError('the host plan must be a C-contiguous int64 array of {} columns'.format(TILE_SYMBOLS_PLAN_COLS))
+    if plan_device.dtype != torch.int64 or tuple(plan_device.shape) != plan_host.shape:
+        raise HipError('the device plan must be int64 of the host plan\'s shape')
+    return _p(plan_device), plan_host.ctypes.data, plan_host.shape[0]
+
+
+def tile_symbols_gather(symbols_planar, tiles, plan_device, plan_host, h, w):
+    """int16 symbols [N, 128, h*w] -> the tile-major runs of the plan's coding tiles in `tiles` (int16, 1-D). One plan row per
+    tile: image, origin (row, col), extent (rows, cols), offset of the tile's map 0 in `tiles`."""
+    if symbols_planar.dtype != torch.int16 or tiles.dtype != torch.int16 or tiles.dim() != 1:
+        raise HipError('symbols and tiles must be int16, tiles one-dimensional')
+    (n, c, hw) = symbols_planar.shape
+    if c != NB_MAPS or hw != h*w:
+        raise HipError('symbols must be [N, 128, h*w]')
+    (plan_p, host_p, rows) = _symbols_plan_pointers(plan_device, plan_host)
+    _check(_native.hip().eae_hip_tile_symbols_gather(_p(symbols_planar), n, h, w, _p(tiles), tiles.numel(), plan_p, host_p, rows,
+                                                     _stream(symbols_planar)), 'eae_hip_tile_symbols_gather')
+
+
+def tile_symbols_dequantize(tiles, plan_device, plan_host, bin_widths, map_mean, out):
+    """Tile-major int16 runs -> float32 out [N, hs, ws, 128] = bin_widths[c] * symbol + map_mean[c] (dequantize_maps' arithmetic)
+    for every pixel of the plan's tiles inside `out`. Plan rows as tile_symbols_gather's, with image and origin in `out`."""
+    if tiles.dtype != torch.int16 or tiles.dim() != 1:
+        raise HipError('tiles must be one-dimensional int16')
+    if out.dtype != torch.float32 or out.dim() != 4 or out.shape[3] != NB_MAPS:
+        raise HipError('out must be float32 [N, hs, ws, 128]')
+    if bin_widths.dtype != torch.float32 or bin_widths.numel() != NB_MAPS or (map_mean is not None and (map_mean.dtype != torch.float32 or map_mean.numel() != NB_MAPS)):
+        raise HipError('bin widths and map means must be float32 of 128 elements')
+    (plan_p, host_p, rows) = _symbols_plan_pointers(plan_device, plan_host)
+    (n, hs, ws) = out.shape[:3]
+    _check(_native.hip().eae_hip_tile_symbols_dequantize(_p(tiles), tiles.numel(), plan_p, host_p, rows, _p(bin_widths), _p(map_mean),
+                                                         _p(out), n, hs, ws, _stream(tiles)), 'eae_hip_tile_symbols_dequantize')
+    return out
+
+
 # ---- lossless coder on the device (include/eae_hip.h, "lossless coder on the device") ---------------------------------
 
 CODER_ROUNDTRIP, CODER_ENCODE_ONLY, CODER_ROUNDTRIP_VERIFY = 0, 1, 2
@@ -653,14 +696,18 @@ def coder_encode_batch(symbols_planar, probabilities, prob_row, truncated_unary_
     return out
 
 
-def coder_decode_batch(streams, probabilities, prob_row, expected=None, workspace=None):
+def coder_decode_batch(streams, probabilities, prob_row, expected=None, workspace=None, out=None):
     """The 64-maps-per-wavefront decoder. expected=None: returns the decoded symbols [n_maps, map_size] (skipped maps
-    zero). With `expected`: decodes into the workspace and compares on the device; failures land in `streams.status`.
+    zero), in `out` when given (int16, n_maps x map_size contiguous elements; skipped maps are left as they are there).
+    With `expected`: decodes into the workspace and compares on the device; failures land in `streams.status`.
     With a workspace (`coder_workspace`; always there with `expected`) the serial core leaves one prefix byte per symbol there
     and a data-parallel pass adds signs and suffixes (csrc/hip/coder_simd.hip); without, the general kernel decodes every
     map. Same results."""
     device = streams.streams.device
-    if expected is None:
+    if expected is None and out is not None:
+        if out.dtype != torch.int16 or out.numel() != streams.n_maps*streams.map_size:
+            raise TypeError('`out` must hold n_maps x map_size int16 symbols.')
+    elif expected is None:
         out = torch.zeros((streams.n_maps, streams.map_size), dtype=torch.int16, device=device)
     else:
         out = None
@@ -735,9 +782,13 @@ def coder_roundtrip_fused(symbols_planar, probabilities, prob_row, truncated_una
     return out
 
 
-def coder_pack_streams(streams, offsets, payload_bytes):
-    """Gathers the valid stream bytes of every map into one uint8 device tensor; `offsets` int64 [n_maps, 2] (device)."""
-    payload = torch.zeros(max(int(payload_bytes), 1), dtype=torch.uint8, device=streams.streams.device)
+def coder_pack_streams(streams, offsets, payload_bytes, payload=None):
+    """Gathers the valid stream bytes of every map into one uint8 device tensor; `offsets` int64 [n_maps, 2] (device).
+    payload: a uint8 device tensor of at least `payload_bytes` bytes to write into (several batches can share one)."""
+    if payload is None:
+        payload = torch.zeros(max(int(payload_bytes), 1), dtype=torch.uint8, device=streams.streams.device)
+    elif payload.dtype != torch.uint8 or payload.numel() < int(payload_bytes):
+        raise HipError('`payload` must be uint8 of at least payload_bytes bytes')
     _check(_native.hip().eae_hip_coder_pack_streams(streams.n_maps, _p(streams.streams), streams.stride, _p(streams.bac_bits),
                                                     _p(streams.bypass_bits), _p(offsets), _p(payload), _stream()),
            'eae_hip_coder_pack_streams')

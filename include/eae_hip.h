@@ -135,6 +135,25 @@ int eae_hip_tile_copy(void* plane, int n, int h, int w, void* windows, int windo
 int eae_hip_tile_stitch_u8(const uint8_t* windows, int window_h, int window_w, uint8_t* image, const uint8_t* ref_u8, uint64_t* sse,
                            int n, int h, int w, const int32_t* plan, const int32_t* host_plan, int n_windows, void* stream);
 
+/* ---- coding tiles of the tile-indexed container EAT1 (csrc/hip/tile_symbols.hip; container.py) -----------
+ * The coder reads each map as one contiguous run. These two move the symbols of a group of coding tiles between the planar layout
+ * and the tile-major layout of the coder. The plan is int64 [n_tiles][EAE_TILE_SYMBOLS_PLAN_COLS]: image, tile origin (row, col),
+ * tile extent (rows, cols), element offset of the tile's map 0 in `tiles`; map m of the tile is the run of rows * cols symbols at
+ * offset + m * rows * cols, in raster order. One plan may mix tiles of several shapes. `plan` is the device copy the kernel reads,
+ * `host_plan` the same rows in host memory, which the argument checks read before any launch. NULL pointer or a non-positive size
+ * -> EAE_HIP_BAD_ARGUMENT; a malformed row, a run outside `tiles` (tile_elems int16), a tile of 2^31 pixels or more, or more than
+ * 65535 tiles -> EAE_HIP_BAD_SHAPE; nothing is launched then. Planes are addressed with 64-bit offsets. One launch per call.
+ * tile_symbols_gather: symbols_planar [n][128][h * w] int16 (eae_hip_quantize_maps) -> `tiles`. Every tile lies inside the h x w plane.
+ * tile_symbols_dequantize: `tiles` -> shifted_out f32 [n][hs][ws][128] = bin_widths[c] * symbol + map_mean[c] (map_mean nullable),
+ *   the arithmetic of eae_hip_dequantize_maps, bit for bit. Image and origin are in the hs x ws output; the origin may be negative
+ *   and a tile may reach past the output: only its pixels inside are written. shifted_out aligned to 16 bytes. */
+#define EAE_TILE_SYMBOLS_PLAN_COLS 6
+int eae_hip_tile_symbols_gather(const int16_t* symbols_planar, int n, int h, int w, int16_t* tiles, int64_t tile_elems,
+                                const int64_t* plan, const int64_t* host_plan, int n_tiles, void* stream);
+int eae_hip_tile_symbols_dequantize(const int16_t* tiles, int64_t tile_elems, const int64_t* plan, const int64_t* host_plan, int n_tiles,
+                                    const float* bin_widths, const float* map_mean, float* shifted_out, int n, int hs, int ws,
+                                    void* stream);
+
 /* ---- analysis transform (eae/graph/components.py:86-142) ---------------------------------------------------------*/
 
 /* conv_1 + bias_add + gdn_1  (components.py:119-125; tf.nn.conv2d 9x9, 1->128, stride 4, 'SAME' = pad 2/3;
