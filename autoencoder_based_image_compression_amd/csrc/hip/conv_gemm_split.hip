@@ -46,12 +46,15 @@ constexpr int RING = 8;
 #define EAE_EPI_RING 4
 #endif
 constexpr int EPI_RING = EAE_EPI_RING;   // gamma ring of the epilogue (see the register budget at the kernel)
-constexpr int ABUF = 32 * AS_STRIDE;                 // one activation buffer of one wave
-// LDS of a block: two activation buffers per wave + ONE copy of the per-channel vectors of the epilogue (bias | beta, or, with
+// A K-step's activations pass through LDS only to move half a row between the two half-waves of one wave (see the loader):
+// one buffer per wave, rows of KC + 1 floats. The odd stride puts the 32 rows of a lane group on 32 different banks for both the
+// 4-byte stores and the 4-byte reads, and leaves no row 8-byte aligned for certain, so hipcc keeps every store a ds_write2_b32
+// fed from the loaded registers as they are (a ds_write2_b64 needs its pairs in adjacent registers: 12 v_mov per K-step).
+constexpr int A_STRIDE = KC + 1;
+constexpr int ABUF = 32 * A_STRIDE;                  // the activation buffer of one wave
+// LDS of a block: one activation buffer per wave + ONE copy of the per-channel vectors of the epilogue (bias | beta, or, with
 // the latent stage behind conv_3, bias | beta_in | beta_out | map_mean | bin_widths). Every wave writes the whole copy itself
-// (identical values: a benign race, no barrier), so three blocks take 3 x 37.9 KB and leave room for two of the coder's
-// decoder blocks (20 KB each) on the same CU: with a copy per wave (3 x 41 KB) a CU that drew two of them ran one GEMM block
-// short for the length of a decode.
+// (identical values: a benign race, no barrier).
 constexpr int vec_floats(int norm) { return (norm >= NORM_LATENT ? 5 : 2) * EAE_C; }
 constexpr int QT_H = 4, QT_W = 8;                    // a wave's tile: 4 x 8 positions
 constexpr int MIN_PIECE = 4;                         // K-steps: no head or tail shorter than this
@@ -70,15 +73,15 @@ __device__ __forceinline__ int head_steps(int d, int D, int T) {
 // WPB: waves (= items) per block, the unit of dispatch (4 is what ships; 1 behind EAE_HIP_SPLIT_WPB and in the parity tests: see the launcher)
 template <int NORM, int WPB>
 __global__ __launch_bounds__(64 * WPB, NORM >= NORM_LATENT ? 2 : 3) void conv_gemm_split_kernel(const ConvGemmParams p) {
-    __shared__ __attribute__((aligned(16))) float lds[WPB * 2 * ABUF + vec_floats(NORM)];
+    __shared__ __attribute__((aligned(16))) float lds[WPB * ABUF + vec_floats(NORM)];
 #ifdef EAE_GEMM_PRIO       // scratch/r04/prio_waves.sh: issue priority of the GEMM waves against the coder's (3: conv_2 1.03 -> 0.96 ms on one
                            // stream, the coder's chains longer, the product mode -0.4 %: not set in the shipped build)
     __builtin_amdgcn_s_setprio(EAE_GEMM_PRIO);
 #endif
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float* wlds = lds + wave * 2 * ABUF;
-    float* vec_lds = lds + WPB * 2 * ABUF;
+    float* wlds = lds + wave * ABUF;
+    float* vec_lds = lds + WPB * ABUF;
     {
         const float2 z = make_float2(0.f, 0.f);
         *reinterpret_cast<float2*>(vec_lds + 2 * lane) = p.bias ? *reinterpret_cast<const float2*>(p.bias + 2 * lane) : z;
@@ -91,7 +94,7 @@ __global__ __launch_bounds__(64 * WPB, NORM >= NORM_LATENT ? 2 : 3) void conv_ge
             *reinterpret_cast<float2*>(vec_lds + 4 * EAE_C + 2 * lane) = *reinterpret_cast<const float2*>(p.bin_widths + 2 * lane);
         }
     }
-    const int hi = lane >> 5, lj = lane & 31, a_q = lane & 7;
+    const int hi = lane >> 5, lj = lane & 31;
     const int cbase = 4 * hi;
 
     // this XCD's share of the spatial tiles, and this wave's item
@@ -110,7 +113,6 @@ __global__ __launch_bounds__(64 * WPB, NORM >= NORM_LATENT ? 2 : 3) void conv_ge
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(p.w), 0, (int)((size_t)MAX_TAPS * EAE_C * EAE_C * sizeof(float)), 0x00020000);
     const int w_lane = (hi * EAE_C + lj * 4) * 4;             // byte offset inside a k-pair of weight rows
-    const int a_off = lj * AS_STRIDE + hi * 16;
 
     {
         const int item = ((int)blockIdx.x >> 3) * WPB + wave;
@@ -140,23 +142,6 @@ __global__ __launch_bounds__(64 * WPB, NORM >= NORM_LATENT ? 2 : 3) void conv_ge
         const int tr = b % p.tiles_r;
         const int img = b / p.tiles_r;
 
-        // activation loader: lane -> (position m_i of this tile, channel quad lane & 7). The eight 8-lane groups of load / staging
-        // store i take the positions 4 (g & 3) + 16 (g >> 2) + i: the rows that one LDS cycle of the 8-byte staging stores touches
-        // (two or four groups) then start 4 rows = 144 floats apart, i.e. 16 banks modulo 32 and modulo 64 -- disjoint bank sets.
-        // (Rounds 1-3: position g + 8 i, adjacent rows per cycle, 36 floats apart: two-way conflicts on every staging store,
-        // SQ_LDS_BANK_CONFLICT 14.05 M per conv_2 launch.)
-        int a_pr[4], a_pc[4], a_ok[4];
-        const int a_m0 = 4 * ((lane >> 3) & 3) + 16 * (lane >> 5);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int m = a_m0 + i;
-            a_pr[i] = tr * QT_H + m / QT_W;
-            a_pc[i] = tc * QT_W + m % QT_W;
-            a_ok[i] = (a_pr[i] < p.hp) & (a_pc[i] < p.wp);
-        }
-        const float* in_img = p.in + (size_t)img * p.hin * p.win * EAE_C;
-        const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(in_img), 0, (int)((size_t)p.hin * p.win * EAE_C * sizeof(float)), 0x00020000);
         // this lane's output pixel (position lj of the tile): also where the accumulators of an interrupted tile wait
         const int pr = tr * QT_H + lj / QT_W, pc = tc * QT_W + lj % QT_W;
         const bool valid = pr < p.hp && pc < p.wp;
@@ -167,30 +152,48 @@ __global__ __launch_bounds__(64 * WPB, NORM >= NORM_LATENT ? 2 : 3) void conv_ge
             out_img, 0, (int)((size_t)p.hout * p.wout * EAE_C * sizeof(float)), 0x00020000);
         const int park = valid ? (o_off + cbase) * 4 : -1;      // byte offset of this lane's parked accumulators (-1: beyond the buffer)
 
+        // activation loader: lane (hi, lj) loads the K-step's 32 channels of ITS OWN position lj (the B column it feeds), channel
+        // quads 2 i + hi in load i: one address per lane and step, the four loads 32 bytes apart (immediate offsets). Which taps
+        // fall outside the image is worked out once per item, one bit per tap (<= 25) in a_inv; a K-step then costs three vector
+        // instructions: base + the tap's wave-uniform offset, with bit 31 set for an outside tap -- an offset of 2 GB or more,
+        // beyond any plane the launchers accept (plane_fits), which the buffer's range check turns into zeros as before. (Rounds
+        // 1-6 tested and addressed each of four loads per step: 28 of the K loop's 40 vector instructions.) The 32-bit sum cannot
+        // wrap into the buffer: a negative one (a tap above or left of the image) is at most -112, the immediates at most 96.
+        const float* in_img = p.in + (size_t)img * p.hin * p.win * EAE_C;
+        const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(in_img), 0, (int)((size_t)p.hin * p.win * EAE_C * sizeof(float)), 0x00020000);
+        const int a_r = pr * p.in_stride, a_c = pc * p.in_stride;    // input pixel of tap (0, 0)
+        const unsigned int a_base = ((unsigned)a_r * (unsigned)p.win + (unsigned)a_c) * (EAE_C * 4) + 16 * hi;
+        unsigned int a_inv = 0;                                      // bit ti: tap ti reads outside the image (all bits: !valid)
+        for (int ti = 0; ti < ntaps; ++ti) {
+            const int packed = EAE_Q_TAP(ti);
+            const int r = a_r + (packed & 0xFF) - 8, c = a_c + ((packed >> 8) & 0xFF) - 8;
+            if (!valid || (unsigned)r >= (unsigned)p.hin || (unsigned)c >= (unsigned)p.win) a_inv |= 1u << ti;
+        }
+
         float4 a_reg[4];
-#define EAE_Q_PREFETCH_A(packed_, ci0_)                                                                              \
+#define EAE_Q_PREFETCH_A(packed_, ti_, ci0_)                                                                         \
         {                                                                                                            \
             const int dr_ = ((packed_) & 0xFF) - 8, dc_ = (((packed_) >> 8) & 0xFF) - 8;                             \
+            const unsigned int off_ = (a_base + (unsigned)(((dr_ * p.win + dc_) * EAE_C + (ci0_)) * 4)) |            \
+                                      ((a_inv >> (ti_)) << 31);                                                      \
             _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                          \
-                const int r_ = a_pr[i] * p.in_stride + dr_;                                                          \
-                const int c_ = a_pc[i] * p.in_stride + dc_;                                                          \
-                const int ok_ = a_ok[i] & ((unsigned)r_ < (unsigned)p.hin) & ((unsigned)c_ < (unsigned)p.win);       \
-                const int lin_ = ((r_ * p.win + c_) * EAE_C + (ci0_) + 4 * a_q) * 4;                                 \
-                const u32x4 v_ = __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, ok_ ? lin_ : -1, 0, 0);              \
+                const u32x4 v_ = __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, (int)off_ + 32 * i, 0, 0);           \
                 a_reg[i] = make_float4(__uint_as_float(v_.x), __uint_as_float(v_.y), __uint_as_float(v_.z),          \
                                        __uint_as_float(v_.w));                                                       \
             }                                                                                                        \
         }
-#define EAE_Q_STAGE_A(buf_)                                                                                          \
+        // The MFMA wants channel 2 kk + hi of position lj from lane (hi, lj): lane (0, lj) holds channels 8 i + 0..3, lane
+        // (1, lj) 8 i + 4..7. Row lj of the buffer takes the 32 channels in order; each half-wave reads back its parity.
+#define EAE_Q_STAGE_A()                                                                                              \
         {                                                                                                            \
             _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                          \
-                float* dst_ = wlds + (buf_) * ABUF + (a_m0 + i) * AS_STRIDE + 2 * a_q;                              \
-                *reinterpret_cast<float2*>(dst_) = make_float2(a_reg[i].x, a_reg[i].z);                              \
-                *reinterpret_cast<float2*>(dst_ + 16) = make_float2(a_reg[i].y, a_reg[i].w);                         \
+                float* dst_ = wlds + lj * A_STRIDE + 8 * i + 4 * hi;                                                 \
+                dst_[0] = a_reg[i].x; dst_[1] = a_reg[i].y; dst_[2] = a_reg[i].z; dst_[3] = a_reg[i].w;              \
             }                                                                                                        \
         }
-        // byte offset of the weight slab of (tap index, 32-channel chunk); K order: chunk (outer), then tap
-#define EAE_Q_SLAB(ti_, ch_) ((((EAE_Q_TAP(ti_) >> 16) * EAE_C + (ch_) * KC) * EAE_C) * 4)
+        // byte offset of the weight slab of (packed tap, 32-channel chunk); K order: chunk (outer), then tap
+#define EAE_Q_SLAB(packed_, ch_) (((((packed_) >> 16) * EAE_C + (ch_) * KC) * EAE_C) * 4)
 #define EAE_Q_W_LOAD(dst_, slab_, kk_)                                                                               \
         {                                                                                                            \
             const u32x4 v_ = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, w_lane + (kk_) * 2 * EAE_C * 4, (slab_), 0); \
@@ -236,24 +239,27 @@ __global__ __launch_bounds__(64 * WPB, NORM >= NORM_LATENT ? 2 : 3) void conv_ge
         }
 
         int tap_i = s0 % ntaps, chunk = s0 / ntaps;
+        int tap_cur = EAE_Q_TAP(tap_i);
         float4 ring[RING];
         {
-            const int slab0 = EAE_Q_SLAB(tap_i, chunk);
+            const int slab0 = EAE_Q_SLAB(tap_cur, chunk);
 #pragma unroll
             for (int i = 0; i < RING; ++i) EAE_Q_W_LOAD(ring[i], slab0, i)
         }
-        EAE_Q_PREFETCH_A(EAE_Q_TAP(tap_i), chunk * KC)
-        EAE_Q_STAGE_A(0)
+        EAE_Q_PREFETCH_A(tap_cur, tap_i, chunk * KC)
+        EAE_Q_STAGE_A()
+        const float* a_rd = wlds + lj * A_STRIDE + hi;
         for (int step = s0; step < s1; ++step) {
             int nti = tap_i + 1, nch = chunk;
             if (nti == ntaps) { nti = 0; ++nch; }
             if (step + 1 >= s1) { nti = tap_i; nch = chunk; }      // the last step re-loads itself: loads stay unconditional
-            const int slab_cur = EAE_Q_SLAB(tap_i, chunk);
-            const int slab_nxt = EAE_Q_SLAB(nti, nch);
-            EAE_Q_PREFETCH_A(EAE_Q_TAP(nti), nch * KC)
-            const float4* a_rd = reinterpret_cast<const float4*>(wlds + ((step - s0) & 1) * ABUF + a_off);
-            const float4 a0 = a_rd[0], a1 = a_rd[1], a2 = a_rd[2], a3 = a_rd[3];
-            const float av[16] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, a2.x, a2.y, a2.z, a2.w, a3.x, a3.y, a3.z, a3.w};
+            const int tap_nxt = EAE_Q_TAP(nti);
+            const int slab_cur = EAE_Q_SLAB(tap_cur, chunk);
+            const int slab_nxt = EAE_Q_SLAB(tap_nxt, nch);
+            EAE_Q_PREFETCH_A(tap_nxt, nti, nch * KC)
+            float av[16];
+#pragma unroll
+            for (int kk = 0; kk < KC / 2; ++kk) av[kk] = a_rd[2 * kk];
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int kk = 0; kk < KC / 2; ++kk) {
@@ -268,9 +274,10 @@ __global__ __launch_bounds__(64 * WPB, NORM >= NORM_LATENT ? 2 : 3) void conv_ge
                 __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
-            EAE_Q_STAGE_A(((step - s0) + 1) & 1)
+            EAE_Q_STAGE_A()           // one buffer: this wave's reads of it above have returned (the MFMAs consumed them)
             tap_i = nti;
             chunk = nch;
+            tap_cur = tap_nxt;
         }
 
         if (s1 == T) {
