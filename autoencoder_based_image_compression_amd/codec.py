@@ -15,9 +15,9 @@ inputs (tests/test_gpu_codec.py); `bench.py` times exactly this class.
 
 Concurrency: the coder is a few latency-bound wavefronts, so its launches go to side streams and overlap the synthesis
 transforms of the same batch and the analysis transforms of the next ones; `nb_in_flight` batches of coder work may be
-pending. Buffers that cross streams are preallocated per slot; results reach the host through a kernel that writes pinned
-memory (no hipMemcpyAsync on the launch thread) and a worker thread turns them into per-image numbers; it polls its events
-and sleeps in between instead of spinning in `synchronize()` (eight ranks share one host CPU quota). For small batches the
+pending. Buffers that cross streams are preallocated per slot (`_Slot`: everything one step in flight owns); results reach
+the host through a kernel that writes pinned memory (no hipMemcpyAsync on the launch thread) and a worker thread turns them
+into per-image numbers; it polls its events and sleeps in between instead of spinning in `synchronize()` (eight ranks share one host CPU quota). For small batches the
 step can be replayed as three hipGraphs per slot (`use_graphs`) over several transform streams (`nb_transform_streams`).
 """
 import contextlib
@@ -168,11 +168,25 @@ class StepTimeout(RuntimeError):
 
 class _Job(object):
     """What the results of one submitted step are made from; whoever claims it first -- the result worker taking it off its queue, or
-    the caller's `Ticket.result()` -- waits for the device and forms the results."""
-    __slots__ = ('fields', '_claimed')
+    the caller's `Ticket.result()` -- waits for the device and forms the results.
+    events: what `_Worker._wait` waits for ('events' wait mode; else empty); views: the slot's pinned blocks (results, histograms,
+    overflow, flags, checks, squared errors) as host arrays; symbols_host: the pinned symbols (host coder) or None; recount:
+    `BatchCodec._recount_exception_maps` of the slot; fetch: `BatchCodec._fetch_job` or None; sequence: (the slot's step counters in
+    pinned memory, the values this step leaves there) or None; early_published: the synthesis side's publication carried the
+    analysis side's blocks too (exception-map histograms, dead-map flags, range check): small steps, whose caller waits for each
+    result -- `BatchCodec._early_publish`."""
+    __slots__ = ('ticket', 'events', 'views', 'symbols_host', 'slot_free', 'recount', 'fetch', 'sequence', 'early_published', '_claimed')
 
-    def __init__(self, *fields):
-        self.fields = fields
+    def __init__(self, ticket, events, views, symbols_host, slot_free, recount, fetch, sequence, early_published=False):
+        self.ticket = ticket
+        self.events = events
+        self.views = views
+        self.symbols_host = symbols_host
+        self.slot_free = slot_free
+        self.recount = recount
+        self.fetch = fetch
+        self.sequence = sequence
+        self.early_published = bool(early_published)
         self._claimed = threading.Lock()
 
     def claim(self):
@@ -290,16 +304,12 @@ class _Worker(threading.Thread):
     def process(self, job, by_caller=False):
         """Waits until the device is through with the step, then forms the ticket's results from the slot's pinned blocks (or the
         exception `result()` raises), frees the slot. On the worker thread, or on the caller's (`Ticket.result()`)."""
-        (ticket, events, views, symbols_host, slot_free, recount, fetch, sequence) = job.fields[:8]
-        # the synthesis side's publication carried the analysis side's blocks too (exception-map histograms, dead-map flags, range
-        # check): small steps, whose caller waits for each result -- `BatchCodec._early_publish`
-        early_published = len(job.fields) > 8 and bool(job.fields[8])
+        ticket = job.ticket
         try:
             if by_caller and not getattr(_THREAD, 'short_sleeps', False):
                 _short_sleeps_for_this_thread()
                 _THREAD.short_sleeps = True
-            arrays = [v if isinstance(v, numpy.ndarray) else v.numpy() for v in views]
-            (results, hist, overflow, flags, checks, sse) = arrays
+            (results, hist, overflow, flags, checks, sse) = [v if isinstance(v, numpy.ndarray) else v.numpy() for v in job.views]
             early = {}
 
             def early_part():
@@ -319,23 +329,23 @@ class _Worker(threading.Thread):
                         if int(overflow.sum()) != 0:
                             # a symbol beyond +-hist_radius: the reference's histogram runs from the smallest to the largest symbol
                             # whatever they are (lossless/compression.py:68-75, tools.py:376-388), so count again over all of int16
-                            rows = recount()
+                            rows = job.recount()
                         early['exception_bits'] = lossless_compression.exception_maps_nb_bits(rows.astype(numpy.int64), self.map_size)
                 except Exception as exc:
                     early['error'] = exc
 
-            if sequence is not None:
+            if job.sequence is not None:
                 if by_caller:
-                    self._wait_sequence_by_caller(*sequence, early=early_part if early_published else None)
+                    self._wait_sequence_by_caller(*job.sequence, early=early_part if job.early_published else None)
                 else:
-                    self._wait_sequence(*sequence)
-            for event in events:
+                    self._wait_sequence(*job.sequence)
+            for event in job.events:
                 self._wait(event)
-            if fetch is not None:
+            if job.fetch is not None:
                 # The copy back is issued HERE, behind events that have completed: on this runtime an asynchronous copy
                 # whose stream still waits for an event holds the calling thread until it can start (the launch thread would
                 # submit the next step only after this one is decoded: 4.5 instead of 3.2 ms per step).
-                (reconstruction, pinned, stream) = fetch
+                (reconstruction, pinned, stream) = job.fetch
                 with torch.cuda.device(reconstruction.device), torch.cuda.stream(stream):
                     pinned.copy_(reconstruction, non_blocking=True)
                     copied = torch.cuda.Event()
@@ -347,9 +357,9 @@ class _Worker(threading.Thread):
             if early['unfinished'] != 0:
                 raise dev.SplitHandOffTimeout('{} tiles of a cut conv launch were not handed over: the results of this batch '
                                               'are invalid (the workspace has been reset; later batches are unaffected)'.format(early['unfinished']))
-            if symbols_host is not None:
+            if job.symbols_host is not None:
                 # encode + decode + compare per map on the host cores, like compress_lossless + the caller's assert
-                (_, nb_bits) = lossless_compression.code_planar_symbols(symbols_host.numpy(), self.host_probabilities,
+                (_, nb_bits) = lossless_compression.code_planar_symbols(job.symbols_host.numpy(), self.host_probabilities,
                                                                        self.idx_map_exception, nb_threads=self.host_threads,
                                                                        roundtrip=True, verify_only=True)
                 results = numpy.zeros_like(results)
@@ -375,7 +385,7 @@ class _Worker(threading.Thread):
         except Exception as exc:      # surfaced by Ticket.result()
             ticket._error = exc
         finally:
-            slot_free.set()
+            job.slot_free.set()
             ticket._done.set()
 
 
@@ -445,6 +455,66 @@ def stream_budget(nb_transform_streams, nb_in_flight, hw_queues=None, copies=0):
                    'streams beyond them share queues and serialise): running {3} + {4}. Set GPU_MAX_HW_QUEUES=16 in the environment before '
                    'the first GPU call, or import this package before anything initialises the GPU.'.format(nt0, nf0, hw_queues, nt, nf))
     return (nt, nf, message)
+
+
+def _no_hook(name, fn):
+    return fn()
+
+
+class _Slot(object):
+    """Everything one step in flight owns; `BatchCodec` goes round `nb_slots` of them. Made once: no launch and no submit cuts a view."""
+    __slots__ = ('block', 'out', 'results', 'hist', 'overflow', 'flags', 'checks', 'sse', 'unfinished', 'pinned_out', 'pinned_sse',
+                 'host_views', 'symbols', 'symbols_2d', 'coder_streams', 'workspace', 'conv_ws', 'seq_dev', 'pinned_seq', 'seq_host',
+                 'coder_seq', 'synthesis_seq', 'counts', 'free', 'pinned_symbols', 'staging', 'pinned_rec', 'graphs')
+
+    def __init__(self, codec):
+        (batch_size, nb_maps, device) = (codec.batch_size, codec.nb_maps, codec.device)
+        n_maps = batch_size*nb_maps
+        nb_hist = batch_size if codec.idx_map_exception >= 0 else 0
+        hist_width = 2*codec.hist_radius + 1
+        layout = (4*n_maps, nb_hist*hist_width, nb_hist, n_maps, 4)
+        nb_words = sum(layout)
+        assert nb_words % 2 == 0
+
+        def cut(block):
+            """[coder results 4 x n_maps | exception histograms | overflow | flags | checks(4)], on the device or in pinned memory."""
+            (results, hist, overflow, flags, checks) = torch.split(block, layout)
+            return (results.view(4, n_maps), hist.view(nb_hist, hist_width) if nb_hist else hist, overflow, flags.view(batch_size, nb_maps), checks)
+
+        # the block for the host, followed by the squared errors (int64 per image, published on their own once the synthesis
+        # transform is through) and behind them one more 64-bit word whose low half is the conv workspace's error word of the step
+        self.block = torch.zeros(nb_words + 2*batch_size + 2, dtype=torch.int32, device=device)
+        self.out = self.block[:nb_words]
+        (self.results, self.hist, self.overflow, self.flags, self.checks) = cut(self.out)
+        self.sse = self.block[nb_words:].view(torch.int64)           # [batch_size] errors + [1] status
+        self.unfinished = self.block[nb_words + 2*batch_size:nb_words + 2*batch_size + 1]
+        self.pinned_out = torch.zeros(nb_words, dtype=torch.int32).pin_memory()
+        self.pinned_sse = torch.zeros(batch_size + 1, dtype=torch.int64).pin_memory()
+        # what the result worker reads (`_Job.views`)
+        self.host_views = tuple(t.numpy() for t in cut(self.pinned_out) + (self.pinned_sse,))
+        self.symbols = torch.empty((batch_size, nb_maps, codec.map_size), dtype=torch.int16, device=device)
+        self.symbols_2d = self.symbols.view(n_maps, codec.map_size)
+        self.coder_streams = dev.CoderStreams(n_maps, codec.map_size, codec.truncated_unary_length, device, results=self.results)
+        make_workspace = dev.coder_trailing_workspace if codec.coder_chunks > 1 else dev.coder_workspace
+        self.workspace = make_workspace(n_maps, codec.map_size, codec.truncated_unary_length, device)
+        # scratch that lets the conv GEMM launches cut their last tiles (device.conv_workspace): a slot's launches never overlap each other
+        self.conv_ws = dev.conv_workspace(device)
+        # step counters: [coder side, synthesis side] on the device (+ the two ticket words of device.publish_step), their published
+        # values in pinned memory, and how many times the host has submitted each side (what the result worker waits for)
+        self.seq_dev = torch.zeros(4, dtype=torch.int32, device=device)
+        self.pinned_seq = torch.zeros(2, dtype=torch.int32).pin_memory()
+        self.seq_host = self.pinned_seq.numpy()
+        # (tickets, counter, published word) of `device.publish_step`, for the coder side and for the synthesis side
+        self.coder_seq = (self.seq_dev[2:3], self.seq_dev[0:1], self.pinned_seq[0:1])
+        self.synthesis_seq = (self.seq_dev[3:4], self.seq_dev[1:2], self.pinned_seq[1:2])
+        self.counts = [0, 0]
+        self.free = threading.Event()
+        self.free.set()
+        self.pinned_symbols = torch.empty((batch_size, nb_maps, codec.map_size), dtype=torch.int16).pin_memory() if codec.coder == 'host' else None
+        self.staging = None          # device copy of a host batch (made at the slot's first host batch)
+        self.pinned_rec = (torch.empty((batch_size, codec.h_in, codec.w_in), dtype=torch.uint8).pin_memory()
+                           if codec.fetch_reconstruction else None)
+        self.graphs = None           # (graphs, static input, latents, reconstruction) once captured (`BatchCodec._capture_all`)
 
 
 class BatchCodec(object):
@@ -526,15 +596,9 @@ class BatchCodec(object):
         # launch_hook(name, fn): called for every timed launch of the launch-by-launch path with name in ('conv1_gdn1',
         # 'conv2_gdn2', 'conv3', 'latent', 'tconv1_igdn5', 'tconv2_igdn6', 'tconv3', 'coder_encode', 'coder_decode') on the
         # stream the launch goes to (bench.py brackets them with HIP events); it must return fn()
-        self.launch_hook = launch_hook if launch_hook is not None else (lambda name, fn: fn())
+        self.launch_hook = launch_hook if launch_hook is not None else _no_hook
         n_maps = batch_size*self.nb_maps
-        nb_hist = batch_size if self.idx_map_exception >= 0 else 0
         self._n_maps = n_maps
-        # per-slot device block for the host: [coder results 4 x n_maps | exception histograms | overflow | flags | checks(4)]
-        # followed by the squared errors (int64 per image, published on their own once the synthesis transform is through)
-        self._layout = (4*n_maps, nb_hist*(2*self.hist_radius + 1), nb_hist, n_maps, 4)
-        nb_words = sum(self._layout)
-        assert nb_words % 2 == 0
         if nb_in_flight is None:
             nb_in_flight = default_nb_in_flight(h_in, w_in)
         if coder == 'device' and not one_stream_steps and os.environ.get('EAE_IGNORE_HW_QUEUES') != '1':
@@ -557,17 +621,6 @@ class BatchCodec(object):
         else:
             self._streams = _side_streams(nb_in_flight, self.device)
             self._transform_streams = _side_streams(nb_private, self.device, kind='transform')
-        # ... and behind the squared errors one more 64-bit word whose low half is the conv workspace's error word of the step
-        self._slot_all = [torch.zeros(nb_words + 2*batch_size + 2, dtype=torch.int32, device=self.device) for _ in range(self.nb_slots)]
-        self._slot_out = [t[:nb_words] for t in self._slot_all]
-        self._pinned_out = [torch.zeros(nb_words, dtype=torch.int32).pin_memory() for _ in range(self.nb_slots)]
-        self._slot_sse = [t[nb_words:].view(torch.int64) for t in self._slot_all]           # [batch_size] errors + [1] status
-        self._slot_unfinished = [t[nb_words + 2*batch_size:nb_words + 2*batch_size + 1] for t in self._slot_all]
-        self._pinned_sse = [torch.zeros(batch_size + 1, dtype=torch.int64).pin_memory() for _ in range(self.nb_slots)]
-        self._symbols = [torch.empty((batch_size, self.nb_maps, self.map_size), dtype=torch.int16, device=self.device)
-                         for _ in range(self.nb_slots)]
-        self._coder_streams = [dev.CoderStreams(n_maps, self.map_size, self.truncated_unary_length, self.device,
-                                                results=self._views(self._slot_out[i])[0]) for i in range(self.nb_slots)]
         self._coder_behind_tconv1 = (n_maps > 256) if _CODER_BEHIND_TCONV1 is None else _CODER_BEHIND_TCONV1 != '0'
         # one or two images per step: the caller usually waits for each result, and what it waits for last is the coder. The analysis
         # side's blocks (exception-map histograms, dead-map flags, range check) then travel with the synthesis side's publication
@@ -578,51 +631,22 @@ class BatchCodec(object):
         self.coder_chunks = int(default_coder_chunks(n_maps) if coder_chunks is None else coder_chunks)
         if self.coder_chunks > 1 and coder != 'device':
             self.coder_chunks = 1
-        make_workspace = dev.coder_trailing_workspace if self.coder_chunks > 1 else dev.coder_workspace
-        self._workspaces = [make_workspace(n_maps, self.map_size, self.truncated_unary_length, self.device) for _ in range(self.nb_slots)]
-        # scratch that lets the conv GEMM launches cut their last tiles (device.conv_workspace): a slot's launches never overlap each other
-        self._conv_ws = [dev.conv_workspace(self.device) for _ in range(self.nb_slots)]
-        # step counters of every slot: [coder side, synthesis side] on the device (+ the two ticket words of device.publish_step), their
-        # published values in pinned memory, and how many times the host has submitted each side (what the result worker waits for)
-        self._seq_dev = [torch.zeros(4, dtype=torch.int32, device=self.device) for _ in range(self.nb_slots)]
-        self._pinned_seq = [torch.zeros(2, dtype=torch.int32).pin_memory() for _ in range(self.nb_slots)]
-        self._seq_host = [t.numpy() for t in self._pinned_seq]
-        self._counts = [[0, 0] for _ in range(self.nb_slots)]
-        self._slot_free = [threading.Event() for _ in range(self.nb_slots)]
-        for event in self._slot_free:
-            event.set()
-        self._pinned_symbols = [torch.empty((batch_size, self.nb_maps, self.map_size), dtype=torch.int16).pin_memory()
-                                if coder == 'host' else None for _ in range(self.nb_slots)]
+        self._slots = [_Slot(self) for _ in range(self.nb_slots)]
+        self._index = 0
+        self.use_graphs = bool(use_graphs)
+        self._warm = False
+        self._recount_stream = None
+        # host in / host out: a copy stream each way
+        self._feed_stream = None
+        self._fetch_stream = torch.cuda.Stream(device=self.device) if self.fetch_reconstruction else None
+        assert not self.use_graphs or self._transform_streams      # replays never go to the caller's stream
+        # last but one: a constructor that raised above has no worker yet, and `close()` has nothing to wait for
         self._worker = _Worker(self.map_size, self.nb_maps, probabilities if coder == 'host' else None, self.idx_map_exception,
                                host_coder_threads)
         self._worker.start()
-        self._index = 0
-        self.use_graphs = bool(use_graphs)
-        self._graphs = [None]*self.nb_slots          # per slot: (three graphs, static input, latents, reconstruction)
-        self._warm = False
-        self._recount_stream = None
-        # host in / host out: a copy stream each way, a pinned buffer per slot for the reconstructions, device staging for the inputs
-        self._feed_stream = None
-        self._staging = [None]*self.nb_slots
-        self._slot_views = [None]*self.nb_slots      # the views of a slot's pinned result block, made once (graph mode)
-        self._fetch_stream = torch.cuda.Stream(device=self.device) if self.fetch_reconstruction else None
-        self._pinned_rec = [torch.empty((batch_size, h_in, w_in), dtype=torch.uint8).pin_memory() if self.fetch_reconstruction else None
-                            for _ in range(self.nb_slots)]
-        assert not self.use_graphs or self._transform_streams      # replays never go to the caller's stream
         # last: a constructor that raised above leaves nothing half-built behind for another codec's `_capture_all` to drain
         with _LIVE_LOCK:
             _LIVE.setdefault(self.device.index, weakref.WeakSet()).add(self)
-
-    def _views(self, t):
-        out = []
-        pos = 0
-        for count in self._layout:
-            out.append(t[pos:pos + count])
-            pos += count
-        (results, hist, overflow, flags, checks) = out
-        nb_hist = overflow.numel()
-        return (results.view(4, self._n_maps), hist.view(nb_hist, 2*self.hist_radius + 1) if nb_hist else hist, overflow,
-                flags.view(self.batch_size, self.nb_maps), checks)
 
     def submit(self, luminances_uint8):
         """uint8 tensor (batch_size, h_in, w_in), on the device or in PINNED host memory -> Ticket. Everything is enqueued; nothing
@@ -638,7 +662,18 @@ class BatchCodec(object):
         if host and not luminances_uint8.is_pinned():
             raise ValueError('a host batch must be in pinned memory (`torch.Tensor.pin_memory()`): its copy is asynchronous.')
         if self.use_graphs:
-            return self._submit_graph(luminances_uint8)
+            # every slot's graphs are captured at the first call, after one ordinary step that gets every lazy initialisation out of
+            # the way (`_capture_all`), and replayed afterwards
+            if not self._warm:
+                self._submit(luminances_uint8).result()          # first launches: function attributes, lazy module loads
+                try:
+                    self._capture_all(luminances_uint8)
+                except BaseException:
+                    for slot in self._slots:                         # a half-captured set is of no use: the next submit starts over
+                        slot.graphs = None
+                    raise
+                self._warm = True
+            return self._submit(luminances_uint8, replay=True)
         if not self._transform_streams:
             return self._submit(luminances_uint8)
         # small batches leave most of the GPU idle and a step is a chain of short dependent kernels: consecutive batches go
@@ -651,11 +686,11 @@ class BatchCodec(object):
             luminances_uint8.record_stream(stream)
         return ticket
 
-    def _feed(self, host_batch, device_batch, ticket_holder, fresh=False):
-        """Host -> device copy of a pinned batch on the codec's feed stream; the CURRENT stream waits for it. fresh: the
-        destination has just come from the caching allocator, which may have handed out a block that kernels still queued on
-        the current stream use (freed intermediates of the previous steps: safe to reuse in stream order only): the copy
-        then goes behind everything the current stream holds."""
+    def _feed(self, host_batch, device_batch, fresh=False):
+        """Host -> device copy of a pinned batch on the codec's feed stream; the CURRENT stream waits for it. Returns the event
+        recorded behind the copy (`Ticket.fed_event`). fresh: the destination has just come from the caching allocator, which
+        may have handed out a block that kernels still queued on the current stream use (freed intermediates of the previous
+        steps: safe to reuse in stream order only): the copy then goes behind everything the current stream holds."""
         if self._feed_stream is None:
             self._feed_stream = torch.cuda.Stream(device=self.device)
         if fresh:
@@ -665,86 +700,84 @@ class BatchCodec(object):
             fed = torch.cuda.Event()
             fed.record()
         torch.cuda.current_stream().wait_event(fed)
-        ticket_holder.append(fed)
+        return fed
 
-    def _submit_graph(self, luminances_uint8):
-        """One step = three hipGraph launches: the analysis side (conv1 .. symbols) and the synthesis side on a transform
-        stream, the coder on a coder stream between two events, exactly the stream structure of the launch-by-launch path.
-        Slot s owns its buffers (symbols, streams, result blocks), so it owns its three graphs too: all captured at the first
-        call (after one ordinary step that gets every lazy initialisation out of the way: `_capture_all`), replayed afterwards."""
-        if not self._warm:
-            self._submit(luminances_uint8).result()          # first launches: function attributes, lazy module loads
-            try:
-                self._capture_all(luminances_uint8)
-            except BaseException:
-                self._graphs = [None]*self.nb_slots          # a half-captured set is of no use: the next submit starts over
-                raise
-            self._warm = True
-        slot = self._index % self.nb_slots
-        stream = self._transform_streams[self._index % len(self._transform_streams)]
-        coder_stream = self._streams[self._index % len(self._streams)] if self._streams else None
+    def _submit(self, luminances_uint8, replay=False):
+        """One step: claims the next slot, launches the step (`_replay_step` / `_launch_step`), hands its job to the result worker.
+        Which events exist: `coded` / `decoded` are what the worker waits for in the 'events' wait mode; in 'sequence' mode it reads
+        the slot's step counters, and an event is only made for whom it serves (`time_coder`: the launch-by-launch path only; a
+        caller reading the reconstruction on another stream waits for `decoded`)."""
+        index = self._index
         self._index += 1
-        self._slot_free[slot].wait()
-        self._slot_free[slot].clear()
+        slot = self._slots[index % self.nb_slots]
+        slot.free.wait()
+        slot.free.clear()
         sequence_mode = _WAIT_MODE == 'sequence'
-        expected = (self._counts[slot][0] + 1, self._counts[slot][1] + 1)      # what the slot's step counters will show behind this step
+        expected = (slot.counts[0] + 1, slot.counts[1] + 1)      # what the slot's step counters will show behind this step
+        timed = self.time_coder and not replay
         try:
-            caller = torch.cuda.current_stream()
-            if self._graphs[slot] is None:
-                raise RuntimeError('slot {} has no captured graphs (a capture failed earlier)'.format(slot))
-            (graphs, static_input, _, reconstruction) = self._graphs[slot]
-            fed = []
-            # the launch thread's time is what the pipelined small-batch rate is made of: the current stream is switched directly
-            # (`with torch.cuda.stream(...)` costs three device-index resolutions per entry and exit) and restored in the `finally`
-            try:
-                torch.cuda.set_stream(stream)
-                if luminances_uint8.device.type == 'cpu':
-                    self._feed(luminances_uint8, static_input, fed)
-                else:
-                    stream.wait_stream(caller)
-                    static_input.copy_(luminances_uint8, non_blocking=True)
-                graphs[0].replay()
-                (coded, decoded) = (None, None)
-                if self.one_stream_steps:
-                    if not sequence_mode:                     # the whole step is graphs[0]: both of the worker's events behind it
-                        coded = torch.cuda.Event()
-                        coded.record(stream)
-                else:
-                    quantized = torch.cuda.Event()
-                    quantized.record(stream)
-                    torch.cuda.set_stream(coder_stream)
-                    coder_stream.wait_event(quantized)
-                    graphs[1].replay()
-                    if not sequence_mode:
-                        coded = torch.cuda.Event()
-                        coded.record(coder_stream)
-                    torch.cuda.set_stream(stream)
-                    graphs[2].replay()
-                if not sequence_mode or self.keep_reconstruction:      # (a caller reading the reconstruction on another stream waits for it)
-                    decoded = torch.cuda.Event()
-                    decoded.record(stream)
-            finally:
-                torch.cuda.set_stream(caller)
-            if not fed:
-                luminances_uint8.record_stream(stream)
             ticket = Ticket(self.batch_size)
-            ticket.decoded_event = decoded
-            ticket.fed_event = fed[0] if fed else None
+            coded = torch.cuda.Event(enable_timing=timed) if (timed or not sequence_mode) else None
+            if timed:
+                ticket._coder_span = (torch.cuda.Event(enable_timing=True), coded)
+            if not sequence_mode or self.keep_reconstruction:
+                ticket.decoded_event = torch.cuda.Event()
+            reconstruction = (self._replay_step if replay else self._launch_step)(luminances_uint8, slot, index, ticket, coded)
             if self.keep_reconstruction:
-                ticket.reconstruction_uint8 = reconstruction       # valid until this slot is replayed again
-            if self._slot_views[slot] is None:
-                self._slot_views[slot] = self._views(self._pinned_out[slot]) + (self._pinned_sse[slot],)
-            job = _Job(ticket, () if sequence_mode else (coded, decoded), self._slot_views[slot], None,
-                       self._slot_free[slot], lambda: self._recount_exception_maps(slot), self._fetch_job(slot, reconstruction),
-                       (self._seq_host[slot], expected) if sequence_mode else None, self._early_publish)
+                ticket.reconstruction_uint8 = reconstruction       # valid until this slot comes round again
+            job = _Job(ticket, () if sequence_mode else (coded, ticket.decoded_event), slot.host_views, slot.pinned_symbols, slot.free,
+                       lambda: self._recount_exception_maps(slot), self._fetch_job(slot, reconstruction),
+                       (slot.seq_host, expected) if sequence_mode else None, self._early_publish)
             ticket._job = (job, self._worker)
             self._worker.jobs.put(job)
-            self._counts[slot] = list(expected)
+            slot.counts = list(expected)
             return ticket
         except BaseException:
             self._resync(slot)
-            self._slot_free[slot].set()       # nobody will report on this slot: without this, drain() / close() wait for ever
+            slot.free.set()       # nobody will report on this slot: without this, drain() / close() wait for ever
             raise
+
+    def _replay_step(self, luminances_uint8, slot, index, ticket, coded):
+        """One step = three hipGraph launches: the analysis side (conv1 .. symbols) and the synthesis side on a transform
+        stream, the coder on a coder stream between two events, exactly the stream structure of the launch-by-launch path.
+        A slot owns its buffers (symbols, streams, result blocks), so it owns its three graphs too. Records `coded` and the
+        ticket's events where they exist; returns the slot's reconstruction."""
+        stream = self._transform_streams[index % len(self._transform_streams)]
+        coder_stream = self._streams[index % len(self._streams)] if self._streams else None
+        caller = torch.cuda.current_stream()
+        if slot.graphs is None:
+            raise RuntimeError('slot {} has no captured graphs (a capture failed earlier)'.format(index % self.nb_slots))
+        (graphs, static_input, _, reconstruction) = slot.graphs
+        # the launch thread's time is what the pipelined small-batch rate is made of: the current stream is switched directly
+        # (`with torch.cuda.stream(...)` costs three device-index resolutions per entry and exit) and restored in the `finally`
+        try:
+            torch.cuda.set_stream(stream)
+            if luminances_uint8.device.type == 'cpu':
+                ticket.fed_event = self._feed(luminances_uint8, static_input)
+            else:
+                stream.wait_stream(caller)
+                static_input.copy_(luminances_uint8, non_blocking=True)
+            graphs[0].replay()
+            if self.one_stream_steps:
+                if coded is not None:                         # the whole step is graphs[0]: both of the worker's events behind it
+                    coded.record(stream)
+            else:
+                quantized = torch.cuda.Event()
+                quantized.record(stream)
+                torch.cuda.set_stream(coder_stream)
+                coder_stream.wait_event(quantized)
+                graphs[1].replay()
+                if coded is not None:
+                    coded.record(coder_stream)
+                torch.cuda.set_stream(stream)
+                graphs[2].replay()
+            if ticket.decoded_event is not None:
+                ticket.decoded_event.record(stream)
+        finally:
+            torch.cuda.set_stream(caller)
+        if ticket.fed_event is None:
+            luminances_uint8.record_stream(stream)
+        return reconstruction
 
     def _capture_all(self, like):
         """Captures the three graphs of EVERY slot now, while nothing of THIS codec is in flight and its result worker is idle
@@ -761,101 +794,74 @@ class BatchCodec(object):
         for other in others:
             other.drain()
         torch.cuda.synchronize(self.device)
-        for slot in range(self.nb_slots):
+        for (number, slot) in enumerate(self._slots):
             # any of the codec's streams will do for the capture: a replay runs on the stream it is launched into, which
-            # `_submit_graph` picks from the submission index (slots and streams go round at different periods)
-            stream = self._transform_streams[slot % len(self._transform_streams)]
-            coder_stream = self._streams[slot % len(self._streams)] if self._streams else None
+            # `_replay_step` picks from the submission index (slots and streams go round at different periods)
+            stream = self._transform_streams[number % len(self._transform_streams)]
+            coder_stream = self._streams[number % len(self._streams)] if self._streams else None
             static_input = torch.empty(tuple(like.shape), dtype=torch.uint8, device=self.device)      # `like` may be a host batch
             if self.one_stream_steps:
                 graphs = [torch.cuda.CUDAGraph()]
                 with torch.cuda.graph(graphs[0], stream=stream, capture_error_mode='thread_local'):
-                    latents = self._launch_analysis(static_input, slot, None)
-                    reconstruction = self._launch_synthesis(latents, static_input, slot, None)
+                    latents = self._launch_analysis(static_input, slot, _no_hook)
+                    reconstruction = self._launch_synthesis(latents, static_input, slot, _no_hook)
                     self._launch_coder(slot)
-                self._graphs[slot] = (graphs, static_input, latents, reconstruction)
+                slot.graphs = (graphs, static_input, latents, reconstruction)
                 continue
             graphs = [torch.cuda.CUDAGraph() for _ in range(3)]
             with torch.cuda.graph(graphs[0], stream=stream, capture_error_mode='thread_local'):
-                latents = self._launch_analysis(static_input, slot, None)
+                latents = self._launch_analysis(static_input, slot, _no_hook)
                 if self._coder_behind_tconv1:
-                    latents = self._launch_synthesis_head(latents, slot, None)
+                    latents = self._launch_synthesis_head(latents, slot, _no_hook)
             with torch.cuda.graph(graphs[1], stream=coder_stream, capture_error_mode='thread_local'):
                 self._launch_coder(slot)
             with torch.cuda.graph(graphs[2], stream=stream, capture_error_mode='thread_local'):
-                reconstruction = self._launch_synthesis(latents, static_input, slot, None, head_done=self._coder_behind_tconv1)
-            self._graphs[slot] = (graphs, static_input, latents, reconstruction)
+                reconstruction = self._launch_synthesis(latents, static_input, slot, _no_hook, head_done=self._coder_behind_tconv1)
+            slot.graphs = (graphs, static_input, latents, reconstruction)
 
-    def _submit(self, luminances_uint8):
-        slot = self._index % self.nb_slots
-        stream = self._streams[self._index % len(self._streams)] if self._streams else None
-        self._index += 1
-        self._slot_free[slot].wait()
-        self._slot_free[slot].clear()
-        sequence_mode = _WAIT_MODE == 'sequence'
-        expected = (self._counts[slot][0] + 1, self._counts[slot][1] + 1)
-        try:
-            hook = self.launch_hook
-            fed = []
-            if luminances_uint8.device.type == 'cpu':
-                fresh = self._staging[slot] is None
-                if fresh:
-                    self._staging[slot] = torch.empty((self.batch_size, self.h_in, self.w_in), dtype=torch.uint8, device=self.device)
-                self._feed(luminances_uint8, self._staging[slot], fed, fresh)
-                luminances_uint8 = self._staging[slot]
-            latents = self._launch_analysis(luminances_uint8, slot, hook)
-            head_done = self._coder_behind_tconv1 and not self.one_stream_steps
-            if head_done:
-                latents = self._launch_synthesis_head(latents, slot, hook)
-            ticket = Ticket(self.batch_size)
-            if self.one_stream_steps:                          # the coder behind the synthesis transform, on this stream
-                reconstruction = self._launch_synthesis(latents, luminances_uint8, slot, hook)
-            else:
-                quantized = torch.cuda.Event()
-                quantized.record()
-            with (contextlib.nullcontext() if self.one_stream_steps else torch.cuda.stream(stream)):
-                if not self.one_stream_steps:
-                    stream.wait_event(quantized)
-                if self.time_coder:
-                    started = torch.cuda.Event(enable_timing=True)
-                    started.record()
-                self._launch_coder(slot, hook)
-                (coded, decoded) = (None, None)
-                if not sequence_mode or self.time_coder:
-                    coded = torch.cuda.Event(enable_timing=self.time_coder)
-                    coded.record()
-                if self.time_coder:
-                    ticket._coder_span = (started, coded)
+    def _launch_step(self, luminances_uint8, slot, index, ticket, coded):
+        """One step launch by launch: the transforms on the current stream, the coder on a coder stream beside the synthesis
+        transform (`one_stream_steps`: behind it, on the current stream). Records `coded` and the ticket's events where they exist;
+        returns the reconstruction."""
+        hook = self.launch_hook
+        stream = self._streams[index % len(self._streams)] if self._streams else None
+        if luminances_uint8.device.type == 'cpu':
+            fresh = slot.staging is None
+            if fresh:
+                slot.staging = torch.empty((self.batch_size, self.h_in, self.w_in), dtype=torch.uint8, device=self.device)
+            ticket.fed_event = self._feed(luminances_uint8, slot.staging, fresh)
+            luminances_uint8 = slot.staging
+        latents = self._launch_analysis(luminances_uint8, slot, hook)
+        head_done = self._coder_behind_tconv1 and not self.one_stream_steps
+        if head_done:
+            latents = self._launch_synthesis_head(latents, slot, hook)
+        if self.one_stream_steps:                          # the coder behind the synthesis transform, on this stream
+            reconstruction = self._launch_synthesis(latents, luminances_uint8, slot, hook)
+        else:
+            quantized = torch.cuda.Event()
+            quantized.record()
+        with (contextlib.nullcontext() if self.one_stream_steps else torch.cuda.stream(stream)):
             if not self.one_stream_steps:
-                reconstruction = self._launch_synthesis(latents, luminances_uint8, slot, hook, head_done=head_done)
-            if not sequence_mode or self.keep_reconstruction:
-                decoded = torch.cuda.Event()
-                decoded.record()
-            ticket.decoded_event = decoded
-            ticket.fed_event = fed[0] if fed else None
-            if self.keep_reconstruction:
-                ticket.reconstruction_uint8 = reconstruction
-            job = _Job(ticket, () if sequence_mode else (coded, decoded), self._views(self._pinned_out[slot]) + (self._pinned_sse[slot],),
-                       self._pinned_symbols[slot], self._slot_free[slot], lambda: self._recount_exception_maps(slot),
-                       self._fetch_job(slot, reconstruction), (self._seq_host[slot], expected) if sequence_mode else None,
-                       self._early_publish)
-            ticket._job = (job, self._worker)
-            self._worker.jobs.put(job)
-            self._counts[slot] = list(expected)
-            return ticket
-        except BaseException:
-            self._resync(slot)
-            self._slot_free[slot].set()       # as in _submit_graph
-            raise
+                stream.wait_event(quantized)
+            if ticket._coder_span is not None:
+                ticket._coder_span[0].record()
+            self._launch_coder(slot, hook)
+            if coded is not None:
+                coded.record()
+        if not self.one_stream_steps:
+            reconstruction = self._launch_synthesis(latents, luminances_uint8, slot, hook, head_done=head_done)
+        if ticket.decoded_event is not None:
+            ticket.decoded_event.record()
+        return reconstruction
 
     def _resync(self, slot):
         """A submit that raised may have launched some of its step: wait for whatever it did launch and take the slot's step
         counters from the device, so that the next job on this slot waits for the right values."""
         try:
             torch.cuda.synchronize(self.device)
-            self._counts[slot] = [int(v) for v in self._seq_dev[slot][:2].cpu().tolist()]
-            self._seq_dev[slot][2:].zero_()                    # ticket words of a publish that never ran to its end
-            self._slot_all[slot][4*self._n_maps:].zero_()      # accumulators a publish would have cleared
+            slot.counts = [int(v) for v in slot.seq_dev[:2].cpu().tolist()]
+            slot.seq_dev[2:].zero_()                    # ticket words of a publish that never ran to its end
+            slot.block[4*self._n_maps:].zero_()         # accumulators a publish would have cleared
         except Exception:      # the device itself is in trouble: the next submit will say so
             pass
 
@@ -864,7 +870,7 @@ class BatchCodec(object):
         if not self.fetch_reconstruction:
             return None
         reconstruction.record_stream(self._fetch_stream)
-        return (reconstruction, self._pinned_rec[slot], self._fetch_stream)
+        return (reconstruction, slot.pinned_rec, self._fetch_stream)
 
     def _recount_exception_maps(self, slot):
         """Histograms of the slot's exception maps over all of int16, as a host array [batch, 65535] (called by the result
@@ -873,106 +879,92 @@ class BatchCodec(object):
             if self._recount_stream is None:
                 self._recount_stream = torch.cuda.Stream(device=self.device)
             with torch.cuda.stream(self._recount_stream):
-                (hist, overflow) = dev.symbol_histograms(self._symbols[slot].view(self._n_maps, self.map_size), 32767,
-                                                         first_map=self.idx_map_exception, map_step=self.nb_maps)
+                (hist, overflow) = dev.symbol_histograms(slot.symbols_2d, 32767, first_map=self.idx_map_exception, map_step=self.nb_maps)
                 host = hist.cpu().numpy()
                 if int(overflow.sum().item()) != 0:          # -32768: cast_float_to_int16 never produces it (tools.py:95-133)
                     raise RuntimeError('exception-map symbol outside [-32767, 32767]')
         return host
 
-    @staticmethod
-    def _no_hook(name, fn):
-        return fn()
-
     def _launch_analysis(self, luminances_uint8, slot, hook):
         """conv1+GDN1 -> conv2+GDN2 -> conv3 -> latent stage (symbols, dead-map flags, decoder input) -> exception-map
         histograms, on the current stream. Returns the synthesis transform's input."""
-        hook = hook or self._no_hook
         enc = self.encoder
         v = enc.v
         d = self.decoder.v
         gdn_1 = hook('conv1_gdn1', lambda: dev.conv9x9s4_u8(luminances_uint8, enc.w1, v['encoder/biases_1'], enc.g[1], v['encoder/beta_1']))
-        ws = self._conv_ws[slot]
+        ws = slot.conv_ws
         gdn_2 = hook('conv2_gdn2', lambda: dev.conv5x5s2(gdn_1, enc.w2, v['encoder/biases_2'], dev.NORM_GDN, enc.g[2], v['encoder/beta_2'], workspace=ws))
         # (histograms, overflow, flags, checks, squared errors are accumulated into: zero when the slot is made, and zeroed again by the
         # launches that publish them, `_launch_coder` / `_launch_synthesis`)
-        (_, hist, overflow, flags, checks) = self._views(self._slot_out[slot])
         gdn_in = None if self.learned else (enc.g[3], v['encoder/beta_3'])
         igdn_out = None if self.learned else (self.decoder.g[4], d['decoder/beta_4'])
         if self.fuse_latent:
             # conv_3 with the latent stage as its epilogue: one launch, the latents never go through HBM in between
             q = hook('conv3', lambda: dev.conv5x5s2_latent(gdn_2, enc.w3, v['encoder/biases_3'], self.bin_widths, self.map_mean, gdn_in=gdn_in,
-                                                           igdn_out=igdn_out, want_flags=True, out_symbols=self._symbols[slot],
-                                                           out_flags=flags, out_checks=checks[:3], workspace=ws))
+                                                           igdn_out=igdn_out, want_flags=True, out_symbols=slot.symbols,
+                                                           out_flags=slot.flags, out_checks=slot.checks[:3], workspace=ws))
         else:
             y_raw = hook('conv3', lambda: dev.conv5x5s2(gdn_2, enc.w3, v['encoder/biases_3'], dev.NORM_NONE, workspace=ws))
             # gdn_3 -> centre / quantise / symbols / dead-map flags -> de-centre -> inverse_gdn_4: one pass over the latents
             q = hook('latent', lambda: dev.latent_stage(y_raw, self.bin_widths, self.map_mean, gdn_in=gdn_in, igdn_out=igdn_out,
                                                         want_shifted=self.learned, want_symbols=True, want_flags=True,
-                                                        out_symbols=self._symbols[slot], out_flags=flags, out_checks=checks[:3]))
+                                                        out_symbols=slot.symbols, out_flags=slot.flags, out_checks=slot.checks[:3]))
         if self.idx_map_exception >= 0:
-            dev.symbol_histograms(self._symbols[slot].view(self._n_maps, self.map_size), self.hist_radius, out=(hist, overflow),
+            dev.symbol_histograms(slot.symbols_2d, self.hist_radius, out=(slot.hist, slot.overflow),
                                   first_map=self.idx_map_exception, map_step=self.nb_maps, zero=False)
         if self._early_publish:
             # The analysis side's blocks are final here and reach pinned memory at once (the coder's publication, which also zeroes them
             # for the slot's next step, copies them again): in FRONT of the event the coder's stream waits for, so the zeroing cannot
             # overtake this copy. The host looks at them when the synthesis side has reported (`_Worker.process`).
             first = 4*self._n_maps
-            dev.publish_to_host(self._slot_out[slot][first:], self._pinned_out[slot][first:])
+            dev.publish_to_host(slot.out[first:], slot.pinned_out[first:])
         return q['shifted'] if self.learned else q['t']
 
-    def _launch_coder(self, slot, hook=None):
+    def _launch_coder(self, slot, hook=_no_hook):
         """The lossless coder over the slot's symbols (encode every map, decode it back, compare) and the publication of the
         slot's result block, on the current stream."""
-        hook = hook or self._no_hook
-        symbols = self._symbols[slot].view(self._n_maps, self.map_size)
+        symbols = slot.symbols_2d
         if self.coder == 'device' and self.coder_chunks > 1:
             hook('coder_roundtrip', lambda: dev.coder_roundtrip_trailing(symbols, self.probabilities, self.prob_row, self.truncated_unary_length,
-                                                                         chunks=self.coder_chunks, out=self._coder_streams[slot],
-                                                                         workspace=self._workspaces[slot]))
+                                                                         chunks=self.coder_chunks, out=slot.coder_streams, workspace=slot.workspace))
         elif self.coder == 'device':
             hook('coder_encode', lambda: dev.coder_encode_batch(symbols, self.probabilities, self.prob_row, self.truncated_unary_length,
-                                                                out=self._coder_streams[slot], workspace=self._workspaces[slot]))
-            hook('coder_decode', lambda: dev.coder_decode_batch(self._coder_streams[slot], self.probabilities, self.prob_row,
-                                                                expected=symbols, workspace=self._workspaces[slot]))
+                                                                out=slot.coder_streams, workspace=slot.workspace))
+            hook('coder_decode', lambda: dev.coder_decode_batch(slot.coder_streams, self.probabilities, self.prob_row, expected=symbols,
+                                                                workspace=slot.workspace))
         elif self.coder == 'host':
-            self._pinned_symbols[slot].copy_(self._symbols[slot], non_blocking=True)
+            slot.pinned_symbols.copy_(slot.symbols, non_blocking=True)
         else:
-            self._views(self._slot_out[slot])[0].zero_()
-        seq = self._seq_dev[slot]
-        dev.publish_step(self._slot_out[slot], self._pinned_out[slot], 4*self._n_maps, seq[2:3], seq[0:1], self._pinned_seq[slot][0:1])
+            slot.results.zero_()
+        dev.publish_step(slot.out, slot.pinned_out, 4*self._n_maps, *slot.coder_seq)
 
     def _launch_synthesis_head(self, latents, slot, hook):
         """tconv1+IGDN5 on the current stream (the first launch of the synthesis side, apart: `_coder_behind_tconv1`)."""
-        hook = hook or self._no_hook
         dec = self.decoder
         d = dec.v
         return hook('tconv1_igdn5', lambda: dev.tconv5x5s2(latents, dec.w4, d['decoder/biases_4'], dev.NORM_IGDN, dec.g[5], d['decoder/beta_5'],
-                                                           workspace=self._conv_ws[slot]))
+                                                           workspace=slot.conv_ws))
 
     def _launch_synthesis(self, latents, luminances_uint8, slot, hook, head_done=False):
         """tconv1+IGDN5 -> tconv2+IGDN6 -> tconv3 + BT.601 cast + squared error against the input, and the publication of the
         squared errors, on the current stream. Returns the uint8 reconstruction. head_done: `latents` is already tconv1's output."""
-        hook = hook or self._no_hook
         dec = self.decoder
         d = dec.v
-        ws = self._conv_ws[slot]
+        ws = slot.conv_ws
         t = latents if head_done else self._launch_synthesis_head(latents, slot, hook)
         t = hook('tconv2_igdn6', lambda: dev.tconv5x5s2(t, dec.w5, d['decoder/biases_5'], dev.NORM_IGDN, dec.g[6], d['decoder/beta_6'], workspace=ws))
         (_, reconstruction, _) = hook('tconv3', lambda: dev.tconv9x9s4_luma(t, dec.w6, want_f32=False, want_u8=True, ref_u8=luminances_uint8,
-                                                                            sse=self._slot_sse[slot][:self.batch_size]))
+                                                                            sse=slot.sse[:self.batch_size]))
         # every conv launch of this step (analysis side too: same stream, same workspace) is behind us: its error word, and a
         # clean workspace for the slot's next step
-        seq = self._seq_dev[slot]
-        dev.publish_step(self._slot_sse[slot], self._pinned_sse[slot], 0, seq[3:4], seq[1:2], self._pinned_seq[slot][1:2],
-                         conv_ws=ws, error_word=self._slot_unfinished[slot])
+        dev.publish_step(slot.sse, slot.pinned_sse, 0, *slot.synthesis_seq, conv_ws=ws, error_word=slot.unfinished)
         return reconstruction
 
     def drain(self):
         """Waits until every submitted batch is through."""
         torch.cuda.synchronize(self.device)
-        for event in self._slot_free:
-            event.wait()
+        for slot in self._slots:
+            slot.free.wait()
 
     def close(self):
         """Waits for the pending batches (whether or not their tickets failed) and joins the result worker: a worker still

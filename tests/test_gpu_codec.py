@@ -151,7 +151,7 @@ def test_batch_codec_graph_replay_equals_the_launch_by_launch_path(learned, stre
     t = graphed.submit(images[8:10])
     t.result()
     assert numpy.array_equal(t.reconstruction_uint8.cpu().numpy(), expected[4][1])
-    assert all(g is not None for g in graphed._graphs)
+    assert all(s.graphs is not None for s in graphed._slots)
     graphed.close()
     with pytest.raises(ValueError):
         codec.BatchCodec(v, learned, bin_widths, map_mean, probabilities, 67, 2, 64, 96, coder='host', use_graphs=True)
