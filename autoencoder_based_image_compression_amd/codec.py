@@ -30,6 +30,7 @@ import weakref
 import numpy
 import torch
 
+from . import container as container_format
 from . import device as dev
 from . import pipeline
 from .kodak.eae.graph import constants as csts
@@ -136,6 +137,7 @@ class Ticket(object):
         #                                       stream before reading `reconstruction_uint8` there (valid until the slot comes round again)
         self._coder_span = None               # (start, stop) timing events on the coder stream (BatchCodec(time_coder=True))
         self._job = None                      # (_Job, _Worker) until somebody has started on the step's results
+        self._container_parts = None          # with BatchCodec(emit_container=True): what `container()` is assembled from, owned by the ticket
 
     def coder_ms(self):
         """Milliseconds the coder launches of this batch took on their stream (from the moment the symbols were ready to the
@@ -161,6 +163,37 @@ class Ticket(object):
             raise self._error
         return self._values
 
+    def _parts(self):
+        self.result()
+        parts = self._container_parts
+        if parts is None:
+            raise RuntimeError('the codec was not built with emit_container=True')
+        if parts['error'] is not None:
+            raise parts['error']
+        if parts['payload'] is None:
+            raise ContainerOverflow('the payload of this step takes {0} bytes, the codec holds {1} per step '
+                                    '(BatchCodec(container_capacity_bytes=...))'.format(parts['payload_bytes'], parts['capacity']))
+        return parts
+
+    def container(self):
+        """Blocks like `result()` (and raises the step's error like it); the batch as one `EAE1` blob (container.py), the bytes
+        `container.encode_images` gives for the same images. The codec has decoded every stream in it and compared the symbols.
+        Raises `ContainerOverflow` when the payload did not fit `container_capacity_bytes`. Only with
+        `BatchCodec(emit_container=True)`; before or after `result()`."""
+        parts = self._parts()
+        return container_format.assemble_blob(*(parts['head'] + (parts['rows'], parts['bits'], parts['payload'])))[0]
+
+    def image_containers(self):
+        """Like `container()`: one single-image `EAE1` blob per image of the batch (the payload is image-major: slices of the
+        batch's, each behind its own header)."""
+        parts = self._parts()
+        return container_format.assemble_image_blobs(*(parts['head'] + (parts['rows'], parts['bits'], parts['payload'])))
+
+
+class ContainerOverflow(RuntimeError):
+    """The coded payload of a step is larger than the codec's `container_capacity_bytes`: the step's results stand, its container
+    was not produced."""
+
 
 class StepTimeout(RuntimeError):
     """The device did not report a submitted step within EAE_WORKER_SEQUENCE_TIMEOUT_SECONDS: the codec is unusable from here on."""
@@ -174,10 +207,12 @@ class _Job(object):
     `BatchCodec._recount_exception_maps` of the slot; fetch: `BatchCodec._fetch_job` or None; sequence: (the slot's step counters in
     pinned memory, the values this step leaves there) or None; early_published: the synthesis side's publication carried the
     analysis side's blocks too (exception-map histograms, dead-map flags, range check): small steps, whose caller waits for each
-    result -- `BatchCodec._early_publish`."""
-    __slots__ = ('ticket', 'events', 'views', 'symbols_host', 'slot_free', 'recount', 'fetch', 'sequence', 'early_published', '_claimed')
+    result -- `BatchCodec._early_publish`; emit: with `emit_container`, (the blob's fixed parts, capacity, the slot's pinned payload,
+    exception rows and index words as host arrays), else None."""
+    __slots__ = ('ticket', 'events', 'views', 'symbols_host', 'slot_free', 'recount', 'fetch', 'sequence', 'early_published', 'emit',
+                 '_claimed')
 
-    def __init__(self, ticket, events, views, symbols_host, slot_free, recount, fetch, sequence, early_published=False):
+    def __init__(self, ticket, events, views, symbols_host, slot_free, recount, fetch, sequence, early_published=False, emit=None):
         self.ticket = ticket
         self.events = events
         self.views = views
@@ -187,6 +222,7 @@ class _Job(object):
         self.fetch = fetch
         self.sequence = sequence
         self.early_published = bool(early_published)
+        self.emit = emit
         self._claimed = threading.Lock()
 
     def claim(self):
@@ -301,6 +337,21 @@ class _Worker(threading.Thread):
             if job.claim():          # (else the caller's `Ticket.result()` got there first and does it itself)
                 self.process(job)
 
+    def _exception_map_error(self, results):
+        """The exception the first failed exception map of a step stands for, or None."""
+        exception_maps = numpy.arange(self.idx_map_exception, results.shape[1], self.nb_maps)
+        bad = exception_maps[results[2, exception_maps] != 0]
+        if bad.size == 0:
+            return None
+        if int(results[2, bad[0]]) == 6:
+            return AssertionError('\nArrays are not equal\nThe lossless compression has altered the centered quantized data.')
+        from .kodak.lossless import interface_cython
+        try:
+            interface_cython.raise_for_status(int(results[2, bad[0]]), int(results[3, bad[0]]))
+        except Exception as exc:
+            return exc
+        return None
+
     def process(self, job, by_caller=False):
         """Waits until the device is through with the step, then forms the ticket's results from the slot's pinned blocks (or the
         exception `result()` raises), frees the slot. On the worker thread, or on the caller's (`Ticket.result()`)."""
@@ -364,8 +415,17 @@ class _Worker(threading.Thread):
                                                                        roundtrip=True, verify_only=True)
                 results = numpy.zeros_like(results)
                 results[0] = nb_bits.reshape(-1)
-            if results[2].any():
-                bad = int(numpy.flatnonzero(results[2])[0])
+            status = results[2]
+            exception_coded = job.emit is not None and self.idx_map_exception >= 0
+            container_error = None
+            if exception_coded:
+                # the exception maps are coded for the container only: the step's results are those of a codec that leaves them
+                # out, so a failure of theirs is the container's (`Ticket.container()` raises it)
+                status = status.copy()
+                status[self.idx_map_exception::self.nb_maps] = 0
+                container_error = self._exception_map_error(results)
+            if status.any():
+                bad = int(numpy.flatnonzero(status)[0])
                 if int(results[2, bad]) == 6:
                     raise AssertionError('\nArrays are not equal\nThe lossless compression has altered the centered quantized data.')
                 from .kodak.lossless import interface_cython
@@ -375,10 +435,23 @@ class _Worker(threading.Thread):
             if 'error' in early:
                 raise early['error']
             n = ticket.nb_images
-            coder_bits = (results[0].astype(numpy.int64) + results[1].astype(numpy.int64)).reshape(n, self.nb_maps).sum(axis=1)
+            map_bits = (results[0].astype(numpy.int64) + results[1].astype(numpy.int64)).reshape(n, self.nb_maps)
+            if exception_coded:
+                map_bits[:, self.idx_map_exception] = 0          # charged by its entropy, as without `emit_container`
+            coder_bits = map_bits.sum(axis=1)
             exception_bits = early['exception_bits']
             ticket._values = {'nb_bits': coder_bits + exception_bits, 'coder_bits': coder_bits,
                               'exception_bits': exception_bits, 'sse': early['sse'], 'nb_deads': early['nb_deads']}
+            if job.emit is not None:
+                # out of the slot's pinned buffers into objects the ticket owns, while the slot is still this step's
+                (head, capacity, payload, rows, index) = job.emit
+                payload_bytes = int(index[0])
+                ticket._values['container_bytes'] = index[2:].astype(numpy.int64)
+                ticket._container_parts = {
+                    'head': head, 'capacity': capacity, 'payload_bytes': payload_bytes, 'error': container_error,
+                    'rows': rows.copy() if self.idx_map_exception >= 0 else rows[:0].copy(),
+                    'bits': numpy.stack([results[0], results[1]], axis=1).astype(numpy.uint32),
+                    'payload': payload[:payload_bytes].tobytes() if int(index[1]) == 0 else None}
         except StepTimeout as exc:    # nothing says the device is through with this slot: no later submit may reuse it
             self.failed = exc
             ticket._error = exc
@@ -465,7 +538,8 @@ class _Slot(object):
     """Everything one step in flight owns; `BatchCodec` goes round `nb_slots` of them. Made once: no launch and no submit cuts a view."""
     __slots__ = ('block', 'out', 'results', 'hist', 'overflow', 'flags', 'checks', 'sse', 'unfinished', 'pinned_out', 'pinned_sse',
                  'host_views', 'symbols', 'symbols_2d', 'coder_streams', 'workspace', 'conv_ws', 'seq_dev', 'pinned_seq', 'seq_host',
-                 'coder_seq', 'synthesis_seq', 'counts', 'free', 'pinned_symbols', 'staging', 'pinned_rec', 'graphs')
+                 'coder_seq', 'synthesis_seq', 'counts', 'free', 'pinned_symbols', 'staging', 'pinned_rec', 'graphs', 'table', 'exception_rows',
+                 'index', 'payload_bytes', 'offsets', 'payload', 'pinned_payload', 'emit_tail', 'pinned_emit', 'emit_host')
 
     def __init__(self, codec):
         (batch_size, nb_maps, device) = (codec.batch_size, codec.nb_maps, codec.device)
@@ -515,6 +589,26 @@ class _Slot(object):
         self.pinned_rec = (torch.empty((batch_size, codec.h_in, codec.w_in), dtype=torch.uint8).pin_memory()
                            if codec.fetch_reconstruction else None)
         self.graphs = None           # (graphs, static input, latents, reconstruction) once captured (`BatchCodec._capture_all`)
+        self.emit_host = None
+        if codec.emit_container:
+            # One float64 block: [the codec's probability table | one row per image for its exception map | index words (int64: payload
+            # bytes, overflow flag, bytes per image)]. The coder reads the first two parts as its table; the last two go to the host.
+            length = codec.truncated_unary_length
+            (table_words, row_words) = (nb_maps*length, batch_size*length)
+            block = torch.zeros(table_words + row_words + 2 + batch_size, dtype=torch.float64, device=device)
+            self.table = block[:table_words + row_words].view(nb_maps + batch_size, length)
+            self.table[:nb_maps].copy_(codec.probabilities)
+            self.exception_rows = self.table[nb_maps:]
+            self.index = block[table_words + row_words:].view(torch.int64)
+            self.payload_bytes = self.index[0:1]
+            self.emit_tail = block[table_words:]
+            self.pinned_emit = torch.zeros(row_words + 2 + batch_size, dtype=torch.float64).pin_memory()
+            self.offsets = torch.zeros((n_maps, 2), dtype=torch.int64, device=device)
+            self.payload = torch.zeros(codec.container_capacity_bytes, dtype=torch.uint8, device=device)
+            self.pinned_payload = torch.zeros(codec.container_capacity_bytes, dtype=torch.uint8).pin_memory()
+            # what the result worker copies from (`_Job.emit`)
+            self.emit_host = (codec._container_head, codec.container_capacity_bytes, self.pinned_payload.numpy(),
+                              self.pinned_emit[:row_words].view(batch_size, length).numpy(), self.pinned_emit[row_words:].view(torch.int64).numpy())
 
 
 class BatchCodec(object):
@@ -523,7 +617,8 @@ class BatchCodec(object):
     def __init__(self, variables, are_bin_widths_learned, bin_widths_test, map_mean, binary_probabilities, idx_map_exception,
                  batch_size, h_in, w_in, device='cuda', nb_in_flight=None, keep_reconstruction=False, launch_hook=None,
                  coder='device', host_coder_threads=0, hist_radius=2047, nb_transform_streams=1, use_graphs=False,
-                 time_coder=False, fuse_latent=False, fetch_reconstruction=False, coder_chunks=None, one_stream_steps=False):
+                 time_coder=False, fuse_latent=False, fetch_reconstruction=False, coder_chunks=None, one_stream_steps=False,
+                 emit_container=False, container_capacity_bytes=None):
         """coder: 'device' (the coder kernels on side streams), 'host' (ONE device -> host copy of the symbols per batch, then
         the host C-ABI coder `eae_coder_compress_maps` on `host_coder_threads` threads: the shape BASELINE.json sketches) or
         'none' (transforms only; the bit counts come back as zeros).
@@ -552,7 +647,15 @@ class BatchCodec(object):
         hist_radius: the exception map's entropy is formed from an exact histogram of its symbols over [-hist_radius,
         hist_radius]; when a symbol falls outside, the result worker counts that batch's exception maps again over the whole
         int16 range (like the image-by-image functions of `kodak/`; the reference's histogram has no bound,
-        lossless/compression.py:68-75)."""
+        lossless/compression.py:68-75).
+        emit_container: every step also leaves its `EAE1` container (container.py) with the ticket: `Ticket.container()`,
+        `Ticket.image_containers()`, and 'container_bytes' per image in `result()`; everything else `result()` returns is what the
+        same codec without it returns. The offsets, the packing and the exception maps' probability rows are formed on the device,
+        behind the coder's launches and in front of the publication of its results; the exception map is then
+        coded too (with a row measured on it, as `container.encode_images` does), which needs `hist_radius >= L`. Needs the device coder.
+        container_capacity_bytes: the payload bytes a step may take (rounded up to 16; a device and a pinned buffer of that size per
+        slot). None: batch_size*h_in*w_in, i.e. 8 bits per pixel. A step beyond it keeps its results; its `Ticket.container()` raises
+        `ContainerOverflow`."""
         if coder not in ('device', 'host', 'none'):
             raise ValueError('`coder` is neither "device" nor "host" nor "none".')
         if use_graphs and coder == 'host':
@@ -579,13 +682,34 @@ class BatchCodec(object):
         self.truncated_unary_length = probabilities.shape[1]
         if self.truncated_unary_length > 255:
             raise OverflowError('value too large to convert to numpy.uint8_t')   # interface_cython.pyx:49
-        self.bin_widths = torch.from_numpy(numpy.ascontiguousarray(bin_widths_test, dtype=numpy.float32)).to(self.device)
-        self.map_mean = torch.from_numpy(numpy.ascontiguousarray(map_mean, dtype=numpy.float32)).to(self.device)
+        self.emit_container = bool(emit_container)
+        if self.emit_container and coder != 'device':
+            raise ValueError('`emit_container` needs the coder on the device: the container is made of its streams.')
+        if self.emit_container and self.idx_map_exception >= 0 and int(hist_radius) < self.truncated_unary_length:
+            raise ValueError('`emit_container` with an exception map needs `hist_radius` >= the truncated unary length: the map\'s '
+                             'probability row is formed from its histogram.')
+        if container_capacity_bytes is None:
+            container_capacity_bytes = batch_size*h_in*w_in
+        self.container_capacity_bytes = max(16, -(-int(container_capacity_bytes)//16)*16)
+        bin_widths_host = numpy.ascontiguousarray(bin_widths_test, dtype=numpy.float32)
+        map_mean_host = numpy.ascontiguousarray(map_mean, dtype=numpy.float32)
+        # the parts of a step's container that no step changes (container.assemble_blob's leading arguments)
+        self._container_head = (bool(are_bin_widths_learned), batch_size, h_in, w_in, self.idx_map_exception, bin_widths_host.copy(),
+                                map_mean_host.copy(), probabilities.copy())
+        self.bin_widths = torch.from_numpy(bin_widths_host).to(self.device)
+        self.map_mean = torch.from_numpy(map_mean_host).to(self.device)
         self.probabilities = torch.from_numpy(probabilities).to(self.device)
         prob_row = torch.arange(self.nb_maps, dtype=torch.int32).repeat(batch_size)
         if self.idx_map_exception >= 0:
             prob_row[self.idx_map_exception::self.nb_maps] = -1        # costed from its histogram (compression.py:68-75)
         self.prob_row = prob_row.to(self.device)
+        self._emit_prob_row = None
+        if self.emit_container:
+            # image i's exception map is coded with row nb_maps + i of the slot's table (`_Slot.exception_rows`)
+            emit_prob_row = torch.arange(self.nb_maps, dtype=torch.int32).repeat(batch_size)
+            if self.idx_map_exception >= 0:
+                emit_prob_row[self.idx_map_exception::self.nb_maps] = self.nb_maps + torch.arange(batch_size, dtype=torch.int32)
+            self._emit_prob_row = emit_prob_row.to(self.device)
         self.fetch_reconstruction = bool(fetch_reconstruction)
         self.keep_reconstruction = bool(keep_reconstruction) or self.fetch_reconstruction
         self.hist_radius = int(hist_radius)
@@ -727,7 +851,7 @@ class BatchCodec(object):
                 ticket.reconstruction_uint8 = reconstruction       # valid until this slot comes round again
             job = _Job(ticket, () if sequence_mode else (coded, ticket.decoded_event), slot.host_views, slot.pinned_symbols, slot.free,
                        lambda: self._recount_exception_maps(slot), self._fetch_job(slot, reconstruction),
-                       (slot.seq_host, expected) if sequence_mode else None, self._early_publish)
+                       (slot.seq_host, expected) if sequence_mode else None, self._early_publish, slot.emit_host)
             ticket._job = (job, self._worker)
             self._worker.jobs.put(job)
             slot.counts = list(expected)
@@ -924,18 +1048,31 @@ class BatchCodec(object):
         """The lossless coder over the slot's symbols (encode every map, decode it back, compare) and the publication of the
         slot's result block, on the current stream."""
         symbols = slot.symbols_2d
+        (table, prob_row) = (self.probabilities, self.prob_row)
+        if self.emit_container:
+            (table, prob_row) = (slot.table, self._emit_prob_row)
+            if self.idx_map_exception >= 0:
+                # the histograms are final since the analysis side and are zeroed only by this side's `publish_step` below
+                dev.exception_rows(slot.hist, slot.overflow, self.map_size, self.truncated_unary_length, out=slot.exception_rows)
         if self.coder == 'device' and self.coder_chunks > 1:
-            hook('coder_roundtrip', lambda: dev.coder_roundtrip_trailing(symbols, self.probabilities, self.prob_row, self.truncated_unary_length,
+            hook('coder_roundtrip', lambda: dev.coder_roundtrip_trailing(symbols, table, prob_row, self.truncated_unary_length,
                                                                          chunks=self.coder_chunks, out=slot.coder_streams, workspace=slot.workspace))
         elif self.coder == 'device':
-            hook('coder_encode', lambda: dev.coder_encode_batch(symbols, self.probabilities, self.prob_row, self.truncated_unary_length,
+            hook('coder_encode', lambda: dev.coder_encode_batch(symbols, table, prob_row, self.truncated_unary_length,
                                                                 out=slot.coder_streams, workspace=slot.workspace))
-            hook('coder_decode', lambda: dev.coder_decode_batch(slot.coder_streams, self.probabilities, self.prob_row, expected=symbols,
+            hook('coder_decode', lambda: dev.coder_decode_batch(slot.coder_streams, table, prob_row, expected=symbols,
                                                                 workspace=slot.workspace))
         elif self.coder == 'host':
             slot.pinned_symbols.copy_(slot.symbols, non_blocking=True)
         else:
             slot.results.zero_()
+        if self.emit_container:
+            # offsets and sizes from the bit counts, the streams packed, the packed bytes and the index words into pinned memory: all in
+            # front of the step counter's publication, so whoever sees the counter finds the payload on the host
+            dev.coder_index_streams(slot.coder_streams, self.nb_maps, self.container_capacity_bytes, offsets=slot.offsets, index=slot.index)
+            dev.coder_pack_indexed(slot.coder_streams, slot.offsets, slot.index, slot.payload)
+            dev.publish_prefix(slot.payload, slot.pinned_payload, slot.payload_bytes)
+            dev.publish_to_host(slot.emit_tail, slot.pinned_emit)
         dev.publish_step(slot.out, slot.pinned_out, 4*self._n_maps, *slot.coder_seq)
 
     def _launch_synthesis_head(self, latents, slot, hook):

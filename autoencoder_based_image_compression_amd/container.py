@@ -88,6 +88,46 @@ def _raise_for_statuses(results):
         interface_cython.raise_for_status(int(results[2, bad[0]]), int(results[3, bad[0]]))
 
 
+def assemble_blob(are_bin_widths_learned, nb_images, height, width, idx_map_exception, bin_widths, map_mean, binary_probabilities,
+                  exception_rows, bits, payload):
+    """The EAE1 blob (module docstring) from its parts -> (blob bytes, header bytes). bin_widths / map_mean float32 [nb_maps],
+    binary_probabilities float64 [nb_maps, L], exception_rows float64 [nb_images, L] ([0, L] without an exception map), bits
+    uint32 [nb_images*nb_maps, 2], payload bytes-like. What `encode_images` ends with, and what a `codec.Ticket` builds its
+    containers with from the pinned blocks of its step."""
+    (nb_maps, truncated_unary_length) = binary_probabilities.shape
+    nb_rows = nb_images if idx_map_exception >= 0 else 0
+    if bin_widths.dtype != numpy.float32 or map_mean.dtype != numpy.float32 or bin_widths.shape != (nb_maps,) or map_mean.shape != (nb_maps,):
+        raise ValueError('`bin_widths` and `map_mean` must be float32 with one element per map.')
+    if binary_probabilities.dtype != numpy.float64 or exception_rows.dtype != numpy.float64 or bits.dtype != numpy.uint32:
+        raise ValueError('The probabilities must be float64 and the bit counts uint32.')
+    if exception_rows.shape != (nb_rows, truncated_unary_length) or bits.shape != (nb_images*nb_maps, 2):
+        raise ValueError('The exception rows or the bit counts do not have the shape the header announces.')
+    if len(payload) != int(((bits.astype(numpy.int64) + 7)//8).sum()):
+        raise ValueError('The payload size does not match the bit counts.')
+    head = _HEADER.pack(MAGIC, VERSION, 1 if are_bin_widths_learned else 0, nb_images, height, width, nb_maps, truncated_unary_length, 0,
+                        idx_map_exception)
+    pieces = [head, bin_widths.tobytes(), map_mean.tobytes(), binary_probabilities.tobytes(), exception_rows.tobytes(), bits.tobytes()]
+    header_bytes = sum(len(piece) for piece in pieces)
+    pieces.append(bytes(payload))
+    return (b''.join(pieces), header_bytes)
+
+
+def assemble_image_blobs(are_bin_widths_learned, nb_images, height, width, idx_map_exception, bin_widths, map_mean, binary_probabilities,
+                         exception_rows, bits, payload):
+    """The parts of a batch's blob (`assemble_blob`) -> one single-image blob per image: the payload is image-major, so an image's
+    blob is its slice of the bit counts, of the exception rows and of the payload behind a header of its own."""
+    nb_maps = binary_probabilities.shape[0]
+    image_bytes = ((bits.astype(numpy.int64) + 7)//8).reshape(nb_images, -1).sum(axis=1)
+    stops = numpy.cumsum(image_bytes)
+    view = memoryview(payload)
+    blobs = []
+    for i in range(nb_images):
+        rows = exception_rows[i:i + 1] if idx_map_exception >= 0 else exception_rows
+        blobs.append(assemble_blob(are_bin_widths_learned, 1, height, width, idx_map_exception, bin_widths, map_mean, binary_probabilities,
+                                   rows, bits[i*nb_maps:(i + 1)*nb_maps], view[int(stops[i] - image_bytes[i]):int(stops[i])])[0])
+    return blobs
+
+
 def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_probabilities, idx_map_exception=-1, tile=None,
                   coding_tile=None, tiles_per_call=64):
     """uint8 (N, H, W) or (N, H, W, 1) luminance images -> (blob bytes, info dict).
@@ -147,11 +187,8 @@ def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_p
     offsets = numpy.concatenate([[0], numpy.cumsum(nbytes.reshape(-1))[:-1]]).astype(numpy.int64).reshape(n_maps, 2)
     payload_bytes = int(nbytes.sum())
     payload = dev.coder_pack_streams(streams, torch.from_numpy(offsets).to(device), payload_bytes)
-    head = _HEADER.pack(MAGIC, VERSION, 1 if encoder.are_bin_widths_learned else 0, nb_images, height, width, nb_maps,
-                        truncated_unary_length, 0, idx_map_exception)
-    pieces = [head, bin_widths.tobytes(), mean.tobytes(), probabilities.tobytes(), exception_rows.tobytes(), bits.tobytes()]
-    header_bytes = sum(len(piece) for piece in pieces)
-    blob = b''.join(pieces) + payload[:payload_bytes].cpu().numpy().tobytes()
+    (blob, header_bytes) = assemble_blob(encoder.are_bin_widths_learned, nb_images, height, width, idx_map_exception, bin_widths, mean,
+                                         probabilities, exception_rows, bits, payload[:payload_bytes].cpu().numpy().tobytes())
     info = {'nb_bits': (bits[:, 0] + bits[:, 1]).reshape(nb_images, nb_maps), 'payload_bytes': payload_bytes,
             'header_bytes': header_bytes}
     return (blob, info)

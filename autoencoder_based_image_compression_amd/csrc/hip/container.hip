@@ -12,10 +12,13 @@ namespace {
 // offsets[2m], offsets[2m + 1]: byte offsets of the two pieces in the payload. A piece never exceeds its half of the
 // region: bit counts come from an untrusted header when unpacking, so the copy is clamped to stride / 2 bytes (the host
 // side rejects such a header before it gets here, container.read_header).
+// index: nullptr, or the index words of eae_hip_coder_index_streams (codec_container.hip): with their overflow flag set the
+// payload buffer is too small for the offsets, and nothing is copied.
 template <bool PACK>
 __global__ __launch_bounds__(64) void move_streams_kernel(uint8_t* __restrict__ streams, uint64_t stride, uint8_t* __restrict__ payload,
                                                           const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ bac_bits,
-                                                          const uint32_t* __restrict__ bypass_bits) {
+                                                          const uint32_t* __restrict__ bypass_bits, const uint64_t* __restrict__ index) {
+    if (index != nullptr && index[1] != 0u) return;
     const uint32_t m = blockIdx.x;
     for (int piece = 0; piece < 2; ++piece) {
         uint64_t bytes = ((uint64_t)(piece ? bypass_bits[m] : bac_bits[m]) + 7u) >> 3;
@@ -65,7 +68,17 @@ extern "C" int eae_hip_coder_pack_streams(uint32_t n_maps, const uint8_t* stream
     if (!streams || !bac_bits || !bypass_bits || !offsets || !payload) return EAE_HIP_BAD_ARGUMENT;
     if (n_maps == 0) return EAE_HIP_OK;
     hipLaunchKernelGGL(move_streams_kernel<true>, dim3(n_maps), dim3(64), 0, (hipStream_t)stream, const_cast<uint8_t*>(streams),
-                       stride, payload, offsets, bac_bits, bypass_bits);
+                       stride, payload, offsets, bac_bits, bypass_bits, (const uint64_t*)nullptr);
+    EAE_HIP_CHECK_LAUNCH();
+    return EAE_HIP_OK;
+}
+
+extern "C" int eae_hip_coder_pack_indexed(uint32_t n_maps, const uint8_t* streams, uint64_t stride, const uint32_t* bac_bits,
+                                          const uint32_t* bypass_bits, const uint64_t* offsets, const uint64_t* index, uint8_t* payload,
+                                          void* stream) {
+    if (!streams || !bac_bits || !bypass_bits || !offsets || !index || !payload || n_maps == 0 || stride < 2) return EAE_HIP_BAD_ARGUMENT;
+    hipLaunchKernelGGL(move_streams_kernel<true>, dim3(n_maps), dim3(64), 0, (hipStream_t)stream, const_cast<uint8_t*>(streams),
+                       stride, payload, offsets, bac_bits, bypass_bits, index);
     EAE_HIP_CHECK_LAUNCH();
     return EAE_HIP_OK;
 }
@@ -76,7 +89,7 @@ extern "C" int eae_hip_coder_unpack_streams(uint32_t n_maps, const uint8_t* payl
     if (!streams || !bac_bits || !bypass_bits || !offsets || !payload || stride < 2) return EAE_HIP_BAD_ARGUMENT;
     if (n_maps == 0) return EAE_HIP_OK;
     hipLaunchKernelGGL(move_streams_kernel<false>, dim3(n_maps), dim3(64), 0, (hipStream_t)stream, streams, stride,
-                       const_cast<uint8_t*>(payload), offsets, bac_bits, bypass_bits);
+                       const_cast<uint8_t*>(payload), offsets, bac_bits, bypass_bits, (const uint64_t*)nullptr);
     EAE_HIP_CHECK_LAUNCH();
     return EAE_HIP_OK;
 }

@@ -816,6 +816,69 @@ def dequantize_maps(symbols_planar, bin_widths, map_mean=None, want_cq=False, wa
     return {'cq': cq, 'shifted': shifted}
 
 
+# ---- containers from the pipelined codec (include/eae_hip.h, csrc/hip/codec_container.hip) -----------------------------------
+# No argument of these four depends on a result of the step, so they can be captured into the coder's hipGraph.
+
+def coder_index_streams(streams, maps_per_image, capacity_bytes, offsets=None, index=None):
+    """Byte offsets of every stream piece of `streams` (CoderStreams) in the payload, and the index words, from the bit counts on
+    the device: -> (offsets int64 [n_maps, 2], index int64 [2 + n_maps/maps_per_image]: total bytes, 1 when the total exceeds
+    `capacity_bytes`, then the bytes of every image). `offsets` / `index`: preallocated outputs. Only the bit counts are read:
+    of `streams`, n_maps, stride, bac_bits and bypass_bits are used."""
+    n_maps = streams.n_maps
+    device = streams.bac_bits.device
+    if maps_per_image < 1 or n_maps % maps_per_image != 0:
+        raise HipError('`n_maps` is not a multiple of `maps_per_image`')
+    if offsets is None:
+        offsets = torch.empty((n_maps, 2), dtype=torch.int64, device=device)
+    if index is None:
+        index = torch.empty(2 + n_maps//maps_per_image, dtype=torch.int64, device=device)
+    if offsets.dtype != torch.int64 or offsets.numel() != 2*n_maps or index.dtype != torch.int64 or index.numel() != 2 + n_maps//maps_per_image:
+        raise HipError('`offsets` must hold 2 n_maps and `index` 2 + n_maps/maps_per_image int64 words')
+    _check(_native.hip().eae_hip_coder_index_streams(n_maps, maps_per_image, _p(streams.bac_bits), _p(streams.bypass_bits),
+                                                     int(streams.stride), int(capacity_bytes), _p(offsets),
+                                                     _p(index), _stream(streams.bac_bits)), 'eae_hip_coder_index_streams')
+    return offsets, index
+
+
+def coder_pack_indexed(streams, offsets, index, payload):
+    """`coder_pack_streams` into `payload` (uint8, the capacity `index` was formed against) with the offsets and the overflow flag
+    of `coder_index_streams`: nothing is copied when the flag is set."""
+    if payload.dtype != torch.uint8 or offsets.numel() != 2*streams.n_maps:
+        raise HipError('`payload` must be uint8 and `offsets` hold 2 n_maps words')
+    _check(_native.hip().eae_hip_coder_pack_indexed(streams.n_maps, _p(streams.streams), streams.stride, _p(streams.bac_bits),
+                                                    _p(streams.bypass_bits), _p(offsets), _p(index), _p(payload), _stream(payload)),
+           'eae_hip_coder_pack_indexed')
+    return payload
+
+
+def publish_prefix(src_device, dst_pinned, nbytes_device):
+    """Stream-ordered copy, by a kernel, of the first `nbytes_device[0]` bytes (an int64 device word; at most the buffers' size) of
+    `src_device` into the pinned host tensor `dst_pinned`, rounded up to 16 bytes; the rest of `dst_pinned` is not written. Both
+    uint8, of one size, a multiple of 16."""
+    capacity = src_device.numel()*src_device.element_size()
+    if not dst_pinned.is_pinned() or dst_pinned.numel()*dst_pinned.element_size() != capacity or not dst_pinned.is_contiguous() or capacity % 16:
+        raise HipError('expected a contiguous pinned host tensor of the same size, a multiple of 16 bytes')
+    if nbytes_device.numel() != 1 or nbytes_device.element_size() != 8:
+        raise HipError('expected one 64-bit word')
+    _check(_native.hip().eae_hip_publish_prefix(_p(src_device), dst_pinned.data_ptr(), capacity, _p(nbytes_device), _stream(src_device)),
+           'eae_hip_publish_prefix')
+
+
+def exception_rows(hist, overflow, map_size, truncated_unary_length, out=None):
+    """`symbol_histograms` of exception maps (hist int32 [n, 2*radius+1], overflow int32 [n]) -> their probability rows, float64
+    [n, L] on the device, bit-equal to container._exception_rows (include/eae_hip.h). Needs radius >= L. `out`: preallocated."""
+    (n, width) = hist.shape
+    if hist.dtype != torch.int32 or overflow.dtype != torch.int32 or overflow.numel() != n or width % 2 != 1:
+        raise HipError('expected int32 histograms [n, 2*radius + 1] and int32 overflow counts [n]')
+    if out is None:
+        out = torch.empty((n, truncated_unary_length), dtype=torch.float64, device=hist.device)
+    if out.dtype != torch.float64 or out.numel() != n*truncated_unary_length:
+        raise HipError('`out` must hold n x L float64')
+    _check(_native.hip().eae_hip_exception_rows(n, _p(hist), _p(overflow), (width - 1)//2, int(map_size), int(truncated_unary_length),
+                                                _p(out), _stream(hist)), 'eae_hip_exception_rows')
+    return out
+
+
 # ---- SVHN float64 path (include/eae_hip.h, "SVHN path") -------------------------------------------------------------
 
 def svhn_dense(x, w, b, leaky_relu):

@@ -433,6 +433,36 @@ int eae_hip_coder_unpack_streams(uint32_t n_maps, const uint8_t* payload, const 
 int eae_hip_dequantize_maps(const int16_t* symbols_planar, const float* bin_widths, const float* map_mean, float* cq_out,
                             float* shifted_out, int n, int hw, int c, void* stream);
 
+/* ---- containers from the pipelined codec (csrc/hip/codec_container.hip) --------------------------
+ * What container.encode_images does between the coder and the blob, with device-resident arguments only: every call is
+ * asynchronous on `stream`, none has an argument the host has to compute from a result of the step, so all four can be captured
+ * into a hipGraph behind the coder's launches.
+ * index_streams: the piece e = 2 m + piece of map m (arithmetic-coded bytes, bypass bytes) is min((bits + 7) >> 3, stride / 2)
+ *   bytes long, as pack_streams copies it. offsets_out[2 n_maps]: the exclusive prefix sum of those lengths in payload order
+ *   (image -> map -> piece), 64-bit; index_out[0] their total, index_out[1] = 1 when the total exceeds capacity_bytes (else 0),
+ *   index_out[2 + i] the bytes of image i (n_maps / maps_per_image images). n_maps >= 1; n_maps not a multiple of
+ *   maps_per_image -> EAE_HIP_BAD_SHAPE.
+ * pack_indexed: pack_streams, except that nothing is copied when index[1] != 0 (the payload buffer holds capacity_bytes).
+ * publish_prefix: the first ceil(min(*nbytes_device, capacity_bytes) / 16) 16-byte words of src_device into pinned,
+ *   device-mapped host memory, visible to the host as eae_hip_publish_to_host's copy is; no byte at or beyond that length is
+ *   written. Both buffers hold capacity_bytes (a multiple of 16) and are 16-byte aligned, else EAE_HIP_BAD_ARGUMENT.
+ * exception_rows: the probability row of an image's exception map from that map's histogram (stats.py:181-195, :56-66 on
+ *   eae_hip_symbol_histograms' output: hist uint32 [n][2 radius + 1], overflow uint32 [n]): with zeros[j] = the symbols of
+ *   magnitude j and ones[j] = map_size - the symbols of magnitude <= j, rows_out[i][j] = zeros / (zeros + ones) in float64, 0 / 0
+ *   -> 0.5, 0 -> 0.01, 1 -> 0.99, j < length. Needs radius >= length (EAE_HIP_BAD_ARGUMENT otherwise): then a symbol beyond the
+ *   radius is a one of every position, which map_size already accounts for, so the rows are exact whatever `overflow` counts
+ *   (it is not read). */
+int eae_hip_coder_index_streams(uint32_t n_maps, uint32_t maps_per_image, const uint32_t* bac_bits, const uint32_t* bypass_bits,
+                                uint64_t stream_stride_bytes, uint64_t capacity_bytes, uint64_t* offsets_out, uint64_t* index_out,
+                                void* stream);
+int eae_hip_coder_pack_indexed(uint32_t n_maps, const uint8_t* streams, uint64_t stream_stride_bytes, const uint32_t* bac_bits,
+                               const uint32_t* bypass_bits, const uint64_t* offsets, const uint64_t* index, uint8_t* payload,
+                               void* stream);
+int eae_hip_publish_prefix(const void* src_device, void* dst_host_mapped, uint64_t capacity_bytes, const uint64_t* nbytes_device,
+                           void* stream);
+int eae_hip_exception_rows(int n, const uint32_t* hist, const uint32_t* overflow, int radius, int map_size, int length,
+                           double* rows_out, void* stream);
+
 /* ==== TEST HOOKS (-DEAE_TEST_HOOKS): NOT exported by the product library lib/libeae_hip.so ====================================
  * Four entry points the test-suite needs and a deployment must not have (they change what later launches do, or only
  * exist to prove something about the kernels). Compiled into lib/libeae_hip_test.so only; tests/test_abi.py checks that
