@@ -34,7 +34,13 @@ probability row per image, measured on the whole map. Layout (little endian):
     to a byte)
 The streams of one (image, tile) are contiguous, so a region of the image needs one byte range per (image, tile) it touches
 (`region_plan`), and `decode_region` reads only those from a file. With one tile per map the payload is EAE1's, byte for byte.
+
+One path serves both formats: EAE1 is the case coding tile = (h, w), one tile per map. `_fixed_header` checks the fixed part of
+either magic and `_read_arrays` reads what follows (`read_header`, `fetch_region`); `_pack_header` writes it; `_encode_entries` codes
+and `_decode_entries` decodes groups of (image, tile) entries. An EAE1 blob is one group of whole maps, coded where the quantiser
+left the symbols.
 """
+import math
 import numbers
 import struct
 
@@ -88,12 +94,36 @@ def _raise_for_statuses(results):
         interface_cython.raise_for_status(int(results[2, bad[0]]), int(results[3, bad[0]]))
 
 
+def _fields(are_bin_widths_learned, nb_images, height, width, idx_map_exception, bin_widths, map_mean, binary_probabilities,
+            exception_rows, coding_tile=None):
+    """The header of a blob to write, under `read_header`'s keys (no 'bits', no 'payload_offset'); EAT1 with a coding tile."""
+    fields = {'nb_images': nb_images, 'height': height, 'width': width, 'nb_maps': binary_probabilities.shape[0],
+              'truncated_unary_length': binary_probabilities.shape[1], 'idx_map_exception': idx_map_exception,
+              'are_bin_widths_learned': bool(are_bin_widths_learned), 'bin_widths': bin_widths, 'map_mean': map_mean,
+              'binary_probabilities': binary_probabilities, 'exception_probabilities': exception_rows}
+    if coding_tile is not None:
+        fields.update({'format': 'EAT1', 'coding_tile': coding_tile})
+    return fields
+
+
+def _pack_header(fields, bits):
+    """Everything in front of the payload (module docstring), as bytes: what `read_header` parses. bits uint32, in payload order."""
+    common = (1 if fields['are_bin_widths_learned'] else 0, fields['nb_images'], fields['height'], fields['width'], fields['nb_maps'],
+              fields['truncated_unary_length'], 0, fields['idx_map_exception'])
+    if fields.get('format') == 'EAT1':
+        head = _TILE_HEADER.pack(TILE_MAGIC, TILE_VERSION, *(common + tuple(fields['coding_tile'])))
+    else:
+        head = _HEADER.pack(MAGIC, VERSION, *common)
+    return b''.join([head, fields['bin_widths'].tobytes(), fields['map_mean'].tobytes(), fields['binary_probabilities'].tobytes(),
+                     fields['exception_probabilities'].tobytes(), bits.tobytes()])
+
+
 def assemble_blob(are_bin_widths_learned, nb_images, height, width, idx_map_exception, bin_widths, map_mean, binary_probabilities,
                   exception_rows, bits, payload):
     """The EAE1 blob (module docstring) from its parts -> (blob bytes, header bytes). bin_widths / map_mean float32 [nb_maps],
     binary_probabilities float64 [nb_maps, L], exception_rows float64 [nb_images, L] ([0, L] without an exception map), bits
-    uint32 [nb_images*nb_maps, 2], payload bytes-like. What `encode_images` ends with, and what a `codec.Ticket` builds its
-    containers with from the pinned blocks of its step."""
+    uint32 [nb_images*nb_maps, 2], payload bytes-like. What a `codec.Ticket` builds its containers with from the pinned blocks of
+    its step; `encode_images` packs the same header."""
     (nb_maps, truncated_unary_length) = binary_probabilities.shape
     nb_rows = nb_images if idx_map_exception >= 0 else 0
     if bin_widths.dtype != numpy.float32 or map_mean.dtype != numpy.float32 or bin_widths.shape != (nb_maps,) or map_mean.shape != (nb_maps,):
@@ -102,14 +132,11 @@ def assemble_blob(are_bin_widths_learned, nb_images, height, width, idx_map_exce
         raise ValueError('The probabilities must be float64 and the bit counts uint32.')
     if exception_rows.shape != (nb_rows, truncated_unary_length) or bits.shape != (nb_images*nb_maps, 2):
         raise ValueError('The exception rows or the bit counts do not have the shape the header announces.')
-    if len(payload) != int(((bits.astype(numpy.int64) + 7)//8).sum()):
+    if len(payload) != int(_entry_bytes(bits.reshape(nb_images, nb_maps, 2)).sum()):
         raise ValueError('The payload size does not match the bit counts.')
-    head = _HEADER.pack(MAGIC, VERSION, 1 if are_bin_widths_learned else 0, nb_images, height, width, nb_maps, truncated_unary_length, 0,
-                        idx_map_exception)
-    pieces = [head, bin_widths.tobytes(), map_mean.tobytes(), binary_probabilities.tobytes(), exception_rows.tobytes(), bits.tobytes()]
-    header_bytes = sum(len(piece) for piece in pieces)
-    pieces.append(bytes(payload))
-    return (b''.join(pieces), header_bytes)
+    header = _pack_header(_fields(are_bin_widths_learned, nb_images, height, width, idx_map_exception, bin_widths, map_mean,
+                                  binary_probabilities, exception_rows), bits)
+    return (header + bytes(payload), len(header))
 
 
 def assemble_image_blobs(are_bin_widths_learned, nb_images, height, width, idx_map_exception, bin_widths, map_mean, binary_probabilities,
@@ -117,7 +144,7 @@ def assemble_image_blobs(are_bin_widths_learned, nb_images, height, width, idx_m
     """The parts of a batch's blob (`assemble_blob`) -> one single-image blob per image: the payload is image-major, so an image's
     blob is its slice of the bit counts, of the exception rows and of the payload behind a header of its own."""
     nb_maps = binary_probabilities.shape[0]
-    image_bytes = ((bits.astype(numpy.int64) + 7)//8).reshape(nb_images, -1).sum(axis=1)
+    image_bytes = _entry_bytes(bits.reshape(nb_images, nb_maps, 2))
     stops = numpy.cumsum(image_bytes)
     view = memoryview(payload)
     blobs = []
@@ -139,7 +166,7 @@ def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_p
     bytes, are those of tile=None, and images beyond the untiled path's size limit can be written.
     coding_tile=(th, tw) latents: write the tile-indexed format EAT1 (module docstring) instead of EAE1. The coder runs on groups
     of `tiles_per_call` (image, tile) pairs, so its streams and workspace are bounded by one group whatever the image size.
-    info then also holds 'tile_bits' uint32 (N, nb_tiles, 128, 2).
+    info then also holds 'tile_bits' uint32 (N, nb_tiles, 128, 2). EAE1 is one tile per map, coded as one group.
     """
     images = numpy.ascontiguousarray(luminances_uint8)
     if images.dtype != numpy.uint8:
@@ -160,92 +187,99 @@ def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_p
         tiles_per_call = _positive_int(tiles_per_call, '`tiles_per_call`')
     device = encoder.device
     y = encoder(torch.from_numpy(images).to(device), tile=tile)
-    map_size = y.shape[1]*y.shape[2]
     q = dev.quantize_maps(y, torch.from_numpy(bin_widths).to(device), torch.from_numpy(mean).to(device), want_symbols=True)
     if int(q['checks'][0].item()) != 0:
         raise AssertionError('The rounded array elements cannot be represented as 16-bit signed integers.')
     symbols = q['symbols']                                              # [N, 128, map_size] int16, stays in HBM
-    prob_row = numpy.tile(numpy.arange(nb_maps, dtype=numpy.int32), nb_images)
-    table = probabilities
     exception_rows = numpy.zeros((0, truncated_unary_length), dtype=numpy.float64)
     if 0 <= idx_map_exception < nb_maps:
         exception_rows = _exception_rows(symbols, idx_map_exception, truncated_unary_length)
-        table = numpy.concatenate([probabilities, exception_rows])
-        prob_row[idx_map_exception::nb_maps] = nb_maps + numpy.arange(nb_images, dtype=numpy.int32)
     else:
         idx_map_exception = -1
     if coding_tile is not None:
-        return _encode_tiles(symbols, (y.shape[1], y.shape[2]), coding_tile, tiles_per_call, table, idx_map_exception, probabilities,
-                             exception_rows, bin_widths, mean, 1 if encoder.are_bin_widths_learned else 0, (height, width))
-    n_maps = nb_images*nb_maps
-    streams = dev.coder_encode_batch(symbols.view(n_maps, map_size), torch.from_numpy(table).to(device),
-                                     torch.from_numpy(prob_row).to(device), truncated_unary_length)
-    results = streams.results.cpu().numpy()
-    _raise_for_statuses(results)
-    bits = numpy.stack([results[0], results[1]], axis=1).astype(numpy.uint32)          # [n_maps, 2]
-    nbytes = (bits.astype(numpy.int64) + 7)//8
-    offsets = numpy.concatenate([[0], numpy.cumsum(nbytes.reshape(-1))[:-1]]).astype(numpy.int64).reshape(n_maps, 2)
-    payload_bytes = int(nbytes.sum())
-    payload = dev.coder_pack_streams(streams, torch.from_numpy(offsets).to(device), payload_bytes)
-    (blob, header_bytes) = assemble_blob(encoder.are_bin_widths_learned, nb_images, height, width, idx_map_exception, bin_widths, mean,
-                                         probabilities, exception_rows, bits, payload[:payload_bytes].cpu().numpy().tobytes())
-    info = {'nb_bits': (bits[:, 0] + bits[:, 1]).reshape(nb_images, nb_maps), 'payload_bytes': payload_bytes,
-            'header_bytes': header_bytes}
-    return (blob, info)
+        coding_tile = (min(coding_tile[0], y.shape[1]), min(coding_tile[1], y.shape[2]))
+        if max(coding_tile) > 0xFFFF:
+            raise ValueError('A coding tile side does not fit the container (65535 latents at most).')
+    fields = _fields(encoder.are_bin_widths_learned, nb_images, height, width, idx_map_exception, bin_widths, mean, probabilities,
+                     exception_rows, coding_tile)
+    return _encode_entries(symbols, fields, nb_images if coding_tile is None else tiles_per_call)
 
 
-def read_header(blob):
-    """Parses everything in front of the payload. Raises ValueError on a malformed or truncated blob.
-    An EAT1 blob gives the same keys, with 'bits' uint32 [nb_images, nb_tiles, nb_maps, 2], plus 'format' ('EAT1') and
-    'coding_tile' (th, tw)."""
-    if bytes(blob[:4]) == TILE_MAGIC:
-        return _read_tile_header(blob, len(blob))
-    if len(blob) < _HEADER.size:
+def _fixed_header(fixed, total_length):
+    """Checks the fixed part of the header of either format (`fixed`: the first bytes of the blob or file, `total_length`: the length
+    of all of it) -> (fields, bytes of the fixed part, bytes of the whole header). Everything that sizes a read or an allocation is
+    checked here, the whole header's length against `total_length` before any array behind the fixed part is read."""
+    tiled = bytes(fixed[:4]) == TILE_MAGIC
+    layout = _TILE_HEADER if tiled else _HEADER
+    if len(fixed) < layout.size:
         raise ValueError('The container is truncated.')
-    (magic, version, flags, nb_images, height, width, nb_maps, truncated_unary_length, _, idx_map_exception) = _HEADER.unpack_from(blob, 0)
-    if magic != MAGIC:
+    (magic, version, flags, nb_images, height, width, nb_maps, length, _, idx_map_exception, *coding_tile) = layout.unpack_from(fixed, 0)
+    if magic != (TILE_MAGIC if tiled else MAGIC):
         raise ValueError('The container does not start with the magic bytes.')
-    if version != VERSION:
+    if version != (TILE_VERSION if tiled else VERSION):
         raise ValueError('The container version {} is not supported.'.format(version))
     # sizes first: they dimension device buffers (a crafted header must not get that far)
     if nb_maps != csts.NB_MAPS_3:
         raise ValueError('The container does not hold {} maps per image.'.format(csts.NB_MAPS_3))
-    if truncated_unary_length < 1:
+    if length < 1:
         raise ValueError('The truncated unary length does not belong to [1, 255].')
     if nb_images < 1 or height < 1 or width < 1 or height % csts.STRIDE_PROD != 0 or width % csts.STRIDE_PROD != 0:
         raise ValueError('The image sizes in the container are not positive multiples of {}.'.format(csts.STRIDE_PROD))
     if not -1 <= idx_map_exception < nb_maps:
         raise ValueError('The index of the exception map in the container is out of range.')
-    pos = _HEADER.size
+    fields = {'nb_images': nb_images, 'height': height, 'width': width, 'nb_maps': nb_maps, 'truncated_unary_length': length,
+              'idx_map_exception': idx_map_exception, 'are_bin_widths_learned': bool(flags & 1)}
+    if tiled:
+        if min(coding_tile) < 1:
+            raise ValueError('The coding tile sizes in the container are not positive.')
+        fields.update({'format': 'EAT1', 'coding_tile': tuple(coding_tile)})
+    nb_tiles = _nb_tiles(height//csts.STRIDE_PROD, width//csts.STRIDE_PROD, _coding_tile(fields))
+    nb_rows = nb_images if idx_map_exception >= 0 else 0
+    header_length = layout.size + 8*nb_maps + 8*nb_maps*length + 8*nb_rows*length + 8*nb_images*nb_tiles*nb_maps
+    if header_length > total_length:
+        raise ValueError('The container is truncated.')
+    return fields, layout.size, header_length
 
-    def take(count, dtype):
+
+def _read_arrays(fields, pos, blob, total_length):
+    """The arrays behind the fixed part (`pos`: its size), which `blob` holds whole, into `fields` -> the header `read_header`
+    returns. No bit count may exceed the capacity of its stream, and the counts must add up to `total_length`."""
+    (nb_images, nb_maps, length) = (fields['nb_images'], fields['nb_maps'], fields['truncated_unary_length'])
+    (h, w) = (fields['height']//csts.STRIDE_PROD, fields['width']//csts.STRIDE_PROD)
+    (tiles, _) = coding_tile_grid(h, w, _coding_tile(fields))
+    nb_rows = nb_images if fields['idx_map_exception'] >= 0 else 0
+    header = dict(fields)
+
+    def take(dtype, *shape):
         nonlocal pos
-        nbytes = count*numpy.dtype(dtype).itemsize
-        if pos + nbytes > len(blob):
-            raise ValueError('The container is truncated.')
-        out = numpy.frombuffer(blob, dtype=dtype, count=count, offset=pos).copy()
-        pos += nbytes
+        out = numpy.frombuffer(blob, dtype=dtype, count=math.prod(shape), offset=pos).copy().reshape(shape)
+        pos += out.nbytes
         return out
 
-    header = {'nb_images': nb_images, 'height': height, 'width': width, 'nb_maps': nb_maps,
-              'truncated_unary_length': truncated_unary_length, 'idx_map_exception': idx_map_exception,
-              'are_bin_widths_learned': bool(flags & 1)}
-    header['bin_widths'] = take(nb_maps, numpy.float32)
-    header['map_mean'] = take(nb_maps, numpy.float32)
-    header['binary_probabilities'] = take(nb_maps*truncated_unary_length, numpy.float64).reshape(nb_maps, truncated_unary_length)
-    nb_rows = nb_images if idx_map_exception >= 0 else 0
-    header['exception_probabilities'] = take(nb_rows*truncated_unary_length, numpy.float64).reshape(nb_rows, truncated_unary_length)
-    header['bits'] = take(nb_images*nb_maps*2, numpy.uint32).reshape(nb_images*nb_maps, 2)
+    header['bin_widths'] = take(numpy.float32, nb_maps)
+    header['map_mean'] = take(numpy.float32, nb_maps)
+    header['binary_probabilities'] = take(numpy.float64, nb_maps, length)
+    header['exception_probabilities'] = take(numpy.float64, nb_rows, length)
+    header['bits'] = take(numpy.uint32, nb_images, len(tiles), nb_maps, 2)
     header['payload_offset'] = pos
-    # a stream can never be longer than the region the coder gives a map (compression.cpp:24): an inflated count would make
-    # the unpacking write past it
-    map_size = (height//csts.STRIDE_PROD)*(width//csts.STRIDE_PROD)
-    if int(header['bits'].max(initial=0)) > stream_capacity_bits(map_size, truncated_unary_length):
+    # a stream can never be longer than the region the coder gives a map of its tile's size (compression.cpp:24): an inflated count
+    # would make the unpacking write past it
+    capacity = numpy.array([stream_capacity_bits(int(r*c), length) for (r, c) in tiles[:, 2:4].tolist()], dtype=numpy.int64)
+    if (header['bits'].max(axis=(0, 2, 3)).astype(numpy.int64) > capacity).any():
         raise ValueError('A bit count of the header exceeds the capacity of a stream.')
-    payload_bytes = int(((header['bits'].astype(numpy.int64) + 7)//8).sum())
-    if pos + payload_bytes != len(blob):
+    if pos + int(_entry_bytes(header['bits']).sum()) != total_length:
         raise ValueError('The payload size does not match the bit counts of the header.')
+    if 'format' not in fields:
+        header['bits'] = header['bits'].reshape(nb_images*nb_maps, 2)
     return header
+
+
+def read_header(blob):
+    """Parses everything in front of the payload. Raises ValueError on a malformed or truncated blob. 'bits' is uint32
+    [nb_images*nb_maps, 2] for EAE1; an EAT1 blob gives the same keys, with 'bits' uint32 [nb_images, nb_tiles, nb_maps, 2], plus
+    'format' ('EAT1') and 'coding_tile' (th, tw)."""
+    (fields, pos, _) = _fixed_header(blob, len(blob))
+    return _read_arrays(fields, pos, blob, len(blob))
 
 
 def decode_symbols(blob, device='cuda'):
@@ -253,49 +287,41 @@ def decode_symbols(blob, device='cuda'):
     header = read_header(blob)
     if header.get('format') == 'EAT1':
         raise ValueError('An EAT1 container codes tiles, not whole maps: use decode_tile_symbols.')
-    (nb_images, nb_maps) = (header['nb_images'], header['nb_maps'])
-    if header['height'] % 16 != 0 or header['width'] % 16 != 0:
-        raise ValueError('The image size in the container is not divisible by 16.')
-    map_size = (header['height']//16)*(header['width']//16)
-    n_maps = nb_images*nb_maps
-    device = torch.device(device)
-    bits = header['bits']
-    nbytes = (bits.astype(numpy.int64) + 7)//8
-    offsets = numpy.concatenate([[0], numpy.cumsum(nbytes.reshape(-1))[:-1]]).astype(numpy.int64).reshape(n_maps, 2)
-    payload = numpy.frombuffer(blob, dtype=numpy.uint8, offset=header['payload_offset'])
-    payload_device = torch.from_numpy(numpy.concatenate([payload, numpy.zeros(8, dtype=numpy.uint8)])).to(device)
-    streams = dev.coder_unpack_streams(payload_device, torch.from_numpy(offsets).to(device),
-                                       torch.from_numpy(bits[:, 0].astype(numpy.int32)).to(device),
-                                       torch.from_numpy(bits[:, 1].astype(numpy.int32)).to(device), map_size,
-                                       header['truncated_unary_length'])
-    table = numpy.concatenate([header['binary_probabilities'], header['exception_probabilities']])
-    prob_row = numpy.tile(numpy.arange(nb_maps, dtype=numpy.int32), nb_images)
-    if header['idx_map_exception'] >= 0:
-        prob_row[header['idx_map_exception']::nb_maps] = nb_maps + numpy.arange(nb_images, dtype=numpy.int32)
-    symbols = dev.coder_decode_batch(streams, torch.from_numpy(table).to(device), torch.from_numpy(prob_row).to(device))
-    _raise_for_statuses(streams.results.cpu().numpy())
-    return (header, symbols.view(nb_images, nb_maps, map_size))
+    (entries, chunks) = _all_entries(header, blob)
+    buffers = []
+
+    def consume(group, decoded, offsets, tiles):
+        buffers.append(decoded)
+
+    # one group of whole maps: its buffer is [N, 128, map_size]
+    _decode_entries(header, entries, chunks, torch.device(device), len(entries), consume)
+    return (header, buffers[0].view(header['nb_images'], header['nb_maps'], -1))
+
+
+def _require_kind(header, decoder):
+    if header['are_bin_widths_learned'] != decoder.are_bin_widths_learned:
+        raise ValueError('The container was written by the other kind of model (learned / fixed bin widths).')
 
 
 def decode_images(blob, decoder, tile=None, tiles_per_call=64):
     """blob + pipeline.DeviceDecoder of the model -> uint8 (N, H, W) reconstructions (BT.601 range, tools.py:61-93).
     tile=(th, tw): run the synthesis transform through windows (pipeline.DeviceDecoder.__call__): same reconstruction.
-    EAT1 blobs are decoded in groups of `tiles_per_call` coding tiles, scattered and dequantised into the latent plane."""
+    EAT1 blobs are decoded in groups of `tiles_per_call` coding tiles, scattered and dequantised into the latent plane; the whole
+    maps of an EAE1 blob are one group, dequantised by `dequantize_maps`."""
     if bytes(blob[:4]) == TILE_MAGIC:
         header = read_header(blob)
         return decode_region(blob, decoder, (0, 0, header['height'], header['width']), tile=tile, tiles_per_call=tiles_per_call)
     (header, symbols) = decode_symbols(blob, decoder.device)
-    if header['are_bin_widths_learned'] != decoder.are_bin_widths_learned:
-        raise ValueError('The container was written by the other kind of model (learned / fixed bin widths).')
+    _require_kind(header, decoder)
     device = decoder.device
     shifted = dev.dequantize_maps(symbols, torch.from_numpy(header['bin_widths']).to(device),
                                   torch.from_numpy(header['map_mean']).to(device))['shifted']
-    (h_map, w_map) = (header['height']//16, header['width']//16)
+    (h_map, w_map) = (header['height']//csts.STRIDE_PROD, header['width']//csts.STRIDE_PROD)
     (_, reconstruction_uint8, _) = decoder(shifted.view(header['nb_images'], h_map, w_map, header['nb_maps']), tile=tile)
     return reconstruction_uint8.cpu().numpy()
 
 
-# ---- the tile-indexed format EAT1 --------------------------------------------------------------------------------------------
+# ---- coding tiles, regions and groups of (image, tile) entries: both formats -------------------------------------------------
 
 def _positive_int(x, what):
     if not isinstance(x, numbers.Integral) or isinstance(x, bool) or x < 1:
@@ -333,77 +359,16 @@ def coding_tile_grid(h, w, coding_tile):
     return tiles, classes
 
 
-def _tile_header_length(fixed, total_length):
-    """Checks the fixed EAT1 header (bytes-like of at least _TILE_HEADER.size bytes) -> (fields, length of the whole header).
-    Everything that sizes a read or an allocation is checked here, against `total_length` (the blob's or the file's)."""
-    if len(fixed) < _TILE_HEADER.size:
-        raise ValueError('The container is truncated.')
-    (magic, version, flags, nb_images, height, width, nb_maps, length, _, idx_map_exception, th, tw) = _TILE_HEADER.unpack_from(fixed, 0)
-    if magic != TILE_MAGIC:
-        raise ValueError('The container does not start with the magic bytes.')
-    if version != TILE_VERSION:
-        raise ValueError('The container version {} is not supported.'.format(version))
-    if nb_maps != csts.NB_MAPS_3:
-        raise ValueError('The container does not hold {} maps per image.'.format(csts.NB_MAPS_3))
-    if length < 1:
-        raise ValueError('The truncated unary length does not belong to [1, 255].')
-    if nb_images < 1 or height < 1 or width < 1 or height % csts.STRIDE_PROD != 0 or width % csts.STRIDE_PROD != 0:
-        raise ValueError('The image sizes in the container are not positive multiples of {}.'.format(csts.STRIDE_PROD))
-    if not -1 <= idx_map_exception < nb_maps:
-        raise ValueError('The index of the exception map in the container is out of range.')
-    if th < 1 or tw < 1:
-        raise ValueError('The coding tile sizes in the container are not positive.')
-    fields = {'nb_images': nb_images, 'height': height, 'width': width, 'nb_maps': nb_maps, 'truncated_unary_length': length,
-              'idx_map_exception': idx_map_exception, 'are_bin_widths_learned': bool(flags & 1), 'format': 'EAT1',
-              'coding_tile': (th, tw)}
-    nb_tiles = _nb_tiles(height//csts.STRIDE_PROD, width//csts.STRIDE_PROD, (th, tw))
-    nb_rows = nb_images if idx_map_exception >= 0 else 0
-    header_length = (_TILE_HEADER.size + 8*nb_maps + 8*nb_maps*length + 8*nb_rows*length + 8*nb_images*nb_tiles*nb_maps)
-    if header_length > total_length:
-        raise ValueError('The container is truncated.')
-    return fields, header_length
-
-
-def _read_tile_header(blob, total_length):
-    """read_header for EAT1: `blob` holds at least the whole header; `total_length` is the blob's (or the file's) length."""
-    (header, header_length) = _tile_header_length(blob, total_length)
-    if len(blob) < header_length:
-        raise ValueError('The container is truncated.')
-    (nb_images, nb_maps, length) = (header['nb_images'], header['nb_maps'], header['truncated_unary_length'])
-    (h, w) = (header['height']//csts.STRIDE_PROD, header['width']//csts.STRIDE_PROD)
-    nb_tiles = _nb_tiles(h, w, header['coding_tile'])
-    pos = _TILE_HEADER.size
-
-    def take(count, dtype):
-        nonlocal pos
-        out = numpy.frombuffer(blob, dtype=dtype, count=count, offset=pos).copy()
-        pos += count*numpy.dtype(dtype).itemsize
-        return out
-
-    header['bin_widths'] = take(nb_maps, numpy.float32)
-    header['map_mean'] = take(nb_maps, numpy.float32)
-    header['binary_probabilities'] = take(nb_maps*length, numpy.float64).reshape(nb_maps, length)
-    nb_rows = nb_images if header['idx_map_exception'] >= 0 else 0
-    header['exception_probabilities'] = take(nb_rows*length, numpy.float64).reshape(nb_rows, length)
-    header['bits'] = take(nb_images*nb_tiles*nb_maps*2, numpy.uint32).reshape(nb_images, nb_tiles, nb_maps, 2)
-    header['payload_offset'] = pos
-    # per tile, as EAE1 per map: no count above the capacity of that tile's stream (the unpacking would write past its region)
-    (tiles, _) = coding_tile_grid(h, w, header['coding_tile'])
-    capacity = numpy.array([stream_capacity_bits(int(r*c), length) for (r, c) in tiles[:, 2:4].tolist()], dtype=numpy.int64)
-    if nb_tiles and (header['bits'].max(axis=(0, 2, 3)).astype(numpy.int64) > capacity).any():
-        raise ValueError('A bit count of the header exceeds the capacity of a stream.')
-    payload_bytes = int(((header['bits'].astype(numpy.int64) + 7)//8).sum())
-    if pos + payload_bytes != total_length:
-        raise ValueError('The payload size does not match the bit counts of the header.')
-    return header
+def _coding_tile(fields):
+    """The coding tile of either format: an EAE1 blob is one tile per map."""
+    if fields.get('format') == 'EAT1':
+        return fields['coding_tile']
+    return (fields['height']//csts.STRIDE_PROD, fields['width']//csts.STRIDE_PROD)
 
 
 def _tile_layout(header):
-    """(coding tile, bits [N, nb_tiles, 128, 2]) of either format: an EAE1 blob is one tile per map."""
-    if header.get('format') == 'EAT1':
-        return header['coding_tile'], header['bits']
-    (h, w) = (header['height']//csts.STRIDE_PROD, header['width']//csts.STRIDE_PROD)
-    return (h, w), header['bits'].reshape(header['nb_images'], 1, header['nb_maps'], 2)
+    """(coding tile, bits [N, nb_tiles, 128, 2]) of either format."""
+    return _coding_tile(header), header['bits'].reshape(header['nb_images'], -1, header['nb_maps'], 2)
 
 
 def _entry_bytes(bits):
@@ -468,22 +433,22 @@ def fetch_region(source, region, images=None):
     """Host side of decode_region: (header, region_plan, one bytes-like chunk per plan entry). `source`: a bytes-like blob, or a
     seekable binary file object, from which only the fixed header, then the rest of the header, then the plan's byte ranges
     (adjacent ranges in one read) are read. An EAE1 file is read whole: its maps are coded whole."""
-    if not hasattr(source, 'read'):
+    in_memory = not hasattr(source, 'read')
+    if in_memory:
         blob = memoryview(source).cast('B')
-        header = read_header(blob)
-        plan = region_plan(header, region, images)
-        return header, plan, [blob[a:b] for (a, b) in plan['ranges']]
-    source.seek(0, 2)
-    total = source.tell()
-    fixed = _read_at(source, 0, min(_TILE_HEADER.size, total))
-    if fixed[:4] != TILE_MAGIC:
-        blob = memoryview(fixed + _read_at(source, len(fixed), total - len(fixed)))
-        header = read_header(blob)
-        plan = region_plan(header, region, images)
-        return header, plan, [blob[a:b] for (a, b) in plan['ranges']]
-    (_, header_length) = _tile_header_length(fixed, total)
-    header = _read_tile_header(fixed + _read_at(source, len(fixed), header_length - len(fixed)), total)
+        total = len(blob)
+        (fields, pos, _) = _fixed_header(blob, total)
+    else:
+        source.seek(0, 2)
+        total = source.tell()
+        fixed = _read_at(source, 0, min(_TILE_HEADER.size, total))
+        (fields, pos, header_length) = _fixed_header(fixed, total)
+        in_memory = 'format' not in fields
+        blob = memoryview(fixed + _read_at(source, len(fixed), (total if in_memory else header_length) - len(fixed)))
+    header = _read_arrays(fields, pos, blob, total)
     plan = region_plan(header, region, images)
+    if in_memory:
+        return header, plan, [blob[a:b] for (a, b) in plan['ranges']]
     chunks = [None]*len(plan['ranges'])
     order = sorted(range(len(chunks)), key=lambda k: plan['ranges'][k])
     k = 0
@@ -541,27 +506,24 @@ class _Workspace(object):
         (self.device, self.length, self.tensor) = (device, length, None)
 
     def get(self, n_maps, map_size):
-        from . import _native
-        need = int(_native.hip().eae_hip_coder_workspace_bytes(n_maps, map_size, self.length))
+        need = dev.coder_workspace_bytes(n_maps, map_size, self.length)
         if self.tensor is None or self.tensor.numel() < need:
             self.tensor = None
             self.tensor = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self.tensor
 
 
-def _encode_tiles(symbols, shape, coding_tile, per_call, table, idx_map_exception, probabilities, exception_rows, bin_widths, mean,
-                  flags, image_size):
-    """encode_images' EAT1 half: symbols [N, 128, h*w] (device) -> (blob, info). Per group of `per_call` (image, tile) entries in
-    payload order: one gather launch, one coder batch per shape class, one pack launch per class into the group's payload."""
+def _encode_entries(symbols, fields, per_call):
+    """The coding stage of encode_images: symbols [N, 128, h*w] (device) + the header to write (`_fields`) -> (blob, info). Per
+    group of `per_call` (image, tile) entries in payload order: one gather launch, one coder batch per shape class, one pack launch
+    per class into the group's payload. Whole maps (one tile per map) are the group's layout as they stand: no gather, no copy."""
     (nb_images, nb_maps, _) = symbols.shape
-    (h, w) = shape
-    coding_tile = (min(coding_tile[0], h), min(coding_tile[1], w))
-    if max(coding_tile) > 0xFFFF:
-        raise ValueError('A coding tile side does not fit the container (65535 latents at most).')
-    (tiles, classes) = coding_tile_grid(h, w, coding_tile)
+    (h, w) = (fields['height']//csts.STRIDE_PROD, fields['width']//csts.STRIDE_PROD)
+    (tiles, classes) = coding_tile_grid(h, w, _coding_tile(fields))
     nb_tiles = tiles.shape[0]
-    length = table.shape[1]
+    length = fields['truncated_unary_length']
     device = symbols.device
+    table = numpy.concatenate([fields['binary_probabilities'], fields['exception_probabilities']])
     table_device = torch.from_numpy(table).to(device)
     workspace = _Workspace(device, length)
     bits = numpy.zeros((nb_images, nb_tiles, nb_maps, 2), dtype=numpy.uint32)
@@ -570,14 +532,17 @@ def _encode_tiles(symbols, shape, coding_tile, per_call, table, idx_map_exceptio
     for g0 in range(0, len(all_entries), per_call):
         entries = all_entries[g0:g0 + per_call]
         (runs, offsets, total) = _group_layout(entries, tiles, classes)
-        plan = _symbols_plan(entries, tiles, offsets)
-        gathered = torch.empty(total, dtype=torch.int16, device=device)
-        dev.tile_symbols_gather(symbols, gathered, torch.from_numpy(plan).to(device), plan, h, w)
+        if nb_tiles == 1:
+            gathered = symbols[entries[0][0]:entries[-1][0] + 1].view(-1)
+        else:
+            plan = _symbols_plan(entries, tiles, offsets)
+            gathered = torch.empty(total, dtype=torch.int16, device=device)
+            dev.tile_symbols_gather(symbols, gathered, torch.from_numpy(plan).to(device), plan, h, w)
         coded = []
         for (cls, ks, start) in runs:
             size = classes[cls][0]*classes[cls][1]
             n_maps = len(ks)*nb_maps
-            prob_row = torch.from_numpy(_prob_rows(entries, ks, idx_map_exception)).to(device)
+            prob_row = torch.from_numpy(_prob_rows(entries, ks, fields['idx_map_exception'])).to(device)
             coded.append(dev.coder_encode_batch(gathered[start:start + n_maps*size].view(n_maps, size), table_device, prob_row, length,
                                                 workspace=workspace.get(n_maps, size)))
         group_bits = numpy.zeros((len(entries), nb_maps, 2), dtype=numpy.uint32)
@@ -587,22 +552,21 @@ def _encode_tiles(symbols, shape, coding_tile, per_call, table, idx_map_exceptio
             group_bits[ks] = numpy.stack([results[0], results[1]], axis=1).reshape(len(ks), nb_maps, 2)
         stream_offsets = _stream_offsets(group_bits)
         group_bytes = int(_entry_bytes(group_bits).sum())
-        payload = torch.empty(max(group_bytes, 1), dtype=torch.uint8, device=device)
+        payload = None                              # the first pack allocates it
         for ((_, ks, _), streams) in zip(runs, coded):
-            dev.coder_pack_streams(streams, torch.from_numpy(stream_offsets[ks].reshape(-1, 2)).to(device), group_bytes, payload=payload)
+            payload = dev.coder_pack_streams(streams, torch.from_numpy(stream_offsets[ks].reshape(-1, 2)).to(device), group_bytes,
+                                             payload=payload)
         pieces.append(payload[:group_bytes].cpu().numpy().tobytes())
         for (k, (i, t)) in enumerate(entries):
             bits[i, t] = group_bits[k]
         del gathered, coded, streams, payload       # before the next group allocates its own
-    (height, width) = image_size
-    head = _TILE_HEADER.pack(TILE_MAGIC, TILE_VERSION, flags, nb_images, height, width, nb_maps, length, 0, idx_map_exception,
-                             coding_tile[0], coding_tile[1])
-    parts = [head, bin_widths.tobytes(), mean.tobytes(), probabilities.tobytes(), exception_rows.tobytes(), bits.tobytes()]
-    header_bytes = sum(len(part) for part in parts)
+    header = _pack_header(fields, bits)
     payload = b''.join(pieces)
     info = {'nb_bits': (bits[..., 0].astype(numpy.int64) + bits[..., 1]).sum(axis=1).astype(numpy.uint32), 'payload_bytes': len(payload),
-            'header_bytes': header_bytes, 'tile_bits': bits}
-    return b''.join(parts) + payload, info
+            'header_bytes': len(header)}
+    if 'format' in fields:
+        info['tile_bits'] = bits
+    return header + payload, info
 
 
 def _decode_entries(header, entries, chunks, device, per_call, consume):
@@ -650,16 +614,19 @@ def _decode_entries(header, entries, chunks, device, per_call, consume):
         del payload_device, decoded, streams, results
 
 
+def _all_entries(header, blob):
+    """Every (image, tile) entry of a blob in payload order, and its payload bytes: (entries, chunks) for _decode_entries."""
+    plan = region_plan(header, (0, 0, header['height'], header['width']))
+    view = memoryview(blob).cast('B')
+    return plan['entries'], [view[a:b] for (a, b) in plan['ranges']]
+
+
 def decode_tile_symbols(blob, device='cuda', tiles_per_call=64):
     """An EAT1 (or EAE1) blob -> (header, symbols): symbols[i][t] = int16 [128, rows, cols] (device) of image i, coding tile t
     (row-major; an EAE1 blob has one tile per map), arithmetic decoding only."""
     header = read_header(blob)
-    (coding_tile, bits) = _tile_layout(header)
-    (nb_images, nb_tiles) = bits.shape[:2]
-    plan = region_plan(header, (0, 0, header['height'], header['width']))
-    entries = [(i, t) for i in range(nb_images) for t in range(nb_tiles)]
-    view = memoryview(blob).cast('B')
-    out = [[None]*nb_tiles for _ in range(nb_images)]
+    (entries, chunks) = _all_entries(header, blob)
+    out = [[None]*(len(entries)//header['nb_images']) for _ in range(header['nb_images'])]
 
     def consume(group, decoded, offsets, tiles):
         for (k, (i, t)) in enumerate(group):
@@ -667,9 +634,7 @@ def decode_tile_symbols(blob, device='cuda', tiles_per_call=64):
             start = int(offsets[k])
             out[i][t] = decoded[start:start + dev.NB_MAPS*rows*cols].view(dev.NB_MAPS, rows, cols)
 
-    ranges = dict(zip(plan['entries'], plan['ranges']))
-    _decode_entries(header, entries, [view[slice(*ranges[e])] for e in entries], torch.device(device),
-                    _positive_int(tiles_per_call, '`tiles_per_call`'), consume)
+    _decode_entries(header, entries, chunks, torch.device(device), _positive_int(tiles_per_call, '`tiles_per_call`'), consume)
     return header, out
 
 
@@ -681,8 +646,7 @@ def decode_region(source, decoder, region, images=None, tile=None, tiles_per_cal
     tile=(th, tw): synthesise the sub-plane through windows (pipeline.DeviceDecoder.__call__)."""
     tiles_per_call = _positive_int(tiles_per_call, '`tiles_per_call`')
     (header, plan, chunks) = fetch_region(source, region, images)
-    if header['are_bin_widths_learned'] != decoder.are_bin_widths_learned:
-        raise ValueError('The container was written by the other kind of model (learned / fixed bin widths).')
+    _require_kind(header, decoder)
     device = decoder.device
     (r0, r1, c0, c1) = plan['sub_plane']
     shifted = torch.empty((len(plan['images']), r1 - r0, c1 - c0, header['nb_maps']), dtype=torch.float32, device=device)

@@ -673,10 +673,13 @@ def publish_step(src_device, dst_pinned, clear_from, tickets_device, counter_dev
                                               word_pinned.data_ptr(), _stream(src_device)), 'eae_hip_publish_step')
 
 
+def coder_workspace_bytes(n_maps, map_size, truncated_unary_length):
+    return int(_native.hip().eae_hip_coder_workspace_bytes(n_maps, map_size, truncated_unary_length))
+
+
 def coder_workspace(n_maps, map_size, truncated_unary_length, device):
     """Scratch for coder_encode_batch / coder_decode_batch (one per batch in flight)."""
-    nbytes = int(_native.hip().eae_hip_coder_workspace_bytes(n_maps, map_size, truncated_unary_length))
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return torch.empty(coder_workspace_bytes(n_maps, map_size, truncated_unary_length), dtype=torch.uint8, device=device)
 
 
 def coder_encode_batch(symbols_planar, probabilities, prob_row, truncated_unary_length, out=None, workspace=None):

@@ -71,6 +71,39 @@ def test_one_tile_per_map_is_the_eae1_payload(model, coding_tile):
     assert numpy.array_equal(rec, in_memory_path(model, images, bw, mean)[1])
 
 
+def test_eae1_is_one_group_of_whole_maps_without_a_copy(model, monkeypatch):
+    """EAE1 through the group coder: one tile per map and all images in one group whatever `tiles_per_call` says, so one coder batch
+    over 3 x 128 maps each way, and the symbols are coded where the quantiser left them: no gather launch."""
+    from autoencoder_based_image_compression_amd import container
+    from autoencoder_based_image_compression_amd import device as dev
+    images = _images(21, (3, 32, 48))
+    (expected, _, bw, mean) = _encode(model, images, 0.5, 67)
+    (encode_batch, decode_batch, gather) = (dev.coder_encode_batch, dev.coder_decode_batch, dev.tile_symbols_gather)
+    calls = {'encode': [], 'decode': [], 'gather': 0}
+
+    def counting_encode(symbols_planar, *args, **kwargs):
+        calls['encode'].append(symbols_planar.numel()//symbols_planar.shape[-1])
+        return encode_batch(symbols_planar, *args, **kwargs)
+
+    def counting_decode(streams, *args, **kwargs):
+        calls['decode'].append(streams.n_maps)
+        return decode_batch(streams, *args, **kwargs)
+
+    def counting_gather(*args, **kwargs):
+        calls['gather'] += 1
+        return gather(*args, **kwargs)
+
+    monkeypatch.setattr(dev, 'coder_encode_batch', counting_encode)
+    monkeypatch.setattr(dev, 'coder_decode_batch', counting_decode)
+    monkeypatch.setattr(dev, 'tile_symbols_gather', counting_gather)
+    (blob, _, _, _) = _encode(model, images, 0.5, 67, tiles_per_call=1)
+    assert calls == {'encode': [384], 'decode': [], 'gather': 0}
+    reconstruction = container.decode_images(blob, model['decoder'], tiles_per_call=1)
+    assert calls == {'encode': [384], 'decode': [384], 'gather': 0}
+    assert blob[:4] == b'EAE1' and blob == expected
+    assert numpy.array_equal(reconstruction, in_memory_path(model, images, bw, mean)[1])
+
+
 def host_encode_maps(planar, probs, prob_row):
     from autoencoder_based_image_compression_amd import _native
     lib = _native.coder()
@@ -327,12 +360,11 @@ def test_a_large_image_with_coding_tiles():
     # the coding stage alone: symbols in, blob out
     symbols = dev.quantize_maps(encoder(xd, tile=tile), torch.from_numpy(bw).cuda(), torch.from_numpy(mean).cuda(),
                                 want_symbols=True)['symbols']
-    table = probabilities
     torch.cuda.synchronize()
     base = torch.cuda.memory_allocated()
     torch.cuda.reset_peak_memory_stats()
-    (blob, _) = container._encode_tiles(symbols, (H//16, W//16), tile, per_call, table, -1, probabilities,
-                                        numpy.zeros((0, 10)), bw, mean, 0, (H, W))
+    fields = container._fields(False, 1, H, W, -1, bw, mean, probabilities, numpy.zeros((0, 10)), coding_tile=tile)
+    (blob, _) = container._encode_entries(symbols, fields, per_call)
     torch.cuda.synchronize()
     peak = torch.cuda.max_memory_allocated() - base
     lib = _native.hip()
