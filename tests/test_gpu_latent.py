@@ -1,5 +1,9 @@
 """eae_hip_latent_stage (gdn_3 -> quantiser -> inverse_gdn_4 in one kernel) against the separate kernels it fuses
-(eae_hip_gdn, eae_hip_quantize_maps, eae_hip_gdn), which are themselves pinned to the CPU oracle: identical bits."""
+(eae_hip_gdn, eae_hip_quantize_maps, eae_hip_gdn), which are themselves pinned to the CPU oracle: identical bits.
+
+The `gamma` matrices here are symmetric (0.5*(gamma + gamma.T), or the initialisation of `random_variables`) by history: these
+tests compare kernels with kernels and cannot tell gamma[k][c] from gamma[c][k]. tests/test_gpu_trained_like.py runs the same
+entry points -- and the one-sided stage -- on an asymmetric `gamma` and a per-channel `beta` against the oracle chain."""
 import numpy
 import pytest
 import torch

@@ -146,13 +146,8 @@ def test_oracle_reproduces_the_committed_transform_fixture():
                 assert float(zlib.crc32(a.tobytes())) == g[tag + '_sum_crc_' + name][1], (tag, name)
 
 
-@pytest.mark.parametrize('learned', [False, True])
-def test_the_torch_cpu_stand_in_of_the_cpu_baseline_follows_the_oracle(learned):
-    """oracle/transforms_torch.py (what `bench.py: cpu_baseline` times as the stand-in for TF-CPU's kernels) computes the same
-    graph as the C oracle: equal to float32 rounding of a different summation order (never used as a checker)."""
+def _torch_cpu_stand_in_follows_the_oracle(v, learned):
     from oracle import transforms as orc, transforms_torch
-    from autoencoder_based_image_compression_amd.kodak.eae.graph import variables as var
-    v = var.random_variables(1., learned, seed=21, bias_std=0.01)
     v['decoder/weights_6'] = (v['decoder/weights_6']*numpy.float32(30.)).astype(numpy.float32)
     x = numpy.random.RandomState(22).randint(16, 236, size=(2, 48, 80, 1)).astype(numpy.float32)
     cpu = transforms_torch.CpuTransforms(v, learned)
@@ -163,3 +158,107 @@ def test_the_torch_cpu_stand_in_of_the_cpu_baseline_follows_the_oracle(learned):
     rec_ref = orc.decoder(q, v, learned)
     rec = cpu.decoder(q)
     assert rec.shape == rec_ref.shape and numpy.allclose(rec, rec_ref, rtol=1e-4, atol=1e-4*float(numpy.abs(rec_ref).max()))
+    return (y_ref, rec_ref)
+
+
+@pytest.mark.parametrize('learned', [False, True])
+def test_the_torch_cpu_stand_in_of_the_cpu_baseline_follows_the_oracle(learned):
+    """oracle/transforms_torch.py (what `bench.py: cpu_baseline` times as the stand-in for TF-CPU's kernels) computes the same
+    graph as the C oracle: equal to float32 rounding of a different summation order (never used as a checker)."""
+    from autoencoder_based_image_compression_amd.kodak.eae.graph import variables as var
+    _torch_cpu_stand_in_follows_the_oracle(var.random_variables(1., learned, seed=21, bias_std=0.01), learned)
+
+
+# ---- parameters like a trained model's: asymmetric gamma, one beta per channel (tests/model_cases.py) ---------------------------
+GDN_REL = 4e-6      # |oracle - float64| <= GDN_REL*|float64|: see test_gdn_against_float64_definition_on_trained_like_parameters
+
+
+def _trained_like_gdn_case():
+    import model_cases
+    v = model_cases.trained_like_variables(1., False, seed=2)
+    x = (numpy.random.RandomState(1).standard_normal(size=(500, 128))*3).astype(numpy.float32)
+    return (model_cases, x, v['encoder/gamma_1'], v['encoder/beta_1'])
+
+
+@pytest.mark.parametrize('learned', [False, True])
+def test_trained_like_variables_are_what_they_claim(learned):
+    """The generator's own properties: a valid model (dtype and shapes), every gamma strongly asymmetric, every beta one value per
+    channel, everything at or above the reference's lower clip, and nothing else changed against `random_variables`."""
+    import model_cases
+    from autoencoder_based_image_compression_amd.kodak.eae.graph import constants as csts
+    v = model_cases.trained_like_variables(1., learned, seed=7)
+    base = var.random_variables(1., learned, seed=7, bias_std=0.01)
+    var.check_variables(v, var.model_names(learned))
+    assert set(v) == set(base)
+    (gammas, betas) = ([n for n in v if '/gamma_' in n], [n for n in v if '/beta_' in n])
+    assert len(gammas) == len(betas) == (4 if learned else 6)
+    for name in v:
+        if name in gammas:
+            assert model_cases.asymmetry(v[name]) >= 0.3, name
+            assert model_cases.asymmetry(base[name]) == 0.
+            assert v[name].min() == numpy.float32(csts.MIN_GAMMA_BETA) and v[name].max() < 0.1
+            assert 0.03 < numpy.mean(v[name] == numpy.float32(csts.MIN_GAMMA_BETA)) < 0.07
+        elif name in betas:
+            at_floor = v[name] == numpy.float32(csts.MIN_GAMMA_BETA)
+            assert numpy.array_equal(numpy.flatnonzero(at_floor), numpy.arange(0, 128, 17))
+            assert len(numpy.unique(v[name])) == 128 - int(at_floor.sum()) + 1           # distinct up to the repeated minimum
+            assert v[name][~at_floor].min() >= 0.25 and v[name].max() <= 4.
+        else:
+            assert numpy.array_equal(v[name], base[name]), name
+        assert v[name].dtype == numpy.float32
+    other = model_cases.trained_like_variables(1., learned, seed=7)
+    assert all(numpy.array_equal(v[name], other[name]) for name in v)
+
+
+@pytest.mark.parametrize('inverse', [False, True])
+def test_gdn_against_float64_definition_on_trained_like_parameters(inverse):
+    """orc_gdn on an asymmetric gamma and a per-channel beta against x / sqrt(matmul(x**2, gamma) + beta) in float64.
+    Tolerance, derived for positive terms: the 128-term float32 FMA chain plus the beta add is within 129 * 2^-24 relative; the
+    square root halves that and adds 2^-24; the division or product adds 2^-24: 66.5 * 2^-24 = 3.96e-6 <= 4e-6."""
+    (model_cases, x, g, b) = _trained_like_gdn_case()
+    ref = model_cases.gdn_float64(x, g, b, inverse)
+    got = T.gdn(x, g, b, inverse=inverse)
+    error = numpy.abs(got - ref)/numpy.abs(ref)
+    print('orc_gdn(inverse={0}) against float64: max relative error {1:.3g}'.format(inverse, error.max()))
+    assert numpy.all(numpy.abs(got - ref) <= GDN_REL*numpy.abs(ref))
+
+
+@pytest.mark.parametrize('inverse', [False, True])
+def test_the_trained_like_parameters_tell_the_wrong_indexings_apart(inverse):
+    """The teeth of every comparison on these parameters, as a condition on the float64 references alone: gamma transposed, beta
+    rolled by one channel and beta read in the kernels' packed channel order each move at least 95 % of the elements by more than
+    1e-3 relative, 250 times the tolerance above -- whatever agrees with the true definition to 4e-6 has none of these mistakes.
+    On the symmetric initialisation with beta = 1 none of them moves anything."""
+    (model_cases, x, g, b) = _trained_like_gdn_case()
+    ref = model_cases.gdn_float64(x, g, b, inverse)
+    wrong = {'gamma.T': model_cases.gdn_float64(x, model_cases.gamma_transposed(g), b, inverse),
+             'beta rolled': model_cases.gdn_float64(x, g, model_cases.beta_rolled(b), inverse),
+             'beta packed': model_cases.gdn_float64(x, g, model_cases.beta_in_packed_order(b), inverse)}
+    for (what, values) in wrong.items():
+        fraction = model_cases.fraction_beyond(values, ref)
+        print('{0} (inverse={1}): {2:.1%} of the elements move by more than 1e-3'.format(what, inverse, fraction))
+        assert fraction >= 0.95, what
+    v = var.random_variables(1., False, seed=2)
+    (g0, b0) = (v['encoder/gamma_1'], v['encoder/beta_1'])
+    ref0 = model_cases.gdn_float64(x, g0, b0, inverse)
+    assert numpy.array_equal(model_cases.gdn_float64(x, model_cases.gamma_transposed(g0), model_cases.beta_in_packed_order(b0), inverse), ref0)
+    # and the oracle itself sits on the right side of it
+    assert model_cases.fraction_beyond(T.gdn(x, model_cases.gamma_transposed(g), b, inverse=inverse), ref) >= 0.95
+
+
+@pytest.mark.parametrize('learned', [False, True])
+def test_the_torch_cpu_stand_in_follows_the_oracle_on_trained_like_parameters(learned):
+    """The independent torch implementation (its GDN is a 1x1 convolution with its own weight layout) against the C oracle on an
+    asymmetric gamma and a per-channel beta, at the tolerance of the test above; with gamma transposed in the model the oracle's
+    own latents and reconstruction move by far more than that tolerance, so the agreement pins the orientation on both sides."""
+    import model_cases
+    from oracle import transforms as orc
+    v = model_cases.trained_like_variables(1., learned, seed=21)
+    (y_ref, rec_ref) = _torch_cpu_stand_in_follows_the_oracle(v, learned)
+    x = numpy.random.RandomState(22).randint(16, 236, size=(2, 48, 80, 1)).astype(numpy.float32)
+    swapped = {name: (model_cases.gamma_transposed(a) if '/gamma_' in name else a) for (name, a) in v.items()}
+    y_swapped = orc.encoder(x, swapped, learned)
+    rec_swapped = orc.decoder(numpy.round(y_ref), swapped, learned)
+    assert not numpy.allclose(y_swapped, y_ref, rtol=1e-4, atol=1e-4*float(numpy.abs(y_ref).max()))
+    assert not numpy.allclose(rec_swapped, rec_ref, rtol=1e-4, atol=1e-4*float(numpy.abs(rec_ref).max()))
+    assert numpy.mean(numpy.abs(y_swapped - y_ref) > 1e-2*numpy.abs(y_ref)) > 0.5

@@ -192,6 +192,35 @@ def test_round_trip_of_a_reference_like_checkpoint(tmp_path, layout, learned):
         ckpt.load_checkpoint(prefix, names=['decoder/biases_6'])
 
 
+@pytest.mark.parametrize('layout', ['v1', 'v2', 'npz'])
+@pytest.mark.parametrize('learned', [False, True])
+def test_round_trip_of_trained_like_variables(tmp_path, layout, learned):
+    """The round trips above write the reference's INITIALISATION, whose gamma matrices are symmetric and whose beta vectors are
+    constant: a restore that transposed gamma or reordered beta would pass them. Here every gamma is asymmetric and every beta
+    has one value per channel (tests/model_cases.py), and every array comes back exactly, row-major as written."""
+    import model_cases
+    variables = model_cases.trained_like_variables(0.5, learned, seed=12)
+    prefix = str(tmp_path/'model_10.ckpt')
+    if layout == 'npz':
+        var.save_variables(str(tmp_path/'model_10.npz'), variables)
+    else:
+        (ckpt.save_checkpoint_v1 if layout == 'v1' else ckpt.save_checkpoint)(prefix, variables)
+        everything = ckpt.load_checkpoint(prefix)
+        assert set(everything) == set(variables)
+        for (name, array) in variables.items():
+            assert everything[name].dtype == array.dtype and numpy.array_equal(everything[name], array), name
+    for side in ('encoder', 'decoder', 'both'):
+        restored = var.restore_variables(prefix, learned, side)
+        assert list(restored) == var.model_names(learned, side)
+        for (name, array) in restored.items():
+            assert array.dtype == numpy.float32 and array.flags['C_CONTIGUOUS'] and numpy.array_equal(array, variables[name]), name
+            if '/gamma_' in name:
+                assert not numpy.array_equal(array, variables[name].T), name             # the comparison can see a transposition
+                assert array.tobytes() == variables[name].tobytes(), name
+            if '/beta_' in name:
+                assert not numpy.array_equal(array, numpy.roll(variables[name], 1)), name
+
+
 def test_v1_key_encoding():
     # ordered-code layout of EncodeTensorNameSlice: num(0) | escaped name | 00 01 | num(rank) | (start, length) per dim
     assert ckpt.encode_tensor_name_slice('ab', 0) == b'\x00ab\x00\x01\x00'
