@@ -10,6 +10,17 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+
+@pytest.fixture(autouse=True)
+def _guarded_buffers():
+    """Every test of this module runs on poisoned buffers between guard bands: what device.py / pipeline.py allocate holds 0xFF bytes
+    (NaN, -1) until a kernel writes it, and a byte written outside a tensor fails the test (tests/guarded.py)."""
+    import guarded
+    from autoencoder_based_image_compression_amd import device, pipeline
+    with guarded.guarded((device, pipeline), 0xFF):
+        yield
+
+
 GRID_CAP = 4096*256          # elements one launch of grid_for() covers without looping (csrc/hip/svhn.hip)
 # every layer of 3072-300-200 (BASELINE.json configs[0]), 3072-15-12 and 3072-32-16 (svhn/test_eae.py), encoder then decoder
 LAYERS = sorted({(3072, h) for h in (300, 15, 32)} | {(h, 3072) for h in (300, 15, 32)}

@@ -12,6 +12,20 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+
+@pytest.fixture(autouse=True)
+def _guarded_buffers(request):
+    """Every test of this module runs on poisoned buffers between guard bands: what device.py / pipeline.py allocate holds 0xFF bytes
+    (NaN, -1) until a kernel writes it, and a byte written outside a tensor fails the test (tests/guarded.py). The guard keeps its
+    allocations until the test ends, and test_a_large_image_with_coding_tiles bounds the peak of allocated memory over four groups
+    of tiles: there only requests of up to 1 MB are guarded (the per-group streams, symbols and workspaces are torch's own)."""
+    import guarded
+    from autoencoder_based_image_compression_amd import device, pipeline
+    limits = {'passthrough_bytes': 1 << 20} if request.node.name == 'test_a_large_image_with_coding_tiles' else {}
+    with guarded.guarded((device, pipeline), 0xFF, **limits):
+        yield
+
+
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'coder_golden.npz')
 
 

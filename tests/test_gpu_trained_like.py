@@ -19,6 +19,17 @@ from test_gpu_kernels import FORMS, _assert_handed_over, _image, _select_form
 
 pytestmark = pytest.mark.gpu
 
+
+@pytest.fixture(autouse=True)
+def _guarded_buffers():
+    """Every test of this module runs on poisoned buffers between guard bands: what device.py / pipeline.py allocate holds 0xFF bytes
+    (NaN, -1) until a kernel writes it, and a byte written outside a tensor fails the test (tests/guarded.py)."""
+    import guarded
+    from autoencoder_based_image_compression_amd import device, pipeline
+    with guarded.guarded((device, pipeline), 0xFF):
+        yield
+
+
 GDN_REL = 4e-6        # against the float64 definition: derived in tests/test_oracle_transforms.py
 
 

@@ -106,10 +106,12 @@ def test_allow_list_is_current():
 
 
 def test_removing_a_module_is_noticed():
-    """The check has teeth: without the modules that test the small kernels directly, some entry point is uncovered."""
+    """The check has teeth: without the modules that test the small kernels directly, some entry point is uncovered. (The
+    buffer-discipline module reruns every kernel between guard bands with the helpers it imports from these modules, so it leaves
+    with them.)"""
     texts = gpu_test_texts()
     for module in ('test_gpu_svhn_kernels.py', 'test_gpu_quantize_helpers.py'):
-        assert module in texts
-        rest = {k: v for (k, v) in texts.items() if k != module}
+        assert module in texts and 'test_gpu_buffer_discipline.py' in texts
+        rest = {k: v for (k, v) in texts.items() if k not in (module, 'test_gpu_buffer_discipline.py')}
         lost = sorted(f for (f, modules) in coverage(rest).items() if modules == [] and f not in ALLOWED_UNTESTED)
         assert lost, module
