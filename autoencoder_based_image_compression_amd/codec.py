@@ -152,15 +152,7 @@ class Ticket(object):
         'sse' int64 (sum of squared uint8 differences), 'nb_deads' int64.
         When the result worker has not started on this step yet (one step at a time: the caller is here a few microseconds after
         `submit`), the calling thread waits for the device and forms the results itself (`_Worker.process`)."""
-        pending = self._job
-        if pending is not None:
-            self._job = None
-            (job, worker) = pending
-            if _RESULT_BY_CALLER and not self._done.is_set() and job.claim():
-                worker.process(job, by_caller=True)
-        self._done.wait()
-        if self._error is not None:
-            raise self._error
+        _wait_for_ticket(self)
         return self._values
 
     def _parts(self):
@@ -199,7 +191,33 @@ class StepTimeout(RuntimeError):
     """The device did not report a submitted step within EAE_WORKER_SEQUENCE_TIMEOUT_SECONDS: the codec is unusable from here on."""
 
 
-class _Job(object):
+class _Claimable(object):
+    """A step's job: whoever claims it first -- the result worker taking it off its queue, or the caller's `result()` -- waits for
+    the device and forms the results."""
+    __slots__ = ('_claimed',)
+
+    def __init__(self):
+        self._claimed = threading.Lock()
+
+    def claim(self):
+        return self._claimed.acquire(False)
+
+
+def _wait_for_ticket(ticket):
+    """`result()` of either kind of ticket: when nobody has started on the step yet, the calling thread waits for the device and forms
+    the results itself (`process(job, by_caller=True)` of the ticket's worker); then the step's own error, if any, is raised."""
+    pending = ticket._job
+    if pending is not None:
+        ticket._job = None
+        (job, worker) = pending
+        if _RESULT_BY_CALLER and not ticket._done.is_set() and job.claim():
+            worker.process(job, by_caller=True)
+    ticket._done.wait()
+    if ticket._error is not None:
+        raise ticket._error
+
+
+class _Job(_Claimable):
     """What the results of one submitted step are made from; whoever claims it first -- the result worker taking it off its queue, or
     the caller's `Ticket.result()` -- waits for the device and forms the results.
     events: what `_Worker._wait` waits for ('events' wait mode; else empty); views: the slot's pinned blocks (results, histograms,
@@ -209,10 +227,10 @@ class _Job(object):
     analysis side's blocks too (exception-map histograms, dead-map flags, range check): small steps, whose caller waits for each
     result -- `BatchCodec._early_publish`; emit: with `emit_container`, (the blob's fixed parts, capacity, the slot's pinned payload,
     exception rows and index words as host arrays), else None."""
-    __slots__ = ('ticket', 'events', 'views', 'symbols_host', 'slot_free', 'recount', 'fetch', 'sequence', 'early_published', 'emit',
-                 '_claimed')
+    __slots__ = ('ticket', 'events', 'views', 'symbols_host', 'slot_free', 'recount', 'fetch', 'sequence', 'early_published', 'emit')
 
     def __init__(self, ticket, events, views, symbols_host, slot_free, recount, fetch, sequence, early_published=False, emit=None):
+        super(_Job, self).__init__()
         self.ticket = ticket
         self.events = events
         self.views = views
@@ -223,23 +241,17 @@ class _Job(object):
         self.sequence = sequence
         self.early_published = bool(early_published)
         self.emit = emit
-        self._claimed = threading.Lock()
-
-    def claim(self):
-        return self._claimed.acquire(False)
 
 
 _THREAD = threading.local()
 
 
-class _Worker(threading.Thread):
-    def __init__(self, map_size, nb_maps, host_probabilities, idx_map_exception, host_threads):
-        super(_Worker, self).__init__(daemon=True)
-        self.map_size = map_size
-        self.nb_maps = nb_maps
-        self.host_probabilities = host_probabilities
-        self.idx_map_exception = idx_map_exception
-        self.host_threads = host_threads
+class _StepWorker(threading.Thread):
+    """The thread, the queue of jobs and the waits for a step's counters that `BatchCodec`'s and `BatchDecoder`'s result workers
+    share; a subclass says in `process(job, by_caller=False)` what a finished step's results are made of."""
+
+    def __init__(self):
+        super(_StepWorker, self).__init__(daemon=True)
         self.jobs = queue.Queue()
 
     @staticmethod
@@ -336,6 +348,18 @@ class _Worker(threading.Thread):
                 return
             if job.claim():          # (else the caller's `Ticket.result()` got there first and does it itself)
                 self.process(job)
+
+
+class _Worker(_StepWorker):
+    """The result worker of `BatchCodec`."""
+
+    def __init__(self, map_size, nb_maps, host_probabilities, idx_map_exception, host_threads):
+        super(_Worker, self).__init__()
+        self.map_size = map_size
+        self.nb_maps = nb_maps
+        self.host_probabilities = host_probabilities
+        self.idx_map_exception = idx_map_exception
+        self.host_threads = host_threads
 
     def _exception_map_error(self, results):
         """The exception the first failed exception map of a step stands for, or None."""
@@ -1128,4 +1152,435 @@ class BatchCodec(object):
         try:
             self.close()
         except Exception:      # interpreter shutdown: nothing left to report to
+            pass
+
+
+# ---- the other half: containers in, reconstructions out ---------------------------------------------------
+
+def decode_head_layout(batch_size, nb_maps, truncated_unary_length):
+    """The "step head" of `BatchDecoder`: everything of a step's blobs but their payload, in one fixed-size block that crosses to the
+    device with one copy. -> (fields {name: (byte offset, dtype, shape)}, bytes of the block, a multiple of 16):
+    'bits' uint32 [n_maps][2] (arithmetic-coded stream, bypass stream), 'prob_row' int32 [n_maps] (row of 'table' a map is coded
+    with, -1: not coded), 'bin_widths' and 'map_mean' float32 [batch][nb_maps], 'table' float64 [batch][nb_maps + 1][L] (every
+    image's own probabilities, then the row of its exception map), 'payload_bytes' uint64 [1]."""
+    n_maps = batch_size*nb_maps
+    shapes = (('bits', numpy.uint32, (n_maps, 2)), ('prob_row', numpy.int32, (n_maps,)), ('bin_widths', numpy.float32, (batch_size, nb_maps)),
+              ('map_mean', numpy.float32, (batch_size, nb_maps)), ('table', numpy.float64, (batch_size, nb_maps + 1, truncated_unary_length)),
+              ('payload_bytes', numpy.uint64, (1,)))
+    (fields, pos) = ({}, 0)
+    for (name, dtype, shape) in shapes:
+        pos = -(-pos//8)*8
+        fields[name] = (pos, numpy.dtype(dtype), shape)
+        pos += numpy.dtype(dtype).itemsize*int(numpy.prod(shape))
+    return fields, -(-pos//16)*16
+
+
+def decode_head_views(head, batch_size, nb_maps, truncated_unary_length):
+    """The fields of `decode_head_layout` as numpy views of `head` (uint8, contiguous, at least the block's bytes, 8-byte aligned)."""
+    (fields, nbytes) = decode_head_layout(batch_size, nb_maps, truncated_unary_length)
+    if head.dtype != numpy.uint8 or head.ndim != 1 or head.size < nbytes:
+        raise ValueError('`head` must be a flat uint8 array of at least {0} bytes.'.format(nbytes))
+    return {name: head[pos:pos + dtype.itemsize*int(numpy.prod(shape))].view(dtype).reshape(shape) for (name, (pos, dtype, shape)) in fields.items()}
+
+
+def plan_decode_step(blobs, batch_size, h_in, w_in, truncated_unary_length, are_bin_widths_learned, capacity, head, payload,
+                     nb_maps=csts.NB_MAPS_3):
+    """The host side of one `BatchDecoder` step; numpy only. blobs: one `EAE1` blob or a sequence of them, 1..batch_size images in
+    all, in the order of the step's images. Every header is parsed and checked (`container.read_header`, then the decoder's own
+    height, width, truncated unary length and model kind, the number of images, the payload against `capacity`) BEFORE a byte of
+    `head` or `payload` is written: a refused step (ValueError) leaves both as they were. Then `head` (uint8: `decode_head_layout`)
+    is filled -- image i's map m is coded with row i*(nb_maps + 1) + m of the table, its exception map with row
+    i*(nb_maps + 1) + nb_maps, the maps of absent images get -1 -- and the payloads go to `payload` (uint8) one behind the other.
+    -> (images, payload bytes)."""
+    if isinstance(blobs, (bytes, bytearray, memoryview)):
+        blobs = [blobs]
+    blobs = list(blobs)
+    if not blobs:
+        raise ValueError('A step needs at least one blob.')
+    headers = []
+    for blob in blobs:
+        if bytes(blob[:4]) == container_format.TILE_MAGIC:
+            raise ValueError('An EAT1 container codes tiles: BatchDecoder takes EAE1 blobs only, use container.decode_region.')
+        header = container_format.read_header(blob)
+        if (header['height'], header['width']) != (h_in, w_in):
+            raise ValueError('The container holds {0} x {1} images, the decoder was built for {2} x {3}.'.format(
+                header['height'], header['width'], h_in, w_in))
+        if header['truncated_unary_length'] != truncated_unary_length:          # (`read_header` has refused anything but `nb_maps` maps)
+            raise ValueError('The container was coded with a truncated unary length of {0}, the decoder was built for {1}.'.format(
+                header['truncated_unary_length'], truncated_unary_length))
+        if header['are_bin_widths_learned'] != bool(are_bin_widths_learned):
+            raise ValueError('The container was written by the other kind of model (learned / fixed bin widths).')
+        headers.append(header)
+    nb_images = sum(header['nb_images'] for header in headers)
+    if nb_images > batch_size:
+        raise ValueError('The blobs hold {0} images, a step of this decoder takes {1} at most.'.format(nb_images, batch_size))
+    sizes = [len(blob) - header['payload_offset'] for (blob, header) in zip(blobs, headers)]
+    payload_bytes = sum(sizes)
+    if payload_bytes > capacity or payload_bytes > payload.size:
+        raise ValueError('The payload of this step takes {0} bytes, the decoder holds {1} per step '
+                         '(BatchDecoder(payload_capacity_bytes=...)).'.format(payload_bytes, min(capacity, payload.size)))
+    views = decode_head_views(head, batch_size, nb_maps, truncated_unary_length)
+    (first, pos) = (0, 0)
+    for (blob, header, size) in zip(blobs, headers, sizes):
+        n = header['nb_images']
+        views['bits'][first*nb_maps:(first + n)*nb_maps] = header['bits']
+        rows = (numpy.arange(first, first + n, dtype=numpy.int32)*(nb_maps + 1))[:, None] + numpy.arange(nb_maps, dtype=numpy.int32)[None, :]
+        exception = header['idx_map_exception']
+        if exception >= 0:
+            rows[:, exception] = numpy.arange(first, first + n, dtype=numpy.int32)*(nb_maps + 1) + nb_maps
+            views['table'][first:first + n, nb_maps] = header['exception_probabilities']
+        else:
+            views['table'][first:first + n, nb_maps] = 0.5
+        views['prob_row'][first*nb_maps:(first + n)*nb_maps] = rows.reshape(-1)
+        views['bin_widths'][first:first + n] = header['bin_widths']
+        views['map_mean'][first:first + n] = header['map_mean']
+        views['table'][first:first + n, :nb_maps] = header['binary_probabilities']
+        payload[pos:pos + size] = numpy.frombuffer(blob, dtype=numpy.uint8, count=size, offset=header['payload_offset'])
+        first += n
+        pos += size
+    views['bits'][nb_images*nb_maps:] = 0
+    views['prob_row'][nb_images*nb_maps:] = -1
+    views['bin_widths'][nb_images:] = 0.
+    views['map_mean'][nb_images:] = 0.
+    views['table'][nb_images:] = 0.5
+    views['payload_bytes'][0] = payload_bytes
+    return nb_images, payload_bytes
+
+
+# Streams of a `BatchDecoder` whose caller does not say (`nb_in_flight` is then two more than the streams it runs, so that the host
+# fills the next slots' pinned buffers while the streams are busy). From a sweep in a process with 16 hardware queues
+# (profiles/batch_decoder.md; graphs on, bin width 1.0): 1 / 2 / 3 / 4 streams take 2.12 / 1.84 / 1.73 / 1.68 ms per 24 Kodak images
+# and 0.52 / 0.30 / 0.26 / 0.23 ms per single image; four is the most that was measured. A process with fewer queues runs what
+# `stream_budget` leaves (two streams on four queues).
+DECODER_STREAMS = 4
+
+
+class DecodeTicket(object):
+    """Handle on one submitted `BatchDecoder` step."""
+
+    def __init__(self, nb_images):
+        self.nb_images = nb_images
+        self.errors = None                    # after result(): one entry per image, None or the exception of its first failing map
+        self._done = threading.Event()
+        self._error = None                    # the step's own failure (StepTimeout, a hand-off failure of the transforms)
+        self._value = None
+        self._job = None
+
+    def result(self, raise_errors=True):
+        """Blocks until the step is through; uint8 (nb_images, h_in, w_in): a numpy view of the slot's pinned buffer
+        (`fetch_reconstruction=True`) or the device tensor, valid until the slot comes round again. Raises the first image's error
+        unless `raise_errors` is False: `errors` then says which images of the array to leave alone."""
+        _wait_for_ticket(self)
+        if raise_errors:
+            for error in self.errors:
+                if error is not None:
+                    raise error
+        return self._value
+
+
+class _DecodeJob(_Claimable):
+    __slots__ = ('ticket', 'slot', 'sequence', 'payload_bytes')
+
+    def __init__(self, ticket, slot, sequence, payload_bytes):
+        super(_DecodeJob, self).__init__()
+        (self.ticket, self.slot, self.sequence, self.payload_bytes) = (ticket, slot, sequence, payload_bytes)
+
+
+class _DecodeWorker(_StepWorker):
+    """The result worker of `BatchDecoder`."""
+
+    def __init__(self, nb_maps):
+        super(_DecodeWorker, self).__init__()
+        self.nb_maps = nb_maps
+
+    def process(self, job, by_caller=False):
+        (ticket, slot) = (job.ticket, job.slot)
+        try:
+            if by_caller and not getattr(_THREAD, 'short_sleeps', False):
+                _short_sleeps_for_this_thread()
+                _THREAD.short_sleeps = True
+            if by_caller:
+                self._wait_sequence_by_caller(*job.sequence)
+            else:
+                self._wait_sequence(*job.sequence)
+            if int(slot.unfinished_host[0]) != 0:
+                raise dev.SplitHandOffTimeout('{} tiles of a cut conv launch were not handed over: the reconstructions of this step '
+                                              'are invalid (later steps are unaffected)'.format(int(slot.unfinished_host[0])))
+            if int(slot.index_host[0]) != job.payload_bytes or int(slot.index_host[1]) != 0:
+                raise RuntimeError('the device placed {0} payload bytes, the headers of the step announce {1}'.format(
+                    int(slot.index_host[0]), job.payload_bytes))
+            from .kodak.lossless import interface_cython
+            errors = []
+            for i in range(ticket.nb_images):
+                status = slot.results_host[2, i*self.nb_maps:(i + 1)*self.nb_maps]
+                error = None
+                if status.any():
+                    bad = i*self.nb_maps + int(numpy.flatnonzero(status)[0])
+                    try:
+                        interface_cython.raise_for_status(int(slot.results_host[2, bad]), int(slot.results_host[3, bad]))
+                    except Exception as exc:
+                        error = exc
+                errors.append(error)
+            ticket.errors = errors
+            ticket._value = slot.rec_host[:ticket.nb_images] if slot.rec_host is not None else slot.planes[:ticket.nb_images]
+        except StepTimeout as exc:
+            self.failed = exc
+            ticket._error = exc
+        except Exception as exc:
+            ticket._error = exc
+        finally:
+            if ticket.errors is None:
+                ticket.errors = [ticket._error]*ticket.nb_images
+            slot.free.set()
+            ticket._done.set()
+
+
+class _DecodeLane(object):
+    """The device side of one slot: the stream its steps run on and every device buffer between a step's first and last launch
+    (the largest are the activations of the synthesis transform, 17 MB per Kodak image). No two steps in flight share a buffer."""
+
+    def __init__(self, decoder, stream):
+        (batch_size, nb_maps, device, length) = (decoder.batch_size, decoder.nb_maps, decoder.device, decoder.truncated_unary_length)
+        n_maps = batch_size*nb_maps
+        self.stream = stream
+        (fields, head_bytes) = decode_head_layout(batch_size, nb_maps, length)
+        self.head = torch.zeros(head_bytes, dtype=torch.uint8, device=device)
+
+        def field(name, dtype):
+            (pos, numpy_dtype, shape) = fields[name]
+            return self.head[pos:pos + numpy_dtype.itemsize*int(numpy.prod(shape))].view(dtype).view(shape)
+
+        self.head_bits = field('bits', torch.int32)
+        self.prob_row = field('prob_row', torch.int32)
+        self.bin_widths = field('bin_widths', torch.float32)
+        self.map_mean = field('map_mean', torch.float32)
+        self.table = field('table', torch.float64).view(batch_size*(nb_maps + 1), length)
+        self.payload_bytes = field('payload_bytes', torch.int64)
+        self.head_bytes = torch.full((1,), head_bytes, dtype=torch.int64, device=device)
+        self.payload = torch.zeros(decoder.payload_capacity_bytes, dtype=torch.uint8, device=device)
+        # what goes to the host behind a step: [coder results 4 x n_maps | index words (int64: payload bytes, overflow flag, bytes per image)]
+        self.status = torch.zeros(4*n_maps + 2*(2 + batch_size), dtype=torch.int32, device=device)
+        self.results = self.status[:4*n_maps].view(4, n_maps)
+        self.index = self.status[4*n_maps:].view(torch.int64)
+        self.offsets = torch.zeros((n_maps, 2), dtype=torch.int64, device=device)
+        self.coder_streams = dev.CoderStreams(n_maps, decoder.map_size, length, device, results=self.results)
+        self.workspace = dev.coder_workspace(n_maps, decoder.map_size, length, device)
+        self.symbols = torch.zeros((batch_size, nb_maps, decoder.map_size), dtype=torch.int16, device=device)
+        self.shifted = torch.zeros((batch_size, decoder.h_in//csts.STRIDE_PROD, decoder.w_in//csts.STRIDE_PROD, nb_maps), dtype=torch.float32,
+                                   device=device)
+        (self.scratch, self.unfinished) = decoder.decoder.model.decode_scratch(batch_size, decoder.h_in//csts.STRIDE_PROD,
+                                                                               decoder.w_in//csts.STRIDE_PROD)
+
+
+class _DecodeSlot(object):
+    """What one step in flight owns: its device buffers (`lane`), the pinned buffers the host fills and reads, the planes, the step
+    counter, the captured graph. Made once."""
+
+    def __init__(self, decoder, lane):
+        (batch_size, nb_maps, device) = (decoder.batch_size, decoder.nb_maps, decoder.device)
+        n_maps = batch_size*nb_maps
+        self.lane = lane
+        self.pinned_head = torch.zeros(lane.head.numel(), dtype=torch.uint8).pin_memory()
+        self.pinned_payload = torch.zeros(decoder.payload_capacity_bytes, dtype=torch.uint8).pin_memory()
+        (self.head_host, self.payload_host) = (self.pinned_head.numpy(), self.pinned_payload.numpy())
+        self.pinned_status = torch.zeros(lane.status.numel(), dtype=torch.int32).pin_memory()
+        self.results_host = self.pinned_status[:4*n_maps].view(4, n_maps).numpy()
+        self.index_host = self.pinned_status[4*n_maps:].view(torch.int64).numpy()
+        self.pinned_unfinished = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self.unfinished_host = self.pinned_unfinished.numpy()
+        self.planes = torch.zeros((batch_size, decoder.h_in, decoder.w_in), dtype=torch.uint8, device=device)
+        self.pinned_rec = torch.zeros((batch_size, decoder.h_in, decoder.w_in), dtype=torch.uint8).pin_memory() if decoder.fetch_reconstruction else None
+        self.rec_host = self.pinned_rec.numpy() if self.pinned_rec is not None else None
+        self.seq_dev = torch.zeros(2, dtype=torch.int32, device=device)      # [step counter, ticket word of device.publish_step]
+        self.pinned_seq = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self.seq_host = self.pinned_seq.numpy()
+        self.count = 0
+        self.free = threading.Event()
+        self.free.set()
+        self.graph = None
+
+
+class BatchDecoder(object):
+    """`EAE1` containers -> uint8 reconstructions for steps of a fixed shape, resident and pipelined: what `container.decode_images`
+    computes (same bytes), with every buffer made once, the host work of a step in `plan_decode_step`, and the step as one chain of
+    launches on one of `nb_streams` private streams (one hipGraph per slot with `use_graphs`). DESIGN.md section 14."""
+
+    def __init__(self, variables, are_bin_widths_learned, batch_size, h_in, w_in, truncated_unary_length, device='cuda', nb_in_flight=None,
+                 nb_streams=None, use_graphs=False, payload_capacity_bytes=None, fetch_reconstruction=True):
+        """nb_streams: consecutive steps go round that many private streams, so that one step's serial decoder core runs beside
+        another step's synthesis transform. nb_in_flight: steps that may be pending at once (= slots: pinned buffers and planes).
+        None: `DECODER_STREAMS` streams, or as many of them as the process's hardware queues allow (`stream_budget`; streams asked
+        for explicitly are capped too, with a warning), and two more steps in flight than streams.
+        use_graphs: capture the step of every slot into a hipGraph at the first submit and replay it afterwards.
+        payload_capacity_bytes: payload bytes a step may hold (rounded up to 16; a device buffer per stream and a pinned one per
+        slot). None: batch_size*h_in*w_in. fetch_reconstruction: the planes reach pinned host memory inside the step and `result()`
+        is a numpy view of them; False: `result()` is the slot's device tensor."""
+        if h_in % csts.STRIDE_PROD != 0 or w_in % csts.STRIDE_PROD != 0 or h_in < 1 or w_in < 1:
+            raise ValueError('The image size is not divisible by the product of the three strides.')
+        if not 1 <= int(truncated_unary_length) <= 255:
+            raise ValueError('The truncated unary length does not belong to [1, 255].')
+        if batch_size < 1:
+            raise ValueError('`batch_size` is not positive.')
+        self.device = torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        if self.device.index != torch.cuda.current_device():
+            raise ValueError('`device` is {0} but the current device is cuda:{1}: build and use the decoder under '
+                             '`torch.cuda.device({0!r})`.'.format(self.device, torch.cuda.current_device()))
+        self.learned = bool(are_bin_widths_learned)
+        self.decoder = pipeline.DeviceDecoder(variables, are_bin_widths_learned, self.device)
+        (self.batch_size, self.h_in, self.w_in) = (int(batch_size), int(h_in), int(w_in))
+        self.nb_maps = csts.NB_MAPS_3
+        self.map_size = (h_in//csts.STRIDE_PROD)*(w_in//csts.STRIDE_PROD)
+        self.truncated_unary_length = int(truncated_unary_length)
+        if payload_capacity_bytes is None:
+            payload_capacity_bytes = self.batch_size*self.h_in*self.w_in
+        if int(payload_capacity_bytes) < 1:
+            raise ValueError('`payload_capacity_bytes` is not positive.')
+        self.payload_capacity_bytes = -(-int(payload_capacity_bytes)//16)*16
+        self.fetch_reconstruction = bool(fetch_reconstruction)
+        self.use_graphs = bool(use_graphs)
+        asked = nb_streams is not None
+        nb_streams = max(1, int(nb_streams)) if asked else DECODER_STREAMS
+        if os.environ.get('EAE_IGNORE_HW_QUEUES') != '1':
+            # (a decoder has no coder streams: the one `stream_budget` always leaves for them is the margin here)
+            (capped, _, _) = stream_budget(nb_streams, 1)
+            # (the default is capped without a word: the caller asked for nothing)
+            if asked and capped != nb_streams and not _BUDGET_WARNED[0]:
+                _BUDGET_WARNED[0] = True
+                import warnings
+                warnings.warn('BatchDecoder: {0} streams asked for, running {1}: this process has too few hardware queues '
+                              '(GPU_MAX_HW_QUEUES; streams beyond them share queues and serialise).'.format(nb_streams, capped),
+                              RuntimeWarning, stacklevel=2)
+            nb_streams = capped
+        self.nb_streams = nb_streams
+        self.nb_in_flight = max(1, int(nb_in_flight)) if nb_in_flight is not None else nb_streams + 2
+        self.nb_slots = self.nb_in_flight
+        streams = _step_streams(self.nb_streams, self.device)
+        self._slots = [_DecodeSlot(self, _DecodeLane(self, streams[k % self.nb_streams])) for k in range(self.nb_slots)]
+        self._index = 0
+        self._warm = False
+        self._worker = _DecodeWorker(self.nb_maps)
+        self._worker.start()
+        with _LIVE_LOCK:
+            _LIVE.setdefault(self.device.index, weakref.WeakSet()).add(self)
+
+    def submit(self, blobs):
+        """One `EAE1` blob of 1..batch_size images, or a sequence of `EAE1` blobs holding that many in all -> DecodeTicket.
+        Everything is checked on the host first (`plan_decode_step`: ValueError, nothing launched); then the step is enqueued and
+        nothing is waited for except a free slot."""
+        if self._worker is None:
+            raise RuntimeError('this decoder is closed')
+        if self._worker.failed is not None:
+            raise StepTimeout('this decoder stopped taking steps: {0}'.format(self._worker.failed))
+        if self.use_graphs and not self._warm:
+            # one ordinary step first (lazy module loads, function attributes), then every slot's graph, while nothing is in flight
+            ticket = self._submit(blobs, replay=False)
+            ticket.result(raise_errors=False)
+            try:
+                self._capture_all()
+            except BaseException:
+                for slot in self._slots:
+                    slot.graph = None
+                raise
+            self._warm = True
+            return ticket
+        return self._submit(blobs, replay=self.use_graphs)
+
+    def _submit(self, blobs, replay):
+        slot = self._slots[self._index % self.nb_slots]
+        slot.free.wait()
+        (nb_images, payload_bytes) = plan_decode_step(blobs, self.batch_size, self.h_in, self.w_in, self.truncated_unary_length, self.learned,
+                                                      self.payload_capacity_bytes, slot.head_host, slot.payload_host, self.nb_maps)
+        slot.free.clear()
+        self._index += 1
+        expected = slot.count + 1
+        try:
+            ticket = DecodeTicket(nb_images)
+            caller = torch.cuda.current_stream()
+            try:
+                torch.cuda.set_stream(slot.lane.stream)
+                if replay:
+                    if slot.graph is None:
+                        raise RuntimeError('this slot has no captured graph (a capture failed earlier)')
+                    slot.graph.replay()
+                else:
+                    self._launch_step(slot)
+            finally:
+                torch.cuda.set_stream(caller)
+            job = _DecodeJob(ticket, slot, (slot.seq_host, (expected,)), payload_bytes)
+            ticket._job = (job, self._worker)
+            self._worker.jobs.put(job)
+            slot.count = expected
+            return ticket
+        except BaseException:
+            try:
+                torch.cuda.synchronize(self.device)
+                slot.count = int(slot.seq_dev[0].item())
+                slot.seq_dev[1:].zero_()
+            except Exception:
+                pass
+            slot.free.set()
+            raise
+
+    def _capture_all(self):
+        """Every slot's step as one hipGraph, while nothing of this decoder is in flight (and the other codecs of the device are
+        idle: they share the process's streams, `BatchCodec._capture_all`)."""
+        with _LIVE_LOCK:
+            others = [c for c in _LIVE.get(self.device.index, ()) if c is not self and getattr(c, '_worker', None) is not None]
+        for other in others:
+            other.drain()
+        torch.cuda.synchronize(self.device)
+        for slot in self._slots:
+            slot.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(slot.graph, stream=slot.lane.stream, capture_error_mode='thread_local'):
+                self._launch_step(slot)
+
+    def _launch_step(self, slot):
+        """The step of `slot` on the current stream: one chain, no argument of which depends on the step's contents."""
+        lane = slot.lane
+        streams = lane.coder_streams
+        dev.fetch_prefix(slot.pinned_head, lane.head, lane.head_bytes)                      # the head: a fixed size
+        dev.fetch_prefix(slot.pinned_payload, lane.payload, lane.payload_bytes)             # the payload: the bytes the head announces
+        lane.results[:2].copy_(lane.head_bits.view(-1, 2).t())                              # [n_maps][2] -> the coder's two arrays
+        dev.coder_index_streams(streams, self.nb_maps, self.payload_capacity_bytes, offsets=lane.offsets, index=lane.index)
+        dev.coder_unpack_into(streams, lane.payload, lane.offsets)
+        dev.coder_decode_batch(streams, lane.table, lane.prob_row, workspace=lane.workspace, out=lane.symbols.view(-1, self.map_size))
+        dev.dequantize_maps_rows(lane.symbols, lane.bin_widths, lane.map_mean, out_shifted=lane.shifted)
+        self.decoder.model.decode_into(lane.shifted, slot.planes, lane.scratch)
+        if slot.pinned_rec is not None:
+            dev.publish_to_host(slot.planes, slot.pinned_rec)
+        dev.publish_to_host(lane.unfinished, slot.pinned_unfinished)
+        dev.publish_step(lane.status, slot.pinned_status, lane.status.numel(), slot.seq_dev[1:2], slot.seq_dev[0:1], slot.pinned_seq)
+
+    def drain(self):
+        """Waits until every submitted step is through."""
+        torch.cuda.synchronize(self.device)
+        for slot in self._slots:
+            slot.free.wait()
+
+    def close(self):
+        """Waits for the pending steps and joins the result worker. Idempotent."""
+        if getattr(self, '_worker', None) is None:
+            return
+        try:
+            self.drain()
+        finally:
+            self._worker.jobs.put(None)
+            self._worker.join()
+            self._worker = None
+            with _LIVE_LOCK:
+                _LIVE.get(self.device.index, weakref.WeakSet()).discard(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, traceback):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
             pass

@@ -184,6 +184,22 @@ class Model(object):
         self._track(scratch)
         return out_f32, out_u8, sse
 
+    def decode_scratch(self, n, h, wd):
+        """A scratch block `decode_into` can use for latents f32 [n, h, wd, 128], and the view of its failure word (int32 [1]: tiles a
+        cut conv launch left unfinished; zeroed by every call, final behind it)."""
+        scratch = torch.empty(int(_native.hip().eae_hip_decode_scratch_bytes(n, h, wd)), dtype=torch.uint8, device=self.device)
+        return scratch, scratch[self._status_offset:self._status_offset + 4].view(torch.int32)
+
+    def decode_into(self, quantized_latents, out_u8, scratch):
+        """`decode(...)` for a caller that owns every buffer (codec.BatchDecoder: one per slot, inside a captured step): nothing is
+        allocated, no event is recorded and nothing is tracked -- the caller publishes the scratch block's failure word
+        (`decode_scratch`) and looks at it itself."""
+        (n, h, wd, c) = quantized_latents.shape
+        if out_u8.dtype != torch.uint8 or out_u8.numel() != n*16*h*16*wd or c != NB_MAPS:
+            raise HipError('`out_u8` must hold N x 16h x 16w uint8 elements')
+        _check(_native.hip().eae_hip_decode(self._handle, _p(quantized_latents), n, h, wd, None, _p(out_u8), None, None, _p(scratch),
+                                            scratch.numel(), _stream(quantized_latents)), 'eae_hip_decode')
+
 
 def conv9x9s4_u8(x_u8, w_packed, bias, gamma_packed=None, beta=None, out=None):
     """conv_1 + bias_add (+ gdn_1). x_u8: uint8 [N,H,W] or [N,H,W,1] -> f32 [N,H/4,W/4,128].
@@ -809,6 +825,14 @@ def coder_unpack_streams(payload, offsets, bac_bits, bypass_bits, map_size, trun
     return streams
 
 
+def coder_unpack_into(streams, payload, offsets):
+    """`coder_unpack_streams` into an existing CoderStreams whose bit counts are already on the device (`offsets` int64 [n_maps, 2])."""
+    if payload.dtype != torch.uint8 or offsets.dtype != torch.int64 or offsets.numel() != 2*streams.n_maps:
+        raise HipError('`payload` must be uint8 and `offsets` hold 2 n_maps int64 words')
+    _check(_native.hip().eae_hip_coder_unpack_streams(streams.n_maps, _p(payload), _p(offsets), _p(streams.bac_bits), _p(streams.bypass_bits),
+                                                      _p(streams.streams), streams.stride, _stream(payload)), 'eae_hip_coder_unpack_streams')
+
+
 def dequantize_maps(symbols_planar, bin_widths, map_mean=None, want_cq=False, want_shifted=True):
     """int16 symbols [N, 128, hw] -> float32 [N, hw, 128]: bw * symbol (and + map_mean), the arrays quantize_maps produced."""
     (n, c, hw) = symbols_planar.shape
@@ -880,6 +904,40 @@ def exception_rows(hist, overflow, map_size, truncated_unary_length, out=None):
     _check(_native.hip().eae_hip_exception_rows(n, _p(hist), _p(overflow), (width - 1)//2, int(map_size), int(truncated_unary_length),
                                                 _p(out), _stream(hist)), 'eae_hip_exception_rows')
     return out
+
+
+# ---- the pipelined decoder's own launches (include/eae_hip.h, csrc/hip/codec_decode.hip) --------------------------------------
+
+def fetch_prefix(src_pinned, dst_device, nbytes_device):
+    """Stream-ordered copy, by a kernel, of the first `nbytes_device[0]` bytes (an int64 device word; at most the buffers' size) of
+    the pinned host tensor `src_pinned` into `dst_device`, rounded up to 16 bytes; the rest of `dst_device` is not written. Both
+    uint8-sized alike, a multiple of 16 bytes. The mirror of `publish_prefix`."""
+    capacity = dst_device.numel()*dst_device.element_size()
+    if not src_pinned.is_pinned() or src_pinned.numel()*src_pinned.element_size() != capacity or not src_pinned.is_contiguous() or capacity % 16:
+        raise HipError('expected a contiguous pinned host tensor of the same size, a multiple of 16 bytes')
+    if nbytes_device.numel() != 1 or nbytes_device.element_size() != 8:
+        raise HipError('expected one 64-bit word')
+    _check(_native.hip().eae_hip_fetch_prefix(src_pinned.data_ptr(), _p(dst_device), capacity, _p(nbytes_device), _stream(dst_device)),
+           'eae_hip_fetch_prefix')
+
+
+def dequantize_maps_rows(symbols_planar, bin_widths_rows, map_mean_rows=None, want_cq=False, want_shifted=True, out_cq=None, out_shifted=None):
+    """`dequantize_maps` with one row of bin widths and means per image: int16 symbols [N, 128, hw], float32 rows [N, 128] ->
+    float32 [N, hw, 128], bit-identical to `dequantize_maps` image by image. `out_cq` / `out_shifted`: preallocated outputs."""
+    (n, c, hw) = symbols_planar.shape
+    device = symbols_planar.device
+    if symbols_planar.dtype != torch.int16 or bin_widths_rows.dtype != torch.float32 or bin_widths_rows.numel() != n*c:
+        raise HipError('expected int16 symbols [N, 128, hw] and float32 bin widths [N, 128]')
+    if map_mean_rows is not None and (map_mean_rows.dtype != torch.float32 or map_mean_rows.numel() != n*c):
+        raise HipError('expected float32 means [N, 128]')
+    for out in (out_cq, out_shifted):
+        if out is not None and (out.dtype != torch.float32 or out.numel() != n*hw*c):
+            raise HipError('an output must hold N x hw x 128 float32')
+    cq = out_cq if out_cq is not None else (torch.empty((n, hw, c), dtype=torch.float32, device=device) if want_cq else None)
+    shifted = out_shifted if out_shifted is not None else (torch.empty((n, hw, c), dtype=torch.float32, device=device) if want_shifted else None)
+    _check(_native.hip().eae_hip_dequantize_maps_rows(_p(symbols_planar), _p(bin_widths_rows), _p(map_mean_rows), _p(cq), _p(shifted), n, hw, c,
+                                                      _stream(symbols_planar)), 'eae_hip_dequantize_maps_rows')
+    return {'cq': cq, 'shifted': shifted}
 
 
 # ---- SVHN float64 path (include/eae_hip.h, "SVHN path") -------------------------------------------------------------

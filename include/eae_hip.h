@@ -463,6 +463,23 @@ int eae_hip_publish_prefix(const void* src_device, void* dst_host_mapped, uint64
 int eae_hip_exception_rows(int n, const uint32_t* hist, const uint32_t* overflow, int radius, int map_size, int length,
                            double* rows_out, void* stream);
 
+/* ---- the pipelined decoder's own launches (csrc/hip/codec_decode.hip) -----------------------------
+ * The rest of a codec.BatchDecoder step is index_streams, unpack_streams, coder_decode_batch, eae_hip_decode and the publish
+ * launches above. Both are asynchronous on `stream` and have no argument the host computes from the step's contents, so a step
+ * can be captured into one hipGraph.
+ * fetch_prefix: the mirror of publish_prefix: the first ceil(min(*nbytes_device, capacity_bytes) / 16) 16-byte words of pinned,
+ *   device-mapped host memory into dst_device; no byte at or beyond that length is written. *nbytes_device is read on the device
+ *   (a word an earlier launch of the stream left there). Both buffers hold capacity_bytes (a multiple of 16) and are 16-byte
+ *   aligned, nbytes_device 8-byte aligned, else EAE_HIP_BAD_ARGUMENT.
+ * dequantize_maps_rows: eae_hip_dequantize_maps with one row of bin widths and means per image: bin_widths_rows and
+ *   map_mean_rows (nullable) are f32 [n][128]. Image i's outputs are bit-identical to eae_hip_dequantize_maps of that image with
+ *   row i. The outputs leave as 16-byte stores: cq_out / shifted_out (each nullable, not both) 16-byte aligned and n <= 65535,
+ *   else EAE_HIP_BAD_SHAPE. */
+int eae_hip_fetch_prefix(const void* src_host_mapped, void* dst_device, uint64_t capacity_bytes, const uint64_t* nbytes_device,
+                         void* stream);
+int eae_hip_dequantize_maps_rows(const int16_t* symbols_planar, const float* bin_widths_rows, const float* map_mean_rows,
+                                 float* cq_out, float* shifted_out, int n, int hw, int c, void* stream);
+
 /* ==== TEST HOOKS (-DEAE_TEST_HOOKS): NOT exported by the product library lib/libeae_hip.so ====================================
  * Four entry points the test-suite needs and a deployment must not have (they change what later launches do, or only
  * exist to prove something about the kernels). Compiled into lib/libeae_hip_test.so only; tests/test_abi.py checks that
