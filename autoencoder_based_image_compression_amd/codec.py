@@ -169,17 +169,20 @@ class Ticket(object):
 
     def container(self):
         """Blocks like `result()` (and raises the step's error like it); the batch as one `EAE1` blob (container.py), the bytes
-        `container.encode_images` gives for the same images. The codec has decoded every stream in it and compared the symbols.
+        `container.encode_images` gives for the same images (`EAT1`, and `encode_images(..., coding_tile=...)`, with
+        `BatchCodec(coding_tile=...)`). The codec has decoded every stream in it and compared the symbols.
         Raises `ContainerOverflow` when the payload did not fit `container_capacity_bytes`. Only with
         `BatchCodec(emit_container=True)`; before or after `result()`."""
         parts = self._parts()
-        return container_format.assemble_blob(*(parts['head'] + (parts['rows'], parts['bits'], parts['payload'])))[0]
+        return container_format.assemble_blob(*(parts['head'] + (parts['rows'], parts['bits'], parts['payload'])),
+                                              coding_tile=parts['coding_tile'])[0]
 
     def image_containers(self):
-        """Like `container()`: one single-image `EAE1` blob per image of the batch (the payload is image-major: slices of the
-        batch's, each behind its own header)."""
+        """Like `container()`: one single-image `EAE1` (`EAT1`) blob per image of the batch (the payload is image-major: slices of
+        the batch's, each behind its own header)."""
         parts = self._parts()
-        return container_format.assemble_image_blobs(*(parts['head'] + (parts['rows'], parts['bits'], parts['payload'])))
+        return container_format.assemble_image_blobs(*(parts['head'] + (parts['rows'], parts['bits'], parts['payload'])),
+                                                     coding_tile=parts['coding_tile'])
 
 
 class ContainerOverflow(RuntimeError):
@@ -353,8 +356,12 @@ class _StepWorker(threading.Thread):
 class _Worker(_StepWorker):
     """The result worker of `BatchCodec`."""
 
-    def __init__(self, map_size, nb_maps, host_probabilities, idx_map_exception, host_threads):
+    def __init__(self, map_size, nb_maps, host_probabilities, idx_map_exception, host_threads, coding_tile=None, payload_order=None):
+        """coding_tile, payload_order: of a codec that codes in tiles (`coding_tile_layout`): the slot's results are in run order,
+        and `payload_order` (int64, one index per stream) takes them into the order of the payload."""
         super(_Worker, self).__init__()
+        self.coding_tile = coding_tile
+        self.payload_order = payload_order
         self.map_size = map_size
         self.nb_maps = nb_maps
         self.host_probabilities = host_probabilities
@@ -439,6 +446,10 @@ class _Worker(_StepWorker):
                                                                        roundtrip=True, verify_only=True)
                 results = numpy.zeros_like(results)
                 results[0] = nb_bits.reshape(-1)
+            if self.payload_order is not None:
+                # the coder's batches keep the tiles of one shape side by side; everything below (the first failing stream, the sums
+                # per image, the container's bit counts) is in the payload's order: image -> tile -> map
+                results = results.take(self.payload_order, axis=1)
             status = results[2]
             exception_coded = job.emit is not None and self.idx_map_exception >= 0
             container_error = None
@@ -459,10 +470,10 @@ class _Worker(_StepWorker):
             if 'error' in early:
                 raise early['error']
             n = ticket.nb_images
-            map_bits = (results[0].astype(numpy.int64) + results[1].astype(numpy.int64)).reshape(n, self.nb_maps)
+            map_bits = (results[0].astype(numpy.int64) + results[1].astype(numpy.int64)).reshape(n, -1, self.nb_maps)      # [image, tile, map]
             if exception_coded:
-                map_bits[:, self.idx_map_exception] = 0          # charged by its entropy, as without `emit_container`
-            coder_bits = map_bits.sum(axis=1)
+                map_bits[:, :, self.idx_map_exception] = 0       # charged by its entropy, as without `emit_container`
+            coder_bits = map_bits.sum(axis=(1, 2))
             exception_bits = early['exception_bits']
             ticket._values = {'nb_bits': coder_bits + exception_bits, 'coder_bits': coder_bits,
                               'exception_bits': exception_bits, 'sse': early['sse'], 'nb_deads': early['nb_deads']}
@@ -472,7 +483,7 @@ class _Worker(_StepWorker):
                 payload_bytes = int(index[0])
                 ticket._values['container_bytes'] = index[2:].astype(numpy.int64)
                 ticket._container_parts = {
-                    'head': head, 'capacity': capacity, 'payload_bytes': payload_bytes, 'error': container_error,
+                    'head': head, 'capacity': capacity, 'payload_bytes': payload_bytes, 'error': container_error, 'coding_tile': self.coding_tile,
                     'rows': rows.copy() if self.idx_map_exception >= 0 else rows[:0].copy(),
                     'bits': numpy.stack([results[0], results[1]], axis=1).astype(numpy.uint32),
                     'payload': payload[:payload_bytes].tobytes() if int(index[1]) == 0 else None}
@@ -558,26 +569,65 @@ def _no_hook(name, fn):
     return fn()
 
 
+def coding_tile_layout(batch_size, h, w, coding_tile, idx_map_exception=-1):
+    """Where everything of a step of `BatchCodec(coding_tile=...)` lies; numpy only, the same for every step of a codec (DESIGN.md
+    section 15). batch_size images of an h x w latent plane, coding_tile=(th, tw) latents, clamped to the plane. An ENTRY is one
+    (image, tile): 128 maps, 128 pairs of streams. The payload, the header's bit counts and the results take the entries in
+    PAYLOAD order (image -> tile, row-major); the coder takes the entries of one shape class as one batch of maps of one size, so
+    the symbols, the streams, the coder's results and the offsets lie in RUN order: class after class, payload order within a
+    class -- `container._group_layout` of the one group that holds every entry of the step. -> dict:
+    'coding_tile' (clamped), 'nb_tiles', 'tiles' and 'classes' (`container.coding_tile_grid`), 'entries' [(image, tile)] in payload
+    order, 'runs' [((rows, cols) of the class, entries, first stream, first symbol element)], class runs starting on 128-element
+    boundaries, 'elements' of the symbol buffer, 'offsets' int64 [entries] (element offset of every payload-order entry's map 0),
+    'plan' int64 [entries, 6] (the rows of `device.tile_symbols_gather`), 'prob_row' int32 [n_streams] in run order (map m -> row
+    m, the exception map of image i -> row 128 + i), 'run_entry' int64 [entries] (run-order index of every payload-order entry),
+    'payload_entry' (its inverse), 'payload_order' int64 [n_streams] (run-order stream of every payload-order stream: what
+    `numpy.take` turns run-order results into payload order with), 'n_streams' = batch_size * nb_tiles * 128."""
+    batch_size = container_format._positive_int(batch_size, '`batch_size`')
+    (th, tw) = container_format._positive_pair(coding_tile, '`coding_tile`')
+    coding_tile = (min(th, h), min(tw, w))
+    (tiles, classes) = container_format.coding_tile_grid(h, w, coding_tile)
+    nb_tiles = tiles.shape[0]
+    nb_maps = csts.NB_MAPS_3
+    entries = [(i, t) for i in range(batch_size) for t in range(nb_tiles)]
+    (group_runs, offsets, elements) = container_format._group_layout(entries, tiles, classes)
+    payload_entry = numpy.concatenate([numpy.asarray(ks, dtype=numpy.int64) for (_, ks, _) in group_runs])
+    run_entry = numpy.empty(len(entries), dtype=numpy.int64)
+    run_entry[payload_entry] = numpy.arange(len(entries), dtype=numpy.int64)
+    (runs, first_entry) = ([], 0)
+    for (cls, ks, first_element) in group_runs:
+        runs.append((tuple(classes[cls]), len(ks), first_entry*nb_maps, int(first_element)))
+        first_entry += len(ks)
+    prob_row = numpy.concatenate([container_format._prob_rows(entries, ks, idx_map_exception) for (_, ks, _) in group_runs])
+    payload_order = (run_entry[:, None]*nb_maps + numpy.arange(nb_maps, dtype=numpy.int64)[None, :]).reshape(-1)
+    return {'coding_tile': coding_tile, 'nb_tiles': nb_tiles, 'tiles': tiles, 'classes': classes, 'entries': entries, 'runs': runs,
+            'elements': int(elements), 'offsets': offsets, 'plan': container_format._symbols_plan(entries, tiles, offsets),
+            'prob_row': prob_row.astype(numpy.int32), 'run_entry': run_entry, 'payload_entry': payload_entry,
+            'payload_order': payload_order, 'n_streams': len(entries)*nb_maps}
+
+
 class _Slot(object):
     """Everything one step in flight owns; `BatchCodec` goes round `nb_slots` of them. Made once: no launch and no submit cuts a view."""
     __slots__ = ('block', 'out', 'results', 'hist', 'overflow', 'flags', 'checks', 'sse', 'unfinished', 'pinned_out', 'pinned_sse',
                  'host_views', 'symbols', 'symbols_2d', 'coder_streams', 'workspace', 'conv_ws', 'seq_dev', 'pinned_seq', 'seq_host',
                  'coder_seq', 'synthesis_seq', 'counts', 'free', 'pinned_symbols', 'staging', 'pinned_rec', 'graphs', 'table', 'exception_rows',
-                 'index', 'payload_bytes', 'offsets', 'payload', 'pinned_payload', 'emit_tail', 'pinned_emit', 'emit_host')
+                 'index', 'payload_bytes', 'offsets', 'payload', 'pinned_payload', 'emit_tail', 'pinned_emit', 'emit_host', 'gathered',
+                 'classes')
 
     def __init__(self, codec):
         (batch_size, nb_maps, device) = (codec.batch_size, codec.nb_maps, codec.device)
         n_maps = batch_size*nb_maps
+        n_streams = codec._n_streams      # pairs of streams the coder leaves results for: n_maps, times the tiles of a map with a coding tile
         nb_hist = batch_size if codec.idx_map_exception >= 0 else 0
         hist_width = 2*codec.hist_radius + 1
-        layout = (4*n_maps, nb_hist*hist_width, nb_hist, n_maps, 4)
+        layout = (4*n_streams, nb_hist*hist_width, nb_hist, n_maps, 4)
         nb_words = sum(layout)
         assert nb_words % 2 == 0
 
         def cut(block):
-            """[coder results 4 x n_maps | exception histograms | overflow | flags | checks(4)], on the device or in pinned memory."""
+            """[coder results 4 x n_streams | exception histograms | overflow | flags | checks(4)], on the device or in pinned memory."""
             (results, hist, overflow, flags, checks) = torch.split(block, layout)
-            return (results.view(4, n_maps), hist.view(nb_hist, hist_width) if nb_hist else hist, overflow, flags.view(batch_size, nb_maps), checks)
+            return (results.view(4, n_streams), hist.view(nb_hist, hist_width) if nb_hist else hist, overflow, flags.view(batch_size, nb_maps), checks)
 
         # the block for the host, followed by the squared errors (int64 per image, published on their own once the synthesis
         # transform is through) and behind them one more 64-bit word whose low half is the conv workspace's error word of the step
@@ -592,9 +642,28 @@ class _Slot(object):
         self.host_views = tuple(t.numpy() for t in cut(self.pinned_out) + (self.pinned_sse,))
         self.symbols = torch.empty((batch_size, nb_maps, codec.map_size), dtype=torch.int16, device=device)
         self.symbols_2d = self.symbols.view(n_maps, codec.map_size)
-        self.coder_streams = dev.CoderStreams(n_maps, codec.map_size, codec.truncated_unary_length, device, results=self.results)
-        make_workspace = dev.coder_trailing_workspace if codec.coder_chunks > 1 else dev.coder_workspace
-        self.workspace = make_workspace(n_maps, codec.map_size, codec.truncated_unary_length, device)
+        (self.gathered, self.classes) = (None, None)
+        if codec.coding_tile is None:
+            self.coder_streams = dev.CoderStreams(n_maps, codec.map_size, codec.truncated_unary_length, device, results=self.results)
+            make_workspace = dev.coder_trailing_workspace if codec.coder_chunks > 1 else dev.coder_workspace
+            self.workspace = make_workspace(n_maps, codec.map_size, codec.truncated_unary_length, device)
+        else:
+            # The step's (image, tile) entries in run order (`coding_tile_layout`): the tile-major symbols, and per shape class one
+            # batch of streams whose results are that class's columns of the ONE results block; the classes run one after the other
+            # on the step's coder stream, so one workspace of the largest class serves them all.
+            tiled = codec._tile_layout
+            self.coder_streams = None
+            # (one tile per map: the planar symbols ARE the tile-major buffer, and nothing is gathered)
+            self.gathered = self.symbols.view(-1) if tiled['nb_tiles'] == 1 else torch.empty(tiled['elements'], dtype=torch.int16, device=device)
+            self.offsets = torch.zeros((n_streams, 2), dtype=torch.int64, device=device)
+            (self.classes, need) = ([], 0)
+            for ((rows, cols), count, first_stream, first_element) in tiled['runs']:
+                (n, size) = (count*nb_maps, rows*cols)
+                streams = dev.CoderStreams(n, size, codec.truncated_unary_length, device, results=self.results[:, first_stream:first_stream + n])
+                self.classes.append((streams, self.gathered[first_element:first_element + n*size].view(n, size),
+                                     codec._tile_prob_row[first_stream:first_stream + n], self.offsets[first_stream:first_stream + n]))
+                need = max(need, dev.coder_workspace_bytes(n, size, codec.truncated_unary_length))
+            self.workspace = torch.empty(need, dtype=torch.uint8, device=device)
         # scratch that lets the conv GEMM launches cut their last tiles (device.conv_workspace): a slot's launches never overlap each other
         self.conv_ws = dev.conv_workspace(device)
         # step counters: [coder side, synthesis side] on the device (+ the two ticket words of device.publish_step), their published
@@ -627,7 +696,8 @@ class _Slot(object):
             self.payload_bytes = self.index[0:1]
             self.emit_tail = block[table_words:]
             self.pinned_emit = torch.zeros(row_words + 2 + batch_size, dtype=torch.float64).pin_memory()
-            self.offsets = torch.zeros((n_maps, 2), dtype=torch.int64, device=device)
+            if codec.coding_tile is None:
+                self.offsets = torch.zeros((n_maps, 2), dtype=torch.int64, device=device)
             self.payload = torch.zeros(codec.container_capacity_bytes, dtype=torch.uint8, device=device)
             self.pinned_payload = torch.zeros(codec.container_capacity_bytes, dtype=torch.uint8).pin_memory()
             # what the result worker copies from (`_Job.emit`)
@@ -642,7 +712,7 @@ class BatchCodec(object):
                  batch_size, h_in, w_in, device='cuda', nb_in_flight=None, keep_reconstruction=False, launch_hook=None,
                  coder='device', host_coder_threads=0, hist_radius=2047, nb_transform_streams=1, use_graphs=False,
                  time_coder=False, fuse_latent=False, fetch_reconstruction=False, coder_chunks=None, one_stream_steps=False,
-                 emit_container=False, container_capacity_bytes=None):
+                 emit_container=False, container_capacity_bytes=None, coding_tile=None):
         """coder: 'device' (the coder kernels on side streams), 'host' (ONE device -> host copy of the symbols per batch, then
         the host C-ABI coder `eae_coder_compress_maps` on `host_coder_threads` threads: the shape BASELINE.json sketches) or
         'none' (transforms only; the bit counts come back as zeros).
@@ -679,13 +749,36 @@ class BatchCodec(object):
         coded too (with a row measured on it, as `container.encode_images` does), which needs `hist_radius >= L`. Needs the device coder.
         container_capacity_bytes: the payload bytes a step may take (rounded up to 16; a device and a pinned buffer of that size per
         slot). None: batch_size*h_in*w_in, i.e. 8 bits per pixel. A step beyond it keeps its results; its `Ticket.container()` raises
-        `ContainerOverflow`."""
+        `ContainerOverflow`.
+        coding_tile: (th, tw) in latents, with `emit_container`: every (image, tile, map) is coded as its own pair of streams and
+        the step's container is the tile-indexed `EAT1` -- `Ticket.container()` / `image_containers()` are byte for byte what
+        `container.encode_images(..., coding_tile=(th, tw))` writes, so `container.decode_region` reads a crop out of them. The tile
+        is clamped to the latent plane. 'coder_bits' sums an image's tiles (every tile's streams pay their own termination, so it is
+        larger than without tiles); 'sse', 'nb_deads' and 'exception_bits' do not change. The serial chains are then a tile long
+        instead of a map. At most 65,535 (image, tile) pairs per step; not with `coder_chunks`."""
         if coder not in ('device', 'host', 'none'):
             raise ValueError('`coder` is neither "device" nor "host" nor "none".')
         if use_graphs and coder == 'host':
             raise ValueError('`use_graphs` needs the coder on the device (or none).')
         if h_in % csts.STRIDE_PROD != 0 or w_in % csts.STRIDE_PROD != 0:
             raise ValueError('The image size is not divisible by the product of the three strides.')
+        self.coding_tile = None
+        if coding_tile is not None:
+            # refused in front of every allocation
+            if not emit_container:
+                raise ValueError('`coding_tile` needs `emit_container=True`: the tiles are those of the step\'s `EAT1` container.')
+            if coder != 'device':
+                raise ValueError('`coding_tile` needs the coder on the device.')
+            if int(default_coder_chunks(batch_size*csts.NB_MAPS_3) if coder_chunks is None else coder_chunks) > 1:
+                raise ValueError('`coding_tile` does not go with `coder_chunks` > 1: the chunked coder codes whole maps.')
+            coding_tile = container_format._positive_pair(coding_tile, '`coding_tile`')
+            if max(coding_tile) > 0xFFFF:
+                raise ValueError('A side of `coding_tile` does not fit the container (65535 latents at most).')
+            (h_map, w_map) = (h_in//csts.STRIDE_PROD, w_in//csts.STRIDE_PROD)
+            self.coding_tile = (min(coding_tile[0], h_map), min(coding_tile[1], w_map))
+            if batch_size*container_format._nb_tiles(h_map, w_map, self.coding_tile) > 65535:
+                raise ValueError('`batch_size` images of {0} coding tiles each are more than the 65535 (image, tile) pairs a step can hold.'.format(
+                    container_format._nb_tiles(h_map, w_map, self.coding_tile)))
         self.device = torch.device(device)
         if self.device.index is None:
             self.device = torch.device('cuda', torch.cuda.current_device())
@@ -747,6 +840,20 @@ class BatchCodec(object):
         self.launch_hook = launch_hook if launch_hook is not None else _no_hook
         n_maps = batch_size*self.nb_maps
         self._n_maps = n_maps
+        self._n_streams = n_maps          # pairs of streams per step: what sizes the head of a slot's result block
+        self._tile_layout = None
+        if self.coding_tile is not None:
+            # everything a step in tiles needs beyond its symbols is the same for every step: made once, shared by the slots
+            tiled = coding_tile_layout(batch_size, h_in//csts.STRIDE_PROD, w_in//csts.STRIDE_PROD, self.coding_tile, self.idx_map_exception)
+            self._tile_layout = tiled
+            self._n_streams = tiled['n_streams']
+            self._tile_plan_host = tiled['plan']
+            self._tile_plan = torch.from_numpy(tiled['plan']).to(self.device)
+            self._tile_prob_row = torch.from_numpy(tiled['prob_row']).to(self.device)
+            # `device.coder_index_tiles`: per payload-order entry, its run-order index and half the stream stride of its class
+            half_stride = numpy.array([dev.coder_stream_stride_bytes(int(tiled['tiles'][t, 2]*tiled['tiles'][t, 3]), self.truncated_unary_length)//2
+                                       for (_, t) in tiled['entries']], dtype=numpy.int64)
+            self._tile_table = torch.from_numpy(numpy.stack([tiled['run_entry'], half_stride], axis=1)).to(self.device)
         if nb_in_flight is None:
             nb_in_flight = default_nb_in_flight(h_in, w_in)
         if coder == 'device' and not one_stream_steps and os.environ.get('EAE_IGNORE_HW_QUEUES') != '1':
@@ -790,7 +897,7 @@ class BatchCodec(object):
         assert not self.use_graphs or self._transform_streams      # replays never go to the caller's stream
         # last but one: a constructor that raised above has no worker yet, and `close()` has nothing to wait for
         self._worker = _Worker(self.map_size, self.nb_maps, probabilities if coder == 'host' else None, self.idx_map_exception,
-                               host_coder_threads)
+                               host_coder_threads, self.coding_tile, self._tile_layout['payload_order'] if self._tile_layout else None)
         self._worker.start()
         # last: a constructor that raised above leaves nothing half-built behind for another codec's `_capture_all` to drain
         with _LIVE_LOCK:
@@ -1009,7 +1116,7 @@ class BatchCodec(object):
             torch.cuda.synchronize(self.device)
             slot.counts = [int(v) for v in slot.seq_dev[:2].cpu().tolist()]
             slot.seq_dev[2:].zero_()                    # ticket words of a publish that never ran to its end
-            slot.block[4*self._n_maps:].zero_()         # accumulators a publish would have cleared
+            slot.block[4*self._n_streams:].zero_()      # accumulators a publish would have cleared
         except Exception:      # the device itself is in trouble: the next submit will say so
             pass
 
@@ -1064,7 +1171,7 @@ class BatchCodec(object):
             # The analysis side's blocks are final here and reach pinned memory at once (the coder's publication, which also zeroes them
             # for the slot's next step, copies them again): in FRONT of the event the coder's stream waits for, so the zeroing cannot
             # overtake this copy. The host looks at them when the synthesis side has reported (`_Worker.process`).
-            first = 4*self._n_maps
+            first = 4*self._n_streams
             dev.publish_to_host(slot.out[first:], slot.pinned_out[first:])
         return q['shifted'] if self.learned else q['t']
 
@@ -1078,6 +1185,24 @@ class BatchCodec(object):
             if self.idx_map_exception >= 0:
                 # the histograms are final since the analysis side and are zeroed only by this side's `publish_step` below
                 dev.exception_rows(slot.hist, slot.overflow, self.map_size, self.truncated_unary_length, out=slot.exception_rows)
+        if self.coding_tile is not None:
+            # (image, tile) entries instead of whole maps: the symbols tile-major, one coder batch per shape
+            # class, then the index over all of them and one pack per class into the one payload
+            length = self.truncated_unary_length
+            if slot.gathered.data_ptr() != slot.symbols.data_ptr():
+                dev.tile_symbols_gather(slot.symbols, slot.gathered, self._tile_plan, self._tile_plan_host, self.h_in//csts.STRIDE_PROD,
+                                        self.w_in//csts.STRIDE_PROD)
+            for (streams, tiles, rows, _) in slot.classes:
+                hook('coder_encode', lambda: dev.coder_encode_batch(tiles, table, rows, length, out=streams, workspace=slot.workspace))
+                hook('coder_decode', lambda: dev.coder_decode_batch(streams, table, rows, expected=tiles, workspace=slot.workspace))
+            dev.coder_index_tiles(slot.results[0], slot.results[1], self._tile_table, self.nb_maps, self._tile_layout['nb_tiles'],
+                                  self.container_capacity_bytes, offsets=slot.offsets, index=slot.index)
+            for (streams, _, _, offsets) in slot.classes:
+                dev.coder_pack_indexed(streams, offsets, slot.index, slot.payload)
+            dev.publish_prefix(slot.payload, slot.pinned_payload, slot.payload_bytes)
+            dev.publish_to_host(slot.emit_tail, slot.pinned_emit)
+            dev.publish_step(slot.out, slot.pinned_out, 4*self._n_streams, *slot.coder_seq)
+            return
         if self.coder == 'device' and self.coder_chunks > 1:
             hook('coder_roundtrip', lambda: dev.coder_roundtrip_trailing(symbols, table, prob_row, self.truncated_unary_length,
                                                                          chunks=self.coder_chunks, out=slot.coder_streams, workspace=slot.workspace))
@@ -1097,7 +1222,7 @@ class BatchCodec(object):
             dev.coder_pack_indexed(slot.coder_streams, slot.offsets, slot.index, slot.payload)
             dev.publish_prefix(slot.payload, slot.pinned_payload, slot.payload_bytes)
             dev.publish_to_host(slot.emit_tail, slot.pinned_emit)
-        dev.publish_step(slot.out, slot.pinned_out, 4*self._n_maps, *slot.coder_seq)
+        dev.publish_step(slot.out, slot.pinned_out, 4*self._n_streams, *slot.coder_seq)
 
     def _launch_synthesis_head(self, latents, slot, hook):
         """tconv1+IGDN5 on the current stream (the first launch of the synthesis side, apart: `_coder_behind_tconv1`)."""

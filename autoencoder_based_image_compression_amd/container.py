@@ -118,40 +118,58 @@ def _pack_header(fields, bits):
                      fields['exception_probabilities'].tobytes(), bits.tobytes()])
 
 
+def _clamped_coding_tile(coding_tile, height, width):
+    """A coding tile to write: a pair of positive integers, clamped to the latent plane of a height x width image; its sides must fit
+    the header's 16 bits."""
+    coding_tile = _positive_pair(coding_tile, '`coding_tile`')
+    coding_tile = (min(coding_tile[0], height//csts.STRIDE_PROD), min(coding_tile[1], width//csts.STRIDE_PROD))
+    if max(coding_tile) > 0xFFFF:
+        raise ValueError('A coding tile side does not fit the container (65535 latents at most).')
+    return coding_tile
+
+
 def assemble_blob(are_bin_widths_learned, nb_images, height, width, idx_map_exception, bin_widths, map_mean, binary_probabilities,
-                  exception_rows, bits, payload):
+                  exception_rows, bits, payload, coding_tile=None):
     """The EAE1 blob (module docstring) from its parts -> (blob bytes, header bytes). bin_widths / map_mean float32 [nb_maps],
     binary_probabilities float64 [nb_maps, L], exception_rows float64 [nb_images, L] ([0, L] without an exception map), bits
     uint32 [nb_images*nb_maps, 2], payload bytes-like. What a `codec.Ticket` builds its containers with from the pinned blocks of
-    its step; `encode_images` packs the same header."""
+    its step; `encode_images` packs the same header.
+    coding_tile=(th, tw) latents (clamped to the latent plane as `encode_images` clamps it): the EAT1 blob instead; bits uint32
+    [nb_images*nb_tiles*nb_maps, 2] in payload order (image -> tile, row-major -> map)."""
     (nb_maps, truncated_unary_length) = binary_probabilities.shape
     nb_rows = nb_images if idx_map_exception >= 0 else 0
+    nb_tiles = 1
+    if coding_tile is not None:
+        coding_tile = _clamped_coding_tile(coding_tile, height, width)
+        nb_tiles = _nb_tiles(height//csts.STRIDE_PROD, width//csts.STRIDE_PROD, coding_tile)
     if bin_widths.dtype != numpy.float32 or map_mean.dtype != numpy.float32 or bin_widths.shape != (nb_maps,) or map_mean.shape != (nb_maps,):
         raise ValueError('`bin_widths` and `map_mean` must be float32 with one element per map.')
     if binary_probabilities.dtype != numpy.float64 or exception_rows.dtype != numpy.float64 or bits.dtype != numpy.uint32:
         raise ValueError('The probabilities must be float64 and the bit counts uint32.')
-    if exception_rows.shape != (nb_rows, truncated_unary_length) or bits.shape != (nb_images*nb_maps, 2):
+    if exception_rows.shape != (nb_rows, truncated_unary_length) or bits.shape != (nb_images*nb_tiles*nb_maps, 2):
         raise ValueError('The exception rows or the bit counts do not have the shape the header announces.')
-    if len(payload) != int(_entry_bytes(bits.reshape(nb_images, nb_maps, 2)).sum()):
+    if len(payload) != int(_entry_bytes(bits.reshape(nb_images*nb_tiles, nb_maps, 2)).sum()):
         raise ValueError('The payload size does not match the bit counts.')
     header = _pack_header(_fields(are_bin_widths_learned, nb_images, height, width, idx_map_exception, bin_widths, map_mean,
-                                  binary_probabilities, exception_rows), bits)
+                                  binary_probabilities, exception_rows, coding_tile), bits)
     return (header + bytes(payload), len(header))
 
 
 def assemble_image_blobs(are_bin_widths_learned, nb_images, height, width, idx_map_exception, bin_widths, map_mean, binary_probabilities,
-                         exception_rows, bits, payload):
+                         exception_rows, bits, payload, coding_tile=None):
     """The parts of a batch's blob (`assemble_blob`) -> one single-image blob per image: the payload is image-major, so an image's
     blob is its slice of the bit counts, of the exception rows and of the payload behind a header of its own."""
     nb_maps = binary_probabilities.shape[0]
-    image_bytes = _entry_bytes(bits.reshape(nb_images, nb_maps, 2))
+    per_image = bits.shape[0]//nb_images          # nb_maps, times the tiles of an image with a coding tile (`assemble_blob` checks it)
+    image_bytes = _entry_bytes(bits.reshape(nb_images, per_image//nb_maps, nb_maps, 2)).sum(axis=1)
     stops = numpy.cumsum(image_bytes)
     view = memoryview(payload)
     blobs = []
     for i in range(nb_images):
         rows = exception_rows[i:i + 1] if idx_map_exception >= 0 else exception_rows
         blobs.append(assemble_blob(are_bin_widths_learned, 1, height, width, idx_map_exception, bin_widths, map_mean, binary_probabilities,
-                                   rows, bits[i*nb_maps:(i + 1)*nb_maps], view[int(stops[i] - image_bytes[i]):int(stops[i])])[0])
+                                   rows, bits[i*per_image:(i + 1)*per_image], view[int(stops[i] - image_bytes[i]):int(stops[i])],
+                                   coding_tile)[0])
     return blobs
 
 
@@ -197,9 +215,7 @@ def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_p
     else:
         idx_map_exception = -1
     if coding_tile is not None:
-        coding_tile = (min(coding_tile[0], y.shape[1]), min(coding_tile[1], y.shape[2]))
-        if max(coding_tile) > 0xFFFF:
-            raise ValueError('A coding tile side does not fit the container (65535 latents at most).')
+        coding_tile = _clamped_coding_tile(coding_tile, height, width)
     fields = _fields(encoder.are_bin_widths_learned, nb_images, height, width, idx_map_exception, bin_widths, mean, probabilities,
                      exception_rows, coding_tile)
     return _encode_entries(symbols, fields, nb_images if coding_tile is None else tiles_per_call)

@@ -78,6 +78,103 @@ __global__ __launch_bounds__(INDEX_THREADS) void index_streams_kernel(uint64_t e
     }
 }
 
+// ---- the index of a step coded in tiles (eae_hip_coder_index_tiles) ---------------------------------------
+// An entry is one (image, coding tile): maps_per_entry maps, 2 * maps_per_entry pieces. The coder keeps the entries of one shape
+// class side by side (RUN order: bit counts, stream regions and offsets), the payload keeps them image -> tile (PAYLOAD order), and
+// a piece is clamped to half of its own class's stride. table[2 p], table[2 p + 1]: the run-order index of payload-order entry p
+// and the half stride of its class. Two levels instead of one block over every piece (36,864 for 24 Kodak images in tiles of 16 x
+// 16): a block per entry scans the entry's pieces, one block scans the entries' totals, a block per entry adds the entry's base.
+// The slot of an entry's first piece carries the hand-over between the three launches: its own local offset is zero, so it holds
+// the entry's bytes behind the first launch, the entry's offset in the payload behind the second -- its final value --, and the
+// third reads it and leaves it alone. A table row that names no entry of the step is skipped by all three.
+constexpr int ENTRY_THREADS = 256;
+constexpr int ENTRY_WAVES = ENTRY_THREADS / 64;
+
+__global__ __launch_bounds__(ENTRY_THREADS) void index_entry_pieces_kernel(uint64_t entries, uint32_t maps_per_entry,
+                                                                           const uint32_t* __restrict__ bac_bits,
+                                                                           const uint32_t* __restrict__ bypass_bits,
+                                                                           const uint64_t* __restrict__ table, uint64_t* offsets) {
+    __shared__ uint64_t wave_total[ENTRY_WAVES];
+    const uint64_t run_entry = table[2 * (uint64_t)blockIdx.x], half_stride = table[2 * (uint64_t)blockIdx.x + 1];
+    if (run_entry >= entries) return;                      // block-uniform, in front of every barrier
+    const uint64_t first = run_entry * maps_per_entry;     // the entry's first stream
+    const uint64_t pieces = 2 * (uint64_t)maps_per_entry;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint64_t carry = 0;
+    for (uint64_t base = 0; base < pieces; base += ENTRY_THREADS) {
+        const uint64_t j = base + threadIdx.x;
+        uint64_t len = 0;
+        if (j < pieces) {
+            len = ((uint64_t)((j & 1u) ? bypass_bits[first + (j >> 1)] : bac_bits[first + (j >> 1)]) + 7u) >> 3;
+            if (len > half_stride) len = half_stride;
+        }
+        const uint64_t inclusive = wave_inclusive_scan64(len);
+        if (lane == 63u) wave_total[wave] = inclusive;
+        __syncthreads();
+        uint64_t before = carry, chunk = 0;
+        for (uint32_t w = 0; w < (uint32_t)ENTRY_WAVES; ++w) {
+            const uint64_t t = wave_total[w];
+            if (w < wave) before += t;
+            chunk += t;
+        }
+        if (j < pieces && j != 0) offsets[2 * first + j] = before + inclusive - len;
+        carry += chunk;
+        __syncthreads();      // wave_total is rewritten by the next chunk
+    }
+    if (threadIdx.x == 0) offsets[2 * first] = carry;
+}
+
+// index_streams_kernel's scan over the entries' bytes in payload order, read from and written back to the slots of the entries'
+// first pieces; then the bytes of every image, the total and the overflow flag as index_streams_kernel leaves them.
+__global__ __launch_bounds__(INDEX_THREADS) void index_entry_bases_kernel(uint64_t entries, uint64_t entries_per_image,
+                                                                          uint32_t maps_per_entry, const uint64_t* __restrict__ table,
+                                                                          uint64_t capacity, uint64_t* offsets, uint64_t* index) {
+    __shared__ uint64_t wave_total[INDEX_WAVES];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint64_t carry = 0;
+    for (uint64_t base = 0; base < entries; base += INDEX_THREADS) {
+        const uint64_t p = base + threadIdx.x;
+        uint64_t* slot = nullptr;
+        if (p < entries && table[2 * p] < entries) slot = offsets + 2 * table[2 * p] * maps_per_entry;
+        const uint64_t len = slot ? *slot : 0;
+        const uint64_t inclusive = wave_inclusive_scan64(len);
+        if (lane == 63u) wave_total[wave] = inclusive;
+        __syncthreads();
+        uint64_t before = carry, chunk = 0;
+        for (uint32_t w = 0; w < (uint32_t)INDEX_WAVES; ++w) {
+            const uint64_t t = wave_total[w];
+            if (w < wave) before += t;
+            chunk += t;
+        }
+        if (slot) *slot = before + inclusive - len;
+        carry += chunk;
+        __syncthreads();      // wave_total is rewritten by the next chunk; the slots written are visible to the block behind it
+    }
+    // an image's bytes are the distance between its first entry's offset and the next image's (a skipped row counts from zero)
+    const uint64_t images = entries / entries_per_image;
+    for (uint64_t i = threadIdx.x; i < images; i += INDEX_THREADS) {
+        const uint64_t a = table[2 * i * entries_per_image];
+        const uint64_t b = i + 1 < images ? table[2 * (i + 1) * entries_per_image] : 0;
+        const uint64_t first = a < entries ? offsets[2 * a * maps_per_entry] : 0;
+        const uint64_t next = i + 1 < images ? (b < entries ? offsets[2 * b * maps_per_entry] : 0) : carry;
+        index[2 + i] = next - first;
+    }
+    if (threadIdx.x == 0) {
+        index[0] = carry;
+        index[1] = carry > capacity ? 1u : 0u;
+    }
+}
+
+__global__ __launch_bounds__(ENTRY_THREADS) void index_entry_add_kernel(uint64_t entries, uint32_t maps_per_entry,
+                                                                        const uint64_t* __restrict__ table, uint64_t* offsets) {
+    const uint64_t run_entry = table[2 * (uint64_t)blockIdx.x];
+    if (run_entry >= entries) return;
+    uint64_t* entry = offsets + 2 * run_entry * maps_per_entry;
+    const uint64_t entry_base = entry[0];                  // nobody writes it here
+    for (uint64_t j = threadIdx.x; j < 2 * (uint64_t)maps_per_entry; j += ENTRY_THREADS)
+        if (j != 0) entry[j] += entry_base;
+}
+
 // The first *nbytes bytes (at most `capacity`) of `src`, rounded up to whole 16-byte words, into pinned host memory: one 16-byte
 // load and store per lane, a fixed grid striding over the words. The length is read on the device, so the launch has no
 // host-dependent argument. Visibility as publish_kernel (misc.hip): a system-scope fence behind the stores, and the host looks
@@ -132,6 +229,26 @@ extern "C" int eae_hip_coder_index_streams(uint32_t n_maps, uint32_t maps_per_im
     if (n_maps % maps_per_image != 0) return EAE_HIP_BAD_SHAPE;
     hipLaunchKernelGGL(index_streams_kernel, dim3(1), dim3(INDEX_THREADS), 0, (hipStream_t)stream, 2 * (uint64_t)n_maps,
                        2 * (uint64_t)maps_per_image, bac_bits, bypass_bits, stream_stride_bytes / 2, capacity_bytes, offsets_out, index_out);
+    EAE_HIP_CHECK_LAUNCH();
+    return EAE_HIP_OK;
+}
+
+extern "C" int eae_hip_coder_index_tiles(uint32_t n_streams, uint32_t maps_per_entry, uint32_t entries_per_image, const uint32_t* bac_bits,
+                                         const uint32_t* bypass_bits, const uint64_t* entry_table, uint64_t capacity_bytes,
+                                         uint64_t* offsets_out, uint64_t* index_out, void* stream) {
+    if (!bac_bits || !bypass_bits || !entry_table || !offsets_out || !index_out || n_streams == 0 || maps_per_entry == 0 ||
+        entries_per_image == 0)
+        return EAE_HIP_BAD_ARGUMENT;
+    if ((uint64_t)n_streams % ((uint64_t)maps_per_entry * entries_per_image) != 0) return EAE_HIP_BAD_SHAPE;
+    const uint64_t entries = n_streams / maps_per_entry;
+    hipLaunchKernelGGL(index_entry_pieces_kernel, dim3((unsigned)entries), dim3(ENTRY_THREADS), 0, (hipStream_t)stream, entries,
+                       maps_per_entry, bac_bits, bypass_bits, entry_table, offsets_out);
+    EAE_HIP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(index_entry_bases_kernel, dim3(1), dim3(INDEX_THREADS), 0, (hipStream_t)stream, entries,
+                       (uint64_t)entries_per_image, maps_per_entry, entry_table, capacity_bytes, offsets_out, index_out);
+    EAE_HIP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(index_entry_add_kernel, dim3((unsigned)entries), dim3(ENTRY_THREADS), 0, (hipStream_t)stream, entries,
+                       maps_per_entry, entry_table, offsets_out);
     EAE_HIP_CHECK_LAUNCH();
     return EAE_HIP_OK;
 }

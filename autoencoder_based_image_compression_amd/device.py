@@ -604,12 +604,13 @@ class CoderStreams(object):
         self.n_maps = n_maps
         self.map_size = map_size
         self.truncated_unary_length = truncated_unary_length
-        self.stride = int(_native.hip().eae_hip_coder_stream_stride_bytes(map_size, truncated_unary_length))
+        self.stride = coder_stream_stride_bytes(map_size, truncated_unary_length)
         self.streams = torch.empty((n_maps, self.stride), dtype=torch.uint8, device=device)
         # one allocation so that a caller can fetch all four per-map results with a single device -> host copy
         self.results = results if results is not None else torch.zeros((4, n_maps), dtype=torch.int32, device=device)
-        if self.results.shape != (4, n_maps) or self.results.dtype != torch.int32 or not self.results.is_contiguous():
-            raise TypeError('`results` must be a contiguous int32 tensor of shape (4, n_maps).')
+        # (its four rows are what the launches read and write: a block of columns of a wider results block will do)
+        if self.results.shape != (4, n_maps) or self.results.dtype != torch.int32 or self.results.stride(1) != 1:
+            raise TypeError('`results` must be an int32 tensor of shape (4, n_maps) with contiguous rows.')
         (self.bac_bits, self.bypass_bits, self.status, self.stage) = self.results.unbind(0)
 
     def nb_bits(self):
@@ -687,6 +688,11 @@ def publish_step(src_device, dst_pinned, clear_from, tickets_device, counter_dev
     _check(_native.hip().eae_hip_publish_step(_p(src_device), dst_pinned.data_ptr(), nbytes, int(clear_from)*src_device.element_size(),
                                               _p(conv_ws), _p(error_word), _p(tickets_device), _p(counter_device),
                                               word_pinned.data_ptr(), _stream(src_device)), 'eae_hip_publish_step')
+
+
+def coder_stream_stride_bytes(map_size, truncated_unary_length):
+    """Bytes of one map's stream region (`CoderStreams.stride`): arithmetic-coded bytes at +0, bypass bytes at half of it."""
+    return int(_native.hip().eae_hip_coder_stream_stride_bytes(map_size, truncated_unary_length))
 
 
 def coder_workspace_bytes(n_maps, map_size, truncated_unary_length):
@@ -844,7 +850,7 @@ def dequantize_maps(symbols_planar, bin_widths, map_mean=None, want_cq=False, wa
 
 
 # ---- containers from the pipelined codec (include/eae_hip.h, csrc/hip/codec_container.hip) -----------------------------------
-# No argument of these four depends on a result of the step, so they can be captured into the coder's hipGraph.
+# No argument of these five depends on a result of the step, so they can be captured into the coder's hipGraph.
 
 def coder_index_streams(streams, maps_per_image, capacity_bytes, offsets=None, index=None):
     """Byte offsets of every stream piece of `streams` (CoderStreams) in the payload, and the index words, from the bit counts on
@@ -864,6 +870,33 @@ def coder_index_streams(streams, maps_per_image, capacity_bytes, offsets=None, i
     _check(_native.hip().eae_hip_coder_index_streams(n_maps, maps_per_image, _p(streams.bac_bits), _p(streams.bypass_bits),
                                                      int(streams.stride), int(capacity_bytes), _p(offsets),
                                                      _p(index), _stream(streams.bac_bits)), 'eae_hip_coder_index_streams')
+    return offsets, index
+
+
+def coder_index_tiles(bac_bits, bypass_bits, entry_table, maps_per_entry, entries_per_image, capacity_bytes, offsets=None, index=None):
+    """`coder_index_streams` for a step coded in coding tiles (include/eae_hip.h: eae_hip_coder_index_tiles). bac_bits / bypass_bits
+    int32 [n_streams] in run order (the entries -- (image, tile) pairs of `maps_per_entry` maps -- of one shape class side by side);
+    entry_table int64 [n_entries, 2] on the device, one row per entry in payload order: its run-order index and half the stream
+    stride of its class. -> (offsets int64 [n_streams, 2] in run order: where every piece lies in the payload, index int64
+    [2 + n_entries/entries_per_image]: total bytes, overflow flag, bytes per image)."""
+    n_streams = bac_bits.numel()
+    if maps_per_entry < 1 or entries_per_image < 1 or n_streams % (maps_per_entry*entries_per_image) != 0:
+        raise HipError('`n_streams` is not a multiple of `maps_per_entry*entries_per_image`')
+    n_entries = n_streams//maps_per_entry
+    if bypass_bits.numel() != n_streams or bac_bits.element_size() != 4 or bypass_bits.element_size() != 4:
+        raise HipError('`bac_bits` and `bypass_bits` must hold n_streams 32-bit words each')
+    if entry_table.dtype != torch.int64 or entry_table.numel() != 2*n_entries or not entry_table.is_contiguous():
+        raise HipError('`entry_table` must be contiguous int64 [n_entries, 2]')
+    device = bac_bits.device
+    if offsets is None:
+        offsets = torch.empty((n_streams, 2), dtype=torch.int64, device=device)
+    if index is None:
+        index = torch.empty(2 + n_entries//entries_per_image, dtype=torch.int64, device=device)
+    if offsets.dtype != torch.int64 or offsets.numel() != 2*n_streams or index.dtype != torch.int64 or index.numel() != 2 + n_entries//entries_per_image:
+        raise HipError('`offsets` must hold 2 n_streams and `index` 2 + n_entries/entries_per_image int64 words')
+    _check(_native.hip().eae_hip_coder_index_tiles(n_streams, int(maps_per_entry), int(entries_per_image), _p(bac_bits), _p(bypass_bits),
+                                                   _p(entry_table), int(capacity_bytes), _p(offsets), _p(index), _stream(bac_bits)),
+           'eae_hip_coder_index_tiles')
     return offsets, index
 
 

@@ -435,7 +435,7 @@ int eae_hip_dequantize_maps(const int16_t* symbols_planar, const float* bin_widt
 
 /* ---- containers from the pipelined codec (csrc/hip/codec_container.hip) --------------------------
  * What container.encode_images does between the coder and the blob, with device-resident arguments only: every call is
- * asynchronous on `stream`, none has an argument the host has to compute from a result of the step, so all four can be captured
+ * asynchronous on `stream`, none has an argument the host has to compute from a result of the step, so all five can be captured
  * into a hipGraph behind the coder's launches.
  * index_streams: the piece e = 2 m + piece of map m (arithmetic-coded bytes, bypass bytes) is min((bits + 7) >> 3, stride / 2)
  *   bytes long, as pack_streams copies it. offsets_out[2 n_maps]: the exclusive prefix sum of those lengths in payload order
@@ -451,7 +451,22 @@ int eae_hip_dequantize_maps(const int16_t* symbols_planar, const float* bin_widt
  *   magnitude j and ones[j] = map_size - the symbols of magnitude <= j, rows_out[i][j] = zeros / (zeros + ones) in float64, 0 / 0
  *   -> 0.5, 0 -> 0.01, 1 -> 0.99, j < length. Needs radius >= length (EAE_HIP_BAD_ARGUMENT otherwise): then a symbol beyond the
  *   radius is a one of every position, which map_size already accounts for, so the rows are exact whatever `overflow` counts
- *   (it is not read). */
+ *   (it is not read).
+ * index_tiles: index_streams for a step coded in coding tiles (codec.BatchCodec(coding_tile=...)). An entry
+ *   is one (image, tile): maps_per_entry maps. bac_bits / bypass_bits [n_streams] and offsets_out [2 n_streams] are in RUN order
+ *   (the entries of one shape class side by side, as the coder batches them); the payload is in PAYLOAD order (image -> tile,
+ *   row-major -> map -> piece). entry_table uint64 [n_streams / maps_per_entry][2], device memory, one row per payload-order
+ *   entry: its run-order entry index, and half the stream stride of its class, to which its pieces are clamped as pack_indexed
+ *   clamps them. offsets_out of a piece: the exclusive prefix sum, taken in payload order, of the clamped lengths, so that a
+ *   class's pack_indexed takes a plain slice of it. index_out as index_streams', image i = the payload-order entries
+ *   [i entries_per_image, (i + 1) entries_per_image). With one entry per image, the identity table and one stride it writes
+ *   what index_streams writes, word for word. Three launches (per entry, over the entries, per entry), no scratch: plain loads
+ *   and stores. A table row that names no entry is skipped. NULL pointers, n_streams == 0, maps_per_entry == 0 or
+ *   entries_per_image == 0 -> EAE_HIP_BAD_ARGUMENT; n_streams not a multiple of maps_per_entry * entries_per_image ->
+ *   EAE_HIP_BAD_SHAPE; both before any launch. */
+int eae_hip_coder_index_tiles(uint32_t n_streams, uint32_t maps_per_entry, uint32_t entries_per_image, const uint32_t* bac_bits,
+                              const uint32_t* bypass_bits, const uint64_t* entry_table, uint64_t capacity_bytes,
+                              uint64_t* offsets_out, uint64_t* index_out, void* stream);
 int eae_hip_coder_index_streams(uint32_t n_maps, uint32_t maps_per_image, const uint32_t* bac_bits, const uint32_t* bypass_bits,
                                 uint64_t stream_stride_bytes, uint64_t capacity_bytes, uint64_t* offsets_out, uint64_t* index_out,
                                 void* stream);
