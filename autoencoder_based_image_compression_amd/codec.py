@@ -1282,13 +1282,15 @@ class BatchCodec(object):
 
 # ---- the other half: containers in, reconstructions out ---------------------------------------------------
 
-def decode_head_layout(batch_size, nb_maps, truncated_unary_length):
+def decode_head_layout(batch_size, nb_maps, truncated_unary_length, n_streams=None):
     """The "step head" of `BatchDecoder`: everything of a step's blobs but their payload, in one fixed-size block that crosses to the
     device with one copy. -> (fields {name: (byte offset, dtype, shape)}, bytes of the block, a multiple of 16):
     'bits' uint32 [n_maps][2] (arithmetic-coded stream, bypass stream), 'prob_row' int32 [n_maps] (row of 'table' a map is coded
     with, -1: not coded), 'bin_widths' and 'map_mean' float32 [batch][nb_maps], 'table' float64 [batch][nb_maps + 1][L] (every
-    image's own probabilities, then the row of its exception map), 'payload_bytes' uint64 [1]."""
-    n_maps = batch_size*nb_maps
+    image's own probabilities, then the row of its exception map), 'payload_bytes' uint64 [1].
+    n_streams: pairs of streams per step, None = batch_size*nb_maps, one per map. A decoder of coding tiles has one per (image, tile,
+    map), `coding_tile_layout(...)['n_streams']`: 'bits' and 'prob_row' then hold that many entries, in RUN order."""
+    n_maps = batch_size*nb_maps if n_streams is None else int(n_streams)
     shapes = (('bits', numpy.uint32, (n_maps, 2)), ('prob_row', numpy.int32, (n_maps,)), ('bin_widths', numpy.float32, (batch_size, nb_maps)),
               ('map_mean', numpy.float32, (batch_size, nb_maps)), ('table', numpy.float64, (batch_size, nb_maps + 1, truncated_unary_length)),
               ('payload_bytes', numpy.uint64, (1,)))
@@ -1300,31 +1302,46 @@ def decode_head_layout(batch_size, nb_maps, truncated_unary_length):
     return fields, -(-pos//16)*16
 
 
-def decode_head_views(head, batch_size, nb_maps, truncated_unary_length):
+def decode_head_views(head, batch_size, nb_maps, truncated_unary_length, n_streams=None):
     """The fields of `decode_head_layout` as numpy views of `head` (uint8, contiguous, at least the block's bytes, 8-byte aligned)."""
-    (fields, nbytes) = decode_head_layout(batch_size, nb_maps, truncated_unary_length)
+    (fields, nbytes) = decode_head_layout(batch_size, nb_maps, truncated_unary_length, n_streams)
     if head.dtype != numpy.uint8 or head.ndim != 1 or head.size < nbytes:
         raise ValueError('`head` must be a flat uint8 array of at least {0} bytes.'.format(nbytes))
     return {name: head[pos:pos + dtype.itemsize*int(numpy.prod(shape))].view(dtype).reshape(shape) for (name, (pos, dtype, shape)) in fields.items()}
 
 
 def plan_decode_step(blobs, batch_size, h_in, w_in, truncated_unary_length, are_bin_widths_learned, capacity, head, payload,
-                     nb_maps=csts.NB_MAPS_3):
+                     nb_maps=csts.NB_MAPS_3, coding_tile=None, layout=None):
     """The host side of one `BatchDecoder` step; numpy only. blobs: one `EAE1` blob or a sequence of them, 1..batch_size images in
     all, in the order of the step's images. Every header is parsed and checked (`container.read_header`, then the decoder's own
     height, width, truncated unary length and model kind, the number of images, the payload against `capacity`) BEFORE a byte of
     `head` or `payload` is written: a refused step (ValueError) leaves both as they were. Then `head` (uint8: `decode_head_layout`)
     is filled -- image i's map m is coded with row i*(nb_maps + 1) + m of the table, its exception map with row
     i*(nb_maps + 1) + nb_maps, the maps of absent images get -1 -- and the payloads go to `payload` (uint8) one behind the other.
+    coding_tile=(th, tw) latents: the step of a decoder of coding tiles. The blobs are then `EAT1` blobs whose
+    coding tile, clamped to the latent plane, is the decoder's clamped tile: anything else (an `EAE1` blob, another tile) is refused
+    like the rest, with a ValueError that names `coding_tile`. `head` is `decode_head_layout(..., n_streams)`: the headers' bit
+    counts, which are in payload order (image -> tile -> map), go to 'bits' in RUN order through the one static index array
+    `layout['payload_order']`, and so do the rows of 'prob_row' -- every stream of image i, map m gets row i*(nb_maps + 1) + m, the
+    exception map of the image's blob row i*(nb_maps + 1) + nb_maps in every tile, every stream of an absent image -1 and zero bits.
+    The other fields and the payload are as without tiles: payload order is image-major, so blobs one behind the other are images one
+    behind the other. layout: `coding_tile_layout(batch_size, h_in/16, w_in/16, coding_tile)` when the caller has it (it is the same
+    for every step: its clamped tile is then the step's, and `coding_tile` is not looked at again), else it is computed here.
     -> (images, payload bytes)."""
     if isinstance(blobs, (bytes, bytearray, memoryview)):
         blobs = [blobs]
     blobs = list(blobs)
     if not blobs:
         raise ValueError('A step needs at least one blob.')
+    (h_map, w_map) = (h_in//csts.STRIDE_PROD, w_in//csts.STRIDE_PROD)
+    if layout is not None:
+        coding_tile = layout['coding_tile']          # validated and clamped once, by whoever made the layout
+    elif coding_tile is not None:
+        (th, tw) = container_format._positive_pair(coding_tile, '`coding_tile`')
+        coding_tile = (min(th, h_map), min(tw, w_map))
     headers = []
     for blob in blobs:
-        if bytes(blob[:4]) == container_format.TILE_MAGIC:
+        if coding_tile is None and bytes(blob[:4]) == container_format.TILE_MAGIC:
             raise ValueError('An EAT1 container codes tiles: BatchDecoder takes EAE1 blobs only, use container.decode_region.')
         header = container_format.read_header(blob)
         if (header['height'], header['width']) != (h_in, w_in):
@@ -1335,6 +1352,14 @@ def plan_decode_step(blobs, batch_size, h_in, w_in, truncated_unary_length, are_
                 header['truncated_unary_length'], truncated_unary_length))
         if header['are_bin_widths_learned'] != bool(are_bin_widths_learned):
             raise ValueError('The container was written by the other kind of model (learned / fixed bin widths).')
+        if coding_tile is not None:
+            if header.get('format') != 'EAT1':
+                raise ValueError('This decoder was built with `coding_tile`={0}: it takes EAT1 blobs of that coding tile, this is an EAE1 '
+                                 'blob (a decoder built without `coding_tile` reads it).'.format(coding_tile))
+            blob_tile = (min(header['coding_tile'][0], h_map), min(header['coding_tile'][1], w_map))
+            if blob_tile != coding_tile:
+                raise ValueError('The container was coded in tiles of {0} latents, the decoder was built with `coding_tile`={1}.'.format(
+                    blob_tile, coding_tile))
         headers.append(header)
     nb_images = sum(header['nb_images'] for header in headers)
     if nb_images > batch_size:
@@ -1344,11 +1369,19 @@ def plan_decode_step(blobs, batch_size, h_in, w_in, truncated_unary_length, are_
     if payload_bytes > capacity or payload_bytes > payload.size:
         raise ValueError('The payload of this step takes {0} bytes, the decoder holds {1} per step '
                          '(BatchDecoder(payload_capacity_bytes=...)).'.format(payload_bytes, min(capacity, payload.size)))
-    views = decode_head_views(head, batch_size, nb_maps, truncated_unary_length)
+    if coding_tile is None:
+        views = decode_head_views(head, batch_size, nb_maps, truncated_unary_length)
+    else:
+        if layout is None:
+            layout = coding_tile_layout(batch_size, h_map, w_map, coding_tile)
+        nb_tiles = layout['nb_tiles']
+        views = decode_head_views(head, batch_size, nb_maps, truncated_unary_length, layout['n_streams'])
+        # the step in payload order, the order of the headers; one scatter each takes them to run order behind the loop
+        ordered_bits = numpy.zeros((batch_size, nb_tiles, nb_maps, 2), dtype=numpy.uint32)
+        ordered_rows = numpy.full((batch_size, nb_tiles, nb_maps), -1, dtype=numpy.int32)
     (first, pos) = (0, 0)
     for (blob, header, size) in zip(blobs, headers, sizes):
         n = header['nb_images']
-        views['bits'][first*nb_maps:(first + n)*nb_maps] = header['bits']
         rows = (numpy.arange(first, first + n, dtype=numpy.int32)*(nb_maps + 1))[:, None] + numpy.arange(nb_maps, dtype=numpy.int32)[None, :]
         exception = header['idx_map_exception']
         if exception >= 0:
@@ -1356,15 +1389,24 @@ def plan_decode_step(blobs, batch_size, h_in, w_in, truncated_unary_length, are_
             views['table'][first:first + n, nb_maps] = header['exception_probabilities']
         else:
             views['table'][first:first + n, nb_maps] = 0.5
-        views['prob_row'][first*nb_maps:(first + n)*nb_maps] = rows.reshape(-1)
+        if coding_tile is None:
+            views['bits'][first*nb_maps:(first + n)*nb_maps] = header['bits']
+            views['prob_row'][first*nb_maps:(first + n)*nb_maps] = rows.reshape(-1)
+        else:
+            ordered_bits[first:first + n] = header['bits']
+            ordered_rows[first:first + n] = rows[:, None, :]
         views['bin_widths'][first:first + n] = header['bin_widths']
         views['map_mean'][first:first + n] = header['map_mean']
         views['table'][first:first + n, :nb_maps] = header['binary_probabilities']
         payload[pos:pos + size] = numpy.frombuffer(blob, dtype=numpy.uint8, count=size, offset=header['payload_offset'])
         first += n
         pos += size
-    views['bits'][nb_images*nb_maps:] = 0
-    views['prob_row'][nb_images*nb_maps:] = -1
+    if coding_tile is None:
+        views['bits'][nb_images*nb_maps:] = 0
+        views['prob_row'][nb_images*nb_maps:] = -1
+    else:
+        views['bits'][layout['payload_order']] = ordered_bits.reshape(-1, 2)
+        views['prob_row'][layout['payload_order']] = ordered_rows.reshape(-1)
     views['bin_widths'][nb_images:] = 0.
     views['map_mean'][nb_images:] = 0.
     views['table'][nb_images:] = 0.5
@@ -1414,9 +1456,13 @@ class _DecodeJob(_Claimable):
 class _DecodeWorker(_StepWorker):
     """The result worker of `BatchDecoder`."""
 
-    def __init__(self, nb_maps):
+    def __init__(self, streams_per_image, payload_order=None):
+        """streams_per_image: pairs of streams of one image: its maps, times its tiles with a coding tile. payload_order: of a decoder
+        of coding tiles (`coding_tile_layout`): the slot's results are in run order, and this index array takes them into the order
+        of the payload, image -> tile -> map."""
         super(_DecodeWorker, self).__init__()
-        self.nb_maps = nb_maps
+        self.streams_per_image = streams_per_image
+        self.payload_order = payload_order
 
     def process(self, job, by_caller=False):
         (ticket, slot) = (job.ticket, job.slot)
@@ -1436,13 +1482,18 @@ class _DecodeWorker(_StepWorker):
                     int(slot.index_host[0]), job.payload_bytes))
             from .kodak.lossless import interface_cython
             errors = []
+            (results, per_image) = (slot.results_host, self.streams_per_image)
+            if self.payload_order is not None:
+                # status and stage of every stream in payload order: an image's first failing stream is the first of its first
+                # failing tile, as `container.decode_images` meets them in the image's own blob
+                results = results.take(self.payload_order, axis=1)
             for i in range(ticket.nb_images):
-                status = slot.results_host[2, i*self.nb_maps:(i + 1)*self.nb_maps]
+                status = results[2, i*per_image:(i + 1)*per_image]
                 error = None
                 if status.any():
-                    bad = i*self.nb_maps + int(numpy.flatnonzero(status)[0])
+                    bad = i*per_image + int(numpy.flatnonzero(status)[0])
                     try:
-                        interface_cython.raise_for_status(int(slot.results_host[2, bad]), int(slot.results_host[3, bad]))
+                        interface_cython.raise_for_status(int(results[2, bad]), int(results[3, bad]))
                     except Exception as exc:
                         error = exc
                 errors.append(error)
@@ -1466,9 +1517,9 @@ class _DecodeLane(object):
 
     def __init__(self, decoder, stream):
         (batch_size, nb_maps, device, length) = (decoder.batch_size, decoder.nb_maps, decoder.device, decoder.truncated_unary_length)
-        n_maps = batch_size*nb_maps
+        n_maps = decoder._n_streams      # pairs of streams per step: batch_size*nb_maps, times the tiles of a map with a coding tile
         self.stream = stream
-        (fields, head_bytes) = decode_head_layout(batch_size, nb_maps, length)
+        (fields, head_bytes) = decode_head_layout(batch_size, nb_maps, length, n_maps)
         self.head = torch.zeros(head_bytes, dtype=torch.uint8, device=device)
 
         def field(name, dtype):
@@ -1488,9 +1539,24 @@ class _DecodeLane(object):
         self.results = self.status[:4*n_maps].view(4, n_maps)
         self.index = self.status[4*n_maps:].view(torch.int64)
         self.offsets = torch.zeros((n_maps, 2), dtype=torch.int64, device=device)
-        self.coder_streams = dev.CoderStreams(n_maps, decoder.map_size, length, device, results=self.results)
-        self.workspace = dev.coder_workspace(n_maps, decoder.map_size, length, device)
-        self.symbols = torch.zeros((batch_size, nb_maps, decoder.map_size), dtype=torch.int16, device=device)
+        if decoder.coding_tile is None:
+            self.coder_streams = dev.CoderStreams(n_maps, decoder.map_size, length, device, results=self.results)
+            self.workspace = dev.coder_workspace(n_maps, decoder.map_size, length, device)
+            self.symbols = torch.zeros((batch_size, nb_maps, decoder.map_size), dtype=torch.int16, device=device)
+        else:
+            # The buffers of `BatchCodec`'s slot (`_Slot`), read the other way: the step's (image, tile) entries in run order, per
+            # shape class one batch of streams on that class's columns of the ONE results block, decoded into that class's run of
+            # the tile-major buffer; the classes run one after the other, so one workspace of the largest class serves them all.
+            tiled = decoder._tile_layout
+            self.decoded = torch.zeros(tiled['elements'], dtype=torch.int16, device=device)
+            (self.classes, need) = ([], 0)
+            for ((rows, cols), count, first_stream, first_element) in tiled['runs']:
+                (n, size) = (count*nb_maps, rows*cols)
+                streams = dev.CoderStreams(n, size, length, device, results=self.results[:, first_stream:first_stream + n])
+                self.classes.append((streams, self.decoded[first_element:first_element + n*size].view(n, size),
+                                     self.prob_row[first_stream:first_stream + n], self.offsets[first_stream:first_stream + n]))
+                need = max(need, dev.coder_workspace_bytes(n, size, length))
+            self.workspace = torch.empty(need, dtype=torch.uint8, device=device)
         self.shifted = torch.zeros((batch_size, decoder.h_in//csts.STRIDE_PROD, decoder.w_in//csts.STRIDE_PROD, nb_maps), dtype=torch.float32,
                                    device=device)
         (self.scratch, self.unfinished) = decoder.decoder.model.decode_scratch(batch_size, decoder.h_in//csts.STRIDE_PROD,
@@ -1503,7 +1569,7 @@ class _DecodeSlot(object):
 
     def __init__(self, decoder, lane):
         (batch_size, nb_maps, device) = (decoder.batch_size, decoder.nb_maps, decoder.device)
-        n_maps = batch_size*nb_maps
+        n_maps = decoder._n_streams
         self.lane = lane
         self.pinned_head = torch.zeros(lane.head.numel(), dtype=torch.uint8).pin_memory()
         self.pinned_payload = torch.zeros(decoder.payload_capacity_bytes, dtype=torch.uint8).pin_memory()
@@ -1528,10 +1594,11 @@ class _DecodeSlot(object):
 class BatchDecoder(object):
     """`EAE1` containers -> uint8 reconstructions for steps of a fixed shape, resident and pipelined: what `container.decode_images`
     computes (same bytes), with every buffer made once, the host work of a step in `plan_decode_step`, and the step as one chain of
-    launches on one of `nb_streams` private streams (one hipGraph per slot with `use_graphs`). DESIGN.md section 14."""
+    launches on one of `nb_streams` private streams (one hipGraph per slot with `use_graphs`). DESIGN.md section 14. With
+    `coding_tile`: the same for the tile-indexed `EAT1` containers of that coding tile (section 16)."""
 
     def __init__(self, variables, are_bin_widths_learned, batch_size, h_in, w_in, truncated_unary_length, device='cuda', nb_in_flight=None,
-                 nb_streams=None, use_graphs=False, payload_capacity_bytes=None, fetch_reconstruction=True):
+                 nb_streams=None, use_graphs=False, payload_capacity_bytes=None, fetch_reconstruction=True, coding_tile=None):
         """nb_streams: consecutive steps go round that many private streams, so that one step's serial decoder core runs beside
         another step's synthesis transform. nb_in_flight: steps that may be pending at once (= slots: pinned buffers and planes).
         None: `DECODER_STREAMS` streams, or as many of them as the process's hardware queues allow (`stream_budget`; streams asked
@@ -1539,13 +1606,29 @@ class BatchDecoder(object):
         use_graphs: capture the step of every slot into a hipGraph at the first submit and replay it afterwards.
         payload_capacity_bytes: payload bytes a step may hold (rounded up to 16; a device buffer per stream and a pinned one per
         slot). None: batch_size*h_in*w_in. fetch_reconstruction: the planes reach pinned host memory inside the step and `result()`
-        is a numpy view of them; False: `result()` is the slot's device tensor."""
+        is a numpy view of them; False: `result()` is the slot's device tensor.
+        coding_tile: (th, tw) in latents: the decoder reads `EAT1` blobs coded in that tile (clamped to the latent plane) -- what
+        `BatchCodec(emit_container=True, coding_tile=(th, tw))` and `container.encode_images(..., coding_tile=(th, tw))` write --
+        and nothing else: an `EAE1` blob or another tile is refused by `submit` (ValueError). Every (image, tile, map) is a pair of
+        streams of its own, so the decoder core's serial chains are a tile long instead of a map. At most 65,535 (image, tile) pairs
+        per step. None: `EAE1` blobs only."""
         if h_in % csts.STRIDE_PROD != 0 or w_in % csts.STRIDE_PROD != 0 or h_in < 1 or w_in < 1:
             raise ValueError('The image size is not divisible by the product of the three strides.')
         if not 1 <= int(truncated_unary_length) <= 255:
             raise ValueError('The truncated unary length does not belong to [1, 255].')
         if batch_size < 1:
             raise ValueError('`batch_size` is not positive.')
+        self.coding_tile = None
+        if coding_tile is not None:
+            # refused in front of every allocation
+            coding_tile = container_format._positive_pair(coding_tile, '`coding_tile`')
+            if max(coding_tile) > 0xFFFF:
+                raise ValueError('A side of `coding_tile` does not fit the container (65535 latents at most).')
+            (h_map, w_map) = (h_in//csts.STRIDE_PROD, w_in//csts.STRIDE_PROD)
+            self.coding_tile = (min(coding_tile[0], h_map), min(coding_tile[1], w_map))
+            if int(batch_size)*container_format._nb_tiles(h_map, w_map, self.coding_tile) > 65535:
+                raise ValueError('`batch_size` images of {0} coding tiles each are more than the 65535 (image, tile) pairs a step can hold.'.format(
+                    container_format._nb_tiles(h_map, w_map, self.coding_tile)))
         self.device = torch.device(device)
         if self.device.index is None:
             self.device = torch.device('cuda', torch.cuda.current_device())
@@ -1581,17 +1664,31 @@ class BatchDecoder(object):
         self.nb_streams = nb_streams
         self.nb_in_flight = max(1, int(nb_in_flight)) if nb_in_flight is not None else nb_streams + 2
         self.nb_slots = self.nb_in_flight
+        self._n_streams = self.batch_size*self.nb_maps
+        self._tile_layout = None
+        if self.coding_tile is not None:
+            # everything a step in tiles needs beyond its blobs is the same for every step: made once, shared by the slots
+            tiled = coding_tile_layout(self.batch_size, h_in//csts.STRIDE_PROD, w_in//csts.STRIDE_PROD, self.coding_tile)
+            self._tile_layout = tiled
+            self._n_streams = tiled['n_streams']
+            self._tile_plan_host = tiled['plan']
+            self._tile_plan = torch.from_numpy(tiled['plan']).to(self.device)
+            # `device.coder_index_tiles`: per payload-order entry, its run-order index and half the stream stride of its class
+            half_stride = numpy.array([dev.coder_stream_stride_bytes(int(tiled['tiles'][t, 2]*tiled['tiles'][t, 3]), self.truncated_unary_length)//2
+                                       for (_, t) in tiled['entries']], dtype=numpy.int64)
+            self._tile_table = torch.from_numpy(numpy.stack([tiled['run_entry'], half_stride], axis=1)).to(self.device)
         streams = _step_streams(self.nb_streams, self.device)
         self._slots = [_DecodeSlot(self, _DecodeLane(self, streams[k % self.nb_streams])) for k in range(self.nb_slots)]
         self._index = 0
         self._warm = False
-        self._worker = _DecodeWorker(self.nb_maps)
+        self._worker = _DecodeWorker(self._n_streams//self.batch_size, self._tile_layout['payload_order'] if self._tile_layout else None)
         self._worker.start()
         with _LIVE_LOCK:
             _LIVE.setdefault(self.device.index, weakref.WeakSet()).add(self)
 
     def submit(self, blobs):
-        """One `EAE1` blob of 1..batch_size images, or a sequence of `EAE1` blobs holding that many in all -> DecodeTicket.
+        """One `EAE1` blob of 1..batch_size images, or a sequence of `EAE1` blobs holding that many in all -> DecodeTicket
+        (`EAT1` blobs of the decoder's coding tile, and only those, for a decoder built with `coding_tile`).
         Everything is checked on the host first (`plan_decode_step`: ValueError, nothing launched); then the step is enqueued and
         nothing is waited for except a free slot."""
         if self._worker is None:
@@ -1616,7 +1713,8 @@ class BatchDecoder(object):
         slot = self._slots[self._index % self.nb_slots]
         slot.free.wait()
         (nb_images, payload_bytes) = plan_decode_step(blobs, self.batch_size, self.h_in, self.w_in, self.truncated_unary_length, self.learned,
-                                                      self.payload_capacity_bytes, slot.head_host, slot.payload_host, self.nb_maps)
+                                                      self.payload_capacity_bytes, slot.head_host, slot.payload_host, self.nb_maps,
+                                                      self.coding_tile, self._tile_layout)
         slot.free.clear()
         self._index += 1
         expected = slot.count + 1
@@ -1664,14 +1762,25 @@ class BatchDecoder(object):
     def _launch_step(self, slot):
         """The step of `slot` on the current stream: one chain, no argument of which depends on the step's contents."""
         lane = slot.lane
-        streams = lane.coder_streams
         dev.fetch_prefix(slot.pinned_head, lane.head, lane.head_bytes)                      # the head: a fixed size
         dev.fetch_prefix(slot.pinned_payload, lane.payload, lane.payload_bytes)             # the payload: the bytes the head announces
         lane.results[:2].copy_(lane.head_bits.view(-1, 2).t())                              # [n_maps][2] -> the coder's two arrays
-        dev.coder_index_streams(streams, self.nb_maps, self.payload_capacity_bytes, offsets=lane.offsets, index=lane.index)
-        dev.coder_unpack_into(streams, lane.payload, lane.offsets)
-        dev.coder_decode_batch(streams, lane.table, lane.prob_row, workspace=lane.workspace, out=lane.symbols.view(-1, self.map_size))
-        dev.dequantize_maps_rows(lane.symbols, lane.bin_widths, lane.map_mean, out_shifted=lane.shifted)
+        if self.coding_tile is None:
+            streams = lane.coder_streams
+            dev.coder_index_streams(streams, self.nb_maps, self.payload_capacity_bytes, offsets=lane.offsets, index=lane.index)
+            dev.coder_unpack_into(streams, lane.payload, lane.offsets)
+            dev.coder_decode_batch(streams, lane.table, lane.prob_row, workspace=lane.workspace, out=lane.symbols.view(-1, self.map_size))
+            dev.dequantize_maps_rows(lane.symbols, lane.bin_widths, lane.map_mean, out_shifted=lane.shifted)
+        else:
+            # (image, tile) entries instead of whole maps (DESIGN.md section 16): the bit counts lie in run order, the index takes the
+            # offsets in payload order, then one unpack and one decoder batch per shape class into the tile-major buffer, and one
+            # launch dequantises every tile of the step, with its image's rows, into the latents (every latent is in exactly one tile)
+            dev.coder_index_tiles(lane.results[0], lane.results[1], self._tile_table, self.nb_maps, self._tile_layout['nb_tiles'],
+                                  self.payload_capacity_bytes, offsets=lane.offsets, index=lane.index)
+            for (streams, tiles, rows, offsets) in lane.classes:
+                dev.coder_unpack_into(streams, lane.payload, offsets)
+                dev.coder_decode_batch(streams, lane.table, rows, workspace=lane.workspace, out=tiles)
+            dev.tile_symbols_dequantize_rows(lane.decoded, self._tile_plan, self._tile_plan_host, lane.bin_widths, lane.map_mean, lane.shifted)
         self.decoder.model.decode_into(lane.shifted, slot.planes, lane.scratch)
         if slot.pinned_rec is not None:
             dev.publish_to_host(slot.planes, slot.pinned_rec)

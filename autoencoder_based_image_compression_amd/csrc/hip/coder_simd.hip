@@ -38,6 +38,7 @@
 
 #include "../coder/lean_step.h"
 #include "eae_hip.h"
+#include "fill.h"
 #include "wave_scan.h"
 
 // coder_device.hip
@@ -1445,7 +1446,7 @@ int eae_hip_coder_encode_batch(uint32_t n_maps, uint32_t map_size, const int16_t
     if (n_maps == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     if (!fast_applies(L) || map_size == 0) {
-        (void)hipMemsetAsync(status, 0, (size_t)n_maps * sizeof(int32_t), s);
+        if (const int rc = eae_fill_async(status, 0, (uint64_t)n_maps * sizeof(int32_t), s)) return rc;
         return eae_coder_generic_encode(n_maps, map_size, symbols, L, probs, prob_row, streams, stride, bac_bits, bypass_bits,
                                         status, stage, 0, s);
     }
@@ -1473,7 +1474,9 @@ int eae_hip_coder_decode_batch(uint32_t n_maps, uint32_t map_size, int16_t* symb
                                const_cast<uint32_t*>(bac_bits), const_cast<uint32_t*>(bypass_bits), status, stage,
                                have_ws ? workspace : nullptr);
     if (symbols_out) p.decoded = symbols_out;
-    if (!expected) (void)hipMemsetAsync(status, 0, (size_t)n_maps * sizeof(int32_t), s);   // a pure decode starts from a clean slate
+    if (!expected) {      // a pure decode starts from a clean slate (a kernel, fill.h: BatchDecoder captures this)
+        if (const int rc = eae_fill_async(status, 0, (uint64_t)n_maps * sizeof(int32_t), s)) return rc;
+    }
     // the 64-maps-per-wavefront kernels need the workspace (prefix bytes) and 16-byte aligned streams; otherwise, or for L == 0 or
     // L > 32, the general kernel decodes every map
     const bool fast = fast_applies(L) && map_size && have_ws && !check_simd_layout(map_size, L, streams, stride);
@@ -1585,8 +1588,8 @@ int eae_hip_coder_roundtrip_trailing(uint32_t n_maps, uint32_t map_size, const i
     }
     const dim3 per_map(n_maps), per_group((n_maps + 63u) / 64u), wave(64);
     // every lane starts "not started" (0xFF..): a decoder chunk that finds too few bits leaves it so
-    (void)hipMemsetAsync(p.dec_state, 0xFF, (size_t)n_maps * 16u, s);
-    (void)hipMemsetAsync(p.avail_bits, 0, (size_t)n_maps * 4u, s);
+    if (const int rc = eae_fill_async(p.dec_state, 0xFF, (uint64_t)n_maps * 16u, s)) return rc;
+    if (const int rc = eae_fill_async(p.avail_bits, 0, (uint64_t)n_maps * 4u, s)) return rc;
     hipLaunchKernelGGL(binarise_kernel, per_map, wave, 0, s, p);
     (void)hipEventRecord(t->start, s);
     (void)hipStreamWaitEvent(t->emit, t->start, 0);

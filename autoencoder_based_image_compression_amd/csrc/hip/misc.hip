@@ -1,5 +1,6 @@
 // misc.hip -- library identity and device probing.
 #include "common.h"
+#include "fill.h"
 #include "conv_gemm.h"
 
 #include <cstdio>
@@ -151,6 +152,29 @@ extern "C" int eae_hip_publish_step(void* src_device, void* dst_host_mapped, uin
     hipLaunchKernelGGL(publish_step_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (uint32_t*)src_device, (uint32_t*)dst_host_mapped, words,
                        clear_from_byte / 4, (unsigned int*)conv_workspace, error_word, (uint32_t*)tickets_device, (uint32_t*)counter_device,
                        (volatile uint32_t*)word_host_mapped);
+    return (int)hipGetLastError();
+}
+
+// eae_fill_async (fill.h). Observed with hipMemsetAsync in its place (two BatchDecoders of 24 images and of one image per step, graphs
+// on, tests/test_gpu_decoders_of_two_batch_sizes.py): once the second decoder had captured its steps, replays of the first left every
+// status of a slot nonzero and a failure word that is no count, while the same step issued launch by launch was right.
+// Head bytes up to a 4-byte boundary and tail bytes singly, the words between as words.
+__global__ __launch_bounds__(256) void fill_kernel(uint8_t* __restrict__ dst, uint32_t word, uint64_t head, uint64_t words, uint64_t tail) {
+    const uint64_t i0 = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x, step = (uint64_t)gridDim.x * blockDim.x;
+    uint32_t* body = reinterpret_cast<uint32_t*>(dst + head);
+    for (uint64_t i = i0; i < words; i += step) body[i] = word;
+    if (i0 < head) dst[i0] = (uint8_t)word;
+    if (i0 < tail) dst[head + 4 * words + i0] = (uint8_t)word;
+}
+int eae_fill_async(void* dst_device, uint8_t value, uint64_t bytes, hipStream_t stream) {
+    if (!dst_device) return EAE_HIP_BAD_ARGUMENT;
+    if (bytes == 0) return EAE_HIP_OK;
+    uint64_t head = (4u - ((uintptr_t)dst_device & 3u)) & 3u;
+    if (head > bytes) head = bytes;
+    const uint64_t words = (bytes - head) / 4, tail = bytes - head - 4 * words;
+    uint64_t blocks = (words + 255) / 256;
+    blocks = blocks > 64 ? 64 : (blocks < 1 ? 1 : blocks);
+    hipLaunchKernelGGL(fill_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (uint8_t*)dst_device, 0x01010101u * value, head, words, tail);
     return (int)hipGetLastError();
 }
 

@@ -9,6 +9,7 @@
 #include <new>
 
 #include "eae_hip.h"
+#include "fill.h"
 
 struct eae_hip_model {
     int learned;
@@ -164,8 +165,8 @@ extern "C" int eae_hip_encode(const eae_hip_model* m, const uint8_t* images, int
     const ScratchLayout s = encode_layout(n, h, w);
     if (scratch_bytes < s.total) return EAE_HIP_BAD_ARGUMENT;
     char* base = static_cast<char*>(scratch);
-    hipError_t e = hipMemsetAsync(base + s.conv_ws, 0, s.status + 256, (hipStream_t)stream);   // workspace + status word
-    if (e != hipSuccess) return (int)e;
+    const int zeroed = eae_fill_async(base + s.conv_ws, 0, s.status + 256, (hipStream_t)stream);   // workspace + status word
+    if (zeroed) return zeroed;
     float* a = reinterpret_cast<float*>(base + s.a);
     float* b = reinterpret_cast<float*>(base + s.b);
     int rc = eae_hip_conv9x9s4_u8(images, m->w1, m->b1, m->g1, m->be1, a, n, h, w, stream);
@@ -195,8 +196,8 @@ extern "C" int eae_hip_decode(const eae_hip_model* m, const float* quantized_lat
     const ScratchLayout s = decode_layout(n, h_latent, w_latent);
     if (scratch_bytes < s.total) return EAE_HIP_BAD_ARGUMENT;
     char* base = static_cast<char*>(scratch);
-    hipError_t e = hipMemsetAsync(base + s.conv_ws, 0, s.status + 256, (hipStream_t)stream);   // workspace + status word
-    if (e != hipSuccess) return (int)e;
+    const int zeroed = eae_fill_async(base + s.conv_ws, 0, s.status + 256, (hipStream_t)stream);   // workspace + status word
+    if (zeroed) return zeroed;
     float* a = reinterpret_cast<float*>(base + s.a);
     float* b = reinterpret_cast<float*>(base + s.b);
     float* c = reinterpret_cast<float*>(base + s.c);

@@ -51,9 +51,12 @@ __global__ __launch_bounds__(TS_THREADS) void tile_symbols_gather_kernel(const i
 // Exactly the arithmetic of dequantize_kernel (csrc/hip/container.hip): cq = bw * symbol, then cq + mean, no contraction.
 // LDS: the reads are ds_read_b64 at dword 66 * pixel + 2 * quad, so each half-wave covers the 64 banks once; the 2-byte writes of a
 // half-wave fall on 16 banks twice.
-__global__ __launch_bounds__(TS_THREADS) void tile_symbols_dequantize_kernel(const int16_t* __restrict__ tiles, const int64_t* __restrict__ plan,
-                                                                             const float* __restrict__ bin_widths, const float* __restrict__ map_mean,
-                                                                             float* __restrict__ out, int64_t hs, int64_t ws) {
+// ROWS: bin_widths and map_mean hold one row of 128 per image, f32 [n][128], and the block takes the row of its plan row's image
+// (eae_hip_tile_symbols_dequantize_rows); else one row serves every image.
+template <bool ROWS>
+__device__ __forceinline__ void tile_symbols_dequantize_body(const int16_t* __restrict__ tiles, const int64_t* __restrict__ plan,
+                                                             const float* __restrict__ bin_widths, const float* __restrict__ map_mean,
+                                                             float* __restrict__ out, int64_t hs, int64_t ws) {
     __shared__ __attribute__((aligned(16))) int16_t lds[DQ_PIX][DQ_PITCH];
     const int64_t* row = plan + (size_t)blockIdx.y * EAE_TILE_SYMBOLS_PLAN_COLS;
     const int64_t img = row[0], r0 = row[1], c0 = row[2], off = row[5];
@@ -71,6 +74,10 @@ __global__ __launch_bounds__(TS_THREADS) void tile_symbols_dequantize_kernel(con
     __syncthreads();
     const int q = tid & 31, sub = tid >> 5;                    // channel quad, pixel of the pass
     float bw[4], m[4];
+    if (ROWS) {
+        bin_widths += img * EAE_C;
+        if (map_mean) map_mean += img * EAE_C;
+    }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         bw[k] = bin_widths[4 * q + k];
@@ -94,6 +101,19 @@ __global__ __launch_bounds__(TS_THREADS) void tile_symbols_dequantize_kernel(con
         }
         *reinterpret_cast<float4*>(out + ((img * hs + R) * ws + C) * EAE_C + 4 * q) = v;
     }
+}
+
+__global__ __launch_bounds__(TS_THREADS) void tile_symbols_dequantize_kernel(const int16_t* __restrict__ tiles, const int64_t* __restrict__ plan,
+                                                                             const float* __restrict__ bin_widths, const float* __restrict__ map_mean,
+                                                                             float* __restrict__ out, int64_t hs, int64_t ws) {
+    tile_symbols_dequantize_body<false>(tiles, plan, bin_widths, map_mean, out, hs, ws);
+}
+
+__global__ __launch_bounds__(TS_THREADS) void tile_symbols_dequantize_rows_kernel(const int16_t* __restrict__ tiles, const int64_t* __restrict__ plan,
+                                                                                  const float* __restrict__ bin_widths_rows,
+                                                                                  const float* __restrict__ map_mean_rows, float* __restrict__ out,
+                                                                                  int64_t hs, int64_t ws) {
+    tile_symbols_dequantize_body<true>(tiles, plan, bin_widths_rows, map_mean_rows, out, hs, ws);
 }
 
 // Largest tile of a plan (pixels), or -1 when a row is malformed. `inside`: rows must lie in an n x h x w plane (gather);
@@ -127,9 +147,11 @@ extern "C" int eae_hip_tile_symbols_gather(const int16_t* symbols_planar, int n,
     return EAE_HIP_OK;
 }
 
-extern "C" int eae_hip_tile_symbols_dequantize(const int16_t* tiles, int64_t tile_elems, const int64_t* plan, const int64_t* host_plan,
-                                               int n_tiles, const float* bin_widths, const float* map_mean, float* shifted_out, int n,
-                                               int hs, int ws, void* stream) {
+namespace {
+
+// The argument checks and the launch of both dequantising entry points; `rows`: one row of bin widths and means per image.
+int launch_symbols_dequantize(bool rows, const int16_t* tiles, int64_t tile_elems, const int64_t* plan, const int64_t* host_plan, int n_tiles,
+                              const float* bin_widths, const float* map_mean, float* shifted_out, int n, int hs, int ws, void* stream) {
     if (!tiles || !plan || !host_plan || !bin_widths || !shifted_out || tile_elems <= 0 || n_tiles < 0 || n <= 0 || hs <= 0 || ws <= 0)
         return EAE_HIP_BAD_ARGUMENT;
     if (((uintptr_t)shifted_out & 15u) != 0 || n_tiles > 65535) return EAE_HIP_BAD_SHAPE;
@@ -137,8 +159,27 @@ extern "C" int eae_hip_tile_symbols_dequantize(const int16_t* tiles, int64_t til
     if (largest < 0) return EAE_HIP_BAD_SHAPE;
     if (n_tiles == 0) return EAE_HIP_OK;
     const dim3 grid((unsigned)((largest + DQ_PIX - 1) / DQ_PIX), (unsigned)n_tiles);
-    hipLaunchKernelGGL(tile_symbols_dequantize_kernel, grid, dim3(TS_THREADS), 0, (hipStream_t)stream, tiles, plan, bin_widths, map_mean,
-                       shifted_out, (int64_t)hs, (int64_t)ws);
+    if (rows)
+        hipLaunchKernelGGL(tile_symbols_dequantize_rows_kernel, grid, dim3(TS_THREADS), 0, (hipStream_t)stream, tiles, plan, bin_widths,
+                           map_mean, shifted_out, (int64_t)hs, (int64_t)ws);
+    else
+        hipLaunchKernelGGL(tile_symbols_dequantize_kernel, grid, dim3(TS_THREADS), 0, (hipStream_t)stream, tiles, plan, bin_widths, map_mean,
+                           shifted_out, (int64_t)hs, (int64_t)ws);
     EAE_HIP_CHECK_LAUNCH();
     return EAE_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" int eae_hip_tile_symbols_dequantize(const int16_t* tiles, int64_t tile_elems, const int64_t* plan, const int64_t* host_plan,
+                                               int n_tiles, const float* bin_widths, const float* map_mean, float* shifted_out, int n,
+                                               int hs, int ws, void* stream) {
+    return launch_symbols_dequantize(false, tiles, tile_elems, plan, host_plan, n_tiles, bin_widths, map_mean, shifted_out, n, hs, ws, stream);
+}
+
+extern "C" int eae_hip_tile_symbols_dequantize_rows(const int16_t* tiles, int64_t tile_elems, const int64_t* plan, const int64_t* host_plan,
+                                                    int n_tiles, const float* bin_widths_rows, const float* map_mean_rows, float* shifted_out,
+                                                    int n, int hs, int ws, void* stream) {
+    return launch_symbols_dequantize(true, tiles, tile_elems, plan, host_plan, n_tiles, bin_widths_rows, map_mean_rows, shifted_out, n, hs, ws,
+                                     stream);
 }

@@ -591,6 +591,24 @@ def tile_symbols_dequantize(tiles, plan_device, plan_host, bin_widths, map_mean,
     return out
 
 
+def tile_symbols_dequantize_rows(tiles, plan_device, plan_host, bin_widths_rows, map_mean_rows, out):
+    """`tile_symbols_dequantize` with one row of bin widths and one row of means (or None) per image of `out`, float32 [N, 128] each:
+    a tile takes the rows of its plan row's image. Bit for bit `tile_symbols_dequantize` called image by image with that image's rows."""
+    if tiles.dtype != torch.int16 or tiles.dim() != 1:
+        raise HipError('tiles must be one-dimensional int16')
+    if out.dtype != torch.float32 or out.dim() != 4 or out.shape[3] != NB_MAPS:
+        raise HipError('out must be float32 [N, hs, ws, 128]')
+    (n, hs, ws) = out.shape[:3]
+    for rows in (bin_widths_rows,) if map_mean_rows is None else (bin_widths_rows, map_mean_rows):
+        if rows.dtype != torch.float32 or rows.numel() != n*NB_MAPS or not rows.is_contiguous():
+            raise HipError('bin widths and map means must be contiguous float32 of 128 elements per image of out')
+    (plan_p, host_p, nb_rows) = _symbols_plan_pointers(plan_device, plan_host)
+    _check(_native.hip().eae_hip_tile_symbols_dequantize_rows(_p(tiles), tiles.numel(), plan_p, host_p, nb_rows, _p(bin_widths_rows),
+                                                              _p(map_mean_rows), _p(out), n, hs, ws, _stream(tiles)),
+           'eae_hip_tile_symbols_dequantize_rows')
+    return out
+
+
 # ---- lossless coder on the device (include/eae_hip.h, "lossless coder on the device") ---------------------------------
 
 CODER_ROUNDTRIP, CODER_ENCODE_ONLY, CODER_ROUNDTRIP_VERIFY = 0, 1, 2

@@ -146,13 +146,21 @@ int eae_hip_tile_stitch_u8(const uint8_t* windows, int window_h, int window_w, u
  * tile_symbols_gather: symbols_planar [n][128][h * w] int16 (eae_hip_quantize_maps) -> `tiles`. Every tile lies inside the h x w plane.
  * tile_symbols_dequantize: `tiles` -> shifted_out f32 [n][hs][ws][128] = bin_widths[c] * symbol + map_mean[c] (map_mean nullable),
  *   the arithmetic of eae_hip_dequantize_maps, bit for bit. Image and origin are in the hs x ws output; the origin may be negative
- *   and a tile may reach past the output: only its pixels inside are written. shifted_out aligned to 16 bytes. */
+ *   and a tile may reach past the output: only its pixels inside are written. shifted_out aligned to 16 bytes.
+ * tile_symbols_dequantize_rows: tile_symbols_dequantize with one row of bin widths and one row of means (nullable) per image of the
+ *   output, f32 [n][128] each: a tile is dequantised with the rows of its plan row's image, bin_widths_rows[image][c] * symbol +
+ *   map_mean_rows[image][c]. Same plan, same checks, same limits, same arithmetic: the output equals, bit for bit, that of
+ *   tile_symbols_dequantize called image by image with that image's rows (codec.BatchDecoder(coding_tile=...), whose step holds
+ *   images of several blobs). */
 #define EAE_TILE_SYMBOLS_PLAN_COLS 6
 int eae_hip_tile_symbols_gather(const int16_t* symbols_planar, int n, int h, int w, int16_t* tiles, int64_t tile_elems,
                                 const int64_t* plan, const int64_t* host_plan, int n_tiles, void* stream);
 int eae_hip_tile_symbols_dequantize(const int16_t* tiles, int64_t tile_elems, const int64_t* plan, const int64_t* host_plan, int n_tiles,
                                     const float* bin_widths, const float* map_mean, float* shifted_out, int n, int hs, int ws,
                                     void* stream);
+int eae_hip_tile_symbols_dequantize_rows(const int16_t* tiles, int64_t tile_elems, const int64_t* plan, const int64_t* host_plan,
+                                         int n_tiles, const float* bin_widths_rows, const float* map_mean_rows, float* shifted_out, int n,
+                                         int hs, int ws, void* stream);
 
 /* ---- analysis transform (eae/graph/components.py:86-142) ---------------------------------------------------------*/
 
