@@ -25,7 +25,8 @@ and those made while the current stream captures a graph (the poison fill would 
 guard keeps every allocation alive until `check()`, so a test that bounds the peak of allocated memory sees what the guard holds.
 
 `guarded(modules, poison)` swaps the module-global `torch` of the listed package modules (device, pipeline; container where a test
-needs it) for a proxy that forwards everything to torch except the six allocation functions, and checks the bands on exit. A new
+needs it; codec where the resident codecs' slots are to lie between bands, tests/test_gpu_codec_slots.py) for a proxy that forwards
+everything to torch except the six allocation functions, and checks the bands on exit. A new
 kernel test should allocate through it: add the module-level autouse fixture the kernel-level GPU modules carry, and upload the
 inputs with `Guard.upload` where reads matter.
 """
@@ -160,10 +161,13 @@ class Guard(object):
     def _bands(self, a):
         return a.raw[a.start - self.band:a.start], a.raw[a.start + a.nbytes:a.start + a.nbytes + self.band]
 
-    def check(self):
+    def check(self, keep=False):
         """Asserts that every band of every allocation since the last check still holds the poison byte, then drops the references.
         On failure: the allocation (shape, dtype, the function that allocated it) and the first changed offset relative to the
-        interior (negative: in front of it; >= nbytes: behind it)."""
+        interior (negative: in front of it; >= nbytes: behind it).
+        keep=True: the bands are verified and the allocations stay with the guard -- a test that checks after every step of a resident
+        codec (tests/test_gpu_codec_slots.py) learns which step overran, and the exit's check still covers the slots' buffers. A failed
+        check drops the references either way."""
         (live, self._live) = (self._live, [])
         if not live:
             return
@@ -185,6 +189,8 @@ class Guard(object):
             failures.append('{0}: {1} band bytes changed, the first at offset {2} of the interior ({3} bytes)'.format(
                 a.describe(), count, offset, a.nbytes))
         assert not failures, 'written outside a tensor (poison 0x{0:02X}):\n  '.format(self.poison) + '\n  '.join(failures)
+        if keep:
+            self._live = live + self._live
 
 
 class _TorchProxy(object):

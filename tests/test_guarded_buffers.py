@@ -177,3 +177,22 @@ def test_the_package_modules_have_a_swappable_torch():
         assert device.torch is pipeline.torch and device.torch is not torch
         assert device.torch.float32 is torch.float32 and device.torch.cuda is torch.cuda
     assert device.torch is torch and pipeline.torch is torch
+
+
+@pytest.mark.parametrize('poison', POISONS)
+def test_check_keep_verifies_without_dropping(poison):
+    """`check(keep=True)` between the steps of a resident codec: the bands are verified, the allocations stay for the next check, and
+    an overrun between two checks is reported by the later one."""
+    guard = guarded.Guard(poison, cpu=True)
+    t = guard.empty(10, dtype=torch.uint8)
+    guard.check(keep=True)
+    assert len(guard._live) == 1
+    u = guard.zeros(3, dtype=torch.int32)
+    guard.check(keep=True)
+    assert [a.nbytes for a in guard._live] == [10, 12]           # in the order they were made
+    (raw, start, nbytes) = _raw_of(guard, 0)
+    raw[start + nbytes + 5] = 1
+    with pytest.raises(AssertionError, match='offset 15 of the interior'):
+        guard.check(keep=True)
+    assert not guard._live and t.numel() == 10 and u.tolist() == [0, 0, 0]      # a failed check drops the references
+    guard.check()

@@ -1,0 +1,124 @@
+"""Every attribute of the resident codecs' slots (`codec._Slot`, `codec._DecodeLane`, `codec._DecodeSlot`) is classified in
+tests/slot_buffers.py: what a step may find in it when it starts. tests/test_gpu_codec_slots.py poisons the SCRATCH ones between the
+steps of `BatchCodec` and `BatchDecoder`; a buffer added to a slot without a word here would simply never be poisoned. CPU-only: it
+reads source text."""
+import ast
+import os
+
+import slot_buffers
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CODEC = os.path.join(ROOT, 'autoencoder_based_image_compression_amd', 'codec.py')
+
+
+def _source():
+    with open(CODEC) as f:
+        return f.read()
+
+
+def _init_of(tree, class_name):
+    for node in tree.body:
+        if isinstance(node, ast.ClassDef) and node.name == class_name:
+            for item in node.body:
+                if isinstance(item, ast.FunctionDef) and item.name == '__init__':
+                    return node, item
+    raise AssertionError('codec.py has no {0}.__init__'.format(class_name))
+
+
+def _self_targets(target):
+    """Names X of every `self.X` a (possibly nested tuple) assignment target holds."""
+    if isinstance(target, (ast.Tuple, ast.List)):
+        return [name for element in target.elts for name in _self_targets(element)]
+    if isinstance(target, ast.Starred):
+        return _self_targets(target.value)
+    if isinstance(target, ast.Attribute) and isinstance(target.value, ast.Name) and target.value.id == 'self':
+        return [target.attr]
+    return []
+
+
+def assigned_attributes(source, class_name):
+    """Every attribute the class's `__init__` assigns (in any branch), and for a class with `__slots__` every slot."""
+    (node, init) = _init_of(ast.parse(source), class_name)
+    names = set()
+    for sub in ast.walk(init):
+        if isinstance(sub, ast.Assign):
+            for target in sub.targets:
+                names.update(_self_targets(target))
+        elif isinstance(sub, (ast.AugAssign, ast.AnnAssign)):
+            names.update(_self_targets(sub.target))
+    for item in node.body:
+        if isinstance(item, ast.Assign) and any(isinstance(t, ast.Name) and t.id == '__slots__' for t in item.targets):
+            names.update(ast.literal_eval(item.value))
+    return names
+
+
+def unclassified(source):
+    """{class: sorted attributes its `__init__` assigns (or its `__slots__` names) that its table does not classify}."""
+    out = {}
+    for (class_name, table) in slot_buffers.TABLES.items():
+        known = {slot_buffers.attribute_of(name) for name in table}
+        out[class_name] = sorted(assigned_attributes(source, class_name) - known)
+    return out
+
+
+def _with_one_more_buffer(source, class_name):
+    """`source` with `self.extra = torch.empty(...)` behind the last statement of the class's `__init__`."""
+    (_, init) = _init_of(ast.parse(source), class_name)
+    last = init.body[-1]
+    lines = source.split('\n')
+    lines.insert(last.end_lineno, ' '*last.col_offset + 'self.extra = torch.empty(16, dtype=torch.uint8, device=device)')
+    return '\n'.join(lines)
+
+
+def test_the_three_inits_parse():
+    source = _source()
+    slot = assigned_attributes(source, '_Slot')
+    assert {'block', 'symbols', 'coder_streams', 'workspace', 'offsets', 'payload', 'staging', 'graphs', 'emit_host'} <= slot
+    assert {'results', 'hist', 'overflow', 'flags', 'checks'} <= slot                  # a tuple target
+    assert {'gathered', 'classes'} <= slot                                              # assigned as a pair
+    assert {'head', 'head_bits', 'status', 'decoded', 'classes', 'scratch', 'unfinished', 'stream'} <= assigned_attributes(source, '_DecodeLane')
+    assert {'lane', 'pinned_head', 'head_host', 'payload_host', 'planes', 'graph', 'count'} <= assigned_attributes(source, '_DecodeSlot')
+
+
+def test_every_assigned_attribute_is_classified():
+    missing = {k: v for (k, v) in unclassified(_source()).items() if v}
+    assert not missing, 'attributes of a slot that tests/slot_buffers.py does not classify (a buffer nobody poisons): {}'.format(missing)
+
+
+def test_every_entry_exists_and_says_why():
+    source = _source()
+    for (class_name, table) in slot_buffers.TABLES.items():
+        assigned = assigned_attributes(source, class_name)
+        for (name, entry) in table.items():
+            assert slot_buffers.attribute_of(name) in assigned, (class_name, name, 'is classified but no longer assigned')
+            assert entry.cls in slot_buffers.CLASSES, (class_name, name)
+            assert entry.reason.strip() and any(c.isdigit() for c in entry.reason), (class_name, name, 'needs a reason that names a line')
+            if entry.cls == slot_buffers.CONTAINER:
+                assert entry.parts and all(part in table and table[part].cls != slot_buffers.CONTAINER for part in entry.parts), (class_name, name)
+            else:
+                assert entry.parts is None, (class_name, name)
+            if entry.alias is not None:
+                assert entry.alias in table and table[entry.alias].cls == entry.cls and table[entry.alias].alias is None, (class_name, name)
+
+
+def test_what_must_be_scratch_is_scratch():
+    assert set(slot_buffers.MUST_BE_SCRATCH) == set(slot_buffers.TABLES)
+    for (class_name, names) in slot_buffers.MUST_BE_SCRATCH.items():
+        table = slot_buffers.TABLES[class_name]
+        for name in names:
+            assert name in table and table[name].cls == slot_buffers.SCRATCH, (class_name, name)
+            assert table[name].alias is None, (class_name, name, 'must be poisoned itself')
+    # the accumulators, counters and constants a step relies on are NOT scratch: poisoning them would hang a worker or derail a launch
+    for (class_name, name) in (('_Slot', 'conv_ws'), ('_Slot', 'seq_dev'), ('_Slot', 'pinned_seq'), ('_Slot', 'hist'), ('_Slot', 'flags'),
+                               ('_Slot', 'sse'), ('_Slot', 'table[:nb_maps]'), ('_DecodeLane', 'head_bytes'), ('_DecodeSlot', 'seq_dev'),
+                               ('_DecodeSlot', 'pinned_seq')):
+        assert slot_buffers.TABLES[class_name][name].cls in (slot_buffers.CARRIED, slot_buffers.CONSTANT), (class_name, name)
+
+
+def test_an_unclassified_buffer_is_noticed():
+    """The check has teeth: one more `self.extra = torch.empty(...)` in any of the three `__init__` bodies is reported, there only."""
+    source = _source()
+    for class_name in slot_buffers.TABLES:
+        grown = _with_one_more_buffer(source, class_name)
+        assert grown != source and 'extra' in assigned_attributes(grown, class_name)
+        assert unclassified(grown) == {k: (['extra'] if k == class_name else []) for k in slot_buffers.TABLES}, class_name
