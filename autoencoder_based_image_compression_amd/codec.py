@@ -1422,6 +1422,36 @@ def plan_decode_step(blobs, batch_size, h_in, w_in, truncated_unary_length, are_
 DECODER_STREAMS = 4
 
 
+def _decoder_device(device):
+    """The device of a resident decoder: the current one, by name or by default (launches go to the current device's streams)."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    if device.index != torch.cuda.current_device():
+        raise ValueError('`device` is {0} but the current device is cuda:{1}: build and use the decoder under '
+                         '`torch.cuda.device({0!r})`.'.format(device, torch.cuda.current_device()))
+    return device
+
+
+def _decoder_streams(nb_streams, name):
+    """The streams a resident decoder (`BatchDecoder`, `RegionDecoder`) runs: what the caller asked for, or `DECODER_STREAMS`, capped
+    to the hardware queues of the process."""
+    asked = nb_streams is not None
+    nb_streams = max(1, int(nb_streams)) if asked else DECODER_STREAMS
+    if os.environ.get('EAE_IGNORE_HW_QUEUES') != '1':
+        # (a decoder has no coder streams: the one `stream_budget` always leaves for them is the margin here)
+        (capped, _, _) = stream_budget(nb_streams, 1)
+        # (the default is capped without a word: the caller asked for nothing)
+        if asked and capped != nb_streams and not _BUDGET_WARNED[0]:
+            _BUDGET_WARNED[0] = True
+            import warnings
+            warnings.warn('{2}: {0} streams asked for, running {1}: this process has too few hardware queues '
+                          '(GPU_MAX_HW_QUEUES; streams beyond them share queues and serialise).'.format(nb_streams, capped, name),
+                          RuntimeWarning, stacklevel=3)
+        nb_streams = capped
+    return nb_streams
+
+
 class DecodeTicket(object):
     """Handle on one submitted `BatchDecoder` step."""
 
@@ -1446,11 +1476,12 @@ class DecodeTicket(object):
 
 
 class _DecodeJob(_Claimable):
-    __slots__ = ('ticket', 'slot', 'sequence', 'payload_bytes')
+    __slots__ = ('ticket', 'slot', 'sequence', 'payload_bytes', 'detail')
 
-    def __init__(self, ticket, slot, sequence, payload_bytes):
+    def __init__(self, ticket, slot, sequence, payload_bytes, detail=None):
+        """detail: what else the worker needs of the step's plan (`RegionDecoder`: where every crop's streams lie)."""
         super(_DecodeJob, self).__init__()
-        (self.ticket, self.slot, self.sequence, self.payload_bytes) = (ticket, slot, sequence, payload_bytes)
+        (self.ticket, self.slot, self.sequence, self.payload_bytes, self.detail) = (ticket, slot, sequence, payload_bytes, detail)
 
 
 class _DecodeWorker(_StepWorker):
@@ -1480,25 +1511,7 @@ class _DecodeWorker(_StepWorker):
             if int(slot.index_host[0]) != job.payload_bytes or int(slot.index_host[1]) != 0:
                 raise RuntimeError('the device placed {0} payload bytes, the headers of the step announce {1}'.format(
                     int(slot.index_host[0]), job.payload_bytes))
-            from .kodak.lossless import interface_cython
-            errors = []
-            (results, per_image) = (slot.results_host, self.streams_per_image)
-            if self.payload_order is not None:
-                # status and stage of every stream in payload order: an image's first failing stream is the first of its first
-                # failing tile, as `container.decode_images` meets them in the image's own blob
-                results = results.take(self.payload_order, axis=1)
-            for i in range(ticket.nb_images):
-                status = results[2, i*per_image:(i + 1)*per_image]
-                error = None
-                if status.any():
-                    bad = i*per_image + int(numpy.flatnonzero(status)[0])
-                    try:
-                        interface_cython.raise_for_status(int(results[2, bad]), int(results[3, bad]))
-                    except Exception as exc:
-                        error = exc
-                errors.append(error)
-            ticket.errors = errors
-            ticket._value = slot.rec_host[:ticket.nb_images] if slot.rec_host is not None else slot.planes[:ticket.nb_images]
+            self._form(job)
         except StepTimeout as exc:
             self.failed = exc
             ticket._error = exc
@@ -1509,6 +1522,29 @@ class _DecodeWorker(_StepWorker):
                 ticket.errors = [ticket._error]*ticket.nb_images
             slot.free.set()
             ticket._done.set()
+
+    def _form(self, job):
+        """The ticket's errors and value from the slot's pinned blocks, once the step is through and its byte count agrees."""
+        (ticket, slot) = (job.ticket, job.slot)
+        from .kodak.lossless import interface_cython
+        errors = []
+        (results, per_image) = (slot.results_host, self.streams_per_image)
+        if self.payload_order is not None:
+            # status and stage of every stream in payload order: an image's first failing stream is the first of its first
+            # failing tile, as `container.decode_images` meets them in the image's own blob
+            results = results.take(self.payload_order, axis=1)
+        for i in range(ticket.nb_images):
+            status = results[2, i*per_image:(i + 1)*per_image]
+            error = None
+            if status.any():
+                bad = i*per_image + int(numpy.flatnonzero(status)[0])
+                try:
+                    interface_cython.raise_for_status(int(results[2, bad]), int(results[3, bad]))
+                except Exception as exc:
+                    error = exc
+            errors.append(error)
+        ticket.errors = errors
+        ticket._value = slot.rec_host[:ticket.nb_images] if slot.rec_host is not None else slot.planes[:ticket.nb_images]
 
 
 class _DecodeLane(object):
@@ -1629,12 +1665,7 @@ class BatchDecoder(object):
             if int(batch_size)*container_format._nb_tiles(h_map, w_map, self.coding_tile) > 65535:
                 raise ValueError('`batch_size` images of {0} coding tiles each are more than the 65535 (image, tile) pairs a step can hold.'.format(
                     container_format._nb_tiles(h_map, w_map, self.coding_tile)))
-        self.device = torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
-        if self.device.index != torch.cuda.current_device():
-            raise ValueError('`device` is {0} but the current device is cuda:{1}: build and use the decoder under '
-                             '`torch.cuda.device({0!r})`.'.format(self.device, torch.cuda.current_device()))
+        self.device = _decoder_device(device)
         self.learned = bool(are_bin_widths_learned)
         self.decoder = pipeline.DeviceDecoder(variables, are_bin_widths_learned, self.device)
         (self.batch_size, self.h_in, self.w_in) = (int(batch_size), int(h_in), int(w_in))
@@ -1648,20 +1679,7 @@ class BatchDecoder(object):
         self.payload_capacity_bytes = -(-int(payload_capacity_bytes)//16)*16
         self.fetch_reconstruction = bool(fetch_reconstruction)
         self.use_graphs = bool(use_graphs)
-        asked = nb_streams is not None
-        nb_streams = max(1, int(nb_streams)) if asked else DECODER_STREAMS
-        if os.environ.get('EAE_IGNORE_HW_QUEUES') != '1':
-            # (a decoder has no coder streams: the one `stream_budget` always leaves for them is the margin here)
-            (capped, _, _) = stream_budget(nb_streams, 1)
-            # (the default is capped without a word: the caller asked for nothing)
-            if asked and capped != nb_streams and not _BUDGET_WARNED[0]:
-                _BUDGET_WARNED[0] = True
-                import warnings
-                warnings.warn('BatchDecoder: {0} streams asked for, running {1}: this process has too few hardware queues '
-                              '(GPU_MAX_HW_QUEUES; streams beyond them share queues and serialise).'.format(nb_streams, capped),
-                              RuntimeWarning, stacklevel=2)
-            nb_streams = capped
-        self.nb_streams = nb_streams
+        self.nb_streams = nb_streams = _decoder_streams(nb_streams, 'BatchDecoder')
         self.nb_in_flight = max(1, int(nb_in_flight)) if nb_in_flight is not None else nb_streams + 2
         self.nb_slots = self.nb_in_flight
         self._n_streams = self.batch_size*self.nb_maps
@@ -1712,9 +1730,7 @@ class BatchDecoder(object):
     def _submit(self, blobs, replay):
         slot = self._slots[self._index % self.nb_slots]
         slot.free.wait()
-        (nb_images, payload_bytes) = plan_decode_step(blobs, self.batch_size, self.h_in, self.w_in, self.truncated_unary_length, self.learned,
-                                                      self.payload_capacity_bytes, slot.head_host, slot.payload_host, self.nb_maps,
-                                                      self.coding_tile, self._tile_layout)
+        (nb_images, payload_bytes, detail) = self._plan_step(slot, blobs)
         slot.free.clear()
         self._index += 1
         expected = slot.count + 1
@@ -1731,7 +1747,7 @@ class BatchDecoder(object):
                     self._launch_step(slot)
             finally:
                 torch.cuda.set_stream(caller)
-            job = _DecodeJob(ticket, slot, (slot.seq_host, (expected,)), payload_bytes)
+            job = _DecodeJob(ticket, slot, (slot.seq_host, (expected,)), payload_bytes, detail)
             ticket._job = (job, self._worker)
             self._worker.jobs.put(job)
             slot.count = expected
@@ -1745,6 +1761,14 @@ class BatchDecoder(object):
                 pass
             slot.free.set()
             raise
+
+    def _plan_step(self, slot, blobs):
+        """The host side of a step, into the slot's pinned head and payload -> (images, payload bytes, detail for the worker).
+        Raises ValueError, with the slot untouched, for a step it refuses."""
+        (nb_images, payload_bytes) = plan_decode_step(blobs, self.batch_size, self.h_in, self.w_in, self.truncated_unary_length, self.learned,
+                                                      self.payload_capacity_bytes, slot.head_host, slot.payload_host, self.nb_maps,
+                                                      self.coding_tile, self._tile_layout)
+        return nb_images, payload_bytes, None
 
     def _capture_all(self):
         """Every slot's step as one hipGraph, while nothing of this decoder is in flight (and the other codecs of the device are
@@ -1818,3 +1842,448 @@ class BatchDecoder(object):
             self.close()
         except Exception:
             pass
+
+
+# ---- crops out of EAT1 containers, resident and pipelined --------------------------------------------------
+
+class RegionSource(object):
+    """An `EAT1` (or `EAE1`) container a `RegionDecoder` cuts crops out of: a bytes-like blob or a seekable binary file object. The
+    header is parsed and checked ONCE, here (`container.read_header`'s checks; of a file only the header is read); what stays is
+    `header`, and per (image, tile) entry the byte offset `starts` and the byte length `sizes` of its streams in the source, int64
+    [nb_images, nb_tiles]. `read(entries)` returns the bytes of [(image, tile)] entries."""
+
+    def __init__(self, source):
+        (self.header, self._blob) = container_format._source_header(source)
+        self._source = source
+        header = self.header
+        (self.h_map, self.w_map) = (header['height']//csts.STRIDE_PROD, header['width']//csts.STRIDE_PROD)
+        (tile, bits) = container_format._tile_layout(header)
+        self.coding_tile = (min(tile[0], self.h_map), min(tile[1], self.w_map))          # clamped, as `coding_tile_grid` cuts the plane
+        self.bits = bits                                                                 # uint32 [nb_images, nb_tiles, nb_maps, 2]
+        self.sizes = container_format._entry_bytes(bits)
+        flat = self.sizes.reshape(-1)
+        self.starts = (header['payload_offset'] + numpy.cumsum(flat) - flat).reshape(self.sizes.shape)
+        # the rows the coder decodes an image's maps with, the exception map's last: float64 [nb_images, nb_maps + 1, L]
+        (nb_images, nb_maps, length) = (header['nb_images'], header['nb_maps'], header['truncated_unary_length'])
+        self.table = numpy.full((nb_images, nb_maps + 1, length), 0.5, dtype=numpy.float64)
+        self.table[:, :nb_maps] = header['binary_probabilities']
+        self.prob_row = numpy.arange(nb_maps, dtype=numpy.int32)
+        if header['idx_map_exception'] >= 0:
+            self.table[:, nb_maps] = header['exception_probabilities']
+            self.prob_row[header['idx_map_exception']] = nb_maps
+
+    def read(self, entries):
+        """One bytes-like chunk per (image, tile) of `entries`: slices of an in-memory blob; of a file, adjacent ranges in one read
+        (`container.fetch_region`'s reader)."""
+        ranges = [(int(self.starts[i, t]), int(self.starts[i, t] + self.sizes[i, t])) for (i, t) in entries]
+        return container_format._read_ranges(self._source, self._blob, ranges)
+
+
+def region_window(h, w, region):
+    """(Rs, Cs): the latent rows and columns of the window a `RegionDecoder` synthesises for crops of region = (rh, rw) pixels out
+    of an h x w latent plane: the region's latents, one more where it is not aligned to 16, and `pipeline.DECODER_HALO` around them,
+    clamped to the plane."""
+    (before, after) = pipeline.DECODER_HALO
+    return (min(h, (region[0] + 14)//16 + 1 + before + after), min(w, (region[1] + 14)//16 + 1 + before + after))
+
+
+def region_origin(h, w, Rs, Cs, y0, x0):
+    """(r0, c0): where the Rs x Cs window of the crop at pixel (y0, x0) starts in the h x w latent plane. The window contains
+    `container.region_plan`'s minimal sub-plane, and where it was shifted to stay inside the plane its edge is the plane's edge."""
+    before = pipeline.DECODER_HALO[0]
+    return (min(max(y0//16 - before, 0), h - Rs), min(max(x0//16 - before, 0), w - Cs))
+
+
+def _axis_kinds(size, tile, window):
+    """One axis of the coding-tile grid against a window of `window` latents at every position: (kind of every grid index -- 0: a
+    full tile, 1: the shorter last one --, per kind the most tiles of it any position touches)."""
+    count = -(-size//tile)
+    kinds = [1 if (k == count - 1 and size % tile) else 0 for k in range(count)]
+    most = [0, 0]
+    for start in range(size - window + 1):
+        touched = kinds[start//tile:(start + window - 1)//tile + 1]
+        most = [max(most[0], touched.count(0)), max(most[1], touched.count(1))]
+    return kinds, most
+
+
+def region_layout(batch_size, h, w, coding_tile, Rs, Cs):
+    """Where everything of a `RegionDecoder` step lies; numpy only, the same for every step. batch_size crops,
+    each an Rs x Cs window of an h x w latent plane coded in `coding_tile` = (th, tw) latents (clamped to the plane). The grid has
+    two kinds of tile rows (full, last) and of tile columns, so at most four shape classes; a crop gets, per class, as many SLOTS as
+    the most tile rows of the class's row kind any window position touches, times the same of the columns. A slot is one (crop,
+    tile) of a step, or absent. Run order -- the order of the streams, the results, the offsets, the tile-major `decoded` buffer AND
+    of the payload -- is class -> crop -> slot. -> dict: 'coding_tile' (clamped), 'h', 'w', 'window' (Rs, Cs), 'batch_size', 'tiles'
+    and 'classes' (`container.coding_tile_grid`), 'class_slots' [slots per crop of every class], 'class_first' [run index of every
+    class's first slot], 'slots_per_crop', 'n_slots', 'n_streams' = n_slots*128, 'runs' [((rows, cols), slots of the class, first
+    stream, first element)] as `coding_tile_layout`'s, class runs on 128-element boundaries, 'elements' of the `decoded` buffer,
+    'slots' int64 [n_slots, 3] (rows, cols, element offset: `device.tile_symbols_dequantize_placed`'s static half)."""
+    batch_size = container_format._positive_int(batch_size, '`batch_size`')
+    (th, tw) = container_format._positive_pair(coding_tile, '`coding_tile`')
+    coding_tile = (min(th, h), min(tw, w))
+    if not (1 <= Rs <= h and 1 <= Cs <= w):
+        raise ValueError('The window does not fit the latent plane.')
+    (tiles, classes) = container_format.coding_tile_grid(h, w, coding_tile)
+    (row_kinds, most_rows) = _axis_kinds(h, coding_tile[0], Rs)
+    (col_kinds, most_cols) = _axis_kinds(w, coding_tile[1], Cs)
+    tiles_per_row = len(col_kinds)
+    class_slots = [0]*len(classes)
+    for (i, rk) in enumerate(row_kinds):
+        for (j, ck) in enumerate(col_kinds):
+            class_slots[int(tiles[i*tiles_per_row + j, 4])] = most_rows[rk]*most_cols[ck]
+    nb_maps = csts.NB_MAPS_3
+    (runs, class_first, slots, first, pos) = ([], [], [], 0, 0)
+    for (cls, (rows, cols)) in enumerate(classes):
+        count = batch_size*class_slots[cls]
+        runs.append(((rows, cols), count, first*nb_maps, pos))
+        class_first.append(first)
+        slots += [(rows, cols, pos + k*nb_maps*rows*cols) for k in range(count)]
+        first += count
+        pos = (pos + count*nb_maps*rows*cols + 127)//128*128
+    return {'coding_tile': coding_tile, 'h': h, 'w': w, 'window': (Rs, Cs), 'batch_size': batch_size, 'tiles': tiles, 'classes': classes,
+            'tiles_per_row': tiles_per_row, 'class_slots': class_slots, 'class_first': class_first, 'slots_per_crop': sum(class_slots),
+            'n_slots': first, 'n_streams': first*nb_maps, 'runs': runs, 'elements': max(pos, 128),
+            'slots': numpy.array(slots, dtype=numpy.int64).reshape(-1, 3)}
+
+
+def region_head_layout(batch_size, n_slots, truncated_unary_length, nb_maps=csts.NB_MAPS_3):
+    """The step head of `RegionDecoder`, in the manner of `decode_head_layout`: one fixed-size block, one copy. -> (fields {name:
+    (byte offset, dtype, shape)}, bytes of the block, a multiple of 16): 'bits' uint32 [n_streams][2] and 'prob_row' int32
+    [n_streams] in run order, n_streams = n_slots*nb_maps (an absent slot: zero bits, -1); 'placement' int32 [n_slots][4] (crop or
+    -1, tile origin row and col in the crop's window, 0); 'crop_origin' int32 [batch][2] (the crop in its window's reconstruction);
+    'bin_widths', 'map_mean' float32 [batch][nb_maps]; 'table' float64 [batch][nb_maps + 1][L] (each crop's own source's rows,
+    the exception map's last); 'payload_bytes' uint64 [1]."""
+    n_streams = int(n_slots)*nb_maps
+    shapes = (('bits', numpy.uint32, (n_streams, 2)), ('prob_row', numpy.int32, (n_streams,)), ('placement', numpy.int32, (int(n_slots), 4)),
+              ('crop_origin', numpy.int32, (batch_size, 2)), ('bin_widths', numpy.float32, (batch_size, nb_maps)),
+              ('map_mean', numpy.float32, (batch_size, nb_maps)), ('table', numpy.float64, (batch_size, nb_maps + 1, truncated_unary_length)),
+              ('payload_bytes', numpy.uint64, (1,)))
+    (fields, pos) = ({}, 0)
+    for (name, dtype, shape) in shapes:
+        pos = -(-pos//8)*8
+        fields[name] = (pos, numpy.dtype(dtype), shape)
+        pos += numpy.dtype(dtype).itemsize*int(numpy.prod(shape))
+    return fields, -(-pos//16)*16
+
+
+def region_head_views(head, batch_size, n_slots, truncated_unary_length, nb_maps=csts.NB_MAPS_3):
+    """The fields of `region_head_layout` as numpy views of `head` (uint8, contiguous, at least the block's bytes, 8-byte aligned)."""
+    (fields, nbytes) = region_head_layout(batch_size, n_slots, truncated_unary_length, nb_maps)
+    if head.dtype != numpy.uint8 or head.ndim != 1 or head.size < nbytes:
+        raise ValueError('`head` must be a flat uint8 array of at least {0} bytes.'.format(nbytes))
+    return {name: head[pos:pos + dtype.itemsize*int(numpy.prod(shape))].view(dtype).reshape(shape) for (name, (pos, dtype, shape)) in fields.items()}
+
+
+def place_region(layout, y0, x0):
+    """The grid tiles the window of the crop at pixel (y0, x0) meets, and where they go -> ((r0, c0), [(tile, slot of the crop's
+    class-major slots: (class, index within the class), tile origin row - r0, tile origin col - c0)]) in tile row-major order."""
+    ((Rs, Cs), (th, tw), tiles) = (layout['window'], layout['coding_tile'], layout['tiles'])
+    (r0, c0) = region_origin(layout['h'], layout['w'], Rs, Cs, y0, x0)
+    used = [0]*len(layout['classes'])
+    placed = []
+    for i in range(r0//th, (r0 + Rs - 1)//th + 1):
+        for j in range(c0//tw, (c0 + Cs - 1)//tw + 1):
+            t = i*layout['tiles_per_row'] + j
+            cls = int(tiles[t, 4])
+            if used[cls] >= layout['class_slots'][cls]:
+                raise AssertionError('the window at ({0}, {1}) needs more slots of class {2} than the layout holds'.format(r0, c0, cls))
+            placed.append((t, (cls, used[cls]), int(tiles[t, 0]) - r0, int(tiles[t, 1]) - c0))
+            used[cls] += 1
+    return (r0, c0), placed
+
+
+def plan_region_step(requests, layout, head, payload, capacity, region, truncated_unary_length, are_bin_widths_learned,
+                     nb_maps=csts.NB_MAPS_3):
+    """The host side of one `RegionDecoder` step; numpy only (and the sources' own reads). requests: 1..batch_size of (RegionSource,
+    image, y0, x0); layout: `region_layout`; region = (rh, rw) pixels. EVERYTHING is checked -- and every byte range is read -- before
+    a byte of `head` (uint8: `region_head_layout`) or `payload` (uint8) is written: a refused step (ValueError) leaves both as they
+    were. Refused: no request or more than the layout's batch; a source of another size, of another clamped coding tile, of another
+    truncated unary length, of the other model kind, or an `EAE1` one; an image the source does not hold; a region that leaves the
+    image; a payload beyond `capacity`. Then the head is filled -- crop k's map m decodes with row k*(nb_maps + 1) + m of the table,
+    its exception map with row k*(nb_maps + 1) + nb_maps; absent slots get zero bits, row -1 and crop -1, absent crops zero bin
+    widths and means and rows of 0.5 -- and the placed entries' bytes go to `payload` in run order, one behind the other.
+    -> (crops, payload bytes, per crop the run-order slots of its tiles in tile row-major order)."""
+    requests = list(requests)
+    (batch_size, n_slots) = (layout['batch_size'], layout['n_slots'])
+    (h, w) = (layout['h'], layout['w'])
+    (rh, rw) = region
+    if not requests:
+        raise ValueError('A step needs at least one request.')
+    if len(requests) > batch_size:
+        raise ValueError('{0} requests, a step of this decoder takes {1} at most.'.format(len(requests), batch_size))
+    (steps, payload_bytes) = ([], 0)
+    for request in requests:
+        if not isinstance(request, (tuple, list)) or len(request) != 4 or not isinstance(request[0], RegionSource):
+            raise ValueError('A request is (RegionSource, image, y0, x0).')
+        (source, image, y0, x0) = request
+        for x in (image, y0, x0):
+            if isinstance(x, bool) or not isinstance(x, (int, numpy.integer)):
+                raise ValueError('A request is (RegionSource, image, y0, x0) in integers.')
+        header = source.header
+        if (source.h_map, source.w_map) != (h, w):
+            raise ValueError('The source holds {0} x {1} images, the decoder was built for {2} x {3}.'.format(
+                header['height'], header['width'], 16*h, 16*w))
+        if header.get('format') != 'EAT1':
+            raise ValueError('This decoder takes EAT1 sources of `coding_tile`={0}: this is an EAE1 source, whose maps are coded whole '
+                             '(container.decode_region reads a crop out of it).'.format(layout['coding_tile']))
+        if source.coding_tile != layout['coding_tile']:
+            raise ValueError('The source was coded in tiles of {0} latents, the decoder was built with `coding_tile`={1}.'.format(
+                source.coding_tile, layout['coding_tile']))
+        if header['truncated_unary_length'] != truncated_unary_length:
+            raise ValueError('The source was coded with a truncated unary length of {0}, the decoder was built for {1}.'.format(
+                header['truncated_unary_length'], truncated_unary_length))
+        if header['are_bin_widths_learned'] != bool(are_bin_widths_learned):
+            raise ValueError('The source was written by the other kind of model (learned / fixed bin widths).')
+        if not 0 <= image < header['nb_images']:
+            raise ValueError('The source holds {0} images: there is no image {1}.'.format(header['nb_images'], image))
+        if y0 < 0 or x0 < 0 or y0 + rh > 16*h or x0 + rw > 16*w:
+            raise ValueError('The region {0} leaves the {1} x {2} image.'.format((int(y0), int(x0), rh, rw), 16*h, 16*w))
+        ((r0, c0), placed) = place_region(layout, int(y0), int(x0))
+        payload_bytes += int(sum(source.sizes[image, t] for (t, _, _, _) in placed))
+        steps.append((source, int(image), (int(y0) - 16*r0, int(x0) - 16*c0), placed))
+    if payload_bytes > capacity or payload_bytes > payload.size:
+        raise ValueError('The payload of this step takes {0} bytes, the decoder holds {1} per step '
+                         '(RegionDecoder(payload_capacity_bytes=...)).'.format(payload_bytes, min(capacity, payload.size)))
+    views = region_head_views(head, batch_size, n_slots, truncated_unary_length, nb_maps)
+    # every range is read before anything is written: a truncated file refuses the step too
+    pieces = []                                          # (run-order slot, chunk)
+    crop_slots = []
+    for (k, (source, image, _, placed)) in enumerate(steps):
+        chunks = source.read([(image, t) for (t, _, _, _) in placed])
+        runs = [layout['class_first'][cls] + k*layout['class_slots'][cls] + s for (_, (cls, s), _, _) in placed]
+        for (run, chunk, (t, _, _, _)) in zip(runs, chunks, placed):
+            if len(chunk) != source.sizes[image, t]:
+                raise ValueError('A payload range does not match the bit counts of the header.')
+            pieces.append((run, chunk))
+        crop_slots.append(runs)
+    bits = views['bits'].reshape(n_slots, nb_maps, 2)
+    prob_row = views['prob_row'].reshape(n_slots, nb_maps)
+    bits[:] = 0
+    prob_row[:] = -1
+    views['placement'][:] = (-1, 0, 0, 0)
+    views['crop_origin'][:] = 0
+    for (k, ((source, image, origin, placed), runs)) in enumerate(zip(steps, crop_slots)):
+        for (run, (t, _, row, col)) in zip(runs, placed):
+            bits[run] = source.bits[image, t]
+            prob_row[run] = source.prob_row + k*(nb_maps + 1)
+            views['placement'][run] = (k, row, col, 0)
+        views['crop_origin'][k] = origin
+        views['bin_widths'][k] = source.header['bin_widths']
+        views['map_mean'][k] = source.header['map_mean']
+        views['table'][k] = source.table[image]
+    n = len(steps)
+    views['bin_widths'][n:] = 0.
+    views['map_mean'][n:] = 0.
+    views['table'][n:] = 0.5
+    views['payload_bytes'][0] = payload_bytes
+    pos = 0
+    for (_, chunk) in sorted(pieces, key=lambda piece: piece[0]):
+        payload[pos:pos + len(chunk)] = numpy.frombuffer(chunk, dtype=numpy.uint8)
+        pos += len(chunk)
+    return n, payload_bytes, crop_slots
+
+
+class _RegionWorker(_DecodeWorker):
+    """The result worker of `RegionDecoder`: a step's streams belong to its crops through the step's placement (`_DecodeJob.detail`)."""
+
+    def _form(self, job):
+        """errors[k]: what `interface_cython.raise_for_status` raises for crop k's first failing stream, its tiles in row-major
+        order as `container.decode_region` meets them, the maps of a tile in order."""
+        from .kodak.lossless import interface_cython
+        (ticket, slot, nb_maps) = (job.ticket, job.slot, self.streams_per_image)
+        results = slot.results_host
+        errors = []
+        for runs in job.detail:
+            error = None
+            for run in runs:
+                status = results[2, run*nb_maps:(run + 1)*nb_maps]
+                if status.any():
+                    bad = run*nb_maps + int(numpy.flatnonzero(status)[0])
+                    try:
+                        interface_cython.raise_for_status(int(results[2, bad]), int(results[3, bad]))
+                    except Exception as exc:
+                        error = exc
+                    break
+            errors.append(error)
+        ticket.errors = errors
+        (n, (rh, rw)) = (ticket.nb_images, slot.region)
+        ticket._value = (slot.crops_host if slot.crops_host is not None else slot.crops)[:n*rh*rw].reshape(n, rh, rw)
+
+
+class _RegionLane(object):
+    """The device side of one `RegionDecoder` slot: `_DecodeLane`'s buffers for a step of slots instead of (image, tile) entries,
+    and a window per crop instead of a plane per image."""
+
+    def __init__(self, decoder, stream):
+        (batch_size, nb_maps, device, length) = (decoder.batch_size, decoder.nb_maps, decoder.device, decoder.truncated_unary_length)
+        layout = decoder._layout
+        (n_slots, n_streams) = (layout['n_slots'], layout['n_streams'])
+        self.stream = stream
+        (fields, head_bytes) = region_head_layout(batch_size, n_slots, length, nb_maps)
+        self.head = torch.zeros(head_bytes, dtype=torch.uint8, device=device)
+
+        def field(name, dtype):
+            (pos, numpy_dtype, shape) = fields[name]
+            return self.head[pos:pos + numpy_dtype.itemsize*int(numpy.prod(shape))].view(dtype).view(shape)
+
+        self.head_bits = field('bits', torch.int32)
+        self.prob_row = field('prob_row', torch.int32)
+        self.placement = field('placement', torch.int32)
+        self.crop_origin = field('crop_origin', torch.int32)
+        self.bin_widths = field('bin_widths', torch.float32)
+        self.map_mean = field('map_mean', torch.float32)
+        self.table = field('table', torch.float64).view(batch_size*(nb_maps + 1), length)
+        self.payload_bytes = field('payload_bytes', torch.int64)
+        self.head_bytes = torch.full((1,), head_bytes, dtype=torch.int64, device=device)
+        self.payload = torch.zeros(decoder.payload_capacity_bytes, dtype=torch.uint8, device=device)
+        # what goes to the host behind a step: [coder results 4 x n_streams | index words (int64: payload bytes, overflow flag, the bytes again)]
+        self.status = torch.zeros(4*n_streams + 2*3, dtype=torch.int32, device=device)
+        self.results = self.status[:4*n_streams].view(4, n_streams)
+        self.index = self.status[4*n_streams:].view(torch.int64)
+        self.offsets = torch.zeros((n_streams, 2), dtype=torch.int64, device=device)
+        self.decoded = torch.zeros(layout['elements'], dtype=torch.int16, device=device)
+        (self.classes, need) = ([], 0)
+        for ((rows, cols), count, first_stream, first_element) in layout['runs']:
+            (n, size) = (count*nb_maps, rows*cols)
+            streams = dev.CoderStreams(n, size, length, device, results=self.results[:, first_stream:first_stream + n])
+            self.classes.append((streams, self.decoded[first_element:first_element + n*size].view(n, size),
+                                 self.prob_row[first_stream:first_stream + n], self.offsets[first_stream:first_stream + n]))
+            need = max(need, dev.coder_workspace_bytes(n, size, length))
+        self.workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        (Rs, Cs) = layout['window']
+        self.shifted = torch.zeros((batch_size, Rs, Cs, nb_maps), dtype=torch.float32, device=device)
+        (self.scratch, self.unfinished) = decoder.decoder.model.decode_scratch(batch_size, Rs, Cs)
+
+
+class _RegionSlot(object):
+    """What one `RegionDecoder` step in flight owns: its lane, the pinned buffers the host fills and reads, the windows'
+    reconstructions, the crops, the step counter, the captured graph. Made once."""
+
+    def __init__(self, decoder, lane):
+        (batch_size, device) = (decoder.batch_size, decoder.device)
+        n_streams = decoder._layout['n_streams']
+        (Rs, Cs) = decoder._layout['window']
+        self.lane = lane
+        self.region = decoder.region
+        self.pinned_head = torch.zeros(lane.head.numel(), dtype=torch.uint8).pin_memory()
+        self.pinned_payload = torch.zeros(decoder.payload_capacity_bytes, dtype=torch.uint8).pin_memory()
+        (self.head_host, self.payload_host) = (self.pinned_head.numpy(), self.pinned_payload.numpy())
+        self.pinned_status = torch.zeros(lane.status.numel(), dtype=torch.int32).pin_memory()
+        self.results_host = self.pinned_status[:4*n_streams].view(4, n_streams).numpy()
+        self.index_host = self.pinned_status[4*n_streams:].view(torch.int64).numpy()
+        self.pinned_unfinished = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self.unfinished_host = self.pinned_unfinished.numpy()
+        self.planes = torch.zeros((batch_size, 16*Rs, 16*Cs), dtype=torch.uint8, device=device)
+        crop_bytes = -(-batch_size*self.region[0]*self.region[1]//16)*16          # whole 16-byte words: `device.publish_crops`
+        (self.crops, self.pinned_crops, self.crops_host) = (None, None, None)
+        if decoder.fetch_reconstruction:
+            self.pinned_crops = torch.zeros(crop_bytes, dtype=torch.uint8).pin_memory()
+            self.crops_host = self.pinned_crops.numpy()
+        else:
+            self.crops = torch.zeros(crop_bytes, dtype=torch.uint8, device=device)
+        self.seq_dev = torch.zeros(2, dtype=torch.int32, device=device)      # [step counter, ticket word of device.publish_step]
+        self.pinned_seq = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self.seq_host = self.pinned_seq.numpy()
+        self.count = 0
+        self.free = threading.Event()
+        self.free.set()
+        self.graph = None
+
+
+class RegionDecoder(BatchDecoder):
+    """(RegionSource, image, y0, x0) requests -> uint8 crops of one fixed size, resident and pipelined: what
+    `container.decode_region(source, decoder, (y0, x0, rh, rw), images=[image])[0]` computes (same bytes), with `BatchDecoder`'s
+    machinery -- slots made once, the host work of a step in `plan_region_step`, the step as one chain of launches on one of
+    `nb_streams` private streams, one hipGraph per slot with `use_graphs` -- around a step whose SHAPE is static (`region_layout`)
+    while its PLACEMENT changes with every step and reaches the kernels through device memory. DESIGN.md section 17.
+    `submit(requests)` takes 1..batch_size requests (RegionSource, image, y0, x0), the sources the same or not -> DecodeTicket, whose
+    `result()` is uint8 (n, rh, rw), crop k the pixels [y0, y0 + rh) x [x0, x0 + rw) of its image, valid until the slot comes round
+    again. Everything is checked on the host first (`plan_region_step`: ValueError, nothing written, nothing launched)."""
+
+    def __init__(self, variables, are_bin_widths_learned, batch_size, h_in, w_in, truncated_unary_length, coding_tile, region,
+                 device='cuda', nb_in_flight=None, nb_streams=None, use_graphs=False, payload_capacity_bytes=None, fetch_reconstruction=True):
+        """h_in, w_in: the size of the SOURCE images, fixed for the decoder's lifetime like `coding_tile` = (th, tw) latents
+        (clamped to the latent plane) and region = (rh, rw) pixels, the size of every crop. Only the window around a crop is
+        synthesised (`region_window`: the region's latents and the decoder's halo), so the source may be larger than the untiled
+        synthesis takes; the window must not be. At most 65,535 slots per step (`batch_size` times `region_layout`'s slots per crop).
+        payload_capacity_bytes: payload bytes a step may hold (rounded up to 16); None: 16 bits per symbol of the step's slots.
+        fetch_reconstruction: the crops reach pinned host memory inside the step and `result()` is a numpy view of them; False:
+        `result()` is a view of the slot's device tensor. The other arguments as `BatchDecoder`'s."""
+        # refused in front of every allocation
+        if h_in % csts.STRIDE_PROD != 0 or w_in % csts.STRIDE_PROD != 0 or h_in < 1 or w_in < 1:
+            raise ValueError('The image size is not divisible by the product of the three strides.')
+        if not 1 <= int(truncated_unary_length) <= 255:
+            raise ValueError('The truncated unary length does not belong to [1, 255].')
+        if batch_size < 1:
+            raise ValueError('`batch_size` is not positive.')
+        coding_tile = container_format._positive_pair(coding_tile, '`coding_tile`')
+        if max(coding_tile) > 0xFFFF:
+            raise ValueError('A side of `coding_tile` does not fit the container (65535 latents at most).')
+        region = container_format._positive_pair(region, '`region`')
+        if region[0] > h_in or region[1] > w_in:
+            raise ValueError('`region` = {0} is larger than the {1} x {2} images.'.format(region, h_in, w_in))
+        (h_map, w_map) = (h_in//csts.STRIDE_PROD, w_in//csts.STRIDE_PROD)
+        (Rs, Cs) = region_window(h_map, w_map, region)
+        if 16*Rs*Cs*512 > 0x7FFFFFFF:
+            raise ValueError('`region` = {0} needs a window of {1} x {2} latents, more than the untiled synthesis takes.'.format(region, Rs, Cs))
+        layout = region_layout(int(batch_size), h_map, w_map, coding_tile, Rs, Cs)
+        if layout['n_slots'] > 65535:
+            raise ValueError('`batch_size` crops of {0} slots each are more than the 65535 slots a step can hold.'.format(layout['slots_per_crop']))
+        if payload_capacity_bytes is not None and int(payload_capacity_bytes) < 1:
+            raise ValueError('`payload_capacity_bytes` is not positive.')
+        self.device = _decoder_device(device)
+        self.learned = bool(are_bin_widths_learned)
+        self.decoder = pipeline.DeviceDecoder(variables, are_bin_widths_learned, self.device)
+        (self.batch_size, self.h_in, self.w_in) = (int(batch_size), int(h_in), int(w_in))
+        self.nb_maps = csts.NB_MAPS_3
+        self.truncated_unary_length = int(truncated_unary_length)
+        (self.coding_tile, self.region, self.window) = (layout['coding_tile'], region, (Rs, Cs))
+        if payload_capacity_bytes is None:
+            payload_capacity_bytes = 2*layout['elements']
+        self.payload_capacity_bytes = -(-int(payload_capacity_bytes)//16)*16
+        self.fetch_reconstruction = bool(fetch_reconstruction)
+        self.use_graphs = bool(use_graphs)
+        self.nb_streams = nb_streams = _decoder_streams(nb_streams, 'RegionDecoder')
+        self.nb_in_flight = max(1, int(nb_in_flight)) if nb_in_flight is not None else nb_streams + 2
+        self.nb_slots = self.nb_in_flight
+        # everything a step needs beyond its requests is the same for every step: made once, shared by the slots
+        self._layout = layout
+        self._n_streams = layout['n_streams']
+        self._slots_host = layout['slots']
+        self._slots_device = torch.from_numpy(layout['slots']).to(self.device)
+        # `device.coder_index_tiles`: the payload is in run order, so every slot is its own entry, clamped to half its class's stride
+        half_stride = numpy.concatenate([numpy.full(count, dev.coder_stream_stride_bytes(rows*cols, self.truncated_unary_length)//2, dtype=numpy.int64)
+                                         for ((rows, cols), count, _, _) in layout['runs']])
+        self._entry_table = torch.from_numpy(numpy.stack([numpy.arange(layout['n_slots'], dtype=numpy.int64), half_stride], axis=1)).to(self.device)
+        streams = _step_streams(self.nb_streams, self.device)
+        self._slots = [_RegionSlot(self, _RegionLane(self, streams[k % self.nb_streams])) for k in range(self.nb_slots)]
+        self._index = 0
+        self._warm = False
+        self._worker = _RegionWorker(self.nb_maps)
+        self._worker.start()
+        with _LIVE_LOCK:
+            _LIVE.setdefault(self.device.index, weakref.WeakSet()).add(self)
+
+    def _plan_step(self, slot, requests):
+        return plan_region_step(requests, self._layout, slot.head_host, slot.payload_host, self.payload_capacity_bytes, self.region,
+                                self.truncated_unary_length, self.learned, self.nb_maps)
+
+    def _launch_step(self, slot):
+        """The step of `slot` on the current stream: one chain, no argument of which depends on the step's requests."""
+        lane = slot.lane
+        (layout, (rh, rw)) = (self._layout, self.region)
+        dev.fetch_prefix(slot.pinned_head, lane.head, lane.head_bytes)                      # the head: a fixed size
+        dev.fetch_prefix(slot.pinned_payload, lane.payload, lane.payload_bytes)             # the payload: the bytes the head announces
+        lane.results[:2].copy_(lane.head_bits.view(-1, 2).t())                              # [n_streams][2] -> the coder's two arrays
+        # every slot is an entry of one "image": the offsets of its pieces in the payload, which lies in run order
+        dev.coder_index_tiles(lane.results[0], lane.results[1], self._entry_table, self.nb_maps, layout['n_slots'],
+                              self.payload_capacity_bytes, offsets=lane.offsets, index=lane.index)
+        for (streams, tiles, rows, offsets) in lane.classes:
+            dev.coder_unpack_into(streams, lane.payload, offsets)
+            dev.coder_decode_batch(streams, lane.table, rows, workspace=lane.workspace, out=tiles)
+        # the placed tiles cover every latent of a present crop's window exactly once
+        dev.tile_symbols_dequantize_placed(lane.decoded, self._slots_device, self._slots_host, lane.placement, lane.bin_widths, lane.map_mean,
+                                           lane.shifted)
+        self.decoder.model.decode_into(lane.shifted, slot.planes, lane.scratch)
+        dev.publish_crops(slot.planes, lane.crop_origin, slot.pinned_crops if slot.pinned_crops is not None else slot.crops, rh, rw)
+        dev.publish_to_host(lane.unfinished, slot.pinned_unfinished)
+        dev.publish_step(lane.status, slot.pinned_status, lane.status.numel(), slot.seq_dev[1:2], slot.seq_dev[0:1], slot.pinned_seq)

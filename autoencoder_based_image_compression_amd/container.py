@@ -445,40 +445,52 @@ def _read_at(f, start, count):
     return data
 
 
+def _source_header(source):
+    """The header of a container given as a bytes-like blob or as a seekable binary file object -> (header, blob): `blob` is a
+    memoryview of the whole container when it is in memory -- a bytes-like source, or an EAE1 file, which is read whole: its maps are
+    coded whole --, else None: of an EAT1 file only the fixed header, then the rest of the header, have been read."""
+    if not hasattr(source, 'read'):
+        blob = memoryview(source).cast('B')
+        total = len(blob)
+        (fields, pos, _) = _fixed_header(blob, total)
+        return _read_arrays(fields, pos, blob, total), blob
+    source.seek(0, 2)
+    total = source.tell()
+    fixed = _read_at(source, 0, min(_TILE_HEADER.size, total))
+    (fields, pos, header_length) = _fixed_header(fixed, total)
+    whole = 'format' not in fields
+    blob = memoryview(fixed + _read_at(source, len(fixed), (total if whole else header_length) - len(fixed)))
+    return _read_arrays(fields, pos, blob, total), (blob if whole else None)
+
+
+def _read_ranges(source, blob, ranges):
+    """One bytes-like chunk per byte range (start, stop) of a container: slices of `blob` when it is in memory (`_source_header`),
+    else read from the file `source`, runs of adjacent ranges in one read."""
+    if blob is not None:
+        return [blob[a:b] for (a, b) in ranges]
+    chunks = [None]*len(ranges)
+    order = sorted(range(len(chunks)), key=lambda k: ranges[k])
+    k = 0
+    while k < len(order):                       # runs of adjacent ranges in one read
+        run = [order[k]]
+        while k + len(run) < len(order) and ranges[order[k + len(run)]][0] == ranges[run[-1]][1]:
+            run.append(order[k + len(run)])
+        start = ranges[run[0]][0]
+        data = memoryview(_read_at(source, start, ranges[run[-1]][1] - start))
+        for e in run:
+            (a, b) = ranges[e]
+            chunks[e] = data[a - start:b - start]
+        k += len(run)
+    return chunks
+
+
 def fetch_region(source, region, images=None):
     """Host side of decode_region: (header, region_plan, one bytes-like chunk per plan entry). `source`: a bytes-like blob, or a
     seekable binary file object, from which only the fixed header, then the rest of the header, then the plan's byte ranges
     (adjacent ranges in one read) are read. An EAE1 file is read whole: its maps are coded whole."""
-    in_memory = not hasattr(source, 'read')
-    if in_memory:
-        blob = memoryview(source).cast('B')
-        total = len(blob)
-        (fields, pos, _) = _fixed_header(blob, total)
-    else:
-        source.seek(0, 2)
-        total = source.tell()
-        fixed = _read_at(source, 0, min(_TILE_HEADER.size, total))
-        (fields, pos, header_length) = _fixed_header(fixed, total)
-        in_memory = 'format' not in fields
-        blob = memoryview(fixed + _read_at(source, len(fixed), (total if in_memory else header_length) - len(fixed)))
-    header = _read_arrays(fields, pos, blob, total)
+    (header, blob) = _source_header(source)
     plan = region_plan(header, region, images)
-    if in_memory:
-        return header, plan, [blob[a:b] for (a, b) in plan['ranges']]
-    chunks = [None]*len(plan['ranges'])
-    order = sorted(range(len(chunks)), key=lambda k: plan['ranges'][k])
-    k = 0
-    while k < len(order):                       # runs of adjacent ranges in one read
-        run = [order[k]]
-        while k + len(run) < len(order) and plan['ranges'][order[k + len(run)]][0] == plan['ranges'][run[-1]][1]:
-            run.append(order[k + len(run)])
-        start = plan['ranges'][run[0]][0]
-        data = memoryview(_read_at(source, start, plan['ranges'][run[-1]][1] - start))
-        for e in run:
-            (a, b) = plan['ranges'][e]
-            chunks[e] = data[a - start:b - start]
-        k += len(run)
-    return header, plan, chunks
+    return header, plan, _read_ranges(source, blob, plan['ranges'])
 
 
 def _group_layout(entries, tiles, classes):

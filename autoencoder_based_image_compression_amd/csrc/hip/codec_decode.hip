@@ -1,5 +1,5 @@
 // codec_decode.hip -- the two launches codec.BatchDecoder needs beside the ones the container path already has (DESIGN.md
-// section 14). container.decode_images uploads the payload with a synchronous copy and dequantises a whole blob with one row of
+// section 14), and the publish of codec.RegionDecoder (section 17: eae_hip_publish_crops, at the end of the namespace). container.decode_images uploads the payload with a synchronous copy and dequantises a whole blob with one row of
 // bin widths and means; a resident decoder replays one captured step per slot, so (1) the payload comes out of the slot's pinned
 // buffer by a kernel whose length is read on the device -- a replay moves the bytes the step has, not the buffer's capacity --
 // and (2) the images of one step may come from different blobs, each with its own bin widths and means.
@@ -71,7 +71,91 @@ __global__ __launch_bounds__(DQ_THREADS) void dequantize_rows_kernel(const int16
     }
 }
 
+// eae_hip_publish_crops (codec.RegionDecoder): one ch x cw rectangle out of each of n planes u8 [n][H][W],
+// at origins the step left in device memory, into dst = [n][ch][cw] u8, flat. A lane forms one 16-byte word of dst -- the only
+// store width that goes to pinned memory -- out of four dwords. A dword whose four bytes lie in one row of one crop comes from the
+// two aligned dwords of the plane around its (unaligned) source address, combined by v_alignbyte_b32; a dword that crosses the end
+// of a row or of a crop, the tail of dst, and a source dword that would reach past the planes, are gathered byte by byte. The
+// bytes behind the last crop in the last word are zero. Origins are clamped to [0, H - ch] x [0, W - cw] here, so no load leaves
+// the planes whatever the words hold. Visibility to the host as publish_kernel (misc.hip).
+struct CropShape {
+    uint32_t n, H, W, ch, cw;
+    uint64_t total;          // n * ch * cw
+    uint64_t plane_bytes;    // n * H * W
+};
+
+__device__ __forceinline__ int clamp_origin(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+// byte offset, in the planes, of pixel (0, 0) of crop k
+__device__ __forceinline__ uint64_t crop_base(const int32_t* __restrict__ origins, const CropShape& s, uint32_t k) {
+    const int oy = clamp_origin(origins[2 * k], (int)(s.H - s.ch)), ox = clamp_origin(origins[2 * k + 1], (int)(s.W - s.cw));
+    return ((uint64_t)k * s.H + (uint32_t)oy) * s.W + (uint32_t)ox;
+}
+
+constexpr int CROP_BLOCKS = 256;
+__global__ __launch_bounds__(256) void publish_crops_kernel(const uint8_t* __restrict__ planes, const int32_t* __restrict__ origins,
+                                                            u32x4* __restrict__ dst, CropShape s) {
+    const uint64_t words = (s.total + 15u) >> 4;
+    const uint32_t per_crop = s.ch * s.cw;
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < words; i += (uint64_t)gridDim.x * blockDim.x) {
+        uint32_t out[4];
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            const uint64_t b = 16 * i + 4 * (uint64_t)d;
+            uint32_t v = 0;
+            if (b < s.total) {
+                uint32_t k = (uint32_t)(b / per_crop);
+                const uint32_t rem = (uint32_t)(b - (uint64_t)k * per_crop);
+                uint32_t y = rem / s.cw, x = rem - y * s.cw;
+                uint64_t base = crop_base(origins, s, k);
+                const uint64_t addr = base + (uint64_t)y * s.W + x;
+                const uint64_t aligned = addr & ~(uint64_t)3;
+                if (x + 4 <= s.cw && aligned + 8 <= s.plane_bytes) {
+                    const uint32_t lo = *reinterpret_cast<const uint32_t*>(planes + aligned);
+                    const uint32_t hi = *reinterpret_cast<const uint32_t*>(planes + aligned + 4);
+                    v = __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)(addr & 3u));
+                } else {
+                    for (int j = 0; j < 4 && k < s.n; ++j) {
+                        v |= (uint32_t)planes[base + (uint64_t)y * s.W + x] << (8 * j);
+                        if (++x == s.cw) {
+                            x = 0;
+                            if (++y == s.ch) {
+                                y = 0;
+                                if (++k < s.n) base = crop_base(origins, s, k);
+                            }
+                        }
+                    }
+                }
+            }
+            out[d] = v;
+        }
+        u32x4 word;
+        word.x = out[0], word.y = out[1], word.z = out[2], word.w = out[3];
+        dst[i] = word;
+    }
+    __threadfence_system();
+}
+
 }  // namespace
+
+extern "C" int eae_hip_publish_crops(const uint8_t* planes, int n, int H, int W, const int32_t* origins, int ch, int cw, void* dst,
+                                     uint64_t dst_capacity_bytes, void* stream) {
+    if (!planes || !origins || !dst || n <= 0 || H <= 0 || W <= 0 || ch <= 0 || cw <= 0) return EAE_HIP_BAD_ARGUMENT;
+    if ((((uintptr_t)dst) & 15u) || (dst_capacity_bytes & 15u) || (((uintptr_t)planes) & 3u) || (((uintptr_t)origins) & 3u))
+        return EAE_HIP_BAD_ARGUMENT;      // 16-byte stores, aligned dword loads
+    if (ch > H || cw > W) return EAE_HIP_BAD_SHAPE;
+    const uint64_t total = (uint64_t)n * (uint64_t)ch * (uint64_t)cw;
+    if ((uint64_t)ch * (uint64_t)cw > 0x7FFFFFFFull || ((total + 15u) & ~(uint64_t)15u) > dst_capacity_bytes) return EAE_HIP_BAD_SHAPE;
+    CropShape s;
+    s.n = (uint32_t)n, s.H = (uint32_t)H, s.W = (uint32_t)W, s.ch = (uint32_t)ch, s.cw = (uint32_t)cw;
+    s.total = total;
+    s.plane_bytes = (uint64_t)n * (uint64_t)H * (uint64_t)W;
+    const uint64_t words = (total + 15u) >> 4;
+    const unsigned blocks = (unsigned)((words + 255) / 256 > (uint64_t)CROP_BLOCKS ? (uint64_t)CROP_BLOCKS : (words + 255) / 256);
+    hipLaunchKernelGGL(publish_crops_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, planes, origins, (u32x4*)dst, s);
+    EAE_HIP_CHECK_LAUNCH();
+    return EAE_HIP_OK;
+}
 
 extern "C" int eae_hip_fetch_prefix(const void* src_host_mapped, void* dst_device, uint64_t capacity_bytes, const uint64_t* nbytes_device,
                                     void* stream) {

@@ -8,6 +8,9 @@
 //   tile-major buffer; map m of the tile starts at [5] + m * rows * cols, pixels in raster order inside the tile.
 // gather: the origin is in the symbol plane and the tile lies inside it. dequantize: image and origin are in the output sub-plane;
 // the origin may be negative and the tile may reach past the sub-plane: only the pixels inside it are written.
+// dequantize_placed (codec.RegionDecoder) splits the row: what never changes -- extent and offset, int64
+// [EAE_TILE_SYMBOLS_SLOT_COLS] per slot -- is checked on the host like a plan row, and image and origin come from an int32
+// [n_slots][4] array in device memory that the kernel reads and trusts for nothing.
 #include "common.h"
 
 namespace {
@@ -53,15 +56,31 @@ __global__ __launch_bounds__(TS_THREADS) void tile_symbols_gather_kernel(const i
 // half-wave fall on 16 banks twice.
 // ROWS: bin_widths and map_mean hold one row of 128 per image, f32 [n][128], and the block takes the row of its plan row's image
 // (eae_hip_tile_symbols_dequantize_rows); else one row serves every image.
-template <bool ROWS>
+// PLACED: (rows, cols, offset) of the block's tile come from the static `plan` of EAE_TILE_SYMBOLS_SLOT_COLS columns, and (image,
+// origin row, origin col) from placement[blockIdx.y][0..2], int32 words a step leaves in device memory: any value is harmless. An
+// image outside [0, n) ends the block in front of every barrier and every access; the origins only ever enter the test that keeps
+// a pixel inside hs x ws (64-bit sums of a 32-bit origin and a pixel index below 2^31). The rows are per image as with ROWS.
+template <bool ROWS, bool PLACED>
 __device__ __forceinline__ void tile_symbols_dequantize_body(const int16_t* __restrict__ tiles, const int64_t* __restrict__ plan,
+                                                             const int32_t* __restrict__ placement, int64_t n,
                                                              const float* __restrict__ bin_widths, const float* __restrict__ map_mean,
                                                              float* __restrict__ out, int64_t hs, int64_t ws) {
     __shared__ __attribute__((aligned(16))) int16_t lds[DQ_PIX][DQ_PITCH];
-    const int64_t* row = plan + (size_t)blockIdx.y * EAE_TILE_SYMBOLS_PLAN_COLS;
-    const int64_t img = row[0], r0 = row[1], c0 = row[2], off = row[5];
-    const uint32_t cols = (uint32_t)row[4];
-    const uint32_t total = (uint32_t)row[3] * cols;
+    int64_t img, r0, c0, off;
+    uint32_t cols, total;
+    if (PLACED) {
+        const int64_t* row = plan + (size_t)blockIdx.y * EAE_TILE_SYMBOLS_SLOT_COLS;
+        const int32_t* place = placement + (size_t)blockIdx.y * 4;
+        img = place[0], r0 = place[1], c0 = place[2], off = row[2];
+        cols = (uint32_t)row[1];
+        total = (uint32_t)row[0] * cols;
+        if (img < 0 || img >= n) return;                       // block-uniform: an absent slot
+    } else {
+        const int64_t* row = plan + (size_t)blockIdx.y * EAE_TILE_SYMBOLS_PLAN_COLS;
+        img = row[0], r0 = row[1], c0 = row[2], off = row[5];
+        cols = (uint32_t)row[4];
+        total = (uint32_t)row[3] * cols;
+    }
     const uint32_t p0 = blockIdx.x * DQ_PIX;
     if (p0 >= total) return;                                   // block-uniform: this tile has fewer chunks than the largest
     const int16_t* src = tiles + off;
@@ -106,14 +125,22 @@ __device__ __forceinline__ void tile_symbols_dequantize_body(const int16_t* __re
 __global__ __launch_bounds__(TS_THREADS) void tile_symbols_dequantize_kernel(const int16_t* __restrict__ tiles, const int64_t* __restrict__ plan,
                                                                              const float* __restrict__ bin_widths, const float* __restrict__ map_mean,
                                                                              float* __restrict__ out, int64_t hs, int64_t ws) {
-    tile_symbols_dequantize_body<false>(tiles, plan, bin_widths, map_mean, out, hs, ws);
+    tile_symbols_dequantize_body<false, false>(tiles, plan, nullptr, 0, bin_widths, map_mean, out, hs, ws);
 }
 
 __global__ __launch_bounds__(TS_THREADS) void tile_symbols_dequantize_rows_kernel(const int16_t* __restrict__ tiles, const int64_t* __restrict__ plan,
                                                                                   const float* __restrict__ bin_widths_rows,
                                                                                   const float* __restrict__ map_mean_rows, float* __restrict__ out,
                                                                                   int64_t hs, int64_t ws) {
-    tile_symbols_dequantize_body<true>(tiles, plan, bin_widths_rows, map_mean_rows, out, hs, ws);
+    tile_symbols_dequantize_body<true, false>(tiles, plan, nullptr, 0, bin_widths_rows, map_mean_rows, out, hs, ws);
+}
+
+__global__ __launch_bounds__(TS_THREADS) void tile_symbols_dequantize_placed_kernel(const int16_t* __restrict__ tiles, const int64_t* __restrict__ slots,
+                                                                                    const int32_t* __restrict__ placement, int64_t n,
+                                                                                    const float* __restrict__ bin_widths_rows,
+                                                                                    const float* __restrict__ map_mean_rows, float* __restrict__ out,
+                                                                                    int64_t hs, int64_t ws) {
+    tile_symbols_dequantize_body<true, true>(tiles, slots, placement, n, bin_widths_rows, map_mean_rows, out, hs, ws);
 }
 
 // Largest tile of a plan (pixels), or -1 when a row is malformed. `inside`: rows must lie in an n x h x w plane (gather);
@@ -182,4 +209,39 @@ extern "C" int eae_hip_tile_symbols_dequantize_rows(const int16_t* tiles, int64_
                                                     int n, int hs, int ws, void* stream) {
     return launch_symbols_dequantize(true, tiles, tile_elems, plan, host_plan, n_tiles, bin_widths_rows, map_mean_rows, shifted_out, n, hs, ws,
                                      stream);
+}
+
+namespace {
+
+// check_symbols_plan for the static half of a placed plan: extent and offset of every slot, nothing about image and origin (the
+// kernel checks those, step by step). Largest slot (pixels), or -1 when a row is malformed or its run leaves `buffer_elems` symbols.
+int64_t check_symbols_slots(const int64_t* host_slots, int n_slots, int64_t buffer_elems) {
+    int64_t largest = 0;
+    for (int t = 0; t < n_slots; ++t) {
+        const int64_t* p = host_slots + (size_t)t * EAE_TILE_SYMBOLS_SLOT_COLS;
+        if (p[0] < 1 || p[1] < 1 || p[2] < 0) return -1;
+        if (p[0] > 0x7FFFFFFFll || p[1] > 0x7FFFFFFFll || p[0] * p[1] > 0x7FFFFFFFll) return -1;   // a tile's pixel index is 32-bit
+        if (p[2] > buffer_elems || EAE_C * p[0] * p[1] > buffer_elems - p[2]) return -1;
+        if (p[0] * p[1] > largest) largest = p[0] * p[1];
+    }
+    return largest;
+}
+
+}  // namespace
+
+extern "C" int eae_hip_tile_symbols_dequantize_placed(const int16_t* tiles, int64_t tile_elems, const int64_t* slots, const int64_t* host_slots,
+                                                      int n_slots, const int32_t* placement, const float* bin_widths_rows,
+                                                      const float* map_mean_rows, float* shifted_out, int n, int hs, int ws, void* stream) {
+    if (!tiles || !slots || !host_slots || !placement || !bin_widths_rows || !shifted_out || tile_elems <= 0 || n_slots < 0 || n <= 0 ||
+        hs <= 0 || ws <= 0)
+        return EAE_HIP_BAD_ARGUMENT;
+    if (((uintptr_t)shifted_out & 15u) != 0 || ((uintptr_t)placement & 3u) != 0 || n_slots > 65535) return EAE_HIP_BAD_SHAPE;
+    const int64_t largest = check_symbols_slots(host_slots, n_slots, tile_elems);
+    if (largest < 0) return EAE_HIP_BAD_SHAPE;
+    if (n_slots == 0) return EAE_HIP_OK;
+    const dim3 grid((unsigned)((largest + DQ_PIX - 1) / DQ_PIX), (unsigned)n_slots);
+    hipLaunchKernelGGL(tile_symbols_dequantize_placed_kernel, grid, dim3(TS_THREADS), 0, (hipStream_t)stream, tiles, slots, placement,
+                       (int64_t)n, bin_widths_rows, map_mean_rows, shifted_out, (int64_t)hs, (int64_t)ws);
+    EAE_HIP_CHECK_LAUNCH();
+    return EAE_HIP_OK;
 }

@@ -609,6 +609,35 @@ def tile_symbols_dequantize_rows(tiles, plan_device, plan_host, bin_widths_rows,
     return out
 
 
+TILE_SYMBOLS_SLOT_COLS = 3
+
+
+def tile_symbols_dequantize_placed(tiles, slots_device, slots_host, placement, bin_widths_rows, map_mean_rows, out):
+    """`tile_symbols_dequantize_rows` with the plan in two halves (include/eae_hip.h): `slots_device` / `slots_host`, int64
+    [n_slots, 3], the same rows on the device and on the host -- extent (rows, cols) and element offset of every slot in `tiles`,
+    checked before the launch --, and `placement`, int32 [n_slots, 4] on the device -- image, origin row, origin col of every slot in
+    `out`, one unused word --, which only the kernel reads: a slot whose image is outside `out` is skipped, an origin may be anything.
+    No argument depends on a step's placement, so the launch can be captured."""
+    if tiles.dtype != torch.int16 or tiles.dim() != 1:
+        raise HipError('tiles must be one-dimensional int16')
+    if out.dtype != torch.float32 or out.dim() != 4 or out.shape[3] != NB_MAPS:
+        raise HipError('out must be float32 [N, hs, ws, 128]')
+    (n, hs, ws) = out.shape[:3]
+    for rows in (bin_widths_rows,) if map_mean_rows is None else (bin_widths_rows, map_mean_rows):
+        if rows.dtype != torch.float32 or rows.numel() != n*NB_MAPS or not rows.is_contiguous():
+            raise HipError('bin widths and map means must be contiguous float32 of 128 elements per image of out')
+    if slots_host.dtype.name != 'int64' or slots_host.ndim != 2 or slots_host.shape[1] != TILE_SYMBOLS_SLOT_COLS or not slots_host.flags.c_contiguous:
+        raise HipError('the host slots must be a C-contiguous int64 array of {} columns'.format(TILE_SYMBOLS_SLOT_COLS))
+    if slots_device.dtype != torch.int64 or tuple(slots_device.shape) != slots_host.shape:
+        raise HipError('the device slots must be int64 of the host slots\' shape')
+    if placement.dtype != torch.int32 or placement.numel() != 4*slots_host.shape[0]:
+        raise HipError('the placement must hold four int32 words per slot')
+    _check(_native.hip().eae_hip_tile_symbols_dequantize_placed(_p(tiles), tiles.numel(), _p(slots_device), slots_host.ctypes.data,
+                                                                slots_host.shape[0], _p(placement), _p(bin_widths_rows), _p(map_mean_rows),
+                                                                _p(out), n, hs, ws, _stream(tiles)), 'eae_hip_tile_symbols_dequantize_placed')
+    return out
+
+
 # ---- lossless coder on the device (include/eae_hip.h, "lossless coder on the device") ---------------------------------
 
 CODER_ROUNDTRIP, CODER_ENCODE_ONLY, CODER_ROUNDTRIP_VERIFY = 0, 1, 2
@@ -989,6 +1018,22 @@ def dequantize_maps_rows(symbols_planar, bin_widths_rows, map_mean_rows=None, wa
     _check(_native.hip().eae_hip_dequantize_maps_rows(_p(symbols_planar), _p(bin_widths_rows), _p(map_mean_rows), _p(cq), _p(shifted), n, hw, c,
                                                       _stream(symbols_planar)), 'eae_hip_dequantize_maps_rows')
     return {'cq': cq, 'shifted': shifted}
+
+
+def publish_crops(planes, origins, dst, crop_h, crop_w):
+    """Stream-ordered, by a kernel: the crop_h x crop_w rectangle at `origins[i]` (int32 [N, 2] on the device: row, col; clamped
+    into the plane by the kernel) of every plane of `planes` (uint8 [N, H, W], device) into `dst` as [N, crop_h, crop_w], flat: a
+    contiguous uint8 tensor, pinned host or device memory, 16-byte aligned, a multiple of 16 bytes and at least N*crop_h*crop_w
+    rounded up to 16. Whole 16-byte words are stored; the pad of the last one is zero, nothing behind it is written."""
+    if planes.dtype != torch.uint8 or planes.dim() != 3:
+        raise HipError('planes must be uint8 [N, H, W]')
+    (n, h, w) = planes.shape
+    if origins.dtype != torch.int32 or origins.numel() != 2*n:
+        raise HipError('origins must hold two int32 words per plane')
+    if dst.dtype != torch.uint8 or not dst.is_contiguous() or not (dst.is_cuda or dst.is_pinned()):
+        raise HipError('dst must be a contiguous uint8 tensor in device or pinned host memory')
+    _check(_native.hip().eae_hip_publish_crops(_p(planes), n, h, w, _p(origins), int(crop_h), int(crop_w), dst.data_ptr(), dst.numel(),
+                                               _stream(planes)), 'eae_hip_publish_crops')
 
 
 # ---- SVHN float64 path (include/eae_hip.h, "SVHN path") -------------------------------------------------------------

@@ -151,8 +151,18 @@ int eae_hip_tile_stitch_u8(const uint8_t* windows, int window_h, int window_w, u
  *   output, f32 [n][128] each: a tile is dequantised with the rows of its plan row's image, bin_widths_rows[image][c] * symbol +
  *   map_mean_rows[image][c]. Same plan, same checks, same limits, same arithmetic: the output equals, bit for bit, that of
  *   tile_symbols_dequantize called image by image with that image's rows (codec.BatchDecoder(coding_tile=...), whose step holds
- *   images of several blobs). */
+ *   images of several blobs).
+ * tile_symbols_dequantize_placed: tile_symbols_dequantize_rows for a step whose SHAPE is static and whose PLACEMENT changes with
+ *   every step (codec.RegionDecoder). The static half of a plan row lives in `slots`, int64
+ *   [n_slots][EAE_TILE_SYMBOLS_SLOT_COLS]: extent (rows, cols) and element offset of the slot's map 0 in `tiles`; `host_slots` is
+ *   its host copy, checked before the launch as a plan row's extent and offset are (a run outside `tiles`, a tile of 2^31 pixels
+ *   or more, more than 65535 slots -> EAE_HIP_BAD_SHAPE). The per-step half lives in `placement`, int32 [n_slots][4] in DEVICE
+ *   memory, read by the kernel only: image, origin row, origin col in the hs x ws output, one unused word. Whatever those words
+ *   hold, nothing outside the buffers is touched: a slot whose image is outside [0, n) is skipped, origins are arbitrary and only
+ *   the pixels inside hs x ws are written. Same arithmetic: the output equals, bit for bit, tile_symbols_dequantize_rows with the
+ *   plan rows (image, origin, extent, offset) put together. shifted_out aligned to 16 bytes, placement to 4. */
 #define EAE_TILE_SYMBOLS_PLAN_COLS 6
+#define EAE_TILE_SYMBOLS_SLOT_COLS 3
 int eae_hip_tile_symbols_gather(const int16_t* symbols_planar, int n, int h, int w, int16_t* tiles, int64_t tile_elems,
                                 const int64_t* plan, const int64_t* host_plan, int n_tiles, void* stream);
 int eae_hip_tile_symbols_dequantize(const int16_t* tiles, int64_t tile_elems, const int64_t* plan, const int64_t* host_plan, int n_tiles,
@@ -161,6 +171,9 @@ int eae_hip_tile_symbols_dequantize(const int16_t* tiles, int64_t tile_elems, co
 int eae_hip_tile_symbols_dequantize_rows(const int16_t* tiles, int64_t tile_elems, const int64_t* plan, const int64_t* host_plan,
                                          int n_tiles, const float* bin_widths_rows, const float* map_mean_rows, float* shifted_out, int n,
                                          int hs, int ws, void* stream);
+int eae_hip_tile_symbols_dequantize_placed(const int16_t* tiles, int64_t tile_elems, const int64_t* slots, const int64_t* host_slots,
+                                           int n_slots, const int32_t* placement, const float* bin_widths_rows,
+                                           const float* map_mean_rows, float* shifted_out, int n, int hs, int ws, void* stream);
 
 /* ---- analysis transform (eae/graph/components.py:86-142) ---------------------------------------------------------*/
 
@@ -486,9 +499,9 @@ int eae_hip_publish_prefix(const void* src_device, void* dst_host_mapped, uint64
 int eae_hip_exception_rows(int n, const uint32_t* hist, const uint32_t* overflow, int radius, int map_size, int length,
                            double* rows_out, void* stream);
 
-/* ---- the pipelined decoder's own launches (csrc/hip/codec_decode.hip) -----------------------------
+/* ---- the pipelined decoders' own launches (csrc/hip/codec_decode.hip; DESIGN.md sections 14 and 17) ---------------------
  * The rest of a codec.BatchDecoder step is index_streams, unpack_streams, coder_decode_batch, eae_hip_decode and the publish
- * launches above. Both are asynchronous on `stream` and have no argument the host computes from the step's contents, so a step
+ * launches above. All three are asynchronous on `stream` and have no argument the host computes from the step's contents, so a step
  * can be captured into one hipGraph.
  * fetch_prefix: the mirror of publish_prefix: the first ceil(min(*nbytes_device, capacity_bytes) / 16) 16-byte words of pinned,
  *   device-mapped host memory into dst_device; no byte at or beyond that length is written. *nbytes_device is read on the device
@@ -502,6 +515,16 @@ int eae_hip_fetch_prefix(const void* src_host_mapped, void* dst_device, uint64_t
                          void* stream);
 int eae_hip_dequantize_maps_rows(const int16_t* symbols_planar, const float* bin_widths_rows, const float* map_mean_rows,
                                  float* cq_out, float* shifted_out, int n, int hw, int c, void* stream);
+/* publish_crops (codec.RegionDecoder): the ch x cw rectangle at origins[i] = (row, col) -- int32 [n][2] in
+ *   DEVICE memory, read by the kernel -- of every plane of planes u8 [n][H][W] into dst = u8 [n][ch][cw], flat: pinned,
+ *   device-mapped host memory (visible to the host as eae_hip_publish_to_host's copy is) or device memory. Every store is one
+ *   16-byte word of dst; the bytes of the last word behind n * ch * cw are zero, and nothing behind that word is written. The
+ *   origins are clamped on the device to [0, H - ch] x [0, W - cw]: no load leaves the planes whatever the words hold. NULL
+ *   pointer, a non-positive size, dst not 16-byte aligned, dst_capacity_bytes no multiple of 16, planes or origins not 4-byte
+ *   aligned -> EAE_HIP_BAD_ARGUMENT; ch > H, cw > W, a crop of 2^31 bytes or more, or a capacity below n * ch * cw rounded up to
+ *   16 -> EAE_HIP_BAD_SHAPE; nothing is launched then. */
+int eae_hip_publish_crops(const uint8_t* planes, int n, int H, int W, const int32_t* origins, int ch, int cw, void* dst,
+                          uint64_t dst_capacity_bytes, void* stream);
 
 /* ==== TEST HOOKS (-DEAE_TEST_HOOKS): NOT exported by the product library lib/libeae_hip.so ====================================
  * Four entry points the test-suite needs and a deployment must not have (they change what later launches do, or only
