@@ -221,6 +221,61 @@ def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_p
     return _encode_entries(symbols, fields, nb_images if coding_tile is None else tiles_per_call)
 
 
+def encode_images_to_budget(luminances_uint8, encoder, ladder, budget_bytes, tile=None):
+    """uint8 (N, H, W) or (N, H, W, 1) luminance images -> (blobs, info): every image compressed into at most `budget_bytes` bytes
+    (a scalar, or one value per image) at the first rate point of `ladder` (ratecontrol.RateLadder, finest first) at which it fits.
+
+    One analysis transform and one pass over the latents (device.ladder_histograms) bound the size of every image at every point
+    (ratecontrol.blob_byte_bounds); ratecontrol.select_rate_points then walks the ladder per image, skips the points whose lower
+    bound exceeds the budget and codes the others -- `quantize_maps` and the coding stage of `encode_images`, one image at a time --
+    until one fits. An image no point fits is coded at the last valid point of the ladder and reported in info['fits'].
+    blobs: one single-image EAE1 blob per image, byte for byte `encode_images(images[i:i + 1], encoder, bin_widths_k, map_mean,
+    table_k, idx_map_exception)[0]` for its point k: `decode_images` and `codec.BatchDecoder.submit(blobs)` read them unchanged.
+    info: 'rate_point' int64 (N,); 'lower_bytes', 'upper_bytes' int64 (N, K); 'blob_bytes' int64 (N,); 'attempts' int64 (N,): the
+    points coded for the image; 'fits' bool (N,); 'upper_bound_misses': points whose upper bound was within the budget and whose
+    blob was not (expected 0: the allowances of ratecontrol.py are measured, not proven).
+    An image whose symbols leave int16 at every point raises the AssertionError of `encode_images`.
+    tile=(th, tw): as in `encode_images`. Not in this function: coding tiles (EAT1: a tile's termination and byte padding need
+    counts per tile), and codec.BatchCodec, which still takes one rate point per codec."""
+    from . import ratecontrol
+    images = numpy.ascontiguousarray(luminances_uint8)
+    if images.dtype != numpy.uint8:
+        raise TypeError('`luminances_uint8.dtype` is not equal to `numpy.uint8`.')
+    if images.ndim == 4:
+        images = images[:, :, :, 0]
+    if not isinstance(ladder, ratecontrol.RateLadder):
+        raise TypeError('`ladder` is not a `ratecontrol.RateLadder`.')
+    (nb_images, height, width) = images.shape
+    budgets = numpy.asarray(budget_bytes)
+    if budgets.ndim > 1 or (budgets.ndim == 1 and budgets.shape[0] != nb_images) or budgets.dtype.kind not in 'iuf':
+        raise ValueError('`budget_bytes` must be a number or one number per image.')
+    length = ladder.truncated_unary_length
+    device = encoder.device
+    y = encoder(torch.from_numpy(images).to(device), tile=tile)
+    mean = torch.from_numpy(ladder.map_mean).to(device)
+    bin_widths_points = torch.from_numpy(ladder.bin_widths_points).to(device)
+    (hist, bypass_bits, _) = dev.ladder_histograms(y, bin_widths_points, mean, length)
+    (hist, bypass_bits) = (hist.cpu().numpy(), bypass_bits.cpu().numpy())
+    (lower, upper) = ratecontrol.blob_byte_bounds(hist, bypass_bits, ladder, height, width)
+    valid = ratecontrol.valid_points(hist, (height//csts.STRIDE_PROD)*(width//csts.STRIDE_PROD))
+    coded = {}
+
+    def size_of(i, k):
+        q = dev.quantize_maps(y[i:i + 1], bin_widths_points[k], mean, want_symbols=True)
+        if int(q['checks'][0].item()) != 0:         # `valid` says it cannot happen: the same symbols were counted
+            raise AssertionError('The rounded array elements cannot be represented as 16-bit signed integers.')
+        e = ladder.idx_map_exception
+        rows = _exception_rows(q['symbols'], e, length) if e >= 0 else numpy.zeros((0, length), dtype=numpy.float64)
+        fields = _fields(encoder.are_bin_widths_learned, 1, height, width, e, ladder.bin_widths_points[k], ladder.map_mean,
+                         ladder.binary_probabilities_points[k], rows)
+        coded[(i, k)] = _encode_entries(q['symbols'], fields, 1)[0]
+        return len(coded[(i, k)])
+
+    info = ratecontrol.select_rate_points(lower, upper, valid, budgets, size_of)
+    info.update({'lower_bytes': lower, 'upper_bytes': upper})
+    return [coded[(i, int(info['rate_point'][i]))] for i in range(nb_images)], info
+
+
 def _fixed_header(fixed, total_length):
     """Checks the fixed part of the header of either format (`fixed`: the first bytes of the blob or file, `total_length`: the length
     of all of it) -> (fields, bytes of the fixed part, bytes of the whole header). Everything that sizes a read or an allocation is

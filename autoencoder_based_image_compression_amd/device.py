@@ -471,6 +471,107 @@ def symbol_histograms(symbols_planar, radius, out=None, first_map=0, map_step=1,
     return hist, overflow
 
 
+def ladder_max_points(length):
+    """The most rate points one `eae_hip_ladder_histograms` launch takes at truncated unary length `length`; 0 when none fits."""
+    return int(_native.hip().eae_hip_ladder_max_points(int(length)))
+
+
+def _bypass_bits_of_magnitudes(magnitudes, length):
+    """Bits |symbol| = magnitudes (int64 array) leaves in the bypass stream (include/eae_hip.h, rate ladder): the sign of a non-zero
+    symbol, and 2 floor(log2(|s| - L + 1)) + 1 bits of suffix from L on."""
+    import numpy
+    suffix = numpy.maximum(magnitudes - length + 1, 1)
+    nb_bits = numpy.frexp(suffix.astype(numpy.float64))[1].astype(numpy.int64) - 1       # floor(log2(.)), exact below 2^53
+    return (magnitudes != 0).astype(numpy.int64) + numpy.where(magnitudes >= length, 2*nb_bits + 1, 0)
+
+
+def _ladder_point_by_passes(y, bin_widths, map_mean, length):
+    """One rate point by the route `stats.compute_binary_probabilities` takes: `quantize_maps`, `symbol_histograms`, a fold on the
+    host -> numpy (hist int64 [N, 128, L + 1], bypass bits int64 [N, 128], range errors). A point with range errors, whose int16
+    symbols have wrapped, is recounted on the host with the quantiser's float32 expressions (numpy divides and rounds as the
+    kernels do), so that the arrays are `eae_hip_ladder_histograms`' in every case."""
+    import numpy
+    (n, c) = (y.shape[0], y.shape[-1])
+    q = quantize_maps(y, bin_widths, map_mean, want_symbols=True)
+    range_errors = int(q['checks'][0].item())
+    if range_errors:
+        host = y.reshape(n, -1, c).cpu().numpy()
+        bw = bin_widths.cpu().numpy()
+        centered = host - (map_mean.cpu().numpy() if map_mean is not None else numpy.float32(0.))
+        with numpy.errstate(all='ignore'):
+            rs = numpy.abs(numpy.rint(bw*numpy.rint(centered/bw)/bw))
+            good = rs < numpy.float32(32768.)
+        magnitudes = numpy.where(good, rs, 0.).astype(numpy.int64)
+        hist = numpy.zeros((n, c, length + 1), dtype=numpy.int64)
+        for b in range(length + 1):
+            hist[:, :, b] = (good & ((magnitudes == b) if b < length else (magnitudes >= length))).sum(axis=1)
+        return hist, (_bypass_bits_of_magnitudes(magnitudes, length)*good).sum(axis=1), range_errors
+    radius = 1024
+    (full, overflow) = symbol_histograms(q['symbols'], radius)
+    if int(overflow.sum().item()) != 0:
+        radius = 32768
+        full = torch.cat([symbol_histograms(q['symbols'][i], radius)[0] for i in range(n)])      # 32 MB of bins per image
+    full = full.cpu().numpy().astype(numpy.int64).reshape(n, c, 2*radius + 1)
+    by_magnitude = full[:, :, radius:].copy()
+    by_magnitude[:, :, 1:] += full[:, :, :radius][:, :, ::-1]
+    hist = numpy.concatenate([by_magnitude[:, :, :length], by_magnitude[:, :, length:].sum(axis=2, keepdims=True)], axis=2)
+    bits = (by_magnitude*_bypass_bits_of_magnitudes(numpy.arange(radius + 1, dtype=numpy.int64), length)).sum(axis=2)
+    return hist, bits, 0
+
+
+def ladder_histograms(y, bin_widths_points, map_mean=None, length=10, out=None):
+    """One pass over y [N, h, w, 128] (or [N, hw, 128]) for the K rate points bin_widths_points float32 [K, 128] (include/eae_hip.h,
+    rate ladder) -> (hist int32 [N, K, 128, L + 1]: |symbol| clipped at L = length; bypass_bits int64 [N, K, 128]: the exact length
+    of every map's bypass stream; range_errors int32 [K]: elements whose symbol does not fit int16, counted nowhere else).
+    A ladder longer than `ladder_max_points(length)` takes several launches. At a length for which not one point fits a launch
+    (large L) every point goes the route of `stats.compute_binary_probabilities` instead -- `quantize_maps`, `symbol_histograms`, a
+    fold on the host -- and the same arrays come back. out: that triple, preallocated, to ACCUMULATE into (the kernel adds)."""
+    n = y.shape[0]
+    c = y.shape[-1]
+    hw = y.numel()//(n*c)
+    d = y.device
+    length = int(length)
+    if c != NB_MAPS or y.dtype != torch.float32:
+        raise HipError('y must be float32 [N, ..., 128]')
+    if bin_widths_points.dtype != torch.float32 or bin_widths_points.dim() != 2 or bin_widths_points.shape[1] != NB_MAPS:
+        raise HipError('bin_widths_points must be float32 [K, 128]')
+    if map_mean is not None and (map_mean.dtype != torch.float32 or map_mean.numel() != NB_MAPS):
+        raise HipError('map_mean must be float32 of 128 elements')
+    if length < 1 or length > 255:
+        raise ValueError('The truncated unary length does not belong to [1, 255].')
+    k_points = bin_widths_points.shape[0]
+    if k_points < 1:
+        raise ValueError('A ladder has at least one rate point.')
+    if out is None:
+        out = (torch.zeros((n, k_points, c, length + 1), dtype=torch.int32, device=d),
+               torch.zeros((n, k_points, c), dtype=torch.int64, device=d), torch.zeros(k_points, dtype=torch.int32, device=d))
+    (hist, bypass_bits, range_errors) = out
+    if (hist.dtype, bypass_bits.dtype, range_errors.dtype) != (torch.int32, torch.int64, torch.int32) \
+            or tuple(hist.shape) != (n, k_points, c, length + 1) or tuple(bypass_bits.shape) != (n, k_points, c) \
+            or tuple(range_errors.shape) != (k_points,):
+        raise HipError('`out` must be (int32 [N, K, 128, L + 1], int64 [N, K, 128], int32 [K])')
+    most = ladder_max_points(length)
+    if most == 0:
+        for k in range(k_points):
+            (hist_k, bits_k, errors_k) = _ladder_point_by_passes(y, bin_widths_points[k].contiguous(), map_mean, length)
+            hist[:, k] += torch.from_numpy(hist_k).to(d).to(torch.int32)
+            bypass_bits[:, k] += torch.from_numpy(bits_k).to(d)
+            range_errors[k] += errors_k
+        return out
+    whole = k_points <= most
+    for k0 in range(0, k_points, most):
+        k1 = min(k0 + most, k_points)
+        # a launch writes [N][its points][...]: a part of a longer ladder gets buffers of its own, added into the whole afterwards
+        part = out if whole else (torch.zeros((n, k1 - k0, c, length + 1), dtype=torch.int32, device=d),
+                                  torch.zeros((n, k1 - k0, c), dtype=torch.int64, device=d), range_errors[k0:k1])
+        _check(_native.hip().eae_hip_ladder_histograms(_p(y), _p(map_mean), _p(bin_widths_points[k0:k1]), k1 - k0, length, _p(part[0]),
+                                                       _p(part[1]), _p(part[2]), n, hw, _stream(y)), 'eae_hip_ladder_histograms')
+        if not whole:
+            hist[:, k0:k1] += part[0]
+            bypass_bits[:, k0:k1] += part[1]
+    return out
+
+
 def cast_bt601(x):
     out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
     _check(_native.hip().eae_hip_cast_bt601(_p(x), _p(out), x.numel(), _stream()), 'eae_hip_cast_bt601')

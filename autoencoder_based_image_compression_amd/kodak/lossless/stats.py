@@ -74,6 +74,33 @@ def compute_binary_probabilities(y_float32, bin_widths_test, map_mean, truncated
     return binary_probabilities
 
 
+def compute_binary_probabilities_ladder(y_float32, bin_widths_points, map_mean, truncated_unary_length):
+    """`compute_binary_probabilities` for the K rate points of a ladder from ONE pass over the latents
+    (device.ladder_histograms) instead of a quantiser pass and a histogram pass per point: element for element what K calls give.
+
+    y_float32 (N, h, w, C) float32; bin_widths_points (K, C) float32; map_mean (C,) float32 -> float64 (K, C, L).
+
+    Raises
+    ------
+    ValueError
+        If a symbol does not fit in 16 bits at a point (as `compute_binary_probabilities` does there).
+    """
+    from ... import device as dev
+    from ... import ratecontrol
+    bin_widths_points = numpy.ascontiguousarray(bin_widths_points, dtype=numpy.float32)
+    if bin_widths_points.ndim != 2 or bin_widths_points.shape[1] != y_float32.shape[3]:
+        raise ValueError('`bin_widths_points` must have one row of bin widths per rate point.')
+    if numpy.any(bin_widths_points <= 0.):
+        raise ValueError('A quantization bin width is not strictly positive.')
+    (hist, _, range_errors) = dev.ladder_histograms(bk.to_device(y_float32, numpy.float32), bk.to_device(bin_widths_points, numpy.float32),
+                                                    bk.to_device(numpy.asarray(map_mean), numpy.float32), truncated_unary_length)
+    if int(range_errors.sum().item()) != 0:
+        raise ValueError('A symbol does not fit in 16 bits: outside the domain of this build (lossless/compression.py:142 '
+                         'casts the symbols to int16).')
+    (cumulated_zeros, cumulated_ones) = ratecontrol.decision_counts(bk.to_host(hist).astype(numpy.int64).sum(axis=0))
+    return ratecontrol.probabilities_from_counts(cumulated_zeros, cumulated_ones)
+
+
 def _unit_interval_counts(y_float32):
     """For every map of y (N, h, w, C): (floor(min), ceil(max), int64 counts over the unit intervals between them), the
     histogram `compute_probabilities_intervals(map, 1.)` takes with `numpy.histogram` (last interval closed)."""

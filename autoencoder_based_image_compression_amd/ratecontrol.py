@@ -1,0 +1,214 @@
+"""Rate ladders: what an image costs at each of K rate points, from counts alone, and the choice of a point for a byte budget
+(DESIGN.md section 18). Host side, numpy only; the one device call is `device.ladder_histograms`, made by the callers
+(`container.encode_images_to_budget`, `kodak.lossless.stats.compute_binary_probabilities_ladder`), which hand its outputs in here
+as numpy arrays.
+
+A rate point is a pair: 128 bin widths and a table of binary probabilities (the reference walks nine, `multipliers` of
+reconstructing_eae_kodak.py, and learns a point's cost by quantising and coding at it). The coder's cost is a function of the
+histogram of |symbol| clipped at the truncated unary length L, per map:
+  * the bypass stream's length is exact: one sign bit per non-zero symbol plus the Exp-Golomb suffix of |s| - L from L on
+    (LosslessCoder.cpp:22-37, 58-111, 232-252) -- the kernel sums it;
+  * the arithmetic-coded stream's length follows the ideal cost -sum zeros[i] log2 p[i] - sum ones[i] log2(1 - p[i]) of the
+    binary decisions of stats.py:181-195: from above to within a constant, from below to within a constant on a table that fits the
+    data and to within the rounding of the coder's 16-bit interval on any table (the allowances below).
+"""
+import numpy
+
+NB_MAPS = 128
+
+# How far the arithmetic-coded stream of the host coder (`interface_cython.encode_flattened_map`: 16-bit interval, E1/E2/E3
+# rescaling, `stop_encoding`'s closing bits) was seen from the cost of its decisions. MEASURED, NOT PROVEN: profiles/rate_ladder.md
+# holds the sweep (`python profiles/rate_ladder.py --sweep`, CPU only): 6670 Laplacian maps of 1 to 16384 symbols, scales 0 (all-zero
+# maps) to 12, L = 1, 4, 10, tables fitted on matched data, on 1.5x, 0.1x and 10x mismatched data and on the map itself (with the
+# 0.5 / 0.01 / 0.99 clamps that brings), and tables whose every entry is 0.99, 0.01, 0.999 or 0.001.
+#   above:  actual - ceil(ideal) <= +2 bits on every map (actual - ideal <= +2.239)                     -> ALLOWANCE_HIGH = 2 + 1
+#   below, tables fitted on matched, 1.5x mismatched or own data:  actual - floor(ideal) >= 0 (actual - ideal >= -0.773)
+#                                                                                                       -> ALLOWANCE_LOW = 0 + 1
+#   below, any table: NO constant holds. The coder gives decision i the share (floor(p R) + 1) / (R + 1) or (R - floor(p R)) / (R + 1)
+#   of its interval, R + 1 >= 2^14 wide after rescaling: up to 2^-14 more than p or 1 - p. A table that calls frequent decisions
+#   rare (every entry 0.999 on a busy map) therefore codes BELOW the ideal cost in proportion to the stream: -652 bits on 16384
+#   symbols, -44 with a table fitted on 10x finer data. `floor_bits` is the cost at the largest shares, p + 2^-14 and 1 - p + 2^-14:
+#   actual - floor(floor_bits) >= +1 on every map of the sweep. The lower bound is built on it, since a point is skipped on the lower
+#   bound alone; on fitted tables it is 2.5 bits below the ideal cost at 1536 symbols, 26 at 16384.
+# The sizes swept end at 16384 symbols per map (a 2048 x 2048 image). `select_rate_points` codes a point before it takes it whatever
+# the bounds say, and counts the points the upper bound promised and the coder did not deliver.
+ALLOWANCE_LOW = 1
+ALLOWANCE_HIGH = 3
+INTERVAL_SHARE_EXCESS = 2.**-14
+
+_FIXED_HEADER_BYTES = 28          # container._HEADER.size: 'EAE1', version, flags, sizes, L, exception map index
+
+
+class RateLadder(object):
+    """K rate points in the caller's order of preference, finest first (no monotonicity is assumed: the selection walks the order).
+    bin_widths_points float32 (K, 128); binary_probabilities_points float64 (K, 128, L); map_mean float32 (128,); idx_map_exception:
+    the map coded with a probability row of its own (container.py), -1 for none."""
+
+    def __init__(self, bin_widths_points, binary_probabilities_points, map_mean, idx_map_exception=-1):
+        for (name, array, dtype, ndim) in (('bin_widths_points', bin_widths_points, numpy.float32, 2),
+                                           ('binary_probabilities_points', binary_probabilities_points, numpy.float64, 3),
+                                           ('map_mean', map_mean, numpy.float32, 1)):
+            if not isinstance(array, numpy.ndarray) or array.dtype != dtype or array.ndim != ndim:
+                raise TypeError('`{0}` must be a {1}-dimensional numpy array of {2}.'.format(name, ndim, numpy.dtype(dtype).name))
+        (nb_points, nb_maps) = bin_widths_points.shape
+        if nb_points < 1 or nb_maps != NB_MAPS:
+            raise ValueError('`bin_widths_points` must be (K, {}) with K >= 1.'.format(NB_MAPS))
+        if binary_probabilities_points.shape[:2] != (nb_points, nb_maps) or map_mean.shape != (nb_maps,):
+            raise ValueError('`binary_probabilities_points` must be (K, {0}, L) and `map_mean` ({0},).'.format(NB_MAPS))
+        length = binary_probabilities_points.shape[2]
+        if length < 1 or length > 255:
+            raise ValueError('The truncated unary length does not belong to [1, 255].')
+        if not (numpy.isfinite(bin_widths_points).all() and (bin_widths_points > 0.).all()):
+            raise ValueError('A quantization bin width is not strictly positive.')
+        if not ((binary_probabilities_points > 0.) & (binary_probabilities_points < 1.)).all():
+            raise ValueError('A binary probability does not belong to ]0, 1[.')
+        if not numpy.isfinite(map_mean).all():
+            raise ValueError('`map_mean` is not finite.')
+        if isinstance(idx_map_exception, bool) or int(idx_map_exception) != idx_map_exception:
+            raise TypeError('`idx_map_exception` must be an integer.')
+        self.bin_widths_points = numpy.ascontiguousarray(bin_widths_points)
+        self.binary_probabilities_points = numpy.ascontiguousarray(binary_probabilities_points)
+        self.map_mean = numpy.ascontiguousarray(map_mean)
+        # as `container.encode_images`: an index outside the maps means no exception map
+        self.idx_map_exception = int(idx_map_exception) if 0 <= idx_map_exception < nb_maps else -1
+        self.nb_points = nb_points
+        self.truncated_unary_length = length
+
+
+def decision_counts(hist):
+    """Clipped histograms of |symbol| (..., L + 1) (bin L: every |s| >= L) -> (zeros, ones), int64 (..., L): how often decision i of
+    the truncated unary prefix is 0 and 1. `stats._decisions_from_hist` of every histogram: a symbol of magnitude a < L is a zero
+    of decision a and a one of every decision before it, a symbol from L on a one of all L."""
+    hist = numpy.asarray(hist).astype(numpy.int64)
+    zeros = hist[..., :-1]
+    beyond = numpy.cumsum(hist[..., ::-1], axis=-1)[..., ::-1]          # beyond[..., j] = symbols of magnitude >= j
+    return numpy.ascontiguousarray(zeros), numpy.ascontiguousarray(beyond[..., 1:])
+
+
+def probabilities_from_counts(zeros, ones):
+    """stats.py:56-66: zeros / (zeros + ones) in float64, 0 / 0 -> 0.5, 0 -> 0.01, 1 -> 0.99."""
+    total = (zeros + ones).astype(numpy.float64)
+    with numpy.errstate(invalid='ignore', divide='ignore'):
+        p = zeros.astype(numpy.float64)/total
+    p[numpy.isnan(p)] = 0.5
+    p[p == 0.] = 0.01
+    p[p == 1.] = 0.99
+    return p
+
+
+def ideal_bits(zeros, ones, probabilities):
+    """-sum zeros[i] log2 p[i] - sum ones[i] log2(1 - p[i]) over the last axis, float64."""
+    return -(zeros*numpy.log2(probabilities) + ones*numpy.log2(1. - probabilities)).sum(axis=-1)
+
+
+def floor_bits(zeros, ones, probabilities):
+    """`ideal_bits` with every decision at the largest share of the interval the coder can give it, p + 2^-14 or 1 - p + 2^-14
+    (at most 1): what the stream costs at least, up to its closing bits, whatever the table (ALLOWANCE_LOW, above)."""
+    share_zero = numpy.minimum(probabilities + INTERVAL_SHARE_EXCESS, 1.)
+    share_one = numpy.minimum(1. - probabilities + INTERVAL_SHARE_EXCESS, 1.)
+    return -(zeros*numpy.log2(share_zero) + ones*numpy.log2(share_one)).sum(axis=-1)
+
+
+def _check_counts(hist, bypass_bits, ladder):
+    hist = numpy.asarray(hist)
+    bypass_bits = numpy.asarray(bypass_bits)
+    if hist.ndim != 4 or hist.shape[1:] != (ladder.nb_points, NB_MAPS, ladder.truncated_unary_length + 1):
+        raise ValueError('`hist` must be (N, K, {}, L + 1) for the K points and the L of the ladder.'.format(NB_MAPS))
+    if bypass_bits.shape != hist.shape[:3]:
+        raise ValueError('`bypass_bits` must be (N, K, {}).'.format(NB_MAPS))
+    return hist, bypass_bits.astype(numpy.int64)
+
+
+def estimate_bits(hist, bypass_bits, ladder):
+    """Outputs of `device.ladder_histograms` (as numpy) -> (ideal arithmetic-coded bits float64 (N, K, 128), exact bypass bits
+    int64 (N, K, 128)). The exception map is costed with the row `container._exception_rows` would form from that very
+    histogram, clamps included: it is the row the blob would carry."""
+    (zeros, ones, tables, bypass_bits) = _decisions_and_tables(hist, bypass_bits, ladder)
+    return ideal_bits(zeros, ones, tables), bypass_bits
+
+
+def _decisions_and_tables(hist, bypass_bits, ladder):
+    """(zeros, ones, the probability row every (image, point, map) is coded with, bypass bits)."""
+    (hist, bypass_bits) = _check_counts(hist, bypass_bits, ladder)
+    (zeros, ones) = decision_counts(hist)
+    tables = numpy.broadcast_to(ladder.binary_probabilities_points[None], zeros.shape).copy()
+    e = ladder.idx_map_exception
+    if e >= 0:
+        tables[:, :, e] = probabilities_from_counts(zeros[:, :, e], ones[:, :, e])
+    return zeros, ones, tables, bypass_bits
+
+
+def header_bytes(ladder):
+    """Bytes in front of the payload of a single-image EAE1 blob written at a point of the ladder (container.py, layout)."""
+    length = ladder.truncated_unary_length
+    return _FIXED_HEADER_BYTES + 8*NB_MAPS + 8*NB_MAPS*length + (8*length if ladder.idx_map_exception >= 0 else 0) + 8*NB_MAPS
+
+
+def blob_byte_bounds(hist, bypass_bits, ladder, height, width):
+    """(lower, upper), int64 (N, K): bounds on the size of the single-image EAE1 blob `container.encode_images` would write for
+    every image at every point. The header is exact; every map adds its bypass stream, ceil(bits / 8) bytes, exact, and its
+    arithmetic-coded stream, between floor(`floor_bits`) - ALLOWANCE_LOW and ceil(`ideal_bits`) + ALLOWANCE_HIGH bits, each rounded up
+    to a byte (on a table fitted to the data the two costs are a few bits apart: the comment at ALLOWANCE_LOW).
+    height, width: of the images (the histograms must count their (height / 16) * (width / 16) symbols per map, except at a point
+    with range errors, which `valid_points` tells apart)."""
+    (zeros, ones, tables, bypass_bits) = _decisions_and_tables(hist, bypass_bits, ladder)
+    if height < 1 or width < 1 or height % 16 != 0 or width % 16 != 0:
+        raise ValueError('The image sizes are not positive multiples of 16.')
+    if int(numpy.asarray(hist).sum(axis=-1).max()) > (height//16)*(width//16):
+        raise ValueError('The histograms count more symbols than a map of a {} x {} image holds.'.format(height, width))
+    fixed = header_bytes(ladder) + ((bypass_bits + 7)//8).sum(axis=-1)
+    low_bits = numpy.maximum(numpy.floor(floor_bits(zeros, ones, tables)).astype(numpy.int64) - ALLOWANCE_LOW, 0)
+    high_bits = numpy.ceil(ideal_bits(zeros, ones, tables)).astype(numpy.int64) + ALLOWANCE_HIGH
+    return fixed + ((low_bits + 7)//8).sum(axis=-1), fixed + ((high_bits + 7)//8).sum(axis=-1)
+
+
+def valid_points(hist, map_size):
+    """bool (N, K): the points at which every symbol of the image fits int16. An element beyond goes into no bin
+    (eae_hip_ladder_histograms), so a valid (image, point) is one whose histograms hold all 128 * map_size symbols."""
+    return numpy.asarray(hist).astype(numpy.int64).sum(axis=(-1, -2)) == NB_MAPS*int(map_size)
+
+
+def select_rate_points(lower, upper, valid, budget_bytes, size_of):
+    """The deterministic choice of a rate point per image. lower, upper int (N, K) (`blob_byte_bounds`); valid bool (N, K);
+    budget_bytes: a scalar or one value per image; size_of(image, k) -> the real size in bytes of the image coded at point k.
+    Per image, in ladder order: a point that is invalid or whose lower bound exceeds the budget is skipped; any other point is
+    coded (`size_of`) and taken if its real size fits. If none fits, the last valid point is taken (and coded, if it was not) and
+    `fits` is False. An image without a valid point raises the AssertionError of `container.encode_images`.
+    -> dict: 'rate_point' int64 (N,), 'blob_bytes' int64 (N,), 'attempts' int64 (N,) (calls of size_of), 'fits' bool (N,),
+    'upper_bound_misses': the attempts at a point with upper <= budget whose real size did not fit (expected: 0)."""
+    lower = numpy.asarray(lower)
+    upper = numpy.asarray(upper)
+    valid = numpy.asarray(valid, dtype=bool)
+    if lower.ndim != 2 or upper.shape != lower.shape or valid.shape != lower.shape:
+        raise ValueError('`lower`, `upper` and `valid` must be (N, K).')
+    (nb_images, nb_points) = lower.shape
+    budgets = numpy.broadcast_to(numpy.asarray(budget_bytes), (nb_images,)) if numpy.ndim(budget_bytes) <= 1 else None
+    if budgets is None:
+        raise ValueError('`budget_bytes` must be a scalar or one value per image.')
+    out = {'rate_point': numpy.zeros(nb_images, dtype=numpy.int64), 'blob_bytes': numpy.zeros(nb_images, dtype=numpy.int64),
+           'attempts': numpy.zeros(nb_images, dtype=numpy.int64), 'fits': numpy.zeros(nb_images, dtype=bool), 'upper_bound_misses': 0}
+    for i in range(nb_images):
+        budget = budgets[i]
+        candidates = numpy.flatnonzero(valid[i])
+        if candidates.size == 0:
+            raise AssertionError('The rounded array elements cannot be represented as 16-bit signed integers.')
+        sizes = {}
+        chosen = None
+        for k in candidates.tolist():
+            if lower[i, k] > budget:
+                continue
+            sizes[k] = int(size_of(i, k))
+            if sizes[k] <= budget:
+                chosen = k
+                break
+            if upper[i, k] <= budget:
+                out['upper_bound_misses'] += 1
+        out['fits'][i] = chosen is not None
+        if chosen is None:
+            chosen = int(candidates[-1])
+            if chosen not in sizes:
+                sizes[chosen] = int(size_of(i, chosen))
+        out['rate_point'][i] = chosen
+        out['blob_bytes'][i] = sizes[chosen]
+        out['attempts'][i] = len(sizes)
+    return out

@@ -339,6 +339,26 @@ int eae_hip_symbol_histograms(const int16_t* symbols_planar, uint32_t* hist, int
 int eae_hip_symbol_histograms_strided(const int16_t* symbols_planar, uint32_t* hist, int hist_radius, uint32_t* overflow,
                                       int n_maps, int map_size, int64_t first_map, int64_t map_step, void* stream);
 
+/* ---- rate ladder (csrc/hip/ladder.hip; ratecontrol.py) ------------------------------------------------
+ * One pass over the latents y [N][hw][128] for the K rate points of a ladder (the reference walks nine, `multipliers`, and
+ * quantises, counts and codes once per point: lossless/stats.py:314-320, reconstructing_eae_kodak.py). For every element and every
+ * point k the symbol is eae_hip_quantize_maps' with bw = bin_widths_points[k][c] and m = map_mean[c] (NULL = 0), the same float32
+ * expressions in the same order:  rs = round_half_even(bw * round_half_even((y - m) / bw) / bw).  Then
+ *   hist[i][k][c][min(|rs|, L)] += 1                      uint32 [N][K][128][L + 1]: the clipped histogram the binary decisions of
+ *                                                         stats.py:181-195 are counted from
+ *   bypass_bits[i][k][c] += (rs != 0) + (|rs| >= L ? 2 * floor(log2(|rs| - L + 1)) + 1 : 0)       uint64 [N][K][128], nullable:
+ *                                                         the exact length of the map's bypass stream (LosslessCoder.cpp:22-37,
+ *                                                         58-111, 232-252: sign bits and Exp-Golomb suffixes)
+ *   an element with !(|rs| < 32768) (NaN included) goes into no bin and no bit count: range_errors[k] += 1 (uint32 [K], nullable),
+ *                                                         the AssertionError of tools.py:130-132 at that point
+ * All three are ACCUMULATED into: the caller zeroes them. L = length, 1..255; k_points 1..eae_hip_ladder_max_points(length), the most
+ * rate points one launch takes at this L (its block keeps (L + 3) * 512 bytes of LDS per point: 9 at L = 10) and 0 when not even
+ * one fits or L is out of range. Those, NULL y / bin_widths_points / hist and non-positive n / hw -> EAE_HIP_BAD_ARGUMENT (a grid
+ * of 2^31 blocks or more, n * hw / 64 at the most: EAE_HIP_BAD_SHAPE). One launch; bin widths are not checked (a zero or negative width gives the symbols the quantiser would give). */
+int eae_hip_ladder_histograms(const float* y, const float* map_mean, const float* bin_widths_points, int k_points, int length,
+                              uint32_t* hist, uint64_t* bypass_bits, uint32_t* range_errors, int n, int hw, void* stream);
+int eae_hip_ladder_max_points(int length);
+
 /* ---- lossless coder on the device: one feature map per lane --------------------------------------------------------
  * Replaces the per-map compress_lossless loop of lossless/compression.py:76-81 (and, underneath it,
  * lossless/c++/source/compression.cpp:3-65) for a whole batch of images whose symbols are already in HBM
