@@ -79,6 +79,46 @@ def test_layout_is_the_documented_one():
     assert all(pos % dtype.itemsize == 0 for (pos, dtype, _) in odd.values())
 
 
+def _check_layout(fields, nbytes, views, head):
+    """A step head's fields do not overlap, each starts on a multiple of 8, the block is a multiple of 16 bytes that the last field
+    ends in, and the views write where the layout says: a value put into the last element of every field is read back from the
+    bytes [end - itemsize, end) of that field, and from nowhere else."""
+    spans = sorted((pos, pos + dtype.itemsize*int(numpy.prod(shape)), name) for (name, (pos, dtype, shape)) in fields.items())
+    assert spans[0][0] == 0
+    for ((_, end, name), (start, _, following)) in zip(spans, spans[1:]):
+        assert end <= start < end + 8, (name, following)
+    assert all(start % 8 == 0 and stop > start for (start, stop, _) in spans)
+    assert nbytes % 16 == 0 and 0 <= nbytes - spans[-1][1] < 16 and head.size == nbytes
+    assert sorted(views) == sorted(fields)
+    head[:] = 0
+    for (k, (start, stop, name)) in enumerate(spans):
+        (_, dtype, shape) = fields[name]
+        assert views[name].shape == shape and views[name].dtype == dtype
+        views[name].reshape(-1)[-1] = 3 + k
+    for (k, (start, stop, name)) in enumerate(spans):
+        dtype = fields[name][1]
+        assert head[stop - dtype.itemsize:stop].view(dtype)[0] == 3 + k, name
+        assert views[name].reshape(-1)[-1] == 3 + k, name
+    written = numpy.zeros(nbytes, dtype=bool)
+    for (start, stop, name) in spans:
+        written[stop - fields[name][1].itemsize:stop] = True
+    assert not head[~written].any()
+
+
+@pytest.mark.parametrize('batch,n_streams', [(1, None), (2, None), (3, None), (4, None), (3, 3*12*NB_MAPS), (2, 2*7*NB_MAPS), (1, 5*NB_MAPS)])
+def test_layout_at_every_length(batch, n_streams):
+    """Every truncated unary length the decoder accepts moves 'payload_bytes' behind the table, by 8*batch*129 bytes a column."""
+    for length in range(1, 256):
+        (fields, nbytes) = codec.decode_head_layout(batch, NB_MAPS, length, n_streams)
+        n = batch*NB_MAPS if n_streams is None else n_streams
+        assert fields['bits'][2] == (n, 2) and fields['prob_row'][2] == (n,) and fields['table'][2] == (batch, NB_MAPS + 1, length)
+        assert fields['payload_bytes'][0] == fields['table'][0] + 8*batch*(NB_MAPS + 1)*length
+        head = numpy.zeros(nbytes, dtype=numpy.uint8)
+        _check_layout(fields, nbytes, codec.decode_head_views(head, batch, NB_MAPS, length, n_streams), head)
+        with pytest.raises(ValueError):
+            codec.decode_head_views(head[:-1], batch, NB_MAPS, length, n_streams)
+
+
 @pytest.mark.parametrize('idx_map_exception', [-1, 0, 127])
 def test_one_multi_image_blob(idx_map_exception):
     (blob, parts) = _blob(1 + idx_map_exception, BATCH, idx_map_exception)

@@ -10,6 +10,8 @@ import numpy
 import pytest
 import torch
 
+from unary_length_cases import host_encode_maps
+
 pytestmark = pytest.mark.gpu
 
 
@@ -116,26 +118,6 @@ def test_eae1_is_one_group_of_whole_maps_without_a_copy(model, monkeypatch):
     assert calls == {'encode': [384], 'decode': [384], 'gather': 0}
     assert blob[:4] == b'EAE1' and blob == expected
     assert numpy.array_equal(reconstruction, in_memory_path(model, images, bw, mean)[1])
-
-
-def host_encode_maps(planar, probs, prob_row):
-    from autoencoder_based_image_compression_amd import _native
-    lib = _native.coder()
-    (n, size) = planar.shape
-    L = probs.shape[1]
-    stride = int(_native.hip().eae_hip_coder_stream_stride_bytes(size, L))
-    streams = numpy.zeros((n, stride), dtype=numpy.uint8)
-    (bac, byp) = (numpy.zeros(n, dtype=numpy.uint32), numpy.zeros(n, dtype=numpy.uint32))
-    (status, stage) = (numpy.zeros(n, dtype=numpy.int32), numpy.zeros(n, dtype=numpy.int32))
-    pp = numpy.ascontiguousarray(probs, dtype=numpy.float64)
-    rows = numpy.ascontiguousarray(prob_row, dtype=numpy.int32)
-    planar = numpy.ascontiguousarray(planar)
-    lib.eae_coder_encode_maps(n, size, _native.ptr(planar, _native.c_i16p), L, _native.ptr(pp, _native.c_f64p),
-                              _native.ptr(rows, _native.c_i32p), _native.ptr(streams, _native.c_u8p), stride,
-                              _native.ptr(bac, _native.c_u32p), _native.ptr(byp, _native.c_u32p),
-                              _native.ptr(status, _native.c_i32p), _native.ptr(stage, _native.c_i32p), 4)
-    assert not status.any()
-    return streams, stride, bac, byp
 
 
 @pytest.mark.parametrize('idx_map_exception', [67, -1])

@@ -80,6 +80,22 @@ def test_the_example_of_the_design():
         codec.region_layout(BATCH, 11, 13, (4, 4), 12, 7)
 
 
+@pytest.mark.parametrize('batch,n_slots', [(1, 1), (1, 12), (2, 24), (3, 36), (3, 3), (4, 7), (5, 65)])
+def test_head_layout_at_every_length(batch, n_slots):
+    """`region_head_layout` at every truncated unary length the decoder accepts: the fields do not overlap, each starts on a multiple
+    of 8, the block is a multiple of 16, and the views write where the layout says (`_check_layout` of tests/test_batch_decoder_host.py)."""
+    from tests.test_batch_decoder_host import _check_layout
+    for length in range(1, 256):
+        (fields, nbytes) = codec.region_head_layout(batch, n_slots, length)
+        assert fields['bits'][2] == (n_slots*NB_MAPS, 2) and fields['prob_row'][2] == (n_slots*NB_MAPS,) and fields['placement'][2] == (n_slots, 4)
+        assert fields['crop_origin'][2] == (batch, 2) and fields['table'][2] == (batch, NB_MAPS + 1, length)
+        assert fields['payload_bytes'][0] == fields['table'][0] + 8*batch*(NB_MAPS + 1)*length
+        head = numpy.zeros(nbytes, dtype=numpy.uint8)
+        _check_layout(fields, nbytes, codec.region_head_views(head, batch, n_slots, length), head)
+        with pytest.raises(ValueError):
+            codec.region_head_views(head[:-1], batch, n_slots, length)
+
+
 @pytest.mark.parametrize('shape,tile,nb_classes', CASES)
 def test_geometry_at_every_position(shape, tile, nb_classes):
     (h, w) = (shape[0]//16, shape[1]//16)

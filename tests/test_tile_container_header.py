@@ -61,6 +61,43 @@ def test_well_formed_tile_header_is_accepted():
     assert container.read_header(build_tile_blob(idx_map_exception=-1))['exception_probabilities'].shape == (0, 10)
 
 
+@pytest.mark.parametrize('idx_map_exception', [67, -1])
+@pytest.mark.parametrize('length', [1, 2, 3, 31, 32, 33, 255])
+def test_written_tile_headers_read_back_at_every_length(length, idx_map_exception):
+    """`assemble_blob(coding_tile=...)` -> `read_header` at the lengths of tests/unary_length_cases.py, with and without the exception
+    row: tiles of (4, 4) on 11 x 13 latents (four shape classes, each with its own stream capacity at that length), and one tile per
+    map, whose header is the EAE1 header `ratecontrol.header_bytes` sizes plus the two sides of the coding tile."""
+    from autoencoder_based_image_compression_amd import ratecontrol
+    from tests.test_container_header import check_round_trip, random_parts
+    for (nb_images, height, width, tile, learned) in ((2, 176, 208, (4, 4), False), (1, 64, 96, (4, 6), True)):
+        (tiles, _) = container.coding_tile_grid(height//16, width//16, tile)
+        sizes = [int(r*c) for (r, c) in tiles[:, 2:4].tolist()]
+        parts = random_parts(length, nb_images, height, width, length, idx_map_exception, len(tiles), sizes)
+        (blob, header_bytes) = container.assemble_blob(learned, nb_images, height, width, idx_map_exception, parts['bin_widths'], parts['map_mean'],
+                                                       parts['probabilities'], parts['exception_rows'], parts['bits'].reshape(-1, 2),
+                                                       parts['payload'], coding_tile=tile)
+        header = container.read_header(blob)
+        check_round_trip(header, parts, nb_images, height, width, length, idx_map_exception, learned)
+        assert header['format'] == 'EAT1' and header['coding_tile'] == tile
+        assert header['bits'].shape == parts['bits'].shape and numpy.array_equal(header['bits'], parts['bits'])
+        assert header['payload_offset'] == header_bytes == len(blob) - len(parts['payload']) and blob[header_bytes:] == parts['payload']
+        if len(tiles) == 1:
+            ladder = ratecontrol.RateLadder(parts['bin_widths'][None], parts['probabilities'][None], parts['map_mean'], idx_map_exception)
+            assert header_bytes == ratecontrol.header_bytes(ladder) + container._TILE_HEADER.size - container._HEADER.size
+        # a count one bit above the capacity of the smallest tile's streams at this length, with a payload to match: refused
+        smallest = int(numpy.argmin(sizes))
+        bits = parts['bits'].copy()
+        bits[0, smallest, 5, 1] = container.stream_capacity_bits(sizes[smallest], length) + 1
+        payload = bytes(int(((bits.astype(numpy.int64) + 7)//8).sum()))
+        (bad, _) = container.assemble_blob(learned, nb_images, height, width, idx_map_exception, parts['bin_widths'], parts['map_mean'],
+                                           parts['probabilities'], parts['exception_rows'], bits.reshape(-1, 2), payload, coding_tile=tile)
+        with pytest.raises(ValueError, match='capacity'):
+            container.read_header(bad)
+        for bad in (blob[:-1], blob + b'\x00'):
+            with pytest.raises(ValueError):
+                container.read_header(bad)
+
+
 @pytest.mark.parametrize('kwargs', [
     dict(coding_tile=(0, 3)), dict(coding_tile=(2, 0)), dict(coding_tile=(0, 0)), dict(payload_extra=1), dict(payload_extra=-1),
     dict(version=container.TILE_VERSION + 1), dict(length=0), dict(height=40, width=0), dict(height=72), dict(nb_images=0),
