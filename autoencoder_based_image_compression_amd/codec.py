@@ -487,6 +487,7 @@ class _Worker(_StepWorker):
                     'rows': rows.copy() if self.idx_map_exception >= 0 else rows[:0].copy(),
                     'bits': numpy.stack([results[0], results[1]], axis=1).astype(numpy.uint32),
                     'payload': payload[:payload_bytes].tobytes() if int(index[1]) == 0 else None}
+            self._finish(job)
         except StepTimeout as exc:    # nothing says the device is through with this slot: no later submit may reuse it
             self.failed = exc
             ticket._error = exc
@@ -495,6 +496,10 @@ class _Worker(_StepWorker):
         finally:
             job.slot_free.set()
             ticket._done.set()
+
+
+    def _finish(self, job):
+        """What a subclass adds to a step's results while the slot is still the step's (`_BudgetWorker`); raises like `process`."""
 
 
 def default_nb_in_flight(h_in, w_in):
@@ -707,6 +712,7 @@ class _Slot(object):
 
 class BatchCodec(object):
     """Encode -> quantise -> entropy-code (with round trip) -> decode -> squared error for batches of a fixed shape."""
+    (_ticket_class, _worker_class) = (Ticket, _Worker)      # what a subclass replaces (`BudgetCodec`)
 
     def __init__(self, variables, are_bin_widths_learned, bin_widths_test, map_mean, binary_probabilities, idx_map_exception,
                  batch_size, h_in, w_in, device='cuda', nb_in_flight=None, keep_reconstruction=False, launch_hook=None,
@@ -896,7 +902,7 @@ class BatchCodec(object):
         self._fetch_stream = torch.cuda.Stream(device=self.device) if self.fetch_reconstruction else None
         assert not self.use_graphs or self._transform_streams      # replays never go to the caller's stream
         # last but one: a constructor that raised above has no worker yet, and `close()` has nothing to wait for
-        self._worker = _Worker(self.map_size, self.nb_maps, probabilities if coder == 'host' else None, self.idx_map_exception,
+        self._worker = self._worker_class(self.map_size, self.nb_maps, probabilities if coder == 'host' else None, self.idx_map_exception,
                                host_coder_threads, self.coding_tile, self._tile_layout['payload_order'] if self._tile_layout else None)
         self._worker.start()
         # last: a constructor that raised above leaves nothing half-built behind for another codec's `_capture_all` to drain
@@ -971,7 +977,7 @@ class BatchCodec(object):
         expected = (slot.counts[0] + 1, slot.counts[1] + 1)      # what the slot's step counters will show behind this step
         timed = self.time_coder and not replay
         try:
-            ticket = Ticket(self.batch_size)
+            ticket = self._ticket_class(self.batch_size)
             coded = torch.cuda.Event(enable_timing=timed) if (timed or not sequence_mode) else None
             if timed:
                 ticket._coder_span = (torch.cuda.Event(enable_timing=True), coded)
@@ -2287,3 +2293,254 @@ class RegionDecoder(BatchDecoder):
         dev.publish_crops(slot.planes, lane.crop_origin, slot.pinned_crops if slot.pinned_crops is not None else slot.crops, rh, rw)
         dev.publish_to_host(lane.unfinished, slot.pinned_unfinished)
         dev.publish_step(lane.status, slot.pinned_status, lane.status.numel(), slot.seq_dev[1:2], slot.seq_dev[0:1], slot.pinned_seq)
+
+
+# ---- a rate point per image, chosen on the device to a byte budget -----------------------------------------
+
+class BudgetTicket(Ticket):
+    """Handle on one submitted `BudgetCodec` step: `result()` also says where every image landed; `image_containers()` gives every
+    image's blob at its own rate point."""
+
+    def container(self):
+        """Always raises: one `EAE1` blob holds one rate point, the images of a step each have their own."""
+        raise RuntimeError('a BudgetCodec step has one rate point per image and one EAE1 blob holds one: use `image_containers()`')
+
+    def image_containers(self):
+        """Blocks like `result()`; one single-image `EAE1` blob per image, byte for byte what `container.encode_images` writes for
+        that image at the point `result()['rate_point']` names. Raises `ContainerOverflow` like `Ticket.container()`."""
+        parts = self._parts()
+        (learned, _, height, width, exception, ladder) = parts['head']
+        (bits, rows, view) = (parts['bits'], parts['rows'], memoryview(parts['payload']))
+        nb_maps = ladder.bin_widths_points.shape[1]
+        image_bytes = container_format._entry_bytes(bits.reshape(self.nb_images, nb_maps, 2))
+        stops = numpy.cumsum(image_bytes)
+        blobs = []
+        for (i, k) in enumerate(parts['rate_point'].tolist()):
+            blobs.append(container_format.assemble_blob(learned, 1, height, width, exception, ladder.bin_widths_points[k], ladder.map_mean,
+                                                        ladder.binary_probabilities_points[k], rows[i:i + 1] if exception >= 0 else rows[:0],
+                                                        bits[i*nb_maps:(i + 1)*nb_maps], view[int(stops[i] - image_bytes[i]):int(stops[i])])[0])
+        return blobs
+
+
+class _BudgetSlot(object):
+    """What one `BudgetCodec` step in flight owns beyond its `_Slot`. Made once; tests/budget_slot_buffers.py says what a step may
+    find in every attribute when it starts."""
+    __slots__ = ('accum', 'hist', 'bypass_bits', 'range_errors', 'pinned_budgets', 'budgets_host', 'budgets', 'budgets_nbytes', 'select',
+                 'upper', 'point', 'flags', 'prob_row', 'pinned_select', 'select_host', 'table', 'points_table', 'exception_rows',
+                 'pinned_rows', 'rows_host')
+
+    def __init__(self, codec):
+        (batch_size, nb_maps, device, ladder) = (codec.batch_size, codec.nb_maps, codec.device, codec.ladder)
+        (nb_points, length) = (ladder.nb_points, ladder.truncated_unary_length)
+        # the ladder's accumulators, zeroed by one launch at the head of every step: [bypass bits int64 | histograms int32 | range errors int32]
+        (nb_bits, nb_bins) = (batch_size*nb_points*nb_maps, batch_size*nb_points*nb_maps*(length + 1))
+        self.accum = torch.zeros(2*nb_bits + nb_bins + nb_points, dtype=torch.int32, device=device)
+        self.bypass_bits = self.accum[:2*nb_bits].view(torch.int64).view(batch_size, nb_points, nb_maps)
+        self.hist = self.accum[2*nb_bits:2*nb_bits + nb_bins].view(batch_size, nb_points, nb_maps, length + 1)
+        self.range_errors = self.accum[2*nb_bits + nb_bins:]
+        # the step's budgets: written by `BudgetCodec._stage` into pinned memory, fetched by a kernel inside the step's chain
+        padded = batch_size + batch_size % 2                       # `device.fetch_prefix` copies multiples of 16 bytes
+        self.pinned_budgets = torch.zeros(padded, dtype=torch.int64).pin_memory()
+        self.budgets_host = self.pinned_budgets.numpy()
+        self.budgets = torch.zeros(padded, dtype=torch.int64, device=device)
+        self.budgets_nbytes = torch.full((1,), 8*padded, dtype=torch.int64, device=device)
+        # what `device.ladder_select` leaves for the host: [upper int64 N x K | point int32 N | flags int32 N]
+        self.select = torch.zeros(2*batch_size*nb_points + 2*batch_size, dtype=torch.int32, device=device)
+        self.upper = self.select[:2*batch_size*nb_points].view(torch.int64).view(batch_size, nb_points)
+        self.point = self.select[2*batch_size*nb_points:2*batch_size*nb_points + batch_size]
+        self.flags = self.select[2*batch_size*nb_points + batch_size:]
+        self.prob_row = torch.zeros((batch_size, nb_maps), dtype=torch.int32, device=device)
+        self.pinned_select = torch.zeros(self.select.numel(), dtype=torch.int32).pin_memory()
+        (upper_host, point_host, flags_host) = torch.split(self.pinned_select, [2*batch_size*nb_points, batch_size, batch_size])
+        # the coder's table: [the K x 128 rows of the ladder | one row per image for its exception map]
+        self.table = torch.zeros((nb_points*nb_maps + batch_size, length), dtype=torch.float64, device=device)
+        self.points_table = self.table[:nb_points*nb_maps]
+        self.points_table.copy_(torch.from_numpy(ladder.binary_probabilities_points.reshape(nb_points*nb_maps, length)))
+        self.exception_rows = self.table[nb_points*nb_maps:]
+        self.pinned_rows = torch.zeros((batch_size, length), dtype=torch.float64).pin_memory()
+        self.rows_host = self.pinned_rows.numpy()
+        # what the result worker reads (`_BudgetWorker._finish`)
+        self.select_host = (upper_host.view(torch.int64).view(batch_size, nb_points).numpy(), point_host.numpy(), flags_host.numpy())
+
+
+class _BudgetHead(object):
+    """The first element of a `BudgetCodec` slot's `emit_host` (what `_Worker.process` keeps as the container's 'head'): the fixed
+    parts of the step's blobs and the host views of the slot's `_BudgetSlot`."""
+    __slots__ = ('fixed', 'budget_slot', 'header_bytes')
+
+    def __init__(self, fixed, budget_slot, header_bytes):
+        (self.fixed, self.budget_slot, self.header_bytes) = (fixed, budget_slot, header_bytes)
+
+
+class _BudgetWorker(_Worker):
+    """The result worker of `BudgetCodec`."""
+
+    def _finish(self, job):
+        """The step's choice out of the slot's pinned blocks into the ticket, while the slot is still the step's."""
+        (ticket, head) = (job.ticket, job.emit[0])
+        (upper, point, flags) = head.budget_slot.select_host
+        n = ticket.nb_images
+        budgets = head.budget_slot.budgets_host[:n].copy()
+        rate_point = point[:n].astype(numpy.int64)
+        blob_bytes = head.header_bytes + ticket._values['container_bytes']
+        ticket._values.update({'rate_point': rate_point, 'upper_bound_bytes': upper[:n].copy(), 'budget_bytes': budgets,
+                               'blob_bytes': blob_bytes, 'promised': (flags[:n] & 1) != 0, 'fits': blob_bytes <= budgets})
+        parts = ticket._container_parts
+        parts['head'] = head.fixed
+        parts['rate_point'] = rate_point
+        if self.idx_map_exception >= 0:
+            parts['rows'] = head.budget_slot.rows_host.copy()
+
+
+class BudgetCodec(BatchCodec):
+    """`BatchCodec` with a rate point per image, chosen inside the step, on the device, so that the image's blob fits a byte budget
+    (DESIGN.md section 19): "N bytes per image" as a property of a step of the resident codec."""
+    (_ticket_class, _worker_class) = (BudgetTicket, _BudgetWorker)
+
+    def __init__(self, variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, budget_bytes=None, **batch_codec_options):
+        """ladder: a `ratecontrol.RateLadder`, finest point first, of at most `device.ladder_max_points(L)` points. budget_bytes: the
+        budget of a `submit` that names none (a scalar or one value per image). batch_codec_options: `BatchCodec`'s keyword arguments
+        (device, nb_in_flight, keep_reconstruction, use_graphs, nb_transform_streams, one_stream_steps, hist_radius,
+        container_capacity_bytes, ...); `emit_container` is always on; `coding_tile`, `fuse_latent`, a coder other than 'device' and
+        `coder_chunks` > 1 are refused.
+        Per image, in ladder order, the step takes the first point whose symbols fit int16 and whose UPPER BOUND on the size of the
+        image's single-image EAE1 blob (ratecontrol.upper_bounds_fixed) is within the budget; if none is, the last valid point.
+        `Ticket.result()` gains 'rate_point' int64 (N,), 'upper_bound_bytes' int64 (N, K), 'budget_bytes' int64 (N,), 'blob_bytes'
+        int64 (N,) (the length of the image's blob), 'promised' bool (N,) (the bound of the point taken was within the budget) and
+        'fits' bool (N,) (blob_bytes <= budget); 'nb_bits', 'coder_bits', 'exception_bits', 'sse', 'nb_deads' and 'container_bytes'
+        are those of the image's own point. `Ticket.image_containers()[i]` is byte for byte `container.encode_images` of image i at
+        its point; `Ticket.container()` raises. An image without a valid point fails the step's range check as in `BatchCodec`."""
+        from . import ratecontrol
+        if not isinstance(ladder, ratecontrol.RateLadder):
+            raise TypeError('`ladder` is not a `ratecontrol.RateLadder`.')
+        # refused in front of every allocation
+        options = dict(batch_codec_options)
+        if not options.pop('emit_container', True):
+            raise ValueError('`BudgetCodec` always emits containers: the budget is that of the image\'s blob.')
+        if options.get('coding_tile') is not None:
+            raise ValueError('`BudgetCodec` does not take `coding_tile`: the bounds are those of whole maps (EAE1).')
+        if options.get('fuse_latent'):
+            raise ValueError('`BudgetCodec` does not take `fuse_latent`: the point is chosen between conv_3 and the quantiser.')
+        if options.get('coder', 'device') != 'device':
+            raise ValueError('`BudgetCodec` needs the coder on the device.')
+        chunks = options.get('coder_chunks')
+        if int(default_coder_chunks(batch_size*csts.NB_MAPS_3) if chunks is None else chunks) > 1:
+            raise ValueError('`BudgetCodec` does not go with `coder_chunks` > 1.')
+        for name in ('bin_widths_test', 'map_mean', 'binary_probabilities', 'idx_map_exception'):
+            if name in options:
+                raise TypeError('`{0}` comes with the ladder.'.format(name))
+        length = ladder.truncated_unary_length
+        if ladder.nb_points > dev.ladder_max_points(length):
+            raise ValueError('The ladder has {0} points, one pass takes {1} at a truncated unary length of {2} '
+                             '(`device.ladder_max_points`).'.format(ladder.nb_points, dev.ladder_max_points(length), length))
+        self.ladder = ladder
+        self._default_budgets = None if budget_bytes is None else self._budgets_of(budget_bytes, batch_size)
+        self._header_bytes = ratecontrol.header_bytes(ladder)
+        # (the base class's own rate point, which no launch of this class reads, is the ladder's first)
+        super(BudgetCodec, self).__init__(variables, are_bin_widths_learned, ladder.bin_widths_points[0], ladder.map_mean,
+                                          ladder.binary_probabilities_points[0], ladder.idx_map_exception, batch_size, h_in, w_in,
+                                          emit_container=True, **options)
+        try:
+            to_device = lambda array: torch.from_numpy(numpy.ascontiguousarray(array)).to(self.device)
+            self._bin_widths_points = to_device(ladder.bin_widths_points)
+            # (32-bit words: torch has no arithmetic on uint32, and none is asked of it)
+            self._fixed_costs = to_device(ratecontrol.fixed_costs(ladder).view(numpy.int32))
+            self._log2_tables = to_device(ratecontrol.log2_tables(self.map_size).view(numpy.int32)) if self.idx_map_exception >= 0 else None
+            self._budget_slots = {}
+            fixed = (bool(are_bin_widths_learned), 1, h_in, w_in, self.idx_map_exception, ladder)
+            for slot in self._slots:
+                budget_slot = _BudgetSlot(self)
+                self._budget_slots[id(slot)] = budget_slot
+                slot.emit_host = (_BudgetHead(fixed, budget_slot, self._header_bytes),) + slot.emit_host[1:]
+            self._staged = None
+        except BaseException:
+            self.close()
+            raise
+
+    @staticmethod
+    def _budgets_of(budget_bytes, batch_size):
+        budgets = numpy.asarray(budget_bytes)
+        if budgets.dtype.kind not in 'iu' or budgets.ndim > 1 or (budgets.ndim == 1 and budgets.shape[0] != batch_size):
+            raise ValueError('`budget_bytes` must be an integer or one integer per image.')
+        return numpy.ascontiguousarray(numpy.broadcast_to(budgets.astype(numpy.int64), (batch_size,)))
+
+    def submit(self, luminances_uint8, budget_bytes=None):
+        """`BatchCodec.submit` with the step's budgets: a scalar or one value per image, bytes of the image's whole blob (header
+        included); None: the constructor's `budget_bytes`."""
+        budgets = self._default_budgets if budget_bytes is None else self._budgets_of(budget_bytes, self.batch_size)
+        if budgets is None:
+            raise ValueError('no `budget_bytes`, and the codec was built without a default.')
+        self._staged = budgets
+        try:
+            return super(BudgetCodec, self).submit(luminances_uint8)
+        finally:
+            self._staged = None
+
+    def _stage(self, slot):
+        """The step's budgets into the slot's pinned block (the slot is this step's: `_submit` has claimed it)."""
+        self._budget_slots[id(slot)].budgets_host[:self.batch_size] = self._staged
+
+    def _launch_step(self, luminances_uint8, slot, index, ticket, coded):
+        self._stage(slot)
+        return super(BudgetCodec, self)._launch_step(luminances_uint8, slot, index, ticket, coded)
+
+    def _replay_step(self, luminances_uint8, slot, index, ticket, coded):
+        self._stage(slot)
+        return super(BudgetCodec, self)._replay_step(luminances_uint8, slot, index, ticket, coded)
+
+    def _launch_analysis(self, luminances_uint8, slot, hook):
+        """conv1+GDN1 -> conv2+GDN2 -> conv3 -> gdn_3 -> the ladder's histograms -> the step's budgets -> the point of every image
+        -> the quantiser with every image's own bin widths (+ inverse_gdn_4) -> exception-map histograms, on the current stream.
+        Everything that varies from step to step travels through device memory: no argument of any launch depends on it."""
+        enc = self.encoder
+        v = enc.v
+        d = self.decoder.v
+        budget = self._budget_slots[id(slot)]
+        length = self.truncated_unary_length
+        budget.accum.zero_()                              # the ladder's accumulators: the head of the step
+        gdn_1 = hook('conv1_gdn1', lambda: dev.conv9x9s4_u8(luminances_uint8, enc.w1, v['encoder/biases_1'], enc.g[1], v['encoder/beta_1']))
+        ws = slot.conv_ws
+        gdn_2 = hook('conv2_gdn2', lambda: dev.conv5x5s2(gdn_1, enc.w2, v['encoder/biases_2'], dev.NORM_GDN, enc.g[2], v['encoder/beta_2'], workspace=ws))
+        y = hook('conv3', lambda: dev.conv5x5s2(gdn_2, enc.w3, v['encoder/biases_3'], dev.NORM_NONE, workspace=ws))
+        if not self.learned:
+            y = hook('gdn3', lambda: dev.gdn(y, enc.g[3], v['encoder/beta_3']))
+        hook('ladder', lambda: dev.ladder_histograms(y, self._bin_widths_points, self.map_mean, length,
+                                                     out=(budget.hist, budget.bypass_bits, budget.range_errors)))
+        dev.fetch_prefix(budget.pinned_budgets, budget.budgets, budget.budgets_nbytes)
+        hook('select', lambda: dev.ladder_select(budget.hist, budget.bypass_bits, self._fixed_costs, self._log2_tables, self.idx_map_exception,
+                                                 self._header_bytes, self.map_size, budget.budgets[:self.batch_size],
+                                                 self.ladder.nb_points*self.nb_maps,
+                                                 out={'point': budget.point, 'prob_row': budget.prob_row, 'upper': budget.upper,
+                                                      'flags': budget.flags}))
+        igdn_out = None if self.learned else (self.decoder.g[4], d['decoder/beta_4'])
+        q = hook('latent', lambda: dev.latent_quantize_rows(y, self._bin_widths_points, budget.point, self.map_mean, igdn_out=igdn_out,
+                                                            want_shifted=self.learned, want_symbols=True, want_flags=True,
+                                                            out_symbols=slot.symbols, out_flags=slot.flags, out_checks=slot.checks[:3]))
+        if self.idx_map_exception >= 0:
+            dev.symbol_histograms(slot.symbols_2d, self.hist_radius, out=(slot.hist, slot.overflow),
+                                  first_map=self.idx_map_exception, map_step=self.nb_maps, zero=False)
+        if self._early_publish:
+            first = 4*self._n_streams
+            dev.publish_to_host(slot.out[first:], slot.pinned_out[first:])
+        return q['shifted'] if self.learned else q['t']
+
+    def _launch_coder(self, slot, hook=_no_hook):
+        """`BatchCodec._launch_coder` over the table of every point's rows with the rows `ladder_select` chose, and the publication
+        of the choice, on the current stream."""
+        budget = self._budget_slots[id(slot)]
+        symbols = slot.symbols_2d
+        prob_row = budget.prob_row.view(-1)
+        if self.idx_map_exception >= 0:
+            dev.exception_rows(slot.hist, slot.overflow, self.map_size, self.truncated_unary_length, out=budget.exception_rows)
+        hook('coder_encode', lambda: dev.coder_encode_batch(symbols, budget.table, prob_row, self.truncated_unary_length,
+                                                            out=slot.coder_streams, workspace=slot.workspace))
+        hook('coder_decode', lambda: dev.coder_decode_batch(slot.coder_streams, budget.table, prob_row, expected=symbols,
+                                                            workspace=slot.workspace))
+        dev.coder_index_streams(slot.coder_streams, self.nb_maps, self.container_capacity_bytes, offsets=slot.offsets, index=slot.index)
+        dev.coder_pack_indexed(slot.coder_streams, slot.offsets, slot.index, slot.payload)
+        dev.publish_prefix(slot.payload, slot.pinned_payload, slot.payload_bytes)
+        dev.publish_to_host(slot.emit_tail, slot.pinned_emit)
+        dev.publish_to_host(budget.select, budget.pinned_select)
+        if self.idx_map_exception >= 0:
+            dev.publish_to_host(budget.exception_rows, budget.pinned_rows)
+        dev.publish_step(slot.out, slot.pinned_out, 4*self._n_streams, *slot.coder_seq)

@@ -236,7 +236,8 @@ def encode_images_to_budget(luminances_uint8, encoder, ladder, budget_bytes, til
     blob was not (expected 0: the allowances of ratecontrol.py are measured, not proven).
     An image whose symbols leave int16 at every point raises the AssertionError of `encode_images`.
     tile=(th, tw): as in `encode_images`. Not in this function: coding tiles (EAT1: a tile's termination and byte padding need
-    counts per tile), and codec.BatchCodec, which still takes one rate point per codec."""
+    counts per tile), and codec.BatchCodec, which takes one rate point per codec (codec.BudgetCodec chooses one per image inside
+    the step, on the upper bound alone: DESIGN.md section 19)."""
     from . import ratecontrol
     images = numpy.ascontiguousarray(luminances_uint8)
     if images.dtype != numpy.uint8:

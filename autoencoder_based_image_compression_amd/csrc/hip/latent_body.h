@@ -155,3 +155,40 @@ __device__ __forceinline__ void wave_latent_body(f32x16 (&v)[4], const float* ve
         LAT_MARK(3)
     }
 }
+
+
+// ---- four wavefronts per 32 positions (latent_quarter_kernel of latent.hip, latent_rows_kernel of latent_rows.hip) ------------
+template <int RING>
+__device__ __forceinline__ f32x16 quarter_denominator(const f32x16 (&x2)[4], const float* __restrict__ gamma_packed, int w, int lane) {
+    const int hi = lane >> 5, lj = lane & 31;
+    const __amdgpu_buffer_rsrc_t g_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(gamma_packed), 0, (int)(EAE_C * EAE_C * sizeof(float)), 0x00020000);
+    const int g_lane = (hi * EAE_C + lj * 4 + w) * 4;      // packed row k = 2 kk + hi, column 4 lj + w = channel 32 w + lj
+    f32x16 d;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) d[r] = 0.f;
+    float ring[RING];
+#pragma unroll
+    for (int i = 0; i < RING; ++i) ring[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(g_rsrc, g_lane, i * 2 * EAE_C * 4, 0));
+#pragma unroll
+    for (int kk = 0; kk < EAE_C / 2; ++kk) {                // k = 2 kk + hi
+        d = mfma32(ring[kk % RING], x2[kk >> 4][kk & 15], d);
+        if (kk + RING < EAE_C / 2)
+            ring[kk % RING] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(g_rsrc, g_lane, (kk + RING) * 2 * EAE_C * 4, 0));
+    }
+    return d;
+}
+
+// One channel tile (16 registers: channel 8 g + 4 hi + q in [4 g + q]) -> its squares as MFMA B operands: [4 g + e] feeds K-step
+// 4 g + e of the tile, k pairs ascending (the swaps of wave_gdn_inplace, done once by the tile's owner instead of by every reader)
+__device__ __forceinline__ f32x16 squares_for_mfma(const f32x16& v) {
+    f32x16 r;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        float s0 = v[4 * g + 0], s1 = v[4 * g + 1], s2 = v[4 * g + 2], s3 = v[4 * g + 3];
+        swap_halves(s0, s1);     // s0 = channels (8g+0 | 8g+1), s1 = (8g+4 | 8g+5) in the (low | high) half-waves
+        swap_halves(s2, s3);     // s2 = (8g+2 | 8g+3), s3 = (8g+6 | 8g+7)
+        r[4 * g + 0] = s0 * s0; r[4 * g + 1] = s2 * s2; r[4 * g + 2] = s1 * s1; r[4 * g + 3] = s3 * s3;
+    }
+    return r;
+}

@@ -572,6 +572,80 @@ def ladder_histograms(y, bin_widths_points, map_mean=None, length=10, out=None):
     return out
 
 
+def ladder_select(hist, bypass_bits, fixed_costs, log2_tables, idx_map_exception, header_bytes, map_size, budgets, exception_row_base,
+                  out=None):
+    """The rate point of every image for its byte budget, on the device (include/eae_hip.h: eae_hip_ladder_select; the host rule is
+    ratecontrol.upper_bounds_fixed + valid_points + select_by_upper_bound). hist int32 [N, K, 128, L + 1] and bypass_bits int64
+    [N, K, 128] as `ladder_histograms` leaves them; fixed_costs int32/uint32 [K, 128, L, 2] (ratecontrol.fixed_costs) and log2_tables
+    [2, map_size + 1] (ratecontrol.log2_tables; None without an exception map), as device tensors of 32-bit words; budgets int64 [N]
+    on the device. -> dict: 'point' int32 [N], 'prob_row' int32 [N, 128], 'upper' int64 [N, K], 'flags' int32 [N] (bit 0 promised,
+    bit 1 no valid point). out: that dict, preallocated; every element is written."""
+    if hist.dim() != 4 or hist.shape[2] != NB_MAPS or hist.dtype != torch.int32:
+        raise HipError('hist must be int32 [N, K, 128, L + 1]')
+    (n, k_points, _, nb) = hist.shape
+    length = nb - 1
+    d = hist.device
+    if bypass_bits.dtype != torch.int64 or tuple(bypass_bits.shape) != (n, k_points, NB_MAPS):
+        raise HipError('bypass_bits must be int64 [N, K, 128]')
+    if fixed_costs.element_size() != 4 or fixed_costs.is_floating_point() or fixed_costs.numel() != k_points*NB_MAPS*length*2:
+        raise HipError('fixed_costs must hold K x 128 x L x 2 32-bit words')
+    map_size = int(map_size)
+    if log2_tables is not None and (log2_tables.element_size() != 4 or log2_tables.is_floating_point()
+                                    or log2_tables.numel() != 2*(map_size + 1)):
+        raise HipError('log2_tables must hold 2 x (map_size + 1) 32-bit words')
+    if budgets.dtype != torch.int64 or budgets.numel() != n:
+        raise HipError('budgets must be int64 [N]')
+    if out is None:
+        out = {'point': torch.empty(n, dtype=torch.int32, device=d), 'prob_row': torch.empty((n, NB_MAPS), dtype=torch.int32, device=d),
+               'upper': torch.empty((n, k_points), dtype=torch.int64, device=d), 'flags': torch.empty(n, dtype=torch.int32, device=d)}
+    for (name, dtype, count) in (('point', torch.int32, n), ('prob_row', torch.int32, n*NB_MAPS), ('upper', torch.int64, n*k_points),
+                                 ('flags', torch.int32, n)):
+        if out[name].dtype != dtype or out[name].numel() != count:
+            raise HipError('`out[{0!r}]` must hold {1} elements of {2}'.format(name, count, dtype))
+    _check(_native.hip().eae_hip_ladder_select(_p(hist), _p(bypass_bits), _p(fixed_costs), _p(log2_tables), k_points, length,
+                                               int(idx_map_exception), int(header_bytes), map_size, _p(budgets), int(exception_row_base),
+                                               _p(out['point']), _p(out['prob_row']), _p(out['upper']), _p(out['flags']), n,
+                                               _stream(hist)), 'eae_hip_ladder_select')
+    return out
+
+
+def latent_quantize_rows(y, bin_widths_points, point, map_mean=None, igdn_out=None, want_shifted=False, want_symbols=True,
+                         want_flags=False, out_symbols=None, out_flags=None, out_checks=None):
+    """The quantiser half of `latent_stage` with one row of bin widths per image (include/eae_hip.h: eae_hip_latent_quantize_rows):
+    y [N, h, w, 128] (or [N, hw, 128]) are the latents after gdn_3, image i is quantised with bin_widths_points[point[i]] (float32
+    [K, 128]; point int32 [N] on the device, clamped to [0, K)). Returns `latent_stage`'s dict without 'y'; image i's part equals
+    `latent_stage(y[i:i + 1], bin_widths_points[point[i]], map_mean, gdn_in=None, igdn_out=igdn_out)` bit for bit. out_* buffers:
+    preallocated, flags / checks already zeroed (see quantize_maps)."""
+    n = y.shape[0]
+    c = y.shape[-1]
+    hw = y.numel()//(n*c)
+    d = y.device
+    if c != NB_MAPS or y.dtype != torch.float32:
+        raise HipError('y must be float32 [N, ..., 128]')
+    if bin_widths_points.dtype != torch.float32 or bin_widths_points.dim() != 2 or bin_widths_points.shape[1] != NB_MAPS:
+        raise HipError('bin_widths_points must be float32 [K, 128]')
+    if point.dtype != torch.int32 or point.numel() != n:
+        raise HipError('point must be int32 [N]')
+    if map_mean is not None and (map_mean.dtype != torch.float32 or map_mean.numel() != NB_MAPS):
+        raise HipError('map_mean must be float32 of 128 elements')
+    shifted = torch.empty_like(y) if want_shifted else None
+    t = torch.empty_like(y) if igdn_out is not None else None
+    symbols = (out_symbols if out_symbols is not None else torch.empty((n, c, hw), dtype=torch.int16, device=d)) if want_symbols else None
+    if symbols is not None and (symbols.dtype != torch.int16 or symbols.numel() != n*c*hw):
+        raise TypeError('`out_symbols` must be an int16 tensor of N x C x hw elements.')
+    flags = (out_flags if out_flags is not None else torch.zeros((n, c), dtype=torch.int32, device=d)) if want_flags else None
+    if flags is not None and flags.numel() != n*c:
+        raise HipError('`out_flags` must hold N x 128 words')
+    checks = out_checks if out_checks is not None else torch.zeros(3, dtype=torch.int32, device=d)
+    if checks.numel() < 3:
+        raise HipError('`out_checks` must hold three words')
+    (g_out, b_out) = igdn_out if igdn_out is not None else (None, None)
+    _check(_native.hip().eae_hip_latent_quantize_rows(_p(y), _p(map_mean), _p(bin_widths_points), _p(point), bin_widths_points.shape[0],
+                                                      _p(g_out), _p(b_out), _p(shifted), _p(t), _p(symbols), _p(flags), _p(checks), n, hw,
+                                                      _stream(y)), 'eae_hip_latent_quantize_rows')
+    return {'shifted': shifted, 't': t, 'symbols': symbols, 'nonzero_flags': flags, 'checks': checks}
+
+
 def cast_bt601(x):
     out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
     _check(_native.hip().eae_hip_cast_bt601(_p(x), _p(out), x.numel(), _stream()), 'eae_hip_cast_bt601')

@@ -1,7 +1,8 @@
 """Rate ladders: what an image costs at each of K rate points, from counts alone, and the choice of a point for a byte budget
 (DESIGN.md section 18). Host side, numpy only; the one device call is `device.ladder_histograms`, made by the callers
 (`container.encode_images_to_budget`, `kodak.lossless.stats.compute_binary_probabilities_ladder`), which hand its outputs in here
-as numpy arrays.
+as numpy arrays. The second half of the file is the rule of `codec.BudgetCodec`: the same upper bound in integer
+arithmetic, which `eae_hip_ladder_select` restates on the device element for element, and the choice on that bound alone.
 
 A rate point is a pair: 128 bin widths and a table of binary probabilities (the reference walks nine, `multipliers` of
 reconstructing_eae_kodak.py, and learns a point's cost by quantising and coding at it). The coder's cost is a function of the
@@ -212,3 +213,90 @@ def select_rate_points(lower, upper, valid, budget_bytes, size_of):
         out['blob_bytes'][i] = sizes[chosen]
         out['attempts'][i] = len(sizes)
     return out
+
+
+# ---- the rule of `codec.BudgetCodec`: a point per image from its upper bound alone, in integers -----------
+# The device reaches the decision below element for element (`eae_hip_ladder_select`), so nothing in it is floating point: every
+# logarithm is taken here, once per ladder, rounded against the budget (a cost up, a subtracted term down) and handed over as a table
+# of 2^-20 bits.
+FIXED_SHIFT = 20
+FIXED_ONE = 1 << FIXED_SHIFT
+# ceil(-log2(0.99) * 2^20): what a decision costs under the 0.99 clamp of `probabilities_from_counts` (a count of one kind only)
+C99 = int(numpy.ceil(-numpy.log2(0.99)*FIXED_ONE))
+
+
+def fixed_costs(ladder):
+    """uint32 (K, 128, L, 2): [..., 0] = ceil(-log2(p) * 2^20), what a zero of the decision costs in 2^-20 bits, [..., 1] =
+    ceil(-log2(1 - p) * 2^20), a one. Below 2^32 for every float64 p in ]0, 1[ (the smallest gives 1074 * 2^20)."""
+    p = ladder.binary_probabilities_points
+    costs = numpy.stack([numpy.ceil(-numpy.log2(p)*FIXED_ONE), numpy.ceil(-numpy.log2(1. - p)*FIXED_ONE)], axis=-1)
+    assert costs.min() >= 0. and costs.max() < 2.**32
+    return numpy.ascontiguousarray(costs.astype(numpy.uint32))
+
+
+def log2_tables(map_size):
+    """uint32 (2, map_size + 1): [0, n] = ceil(log2(n) * 2^20), [1, n] = floor(log2(n) * 2^20); entry 0 of both is 0 (never
+    multiplied by anything but a zero count)."""
+    map_size = int(map_size)
+    if map_size < 1 or map_size > (1 << 24):
+        raise ValueError('`map_size` does not belong to [1, 2^24].')
+    tables = numpy.zeros((2, map_size + 1), dtype=numpy.uint32)
+    scaled = numpy.log2(numpy.arange(1, map_size + 1, dtype=numpy.float64))*FIXED_ONE
+    tables[0, 1:] = numpy.ceil(scaled)
+    tables[1, 1:] = numpy.floor(scaled)
+    return tables
+
+
+def upper_bounds_fixed(hist, bypass_bits, ladder, map_size):
+    """int64 (N, K): an upper bound on the size of every image's single-image EAE1 blob at every point, in integer arithmetic only
+    (64-bit sums of counts times the tables above): what `eae_hip_ladder_select` computes. Per map, fp = sum over the decisions of
+    zeros * c0 + ones * c1 (`fixed_costs`); the exception map, coded with the row `probabilities_from_counts` forms from its own
+    counts, pays per decision t * Lceil[t] - z * Lfloor[z] - o * Lfloor[o] with t = z + o (`log2_tables`), o * C99 when z == 0,
+    z * C99 when o == 0, nothing when t == 0. The stream then takes ((fp + 2^20 - 1) >> 20) + ALLOWANCE_HIGH bits, rounded up to a
+    byte; the bypass stream ceil(bits / 8) bytes; the header `header_bytes`.
+    Never below `blob_byte_bounds(...)[1]` and at most a byte per map above it while map_size * L <= 2^19 (every cost is rounded up
+    by less than 2^-20 bit per decision)."""
+    (hist, bypass_bits) = _check_counts(hist, bypass_bits, ladder)
+    map_size = int(map_size)
+    (zeros, ones) = decision_counts(hist)
+    if int(hist.astype(numpy.int64).sum(axis=-1).max()) > map_size:
+        raise ValueError('The histograms count more symbols than a map of {} holds.'.format(map_size))
+    costs = fixed_costs(ladder).astype(numpy.int64)
+    fp = (zeros*costs[None, ..., 0] + ones*costs[None, ..., 1]).sum(axis=-1)              # (N, K, 128)
+    e = ladder.idx_map_exception
+    if e >= 0:
+        tables = log2_tables(map_size).astype(numpy.int64)
+        (z, o) = (zeros[:, :, e], ones[:, :, e])
+        t = z + o
+        own = t*tables[0][t] - z*tables[1][z] - o*tables[1][o]
+        own = numpy.where(z == 0, o*C99, numpy.where(o == 0, z*C99, own))
+        fp[:, :, e] = own.sum(axis=-1)
+    bits = (fp + (FIXED_ONE - 1)) >> FIXED_SHIFT
+    stream_bytes = (bits + (ALLOWANCE_HIGH + 7))//8
+    return header_bytes(ladder) + (stream_bytes + (bypass_bits + 7)//8).sum(axis=-1)
+
+
+def select_by_upper_bound(upper, valid, budgets):
+    """-> (rate_point int64 (N,), promised bool (N,)). upper int (N, K); valid bool (N, K); budgets: a scalar or one value per
+    image. Per image, in ladder order, the first valid point with upper <= budget (`promised`: the bound says the blob fits); if
+    there is none, the last valid point, not promised; if no point is valid, point K - 1, not promised (quantising at it fails the
+    range check). Unlike `select_rate_points` nothing is coded to find out: a point is taken on its upper bound alone, so an
+    image with lower <= budget < upper at a point goes on to the next one."""
+    upper = numpy.asarray(upper)
+    valid = numpy.asarray(valid, dtype=bool)
+    if upper.ndim != 2 or valid.shape != upper.shape:
+        raise ValueError('`upper` and `valid` must be (N, K).')
+    (nb_images, nb_points) = upper.shape
+    if numpy.ndim(budgets) > 1:
+        raise ValueError('`budgets` must be a scalar or one value per image.')
+    budgets = numpy.broadcast_to(numpy.asarray(budgets, dtype=numpy.int64), (nb_images,))
+    rate_point = numpy.full(nb_images, nb_points - 1, dtype=numpy.int64)
+    promised = numpy.zeros(nb_images, dtype=bool)
+    for i in range(nb_images):
+        candidates = numpy.flatnonzero(valid[i])
+        if candidates.size == 0:
+            continue
+        fitting = candidates[upper[i, candidates] <= budgets[i]]
+        promised[i] = fitting.size != 0
+        rate_point[i] = fitting[0] if fitting.size else candidates[-1]
+    return rate_point, promised

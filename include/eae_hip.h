@@ -359,6 +359,41 @@ int eae_hip_ladder_histograms(const float* y, const float* map_mean, const float
                               uint32_t* hist, uint64_t* bypass_bits, uint32_t* range_errors, int n, int hw, void* stream);
 int eae_hip_ladder_max_points(int length);
 
+/* ---- a rate point per image, on the device (csrc/hip/budget.hip; ratecontrol.py) ------------------------
+ * eae_hip_ladder_select: the point of every image of a batch for its byte budget, from what eae_hip_ladder_histograms left. Integer
+ * arithmetic only; equal, element for element, to ratecontrol.upper_bounds_fixed + valid_points + select_by_upper_bound.
+ *   hist uint32 [N][K][128][L + 1], bypass_bits uint64 [N][K][128]           as eae_hip_ladder_histograms leaves them
+ *   fixed_costs uint32 [K][128][L][2]   ratecontrol.fixed_costs: ceil(-log2(p) 2^20), ceil(-log2(1 - p) 2^20)
+ *   log2_tables uint32 [2][map_size + 1]  ratecontrol.log2_tables: ceil / floor of log2(n) 2^20; NULL without an exception map
+ *   idx_map_exception: the map costed with the row of its own counts (negative: none); header_bytes: ratecontrol.header_bytes;
+ *   map_size: symbols per map (point k of image i is VALID when its histograms hold all 128 * map_size of them);
+ *   budgets int64 [N], in device memory; exception_row_base: the coder's table row of image 0's exception map.
+ * Per (image, point, map): fp = sum_i zeros[i] c0[i] + ones[i] c1[i] in 64 bits (exception map: t Lceil[t] - z Lfloor[z] -
+ * o Lfloor[o], o C99 / z C99 when z / o is 0, 0 when t is 0; counts beyond map_size are clamped as table indices);
+ * bytes = (((fp + 2^20 - 1) >> 20) + 3 + 7) / 8 + (bypass + 7) / 8. Every element of every output is written by every call:
+ *   upper int64 [N][K]     header_bytes + the bytes of the 128 maps
+ *   point int32 [N]        the first valid point with upper <= budget; else the last valid point; else K - 1
+ *   flags uint32 [N]       bit 0: promised (a valid point fitted); bit 1: no valid point
+ *   prob_row int32 [N][128]  point * 128 + m; exception_row_base + i for the exception map
+ * L 1..255, k_points 1..eae_hip_ladder_max_points(L), map_size 1..2^24 (beyond: EAE_HIP_BAD_SHAPE). A NULL among the required
+ * pointers, idx_map_exception >= 128 or >= 0 without log2_tables, a negative header_bytes / exception_row_base, n <= 0, 64-bit
+ * arrays or fixed_costs not 8-byte aligned -> EAE_HIP_BAD_ARGUMENT, before any launch. One launch, one block per image.
+ *
+ * eae_hip_latent_quantize_rows: the quantiser half of eae_hip_latent_stage (no gdn_3: y [N][hw][128] are the latents the quantiser
+ * sees) with one row of bin widths per image: image i takes bin_widths_points[clamp(point[i], 0, K - 1)] (float32 [K][128]; point
+ * int32 [N] in device memory, e.g. eae_hip_ladder_select's). Outputs as eae_hip_latent_stage: planar int16 symbols, dead-map
+ * flags, the three checks (summed over the images; flags and checks are set / added to: the caller zeroes them), shifted_out
+ * (nullable) and, with gamma_out_packed / beta_out, t_out = inverse_gdn_4(shifted). Image i's results are bit for bit
+ * eae_hip_latent_stage's on y[i] with that row, whichever images share a 32-position tile with it. hw <= 2^21 (beyond:
+ * EAE_HIP_BAD_SHAPE); NULL y / bin_widths_points / point, k_points < 1, gamma without beta or without t_out, n or hw <= 0,
+ * float arrays not 16-byte aligned -> EAE_HIP_BAD_ARGUMENT. One launch. */
+int eae_hip_ladder_select(const uint32_t* hist, const uint64_t* bypass_bits, const uint32_t* fixed_costs, const uint32_t* log2_tables,
+                          int k_points, int length, int idx_map_exception, int64_t header_bytes, int map_size, const int64_t* budgets,
+                          int exception_row_base, int32_t* point, int32_t* prob_row, int64_t* upper, uint32_t* flags, int n, void* stream);
+int eae_hip_latent_quantize_rows(const float* y, const float* map_mean, const float* bin_widths_points, const int32_t* point, int k_points,
+                                 const float* gamma_out_packed, const float* beta_out, float* shifted_out, float* t_out,
+                                 int16_t* symbols_planar, uint32_t* nonzero_flags, uint32_t* checks, int n, int hw, void* stream);
+
 /* ---- lossless coder on the device: one feature map per lane --------------------------------------------------------
  * Replaces the per-map compress_lossless loop of lossless/compression.py:76-81 (and, underneath it,
  * lossless/c++/source/compression.cpp:3-65) for a whole batch of images whose symbols are already in HBM
