@@ -57,4 +57,31 @@ constexpr int SPLIT_ERROR_WORD = 255;
 // Returns EAE_HIP_OK, or 1 when the device does not suit the kernel (nothing launched).
 int launch_split(ConvGemmParams& p, hipStream_t stream, int cut);
 
+// What the last launch() / launch_split() of this thread launched (test build only: eae_hip_debug_last_gemm_plan, include/eae_hip.h).
+// Host bookkeeping beside the hipLaunchKernelGGL it describes -- written from the very values that launch used, not derived again --
+// and nothing in the product build: EAE_RECORD_GEMM_PLAN expands to nothing there.
+#ifdef EAE_TEST_HOOKS
+constexpr int PLAN_LDS = 1, PLAN_WAVE = 2, PLAN_SPLIT = 3;
+struct GemmPlan {
+    int family;          // 0 = nothing launched on this thread yet, PLAN_*
+    int waves;           // waves per block
+    int nt;              // 32-channel output tiles per wave: 4 = all 128 channels (fused epilogue), 2 / 1 = channel parts
+    int packed;          // 1 = four-wave blocks holding the channel parts of nt position tiles
+    int cut;             // 1 = the last tiles of each XCD's share are cut in two
+    int k;               // resident waves per SIMD the cut was sized for; 0 when nothing is cut
+    int grid, block;     // blocks, threads per block
+    int norm_pass;       // 1 = the normalisation follows as a pass of its own over the output
+    int latent_fused;    // -1 = not eae_hip_conv5x5s2_latent, 1 = the latent stage is this launch's epilogue, 0 = it follows as its own launch
+    int items;           // tiles x phases as the launcher counted them, in the launched kernel's own tile shape (wave kernel: 8 x 4
+                         // positions per wave, split kernel: 4 x 8, LDS form: its 64- or 128-position blocks)
+};
+constexpr int PLAN_FIELDS = sizeof(GemmPlan) / sizeof(int);
+extern thread_local GemmPlan g_last_gemm_plan;
+#define EAE_RECORD_GEMM_PLAN(...) (::eae_conv_gemm::g_last_gemm_plan = ::eae_conv_gemm::GemmPlan{__VA_ARGS__})
+#define EAE_RECORD_LATENT_FOLLOWS() (::eae_conv_gemm::g_last_gemm_plan.latent_fused = 0)
+#else
+#define EAE_RECORD_GEMM_PLAN(...) ((void)0)
+#define EAE_RECORD_LATENT_FOLLOWS() ((void)0)
+#endif
+
 }  // namespace eae_conv_gemm

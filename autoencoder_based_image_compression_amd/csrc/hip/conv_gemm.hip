@@ -457,6 +457,7 @@ int launch(ConvGemmParams& p, hipStream_t stream) {
         p.tiles_r = (p.hp + TILE_H - 1) / TILE_H;
         p.tiles_c = (p.wp + tile_w - 1) / tile_w;
         const int grid = p.n * p.tiles_r * p.tiles_c * p.n_phases;
+        EAE_RECORD_GEMM_PLAN(PLAN_LDS, 4, 4, 0, 0, 0, grid, 256, 0, -1, grid);
         if (big) hipLaunchKernelGGL(conv_gemm_kernel<128>, dim3(grid), dim3(256), 0, stream, p);
         else hipLaunchKernelGGL(conv_gemm_kernel<64>, dim3(grid), dim3(256), 0, stream, p);
         EAE_HIP_CHECK_LAUNCH();
@@ -509,10 +510,12 @@ int launch(ConvGemmParams& p, hipStream_t stream) {
         if (force_pack != 0 && p.wp % pack_w == 0 && (packed_tiles * p.n_phases >= eae_compute_units() || force_pack == 1)) {
             p.tiles_c = p.wp / pack_w;
             grid = ((packed_tiles + 7) / 8) * 8 * p.n_phases;
+            EAE_RECORD_GEMM_PLAN(PLAN_WAVE, 4, nt, 1, 0, 0, grid, 256, p.norm != EAE_NORM_NONE, -1, tiles * p.n_phases);
             if (nt == 2) hipLaunchKernelGGL((conv_gemm_wave_kernel<4, EAE_NORM_NONE, 2, true>), dim3(grid), dim3(256), 0, stream, p);
             else hipLaunchKernelGGL((conv_gemm_wave_kernel<4, EAE_NORM_NONE, 1, true>), dim3(grid), dim3(256), 0, stream, p);
         } else {
             grid *= 4 / nt;
+            EAE_RECORD_GEMM_PLAN(PLAN_WAVE, 1, nt, 0, 0, 0, grid, 64, p.norm != EAE_NORM_NONE, -1, tiles * p.n_phases);
             if (nt == 2) hipLaunchKernelGGL((conv_gemm_wave_kernel<1, EAE_NORM_NONE, 2>), dim3(grid), dim3(64), 0, stream, p);
             else hipLaunchKernelGGL((conv_gemm_wave_kernel<1, EAE_NORM_NONE, 1>), dim3(grid), dim3(64), 0, stream, p);
         }
@@ -526,6 +529,7 @@ int launch(ConvGemmParams& p, hipStream_t stream) {
     if (p.norm == EAE_NORM_GDN) EAE_LAUNCH_WAVE(W_, EAE_NORM_GDN);            \
     else if (p.norm == EAE_NORM_IGDN) EAE_LAUNCH_WAVE(W_, EAE_NORM_IGDN);     \
     else EAE_LAUNCH_WAVE(W_, EAE_NORM_NONE);
+    EAE_RECORD_GEMM_PLAN(PLAN_WAVE, waves == 4 ? 4 : (waves == 2 ? 2 : 1), 4, 0, 0, 0, grid, (waves == 4 ? 4 : (waves == 2 ? 2 : 1)) * 64, 0, -1, tiles * p.n_phases);
     if (waves == 4) { EAE_LAUNCH_NORM(4) } else if (waves == 2) { EAE_LAUNCH_NORM(2) } else { EAE_LAUNCH_NORM(1) }
     EAE_HIP_CHECK_LAUNCH();
     return EAE_HIP_OK;
@@ -625,6 +629,7 @@ extern "C" int eae_hip_conv5x5s2_latent(const float* x, const float* w_packed, c
     // small layer (or another kernel form forced): the two launches, the stage in place on the convolution's output
     rc = conv5x5s2(x, w_packed, bias, EAE_NORM_NONE, nullptr, nullptr, main_out, n, h, w_in, static_cast<unsigned int*>(workspace), stream);
     if (rc) return rc;
+    EAE_RECORD_LATENT_FOLLOWS();
     return eae_hip_latent_stage(main_out, gamma_in_packed, beta_in, map_mean, bin_widths, gamma_out_packed, beta_out, y_out,
                                 shifted_out, t_out, symbols_planar, nonzero_flags, checks, n, (h / 2) * (w_in / 2), stream);
 }
@@ -687,6 +692,15 @@ __global__ void pack_rows_kernel(const float* __restrict__ src, float* __restric
 extern "C" int eae_hip_debug_set_stamp_buffer(uint64_t* device_buffer) {
     g_stamp_buffer = reinterpret_cast<unsigned long long*>(device_buffer);
     return EAE_HIP_OK;
+}
+// What the last conv GEMM launch of the calling thread launched (conv_gemm.h: GemmPlan, filled in beside the launch itself).
+thread_local eae_conv_gemm::GemmPlan eae_conv_gemm::g_last_gemm_plan{};
+extern "C" int eae_hip_debug_last_gemm_plan(int32_t* out, int count) {
+    if (!out || count < 0) return EAE_HIP_BAD_ARGUMENT;
+    const int* fields = reinterpret_cast<const int*>(&eae_conv_gemm::g_last_gemm_plan);
+    const int n = count < eae_conv_gemm::PLAN_FIELDS ? count : eae_conv_gemm::PLAN_FIELDS;
+    for (int i = 0; i < n; ++i) out[i] = fields[i];
+    return n;
 }
 #endif
 

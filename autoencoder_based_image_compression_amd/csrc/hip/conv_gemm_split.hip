@@ -389,6 +389,7 @@ int eae_conv_gemm::launch_split(ConvGemmParams& p, hipStream_t stream, int cut) 
     // So four it stays; the one-wave instance is kept behind the override and in the parity tests.
     const int wpb = g_eae_launch_options.split_wpb == 1 ? 1 : 4;
     const int grid = (int)((cnt_max + d_max + wpb - 1) / wpb) * 8;
+    EAE_RECORD_GEMM_PLAN(PLAN_SPLIT, wpb, 4, 0, p.split, split ? (int)k : 0, grid, wpb * 64, 0, p.norm >= NORM_LATENT ? 1 : -1, (int)tiles);
 #define EAE_LAUNCH_S(N_)                                                                                                  \
     {                                                                                                                     \
         if (wpb == 1) hipLaunchKernelGGL((conv_gemm_split_kernel<N_, 1>), dim3(grid), dim3(64), 0, stream, p);            \

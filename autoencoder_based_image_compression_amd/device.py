@@ -235,6 +235,27 @@ def conv_workspace_collect(workspace, error_word):
     _check(_native.hip().eae_hip_conv_workspace_collect(_p(workspace), word, _stream(workspace)), 'eae_hip_conv_workspace_collect')
 
 
+GEMM_PLAN_FIELDS = ('family', 'waves', 'nt', 'packed', 'cut', 'k', 'grid', 'block', 'norm_pass', 'latent_fused', 'items')
+GEMM_PLAN_FAMILIES = {0: None, 1: 'lds', 2: 'wave', 3: 'split'}
+
+
+def last_gemm_plan():
+    """What the last conv GEMM launch of the calling thread launched, as its launcher recorded it (include/eae_hip.h:
+    eae_hip_debug_last_gemm_plan): a dict of GEMM_PLAN_FIELDS, 'family' as one of 'lds' / 'wave' / 'split' (None: no launch yet).
+    Test build only: the product library has no such entry point."""
+    import ctypes
+    lib = _native.hip()
+    if not hasattr(lib, 'eae_hip_debug_last_gemm_plan'):
+        raise HipError('eae_hip_debug_last_gemm_plan is a test hook: it lives in lib/libeae_hip_test.so only (EAE_HIP_LIB=test)')
+    words = (ctypes.c_int32*len(GEMM_PLAN_FIELDS))()
+    written = lib.eae_hip_debug_last_gemm_plan(words, len(words))
+    if written != len(words):
+        raise HipError('eae_hip_debug_last_gemm_plan wrote {0} of {1} words'.format(written, len(words)))
+    plan = dict(zip(GEMM_PLAN_FIELDS, (int(w) for w in words)))
+    plan['family'] = GEMM_PLAN_FAMILIES[plan['family']]
+    return plan
+
+
 def conv5x5s2(x, w_packed, bias, norm=NORM_NONE, gamma_packed=None, beta=None, out=None, workspace=None):
     """conv_2 / conv_3 + bias_add (+ gdn). workspace: a `conv_workspace` (the launch may cut its last tiles: same bits, no
     partly empty last round; the caller collects its error word, see `conv_workspace_collect`); None / False -> the entry

@@ -582,7 +582,7 @@ int eae_hip_publish_crops(const uint8_t* planes, int n, int H, int W, const int3
                           uint64_t dst_capacity_bytes, void* stream);
 
 /* ==== TEST HOOKS (-DEAE_TEST_HOOKS): NOT exported by the product library lib/libeae_hip.so ====================================
- * Four entry points the test-suite needs and a deployment must not have (they change what later launches do, or only
+ * Five entry points the test-suite needs and a deployment must not have (they change what later launches do, or only
  * exist to prove something about the kernels). Compiled into lib/libeae_hip_test.so only; tests/test_abi.py checks that
  * the product library exports no symbol of this section (nor any other `debug` symbol). */
 #ifdef EAE_TEST_HOOKS
@@ -605,6 +605,20 @@ int eae_hip_debug_set_split_mute(int on);
  * through sqrt_mid and sqrtf; mode 1: `count` pseudo-random operand pairs of the guarded range (all exponents, random and extreme
  * mantissas) through div_mid and `/`. out2_device[0] += results whose bits differ, out2_device[1] = one such operand (pair). */
 int eae_hip_debug_check_mid_forms(int mode, uint64_t first, uint64_t count, uint64_t seed, uint64_t* out2_device, void* stream);
+/* What the last conv GEMM launch of the CALLING THREAD (eae_hip_conv5x5s2 / _tconv5x5s2, their _ws forms, eae_hip_conv5x5s2_latent)
+ * launched, as the launcher wrote it down beside the launch itself -- not a second evaluation of its rules (tests/
+ * test_gpu_launch_decisions.py holds every leaf of the decision at the size that reaches it). Up to `count` of these 11 words go to
+ * `out` (host memory), in this order:
+ *   [0] kernel family: 0 = no launch on this thread yet, 1 = block-cooperative LDS, 2 = wave kernel, 3 = split kernel
+ *   [1] waves per block            [2] 32-channel tiles per wave (nt): 4 = whole position tiles with the fused epilogue, 2 / 1 = half
+ *   / quarter tiles                [3] 1 = packed (four-wave blocks of channel parts)      [4] 1 = the last tiles are cut
+ *   [5] resident waves per SIMD the cut was sized for (k), 0 when nothing is cut           [6] grid (blocks)   [7] threads per block
+ *   [8] 1 = the normalisation follows as a pass of its own
+ *   [9] eae_hip_conv5x5s2_latent: 1 = the latent stage ran as this launch's epilogue, 0 = as a launch of its own behind the
+ *       convolution; -1 for every other entry point
+ *   [10] tiles x phases as the launcher counted them, in the launched kernel's tile shape.
+ * Returns the number of words written, or EAE_HIP_BAD_ARGUMENT (out NULL, count < 0). */
+int eae_hip_debug_last_gemm_plan(int32_t* out, int count);
 #endif /* EAE_TEST_HOOKS */
 
 /* tls.cast_bt601 (tools.py:61-93) on its own: u8 = uint8(round_half_even(clip(x, 16, 235))). */

@@ -68,7 +68,7 @@ def test_the_product_library_exports_the_product_and_nothing_else():
     experimental = declared('eae_hip.h', 'EAE_EXPERIMENTAL_CODER')
     hooks = declared('eae_hip.h', 'EAE_TEST_HOOKS')
     assert sorted(_native_hip.EXPERIMENTAL_CODER_SYMBOLS) == experimental and len(experimental) == 3
-    assert sorted(_native_hip.TEST_HOOK_SYMBOLS) == hooks and len(hooks) == 4
+    assert sorted(_native_hip.TEST_HOOK_SYMBOLS) == hooks and len(hooks) == 5
     assert all('debug' in name for name in hooks) and not any('debug' in name for name in product + experimental)
     assert exported('libeae_hip.so') == product
     assert not any('debug' in name or 'trailing' in name or 'fused' in name for name in exported('libeae_hip.so'))
