@@ -611,6 +611,21 @@ def coding_tile_layout(batch_size, h, w, coding_tile, idx_map_exception=-1):
             'payload_order': payload_order, 'n_streams': len(entries)*nb_maps}
 
 
+def _class_batches(runs, results, tile_major, rows, offsets, length, device):
+    """The coder's batches of a step in tiles, one per shape class of `runs` (`coding_tile_layout`'s or `region_layout`'s): a
+    `device.CoderStreams` whose results are that class's columns of the ONE block `results`, and that class's run of the tile-major
+    buffer, of the probability `rows` and of the `offsets`. The classes run one after the other on the step's stream, so one
+    workspace of the largest class serves them all. -> ([(streams, tiles, rows, offsets)], bytes of that workspace)."""
+    (classes, need) = ([], 0)
+    for ((tile_rows, tile_cols), count, first_stream, first_element) in runs:
+        (n, size) = (count*csts.NB_MAPS_3, tile_rows*tile_cols)
+        streams = dev.CoderStreams(n, size, length, device, results=results[:, first_stream:first_stream + n])
+        classes.append((streams, tile_major[first_element:first_element + n*size].view(n, size), rows[first_stream:first_stream + n],
+                        offsets[first_stream:first_stream + n]))
+        need = max(need, dev.coder_workspace_bytes(n, size, length))
+    return classes, need
+
+
 class _Slot(object):
     """Everything one step in flight owns; `BatchCodec` goes round `nb_slots` of them. Made once: no launch and no submit cuts a view."""
     __slots__ = ('block', 'out', 'results', 'hist', 'overflow', 'flags', 'checks', 'sse', 'unfinished', 'pinned_out', 'pinned_sse',
@@ -661,13 +676,8 @@ class _Slot(object):
             # (one tile per map: the planar symbols ARE the tile-major buffer, and nothing is gathered)
             self.gathered = self.symbols.view(-1) if tiled['nb_tiles'] == 1 else torch.empty(tiled['elements'], dtype=torch.int16, device=device)
             self.offsets = torch.zeros((n_streams, 2), dtype=torch.int64, device=device)
-            (self.classes, need) = ([], 0)
-            for ((rows, cols), count, first_stream, first_element) in tiled['runs']:
-                (n, size) = (count*nb_maps, rows*cols)
-                streams = dev.CoderStreams(n, size, codec.truncated_unary_length, device, results=self.results[:, first_stream:first_stream + n])
-                self.classes.append((streams, self.gathered[first_element:first_element + n*size].view(n, size),
-                                     codec._tile_prob_row[first_stream:first_stream + n], self.offsets[first_stream:first_stream + n]))
-                need = max(need, dev.coder_workspace_bytes(n, size, codec.truncated_unary_length))
+            (self.classes, need) = _class_batches(tiled['runs'], self.results, self.gathered, codec._tile_prob_row, self.offsets,
+                                                  codec.truncated_unary_length, device)
             self.workspace = torch.empty(need, dtype=torch.uint8, device=device)
         # scratch that lets the conv GEMM launches cut their last tiles (device.conv_workspace): a slot's launches never overlap each other
         self.conv_ws = dev.conv_workspace(device)
@@ -1288,18 +1298,9 @@ class BatchCodec(object):
 
 # ---- the other half: containers in, reconstructions out (DESIGN.md section 14) ---------------------------------------------------
 
-def decode_head_layout(batch_size, nb_maps, truncated_unary_length, n_streams=None):
-    """The "step head" of `BatchDecoder`: everything of a step's blobs but their payload, in one fixed-size block that crosses to the
-    device with one copy. -> (fields {name: (byte offset, dtype, shape)}, bytes of the block, a multiple of 16):
-    'bits' uint32 [n_maps][2] (arithmetic-coded stream, bypass stream), 'prob_row' int32 [n_maps] (row of 'table' a map is coded
-    with, -1: not coded), 'bin_widths' and 'map_mean' float32 [batch][nb_maps], 'table' float64 [batch][nb_maps + 1][L] (every
-    image's own probabilities, then the row of its exception map), 'payload_bytes' uint64 [1].
-    n_streams: pairs of streams per step, None = batch_size*nb_maps, one per map. A decoder of coding tiles has one per (image, tile,
-    map), `coding_tile_layout(...)['n_streams']`: 'bits' and 'prob_row' then hold that many entries, in RUN order."""
-    n_maps = batch_size*nb_maps if n_streams is None else int(n_streams)
-    shapes = (('bits', numpy.uint32, (n_maps, 2)), ('prob_row', numpy.int32, (n_maps,)), ('bin_widths', numpy.float32, (batch_size, nb_maps)),
-              ('map_mean', numpy.float32, (batch_size, nb_maps)), ('table', numpy.float64, (batch_size, nb_maps + 1, truncated_unary_length)),
-              ('payload_bytes', numpy.uint64, (1,)))
+def _pack_head(shapes):
+    """[(name, dtype, shape)] of a step head -> (fields {name: (byte offset, dtype, shape)}, bytes of the block): the fields one
+    behind the other, each on an 8-byte boundary, the block rounded up to 16 bytes."""
     (fields, pos) = ({}, 0)
     for (name, dtype, shape) in shapes:
         pos = -(-pos//8)*8
@@ -1308,12 +1309,34 @@ def decode_head_layout(batch_size, nb_maps, truncated_unary_length, n_streams=No
     return fields, -(-pos//16)*16
 
 
-def decode_head_views(head, batch_size, nb_maps, truncated_unary_length, n_streams=None):
-    """The fields of `decode_head_layout` as numpy views of `head` (uint8, contiguous, at least the block's bytes, 8-byte aligned)."""
-    (fields, nbytes) = decode_head_layout(batch_size, nb_maps, truncated_unary_length, n_streams)
+def _head_views(head, fields, nbytes):
+    """The `fields` of `_pack_head` as numpy views of `head` (uint8, contiguous, at least `nbytes`, 8-byte aligned)."""
     if head.dtype != numpy.uint8 or head.ndim != 1 or head.size < nbytes:
         raise ValueError('`head` must be a flat uint8 array of at least {0} bytes.'.format(nbytes))
     return {name: head[pos:pos + dtype.itemsize*int(numpy.prod(shape))].view(dtype).reshape(shape) for (name, (pos, dtype, shape)) in fields.items()}
+
+
+def _decode_head_fields(batch_size, nb_maps, truncated_unary_length, n_streams=None):
+    n_maps = batch_size*nb_maps if n_streams is None else int(n_streams)
+    return (('bits', numpy.uint32, (n_maps, 2)), ('prob_row', numpy.int32, (n_maps,)), ('bin_widths', numpy.float32, (batch_size, nb_maps)),
+            ('map_mean', numpy.float32, (batch_size, nb_maps)), ('table', numpy.float64, (batch_size, nb_maps + 1, truncated_unary_length)),
+            ('payload_bytes', numpy.uint64, (1,)))
+
+
+def decode_head_layout(batch_size, nb_maps, truncated_unary_length, n_streams=None):
+    """The "step head" of `BatchDecoder`: everything of a step's blobs but their payload, in one fixed-size block that crosses to the
+    device with one copy. -> (fields {name: (byte offset, dtype, shape)}, bytes of the block, a multiple of 16):
+    'bits' uint32 [n_maps][2] (arithmetic-coded stream, bypass stream), 'prob_row' int32 [n_maps] (row of 'table' a map is coded
+    with, -1: not coded), 'bin_widths' and 'map_mean' float32 [batch][nb_maps], 'table' float64 [batch][nb_maps + 1][L] (every
+    image's own probabilities, then the row of its exception map), 'payload_bytes' uint64 [1].
+    n_streams: pairs of streams per step, None = batch_size*nb_maps, one per map. A decoder of coding tiles has one per (image, tile,
+    map), `coding_tile_layout(...)['n_streams']`: 'bits' and 'prob_row' then hold that many entries, in RUN order."""
+    return _pack_head(_decode_head_fields(batch_size, nb_maps, truncated_unary_length, n_streams))
+
+
+def decode_head_views(head, batch_size, nb_maps, truncated_unary_length, n_streams=None):
+    """The fields of `decode_head_layout` as numpy views of `head` (uint8, contiguous, at least the block's bytes, 8-byte aligned)."""
+    return _head_views(head, *decode_head_layout(batch_size, nb_maps, truncated_unary_length, n_streams))
 
 
 def plan_decode_step(blobs, batch_size, h_in, w_in, truncated_unary_length, are_bin_widths_learned, capacity, head, payload,
@@ -1428,6 +1451,22 @@ def plan_decode_step(blobs, batch_size, h_in, w_in, truncated_unary_length, are_
 DECODER_STREAMS = 4
 
 
+def _refuse_shape(batch_size, h_in, w_in, truncated_unary_length, coding_tile):
+    """What every resident decoder refuses of its shape (ValueError) -> `coding_tile` as a pair of positive ints, or None."""
+    if h_in % csts.STRIDE_PROD != 0 or w_in % csts.STRIDE_PROD != 0 or h_in < 1 or w_in < 1:
+        raise ValueError('The image size is not divisible by the product of the three strides.')
+    if not 1 <= int(truncated_unary_length) <= 255:
+        raise ValueError('The truncated unary length does not belong to [1, 255].')
+    if batch_size < 1:
+        raise ValueError('`batch_size` is not positive.')
+    if coding_tile is None:
+        return None
+    coding_tile = container_format._positive_pair(coding_tile, '`coding_tile`')
+    if max(coding_tile) > 0xFFFF:
+        raise ValueError('A side of `coding_tile` does not fit the container (65535 latents at most).')
+    return coding_tile
+
+
 def _decoder_device(device):
     """The device of a resident decoder: the current one, by name or by default (launches go to the current device's streams)."""
     device = torch.device(device)
@@ -1453,7 +1492,7 @@ def _decoder_streams(nb_streams, name):
             import warnings
             warnings.warn('{2}: {0} streams asked for, running {1}: this process has too few hardware queues '
                           '(GPU_MAX_HW_QUEUES; streams beyond them share queues and serialise).'.format(nb_streams, capped, name),
-                          RuntimeWarning, stacklevel=3)
+                          RuntimeWarning, stacklevel=4)          # whoever called the constructor, behind `_build` and `__init__`
         nb_streams = capped
     return nb_streams
 
@@ -1484,21 +1523,36 @@ class DecodeTicket(object):
 class _DecodeJob(_Claimable):
     __slots__ = ('ticket', 'slot', 'sequence', 'payload_bytes', 'detail')
 
-    def __init__(self, ticket, slot, sequence, payload_bytes, detail=None):
-        """detail: what else the worker needs of the step's plan (`RegionDecoder`: where every crop's streams lie)."""
+    def __init__(self, ticket, slot, sequence, payload_bytes, detail):
+        """detail: per image (or crop) of the step, the column ranges [(first, end)] of the slot's results that hold its streams, in
+        the order in which its first failing stream is looked for."""
         super(_DecodeJob, self).__init__()
         (self.ticket, self.slot, self.sequence, self.payload_bytes, self.detail) = (ticket, slot, sequence, payload_bytes, detail)
 
 
-class _DecodeWorker(_StepWorker):
-    """The result worker of `BatchDecoder`."""
+def _first_failure(results, ranges):
+    """What `interface_cython.raise_for_status` raises for the first failing stream among the column `ranges` [(first, end)] of the
+    coder's `results` (rows 2 and 3: status and stage), taken in order; None when every stream of them is fine."""
+    for (first, end) in ranges:
+        status = results[2, first:end]
+        if status.any():
+            from .kodak.lossless import interface_cython
+            bad = first + int(numpy.flatnonzero(status)[0])
+            try:
+                interface_cython.raise_for_status(int(results[2, bad]), int(results[3, bad]))
+            except Exception as exc:
+                return exc
+            return None
+    return None
 
-    def __init__(self, streams_per_image, payload_order=None):
-        """streams_per_image: pairs of streams of one image: its maps, times its tiles with a coding tile. payload_order: of a decoder
-        of coding tiles (`coding_tile_layout`): the slot's results are in run order, and this index array takes them into the order
-        of the payload, image -> tile -> map."""
+
+class _DecodeWorker(_StepWorker):
+    """The result worker of `BatchDecoder` and `RegionDecoder`."""
+
+    def __init__(self, payload_order=None):
+        """payload_order: of a `BatchDecoder` of coding tiles (`coding_tile_layout`): the slot's results are in run order, and this
+        index array takes them into the order of the payload, image -> tile -> map, which the ranges of a job then refer to."""
         super(_DecodeWorker, self).__init__()
-        self.streams_per_image = streams_per_image
         self.payload_order = payload_order
 
     def process(self, job, by_caller=False):
@@ -1532,87 +1586,79 @@ class _DecodeWorker(_StepWorker):
     def _form(self, job):
         """The ticket's errors and value from the slot's pinned blocks, once the step is through and its byte count agrees."""
         (ticket, slot) = (job.ticket, job.slot)
-        from .kodak.lossless import interface_cython
-        errors = []
-        (results, per_image) = (slot.results_host, self.streams_per_image)
+        results = slot.results_host
         if self.payload_order is not None:
             # status and stage of every stream in payload order: an image's first failing stream is the first of its first
             # failing tile, as `container.decode_images` meets them in the image's own blob
             results = results.take(self.payload_order, axis=1)
-        for i in range(ticket.nb_images):
-            status = results[2, i*per_image:(i + 1)*per_image]
-            error = None
-            if status.any():
-                bad = i*per_image + int(numpy.flatnonzero(status)[0])
-                try:
-                    interface_cython.raise_for_status(int(results[2, bad]), int(results[3, bad]))
-                except Exception as exc:
-                    error = exc
-            errors.append(error)
-        ticket.errors = errors
-        ticket._value = slot.rec_host[:ticket.nb_images] if slot.rec_host is not None else slot.planes[:ticket.nb_images]
+        ticket.errors = [_first_failure(results, ranges) for ranges in job.detail]
+        ticket._value = slot.value(ticket.nb_images)
 
 
 class _DecodeLane(object):
-    """The device side of one slot: the stream its steps run on and every device buffer between a step's first and last launch
-    (the largest are the activations of the synthesis transform, 17 MB per Kodak image). No two steps in flight share a buffer."""
+    """The device side of one slot of a resident decoder: the stream its steps run on and every device buffer between a step's
+    first and last launch (the largest are the activations of the synthesis transform, 17 MB per Kodak image). No two steps in flight
+    share a buffer. What differs between the decoders it reads off `decoder` (`BatchDecoder._lay_out`): the head's fields, the
+    streams of a step, the class runs of a step in tiles, the latent window that is synthesised, the images the index counts."""
 
     def __init__(self, decoder, stream):
         (batch_size, nb_maps, device, length) = (decoder.batch_size, decoder.nb_maps, decoder.device, decoder.truncated_unary_length)
-        n_maps = decoder._n_streams      # pairs of streams per step: batch_size*nb_maps, times the tiles of a map with a coding tile
+        # pairs of streams per step: batch_size*nb_maps, times the tiles of a map with a coding tile; `RegionDecoder`: the slots' maps
+        n_maps = decoder._n_streams
+        (rows, cols) = decoder.window
         self.stream = stream
-        (fields, head_bytes) = decode_head_layout(batch_size, nb_maps, length, n_maps)
+        (fields, head_bytes) = _pack_head(decoder._head_fields)
         self.head = torch.zeros(head_bytes, dtype=torch.uint8, device=device)
 
         def field(name, dtype):
+            """The torch twin of `_head_views`; None for a field this decoder's head does not have."""
+            if name not in fields:
+                return None
             (pos, numpy_dtype, shape) = fields[name]
             return self.head[pos:pos + numpy_dtype.itemsize*int(numpy.prod(shape))].view(dtype).view(shape)
 
         self.head_bits = field('bits', torch.int32)
         self.prob_row = field('prob_row', torch.int32)
+        (self.placement, self.crop_origin) = (field('placement', torch.int32), field('crop_origin', torch.int32))      # `RegionDecoder`
         self.bin_widths = field('bin_widths', torch.float32)
         self.map_mean = field('map_mean', torch.float32)
         self.table = field('table', torch.float64).view(batch_size*(nb_maps + 1), length)
         self.payload_bytes = field('payload_bytes', torch.int64)
         self.head_bytes = torch.full((1,), head_bytes, dtype=torch.int64, device=device)
         self.payload = torch.zeros(decoder.payload_capacity_bytes, dtype=torch.uint8, device=device)
-        # what goes to the host behind a step: [coder results 4 x n_maps | index words (int64: payload bytes, overflow flag, bytes per image)]
-        self.status = torch.zeros(4*n_maps + 2*(2 + batch_size), dtype=torch.int32, device=device)
+        # what goes to the host behind a step: [coder results 4 x n_maps | index words (int64: payload bytes, overflow flag, bytes per
+        # image of the index -- `RegionDecoder`'s slots are the entries of ONE image, so the bytes again)]
+        self.status = torch.zeros(4*n_maps + 2*(2 + decoder._index_images), dtype=torch.int32, device=device)
         self.results = self.status[:4*n_maps].view(4, n_maps)
         self.index = self.status[4*n_maps:].view(torch.int64)
         self.offsets = torch.zeros((n_maps, 2), dtype=torch.int64, device=device)
-        if decoder.coding_tile is None:
-            self.coder_streams = dev.CoderStreams(n_maps, decoder.map_size, length, device, results=self.results)
-            self.workspace = dev.coder_workspace(n_maps, decoder.map_size, length, device)
-            self.symbols = torch.zeros((batch_size, nb_maps, decoder.map_size), dtype=torch.int16, device=device)
+        (self.coder_streams, self.symbols, self.decoded, self.classes) = (None, None, None, None)
+        if decoder._runs is None:
+            self.coder_streams = dev.CoderStreams(n_maps, rows*cols, length, device, results=self.results)
+            self.workspace = dev.coder_workspace(n_maps, rows*cols, length, device)
+            self.symbols = torch.zeros((batch_size, nb_maps, rows*cols), dtype=torch.int16, device=device)
         else:
-            # The buffers of `BatchCodec`'s slot (`_Slot`), read the other way: the step's (image, tile) entries in run order, per
-            # shape class one batch of streams on that class's columns of the ONE results block, decoded into that class's run of
-            # the tile-major buffer; the classes run one after the other, so one workspace of the largest class serves them all.
-            tiled = decoder._tile_layout
-            self.decoded = torch.zeros(tiled['elements'], dtype=torch.int16, device=device)
-            (self.classes, need) = ([], 0)
-            for ((rows, cols), count, first_stream, first_element) in tiled['runs']:
-                (n, size) = (count*nb_maps, rows*cols)
-                streams = dev.CoderStreams(n, size, length, device, results=self.results[:, first_stream:first_stream + n])
-                self.classes.append((streams, self.decoded[first_element:first_element + n*size].view(n, size),
-                                     self.prob_row[first_stream:first_stream + n], self.offsets[first_stream:first_stream + n]))
-                need = max(need, dev.coder_workspace_bytes(n, size, length))
+            # The buffers of `BatchCodec`'s slot (`_Slot`), read the other way: the step's entries in run order, every shape class
+            # decoded into its run of the tile-major buffer (`_class_batches`).
+            self.decoded = torch.zeros(decoder._elements, dtype=torch.int16, device=device)
+            (self.classes, need) = _class_batches(decoder._runs, self.results, self.decoded, self.prob_row, self.offsets, length, device)
             self.workspace = torch.empty(need, dtype=torch.uint8, device=device)
-        self.shifted = torch.zeros((batch_size, decoder.h_in//csts.STRIDE_PROD, decoder.w_in//csts.STRIDE_PROD, nb_maps), dtype=torch.float32,
-                                   device=device)
-        (self.scratch, self.unfinished) = decoder.decoder.model.decode_scratch(batch_size, decoder.h_in//csts.STRIDE_PROD,
-                                                                               decoder.w_in//csts.STRIDE_PROD)
+        # a plane per image, or a window per crop
+        self.shifted = torch.zeros((batch_size, rows, cols, nb_maps), dtype=torch.float32, device=device)
+        (self.scratch, self.unfinished) = decoder.decoder.model.decode_scratch(batch_size, rows, cols)
 
 
 class _DecodeSlot(object):
-    """What one step in flight owns: its device buffers (`lane`), the pinned buffers the host fills and reads, the planes, the step
-    counter, the captured graph. Made once."""
+    """What one step in flight of a resident decoder owns: its device buffers (`lane`), the pinned buffers the host fills and reads,
+    the planes (of the images, or of the crops' windows), for a `RegionDecoder` the crops, the step counter, the captured graph.
+    Made once."""
 
     def __init__(self, decoder, lane):
-        (batch_size, nb_maps, device) = (decoder.batch_size, decoder.nb_maps, decoder.device)
+        (batch_size, device, fetch) = (decoder.batch_size, decoder.device, decoder.fetch_reconstruction)
         n_maps = decoder._n_streams
+        (rows, cols) = decoder.window
         self.lane = lane
+        self.region = decoder.region
         self.pinned_head = torch.zeros(lane.head.numel(), dtype=torch.uint8).pin_memory()
         self.pinned_payload = torch.zeros(decoder.payload_capacity_bytes, dtype=torch.uint8).pin_memory()
         (self.head_host, self.payload_host) = (self.pinned_head.numpy(), self.pinned_payload.numpy())
@@ -1621,9 +1667,20 @@ class _DecodeSlot(object):
         self.index_host = self.pinned_status[4*n_maps:].view(torch.int64).numpy()
         self.pinned_unfinished = torch.zeros(1, dtype=torch.int32).pin_memory()
         self.unfinished_host = self.pinned_unfinished.numpy()
-        self.planes = torch.zeros((batch_size, decoder.h_in, decoder.w_in), dtype=torch.uint8, device=device)
-        self.pinned_rec = torch.zeros((batch_size, decoder.h_in, decoder.w_in), dtype=torch.uint8).pin_memory() if decoder.fetch_reconstruction else None
+        self.planes = torch.zeros((batch_size, 16*rows, 16*cols), dtype=torch.uint8, device=device)
+        # what a ticket returns: the planes, fetched or not; of a `RegionDecoder` the crops, cut into pinned memory or on the device
+        (self.pinned_rec, self.crops, self.pinned_crops) = (None, None, None)
+        if self.region is None:
+            if fetch:
+                self.pinned_rec = torch.zeros((batch_size, 16*rows, 16*cols), dtype=torch.uint8).pin_memory()
+        else:
+            crop_bytes = -(-batch_size*self.region[0]*self.region[1]//16)*16          # whole 16-byte words: `device.publish_crops`
+            if fetch:
+                self.pinned_crops = torch.zeros(crop_bytes, dtype=torch.uint8).pin_memory()
+            else:
+                self.crops = torch.zeros(crop_bytes, dtype=torch.uint8, device=device)
         self.rec_host = self.pinned_rec.numpy() if self.pinned_rec is not None else None
+        self.crops_host = self.pinned_crops.numpy() if self.pinned_crops is not None else None
         self.seq_dev = torch.zeros(2, dtype=torch.int32, device=device)      # [step counter, ticket word of device.publish_step]
         self.pinned_seq = torch.zeros(1, dtype=torch.int32).pin_memory()
         self.seq_host = self.pinned_seq.numpy()
@@ -1631,6 +1688,13 @@ class _DecodeSlot(object):
         self.free = threading.Event()
         self.free.set()
         self.graph = None
+
+    def value(self, n):
+        """What the ticket of a step of n images (crops) returns."""
+        if self.region is None:
+            return self.rec_host[:n] if self.rec_host is not None else self.planes[:n]
+        (rh, rw) = self.region
+        return (self.crops_host if self.crops_host is not None else self.crops)[:n*rh*rw].reshape(n, rh, rw)
 
 
 class BatchDecoder(object):
@@ -1654,61 +1718,78 @@ class BatchDecoder(object):
         and nothing else: an `EAE1` blob or another tile is refused by `submit` (ValueError). Every (image, tile, map) is a pair of
         streams of its own, so the decoder core's serial chains are a tile long instead of a map. At most 65,535 (image, tile) pairs
         per step. None: `EAE1` blobs only."""
-        if h_in % csts.STRIDE_PROD != 0 or w_in % csts.STRIDE_PROD != 0 or h_in < 1 or w_in < 1:
-            raise ValueError('The image size is not divisible by the product of the three strides.')
-        if not 1 <= int(truncated_unary_length) <= 255:
-            raise ValueError('The truncated unary length does not belong to [1, 255].')
-        if batch_size < 1:
-            raise ValueError('`batch_size` is not positive.')
-        self.coding_tile = None
+        self._lay_out(batch_size, h_in, w_in, truncated_unary_length, payload_capacity_bytes, coding_tile)
+        self._build(variables, are_bin_widths_learned, device, nb_in_flight, nb_streams, use_graphs, fetch_reconstruction)
+
+    def _lay_out(self, batch_size, h_in, w_in, truncated_unary_length, payload_capacity_bytes, coding_tile):
+        """The first half of construction: refuses what no decoder can be built for, then lays a step out -- everything `_build`,
+        `_DecodeLane` and `_DecodeSlot` size their buffers by. numpy only: nothing is allocated, so every refusal lies in front of
+        every allocation."""
+        coding_tile = _refuse_shape(batch_size, h_in, w_in, truncated_unary_length, coding_tile)
+        (h_map, w_map) = (h_in//csts.STRIDE_PROD, w_in//csts.STRIDE_PROD)
+        # whole images: no crops, and the latents that are synthesised are the plane
+        (self.coding_tile, self.region, self.window, self.map_size) = (None, None, (h_map, w_map), h_map*w_map)
+        # pairs of streams of a step, one per map; in tiles the class runs [((rows, cols), entries, first stream, first element)] too
+        (self._n_streams, self._runs, self._elements) = (int(batch_size)*csts.NB_MAPS_3, None, None)
+        self._tile_layout = None
         if coding_tile is not None:
-            # refused in front of every allocation
-            coding_tile = container_format._positive_pair(coding_tile, '`coding_tile`')
-            if max(coding_tile) > 0xFFFF:
-                raise ValueError('A side of `coding_tile` does not fit the container (65535 latents at most).')
-            (h_map, w_map) = (h_in//csts.STRIDE_PROD, w_in//csts.STRIDE_PROD)
             self.coding_tile = (min(coding_tile[0], h_map), min(coding_tile[1], w_map))
             if int(batch_size)*container_format._nb_tiles(h_map, w_map, self.coding_tile) > 65535:
                 raise ValueError('`batch_size` images of {0} coding tiles each are more than the 65535 (image, tile) pairs a step can hold.'.format(
                     container_format._nb_tiles(h_map, w_map, self.coding_tile)))
-        self.device = _decoder_device(device)
-        self.learned = bool(are_bin_widths_learned)
-        self.decoder = pipeline.DeviceDecoder(variables, are_bin_widths_learned, self.device)
-        (self.batch_size, self.h_in, self.w_in) = (int(batch_size), int(h_in), int(w_in))
-        self.nb_maps = csts.NB_MAPS_3
-        self.map_size = (h_in//csts.STRIDE_PROD)*(w_in//csts.STRIDE_PROD)
-        self.truncated_unary_length = int(truncated_unary_length)
+            # everything a step in tiles needs beyond its blobs is the same for every step: made once, shared by the slots
+            self._tile_layout = tiled = coding_tile_layout(int(batch_size), h_map, w_map, self.coding_tile)
+            (self._n_streams, self._runs, self._elements) = (tiled['n_streams'], tiled['runs'], tiled['elements'])
+        self._payload_order = self._tile_layout['payload_order'] if self._tile_layout else None
+        self._index_images = int(batch_size)          # images whose bytes the index counts
+        self._head_fields = _decode_head_fields(int(batch_size), csts.NB_MAPS_3, int(truncated_unary_length), self._n_streams)
+        # what the worker scans for an image's first failing stream (`_DecodeJob.detail`): its streams, in payload order
+        per_image = self._n_streams//int(batch_size)
+        self._image_ranges = [[(i*per_image, (i + 1)*per_image)] for i in range(int(batch_size))]
+        self._set_sizes(batch_size, h_in, w_in, truncated_unary_length, payload_capacity_bytes, int(batch_size)*int(h_in)*int(w_in))
+
+    def _set_sizes(self, batch_size, h_in, w_in, truncated_unary_length, payload_capacity_bytes, default_capacity):
+        """The end of `_lay_out`: the last refusal, and the sizes every resident decoder has."""
         if payload_capacity_bytes is None:
-            payload_capacity_bytes = self.batch_size*self.h_in*self.w_in
+            payload_capacity_bytes = default_capacity
         if int(payload_capacity_bytes) < 1:
             raise ValueError('`payload_capacity_bytes` is not positive.')
         self.payload_capacity_bytes = -(-int(payload_capacity_bytes)//16)*16
+        (self.batch_size, self.h_in, self.w_in) = (int(batch_size), int(h_in), int(w_in))
+        self.nb_maps = csts.NB_MAPS_3
+        self.truncated_unary_length = int(truncated_unary_length)
+
+    def _build(self, variables, are_bin_widths_learned, device, nb_in_flight, nb_streams, use_graphs, fetch_reconstruction):
+        """The second half of construction, of a decoder `_lay_out` has accepted: the device, the model, the streams, the static
+        tables, the slots, the worker."""
+        self.device = _decoder_device(device)
+        self.learned = bool(are_bin_widths_learned)
+        self.decoder = pipeline.DeviceDecoder(variables, are_bin_widths_learned, self.device)
         self.fetch_reconstruction = bool(fetch_reconstruction)
         self.use_graphs = bool(use_graphs)
-        self.nb_streams = nb_streams = _decoder_streams(nb_streams, 'BatchDecoder')
+        self.nb_streams = nb_streams = _decoder_streams(nb_streams, type(self).__name__)
         self.nb_in_flight = max(1, int(nb_in_flight)) if nb_in_flight is not None else nb_streams + 2
         self.nb_slots = self.nb_in_flight
-        self._n_streams = self.batch_size*self.nb_maps
-        self._tile_layout = None
-        if self.coding_tile is not None:
-            # everything a step in tiles needs beyond its blobs is the same for every step: made once, shared by the slots
-            tiled = coding_tile_layout(self.batch_size, h_in//csts.STRIDE_PROD, w_in//csts.STRIDE_PROD, self.coding_tile)
-            self._tile_layout = tiled
-            self._n_streams = tiled['n_streams']
+        self._upload_tables()
+        streams = _step_streams(self.nb_streams, self.device)
+        self._slots = [_DecodeSlot(self, _DecodeLane(self, streams[k % self.nb_streams])) for k in range(self.nb_slots)]
+        self._index = 0
+        self._warm = False
+        self._worker = _DecodeWorker(self._payload_order)
+        self._worker.start()
+        with _LIVE_LOCK:
+            _LIVE.setdefault(self.device.index, weakref.WeakSet()).add(self)
+
+    def _upload_tables(self):
+        """What the launches of every step read beside the slot's buffers: on the device once, shared by the slots."""
+        tiled = self._tile_layout
+        if tiled is not None:
             self._tile_plan_host = tiled['plan']
             self._tile_plan = torch.from_numpy(tiled['plan']).to(self.device)
             # `device.coder_index_tiles`: per payload-order entry, its run-order index and half the stream stride of its class
             half_stride = numpy.array([dev.coder_stream_stride_bytes(int(tiled['tiles'][t, 2]*tiled['tiles'][t, 3]), self.truncated_unary_length)//2
                                        for (_, t) in tiled['entries']], dtype=numpy.int64)
             self._tile_table = torch.from_numpy(numpy.stack([tiled['run_entry'], half_stride], axis=1)).to(self.device)
-        streams = _step_streams(self.nb_streams, self.device)
-        self._slots = [_DecodeSlot(self, _DecodeLane(self, streams[k % self.nb_streams])) for k in range(self.nb_slots)]
-        self._index = 0
-        self._warm = False
-        self._worker = _DecodeWorker(self._n_streams//self.batch_size, self._tile_layout['payload_order'] if self._tile_layout else None)
-        self._worker.start()
-        with _LIVE_LOCK:
-            _LIVE.setdefault(self.device.index, weakref.WeakSet()).add(self)
 
     def submit(self, blobs):
         """One `EAE1` blob of 1..batch_size images, or a sequence of `EAE1` blobs holding that many in all -> DecodeTicket
@@ -1774,7 +1855,7 @@ class BatchDecoder(object):
         (nb_images, payload_bytes) = plan_decode_step(blobs, self.batch_size, self.h_in, self.w_in, self.truncated_unary_length, self.learned,
                                                       self.payload_capacity_bytes, slot.head_host, slot.payload_host, self.nb_maps,
                                                       self.coding_tile, self._tile_layout)
-        return nb_images, payload_bytes, None
+        return nb_images, payload_bytes, self._image_ranges[:nb_images]
 
     def _capture_all(self):
         """Every slot's step as one hipGraph, while nothing of this decoder is in flight (and the other codecs of the device are
@@ -1795,6 +1876,22 @@ class BatchDecoder(object):
         dev.fetch_prefix(slot.pinned_head, lane.head, lane.head_bytes)                      # the head: a fixed size
         dev.fetch_prefix(slot.pinned_payload, lane.payload, lane.payload_bytes)             # the payload: the bytes the head announces
         lane.results[:2].copy_(lane.head_bits.view(-1, 2).t())                              # [n_maps][2] -> the coder's two arrays
+        self._launch_latents(slot)
+        self.decoder.model.decode_into(lane.shifted, slot.planes, lane.scratch)
+        self._launch_output(slot)
+        dev.publish_to_host(lane.unfinished, slot.pinned_unfinished)
+        dev.publish_step(lane.status, slot.pinned_status, lane.status.numel(), slot.seq_dev[1:2], slot.seq_dev[0:1], slot.pinned_seq)
+
+    @staticmethod
+    def _launch_classes(lane):
+        """One unpack and one decoder batch per shape class of a step in tiles, into the tile-major buffer."""
+        for (streams, tiles, rows, offsets) in lane.classes:
+            dev.coder_unpack_into(streams, lane.payload, offsets)
+            dev.coder_decode_batch(streams, lane.table, rows, workspace=lane.workspace, out=tiles)
+
+    def _launch_latents(self, slot):
+        """The first half of a step: the fetched bit counts and payload -> the dequantised latents in `lane.shifted`."""
+        lane = slot.lane
         if self.coding_tile is None:
             streams = lane.coder_streams
             dev.coder_index_streams(streams, self.nb_maps, self.payload_capacity_bytes, offsets=lane.offsets, index=lane.index)
@@ -1807,15 +1904,13 @@ class BatchDecoder(object):
             # launch dequantises every tile of the step, with its image's rows, into the latents (every latent is in exactly one tile)
             dev.coder_index_tiles(lane.results[0], lane.results[1], self._tile_table, self.nb_maps, self._tile_layout['nb_tiles'],
                                   self.payload_capacity_bytes, offsets=lane.offsets, index=lane.index)
-            for (streams, tiles, rows, offsets) in lane.classes:
-                dev.coder_unpack_into(streams, lane.payload, offsets)
-                dev.coder_decode_batch(streams, lane.table, rows, workspace=lane.workspace, out=tiles)
+            self._launch_classes(lane)
             dev.tile_symbols_dequantize_rows(lane.decoded, self._tile_plan, self._tile_plan_host, lane.bin_widths, lane.map_mean, lane.shifted)
-        self.decoder.model.decode_into(lane.shifted, slot.planes, lane.scratch)
+
+    def _launch_output(self, slot):
+        """The second half of a step, behind the synthesis transform: what the ticket returns reaches the host (if it is to)."""
         if slot.pinned_rec is not None:
             dev.publish_to_host(slot.planes, slot.pinned_rec)
-        dev.publish_to_host(lane.unfinished, slot.pinned_unfinished)
-        dev.publish_step(lane.status, slot.pinned_status, lane.status.numel(), slot.seq_dev[1:2], slot.seq_dev[0:1], slot.pinned_seq)
 
     def drain(self):
         """Waits until every submitted step is through."""
@@ -1951,6 +2046,14 @@ def region_layout(batch_size, h, w, coding_tile, Rs, Cs):
             'slots': numpy.array(slots, dtype=numpy.int64).reshape(-1, 3)}
 
 
+def _region_head_fields(batch_size, n_slots, truncated_unary_length, nb_maps=csts.NB_MAPS_3):
+    n_streams = int(n_slots)*nb_maps
+    return (('bits', numpy.uint32, (n_streams, 2)), ('prob_row', numpy.int32, (n_streams,)), ('placement', numpy.int32, (int(n_slots), 4)),
+            ('crop_origin', numpy.int32, (batch_size, 2)), ('bin_widths', numpy.float32, (batch_size, nb_maps)),
+            ('map_mean', numpy.float32, (batch_size, nb_maps)), ('table', numpy.float64, (batch_size, nb_maps + 1, truncated_unary_length)),
+            ('payload_bytes', numpy.uint64, (1,)))
+
+
 def region_head_layout(batch_size, n_slots, truncated_unary_length, nb_maps=csts.NB_MAPS_3):
     """The step head of `RegionDecoder`, in the manner of `decode_head_layout`: one fixed-size block, one copy. -> (fields {name:
     (byte offset, dtype, shape)}, bytes of the block, a multiple of 16): 'bits' uint32 [n_streams][2] and 'prob_row' int32
@@ -1958,25 +2061,12 @@ def region_head_layout(batch_size, n_slots, truncated_unary_length, nb_maps=csts
     -1, tile origin row and col in the crop's window, 0); 'crop_origin' int32 [batch][2] (the crop in its window's reconstruction);
     'bin_widths', 'map_mean' float32 [batch][nb_maps]; 'table' float64 [batch][nb_maps + 1][L] (each crop's own source's rows,
     the exception map's last); 'payload_bytes' uint64 [1]."""
-    n_streams = int(n_slots)*nb_maps
-    shapes = (('bits', numpy.uint32, (n_streams, 2)), ('prob_row', numpy.int32, (n_streams,)), ('placement', numpy.int32, (int(n_slots), 4)),
-              ('crop_origin', numpy.int32, (batch_size, 2)), ('bin_widths', numpy.float32, (batch_size, nb_maps)),
-              ('map_mean', numpy.float32, (batch_size, nb_maps)), ('table', numpy.float64, (batch_size, nb_maps + 1, truncated_unary_length)),
-              ('payload_bytes', numpy.uint64, (1,)))
-    (fields, pos) = ({}, 0)
-    for (name, dtype, shape) in shapes:
-        pos = -(-pos//8)*8
-        fields[name] = (pos, numpy.dtype(dtype), shape)
-        pos += numpy.dtype(dtype).itemsize*int(numpy.prod(shape))
-    return fields, -(-pos//16)*16
+    return _pack_head(_region_head_fields(batch_size, n_slots, truncated_unary_length, nb_maps))
 
 
 def region_head_views(head, batch_size, n_slots, truncated_unary_length, nb_maps=csts.NB_MAPS_3):
     """The fields of `region_head_layout` as numpy views of `head` (uint8, contiguous, at least the block's bytes, 8-byte aligned)."""
-    (fields, nbytes) = region_head_layout(batch_size, n_slots, truncated_unary_length, nb_maps)
-    if head.dtype != numpy.uint8 or head.ndim != 1 or head.size < nbytes:
-        raise ValueError('`head` must be a flat uint8 array of at least {0} bytes.'.format(nbytes))
-    return {name: head[pos:pos + dtype.itemsize*int(numpy.prod(shape))].view(dtype).reshape(shape) for (name, (pos, dtype, shape)) in fields.items()}
+    return _head_views(head, *region_head_layout(batch_size, n_slots, truncated_unary_length, nb_maps))
 
 
 def place_region(layout, y0, x0):
@@ -2088,113 +2178,6 @@ def plan_region_step(requests, layout, head, payload, capacity, region, truncate
     return n, payload_bytes, crop_slots
 
 
-class _RegionWorker(_DecodeWorker):
-    """The result worker of `RegionDecoder`: a step's streams belong to its crops through the step's placement (`_DecodeJob.detail`)."""
-
-    def _form(self, job):
-        """errors[k]: what `interface_cython.raise_for_status` raises for crop k's first failing stream, its tiles in row-major
-        order as `container.decode_region` meets them, the maps of a tile in order."""
-        from .kodak.lossless import interface_cython
-        (ticket, slot, nb_maps) = (job.ticket, job.slot, self.streams_per_image)
-        results = slot.results_host
-        errors = []
-        for runs in job.detail:
-            error = None
-            for run in runs:
-                status = results[2, run*nb_maps:(run + 1)*nb_maps]
-                if status.any():
-                    bad = run*nb_maps + int(numpy.flatnonzero(status)[0])
-                    try:
-                        interface_cython.raise_for_status(int(results[2, bad]), int(results[3, bad]))
-                    except Exception as exc:
-                        error = exc
-                    break
-            errors.append(error)
-        ticket.errors = errors
-        (n, (rh, rw)) = (ticket.nb_images, slot.region)
-        ticket._value = (slot.crops_host if slot.crops_host is not None else slot.crops)[:n*rh*rw].reshape(n, rh, rw)
-
-
-class _RegionLane(object):
-    """The device side of one `RegionDecoder` slot: `_DecodeLane`'s buffers for a step of slots instead of (image, tile) entries,
-    and a window per crop instead of a plane per image."""
-
-    def __init__(self, decoder, stream):
-        (batch_size, nb_maps, device, length) = (decoder.batch_size, decoder.nb_maps, decoder.device, decoder.truncated_unary_length)
-        layout = decoder._layout
-        (n_slots, n_streams) = (layout['n_slots'], layout['n_streams'])
-        self.stream = stream
-        (fields, head_bytes) = region_head_layout(batch_size, n_slots, length, nb_maps)
-        self.head = torch.zeros(head_bytes, dtype=torch.uint8, device=device)
-
-        def field(name, dtype):
-            (pos, numpy_dtype, shape) = fields[name]
-            return self.head[pos:pos + numpy_dtype.itemsize*int(numpy.prod(shape))].view(dtype).view(shape)
-
-        self.head_bits = field('bits', torch.int32)
-        self.prob_row = field('prob_row', torch.int32)
-        self.placement = field('placement', torch.int32)
-        self.crop_origin = field('crop_origin', torch.int32)
-        self.bin_widths = field('bin_widths', torch.float32)
-        self.map_mean = field('map_mean', torch.float32)
-        self.table = field('table', torch.float64).view(batch_size*(nb_maps + 1), length)
-        self.payload_bytes = field('payload_bytes', torch.int64)
-        self.head_bytes = torch.full((1,), head_bytes, dtype=torch.int64, device=device)
-        self.payload = torch.zeros(decoder.payload_capacity_bytes, dtype=torch.uint8, device=device)
-        # what goes to the host behind a step: [coder results 4 x n_streams | index words (int64: payload bytes, overflow flag, the bytes again)]
-        self.status = torch.zeros(4*n_streams + 2*3, dtype=torch.int32, device=device)
-        self.results = self.status[:4*n_streams].view(4, n_streams)
-        self.index = self.status[4*n_streams:].view(torch.int64)
-        self.offsets = torch.zeros((n_streams, 2), dtype=torch.int64, device=device)
-        self.decoded = torch.zeros(layout['elements'], dtype=torch.int16, device=device)
-        (self.classes, need) = ([], 0)
-        for ((rows, cols), count, first_stream, first_element) in layout['runs']:
-            (n, size) = (count*nb_maps, rows*cols)
-            streams = dev.CoderStreams(n, size, length, device, results=self.results[:, first_stream:first_stream + n])
-            self.classes.append((streams, self.decoded[first_element:first_element + n*size].view(n, size),
-                                 self.prob_row[first_stream:first_stream + n], self.offsets[first_stream:first_stream + n]))
-            need = max(need, dev.coder_workspace_bytes(n, size, length))
-        self.workspace = torch.empty(need, dtype=torch.uint8, device=device)
-        (Rs, Cs) = layout['window']
-        self.shifted = torch.zeros((batch_size, Rs, Cs, nb_maps), dtype=torch.float32, device=device)
-        (self.scratch, self.unfinished) = decoder.decoder.model.decode_scratch(batch_size, Rs, Cs)
-
-
-class _RegionSlot(object):
-    """What one `RegionDecoder` step in flight owns: its lane, the pinned buffers the host fills and reads, the windows'
-    reconstructions, the crops, the step counter, the captured graph. Made once."""
-
-    def __init__(self, decoder, lane):
-        (batch_size, device) = (decoder.batch_size, decoder.device)
-        n_streams = decoder._layout['n_streams']
-        (Rs, Cs) = decoder._layout['window']
-        self.lane = lane
-        self.region = decoder.region
-        self.pinned_head = torch.zeros(lane.head.numel(), dtype=torch.uint8).pin_memory()
-        self.pinned_payload = torch.zeros(decoder.payload_capacity_bytes, dtype=torch.uint8).pin_memory()
-        (self.head_host, self.payload_host) = (self.pinned_head.numpy(), self.pinned_payload.numpy())
-        self.pinned_status = torch.zeros(lane.status.numel(), dtype=torch.int32).pin_memory()
-        self.results_host = self.pinned_status[:4*n_streams].view(4, n_streams).numpy()
-        self.index_host = self.pinned_status[4*n_streams:].view(torch.int64).numpy()
-        self.pinned_unfinished = torch.zeros(1, dtype=torch.int32).pin_memory()
-        self.unfinished_host = self.pinned_unfinished.numpy()
-        self.planes = torch.zeros((batch_size, 16*Rs, 16*Cs), dtype=torch.uint8, device=device)
-        crop_bytes = -(-batch_size*self.region[0]*self.region[1]//16)*16          # whole 16-byte words: `device.publish_crops`
-        (self.crops, self.pinned_crops, self.crops_host) = (None, None, None)
-        if decoder.fetch_reconstruction:
-            self.pinned_crops = torch.zeros(crop_bytes, dtype=torch.uint8).pin_memory()
-            self.crops_host = self.pinned_crops.numpy()
-        else:
-            self.crops = torch.zeros(crop_bytes, dtype=torch.uint8, device=device)
-        self.seq_dev = torch.zeros(2, dtype=torch.int32, device=device)      # [step counter, ticket word of device.publish_step]
-        self.pinned_seq = torch.zeros(1, dtype=torch.int32).pin_memory()
-        self.seq_host = self.pinned_seq.numpy()
-        self.count = 0
-        self.free = threading.Event()
-        self.free.set()
-        self.graph = None
-
-
 class RegionDecoder(BatchDecoder):
     """(RegionSource, image, y0, x0) requests -> uint8 crops of one fixed size, resident and pipelined: what
     `container.decode_region(source, decoder, (y0, x0, rh, rw), images=[image])[0]` computes (same bytes), with `BatchDecoder`'s
@@ -2214,16 +2197,11 @@ class RegionDecoder(BatchDecoder):
         payload_capacity_bytes: payload bytes a step may hold (rounded up to 16); None: 16 bits per symbol of the step's slots.
         fetch_reconstruction: the crops reach pinned host memory inside the step and `result()` is a numpy view of them; False:
         `result()` is a view of the slot's device tensor. The other arguments as `BatchDecoder`'s."""
-        # refused in front of every allocation
-        if h_in % csts.STRIDE_PROD != 0 or w_in % csts.STRIDE_PROD != 0 or h_in < 1 or w_in < 1:
-            raise ValueError('The image size is not divisible by the product of the three strides.')
-        if not 1 <= int(truncated_unary_length) <= 255:
-            raise ValueError('The truncated unary length does not belong to [1, 255].')
-        if batch_size < 1:
-            raise ValueError('`batch_size` is not positive.')
-        coding_tile = container_format._positive_pair(coding_tile, '`coding_tile`')
-        if max(coding_tile) > 0xFFFF:
-            raise ValueError('A side of `coding_tile` does not fit the container (65535 latents at most).')
+        self._lay_out(batch_size, h_in, w_in, truncated_unary_length, payload_capacity_bytes, coding_tile, region)
+        self._build(variables, are_bin_widths_learned, device, nb_in_flight, nb_streams, use_graphs, fetch_reconstruction)
+
+    def _lay_out(self, batch_size, h_in, w_in, truncated_unary_length, payload_capacity_bytes, coding_tile, region):
+        coding_tile = _refuse_shape(batch_size, h_in, w_in, truncated_unary_length, coding_tile)
         region = container_format._positive_pair(region, '`region`')
         if region[0] > h_in or region[1] > w_in:
             raise ValueError('`region` = {0} is larger than the {1} x {2} images.'.format(region, h_in, w_in))
@@ -2234,65 +2212,47 @@ class RegionDecoder(BatchDecoder):
         layout = region_layout(int(batch_size), h_map, w_map, coding_tile, Rs, Cs)
         if layout['n_slots'] > 65535:
             raise ValueError('`batch_size` crops of {0} slots each are more than the 65535 slots a step can hold.'.format(layout['slots_per_crop']))
-        if payload_capacity_bytes is not None and int(payload_capacity_bytes) < 1:
-            raise ValueError('`payload_capacity_bytes` is not positive.')
-        self.device = _decoder_device(device)
-        self.learned = bool(are_bin_widths_learned)
-        self.decoder = pipeline.DeviceDecoder(variables, are_bin_widths_learned, self.device)
-        (self.batch_size, self.h_in, self.w_in) = (int(batch_size), int(h_in), int(w_in))
-        self.nb_maps = csts.NB_MAPS_3
-        self.truncated_unary_length = int(truncated_unary_length)
         (self.coding_tile, self.region, self.window) = (layout['coding_tile'], region, (Rs, Cs))
-        if payload_capacity_bytes is None:
-            payload_capacity_bytes = 2*layout['elements']
-        self.payload_capacity_bytes = -(-int(payload_capacity_bytes)//16)*16
-        self.fetch_reconstruction = bool(fetch_reconstruction)
-        self.use_graphs = bool(use_graphs)
-        self.nb_streams = nb_streams = _decoder_streams(nb_streams, 'RegionDecoder')
-        self.nb_in_flight = max(1, int(nb_in_flight)) if nb_in_flight is not None else nb_streams + 2
-        self.nb_slots = self.nb_in_flight
         # everything a step needs beyond its requests is the same for every step: made once, shared by the slots
         self._layout = layout
-        self._n_streams = layout['n_streams']
+        (self._n_streams, self._runs, self._elements) = (layout['n_streams'], layout['runs'], layout['elements'])
+        self._payload_order = None                    # the payload of a step lies in run order
+        self._index_images = 1                        # every slot is an entry of one "image"
+        self._head_fields = _region_head_fields(int(batch_size), layout['n_slots'], int(truncated_unary_length))
+        # what the worker scans (`_DecodeJob.detail`): the streams of every run-order slot, picked per step by the crops' placement
+        self._slot_ranges = [(k*csts.NB_MAPS_3, (k + 1)*csts.NB_MAPS_3) for k in range(layout['n_slots'])]
+        self._set_sizes(batch_size, h_in, w_in, truncated_unary_length, payload_capacity_bytes, 2*layout['elements'])
+
+    def _upload_tables(self):
+        layout = self._layout
         self._slots_host = layout['slots']
         self._slots_device = torch.from_numpy(layout['slots']).to(self.device)
         # `device.coder_index_tiles`: the payload is in run order, so every slot is its own entry, clamped to half its class's stride
         half_stride = numpy.concatenate([numpy.full(count, dev.coder_stream_stride_bytes(rows*cols, self.truncated_unary_length)//2, dtype=numpy.int64)
                                          for ((rows, cols), count, _, _) in layout['runs']])
         self._entry_table = torch.from_numpy(numpy.stack([numpy.arange(layout['n_slots'], dtype=numpy.int64), half_stride], axis=1)).to(self.device)
-        streams = _step_streams(self.nb_streams, self.device)
-        self._slots = [_RegionSlot(self, _RegionLane(self, streams[k % self.nb_streams])) for k in range(self.nb_slots)]
-        self._index = 0
-        self._warm = False
-        self._worker = _RegionWorker(self.nb_maps)
-        self._worker.start()
-        with _LIVE_LOCK:
-            _LIVE.setdefault(self.device.index, weakref.WeakSet()).add(self)
 
     def _plan_step(self, slot, requests):
-        return plan_region_step(requests, self._layout, slot.head_host, slot.payload_host, self.payload_capacity_bytes, self.region,
-                                self.truncated_unary_length, self.learned, self.nb_maps)
+        """As `BatchDecoder._plan_step`; a crop's streams are those of its tiles' slots, its tiles in row-major order as
+        `container.decode_region` meets them, the maps of a tile in order."""
+        (crops, payload_bytes, crop_slots) = plan_region_step(requests, self._layout, slot.head_host, slot.payload_host, self.payload_capacity_bytes,
+                                                              self.region, self.truncated_unary_length, self.learned, self.nb_maps)
+        ranges = self._slot_ranges
+        return crops, payload_bytes, [[ranges[run] for run in runs] for runs in crop_slots]
 
-    def _launch_step(self, slot):
-        """The step of `slot` on the current stream: one chain, no argument of which depends on the step's requests."""
+    def _launch_latents(self, slot):
         lane = slot.lane
-        (layout, (rh, rw)) = (self._layout, self.region)
-        dev.fetch_prefix(slot.pinned_head, lane.head, lane.head_bytes)                      # the head: a fixed size
-        dev.fetch_prefix(slot.pinned_payload, lane.payload, lane.payload_bytes)             # the payload: the bytes the head announces
-        lane.results[:2].copy_(lane.head_bits.view(-1, 2).t())                              # [n_streams][2] -> the coder's two arrays
         # every slot is an entry of one "image": the offsets of its pieces in the payload, which lies in run order
-        dev.coder_index_tiles(lane.results[0], lane.results[1], self._entry_table, self.nb_maps, layout['n_slots'],
+        dev.coder_index_tiles(lane.results[0], lane.results[1], self._entry_table, self.nb_maps, self._layout['n_slots'],
                               self.payload_capacity_bytes, offsets=lane.offsets, index=lane.index)
-        for (streams, tiles, rows, offsets) in lane.classes:
-            dev.coder_unpack_into(streams, lane.payload, offsets)
-            dev.coder_decode_batch(streams, lane.table, rows, workspace=lane.workspace, out=tiles)
+        self._launch_classes(lane)
         # the placed tiles cover every latent of a present crop's window exactly once
         dev.tile_symbols_dequantize_placed(lane.decoded, self._slots_device, self._slots_host, lane.placement, lane.bin_widths, lane.map_mean,
                                            lane.shifted)
-        self.decoder.model.decode_into(lane.shifted, slot.planes, lane.scratch)
-        dev.publish_crops(slot.planes, lane.crop_origin, slot.pinned_crops if slot.pinned_crops is not None else slot.crops, rh, rw)
-        dev.publish_to_host(lane.unfinished, slot.pinned_unfinished)
-        dev.publish_step(lane.status, slot.pinned_status, lane.status.numel(), slot.seq_dev[1:2], slot.seq_dev[0:1], slot.pinned_seq)
+
+    def _launch_output(self, slot):
+        (rh, rw) = self.region
+        dev.publish_crops(slot.planes, slot.lane.crop_origin, slot.pinned_crops if slot.pinned_crops is not None else slot.crops, rh, rw)
 
 
 # ---- a rate point per image, chosen on the device to a byte budget (DESIGN.md section 19) -----------------------------------------

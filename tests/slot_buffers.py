@@ -1,9 +1,11 @@
 """What every buffer of a resident codec's slot may hold when a step starts (a plain helper module: import it, no fixture lives here).
 
-`codec.BatchCodec` and `codec.BatchDecoder` make their buffers once (`codec._Slot`, `codec._DecodeLane`, `codec._DecodeSlot`) and reuse
-them step after step. A step that reads what the previous step left usually finds plausible data -- most tests leave the same data --,
-so tests/test_gpu_codec_slots.py fills, between two steps, every buffer a step must not depend on with a poison byte. Which buffers
-those are is decided HERE, attribute by attribute, from the source; tests/test_slot_inventory.py keeps the three tables complete.
+`codec.BatchCodec` makes its buffers once (`codec._Slot`), and so do the three resident decoders -- `codec.BatchDecoder`,
+`BatchDecoder(coding_tile=...)` and `codec.RegionDecoder` --, which share ONE lane and ONE slot class (`codec._DecodeLane`,
+`codec._DecodeSlot`); they reuse them step after step. A step that reads what the previous step left usually finds plausible data --
+most tests leave the same data --, so tests/test_gpu_codec_slots.py and tests/test_gpu_region_decoder.py fill, between two steps, every
+buffer a step must not depend on with a poison byte. Which buffers those are is decided HERE, attribute by attribute, from the
+source; tests/test_slot_inventory.py keeps the three tables complete.
 
 SCRATCH       a step defines all of it that it later reads, before reading it: it may hold anything when the step starts. Pinned
               buffers count on both sides: the device defines what the host reads, the host (`plan_decode_step`, `submit`) what the
@@ -44,7 +46,7 @@ def _graph_member(position):
 
 
 _RESULT_ROWS = ('`CoderStreams.results` and its rows `.bac_bits`, `.bypass_bits`, `.status`, `.stage` are views of the results block the '
-                'slot passes in (device.py:628, 632; codec.py:647, 662 / 1543, 1555)')
+                'slot passes in (device.py:628, 632; codec.py:667, 622 / 1637, 622)')
 _RESULT_ROW = 'a row of `CoderStreams.results` (device.py:632), itself a view of the slot\'s results block'
 
 
@@ -78,13 +80,13 @@ SLOT = {
     'symbols_2d': _entry(SCRATCH, 'a view of `symbols` (codec.py:644)', alias='symbols'),
     'gathered': _entry(SCRATCH, 'tile_symbols_gather writes every tile of the plan (codec.py:1193); the pad between two class runs is '
                                 'never read (the classes\' views end at n*size, codec.py:663); with one tile it IS `symbols` (codec.py:657)'),
-    'classes': _entry(NOT_A_BUFFER, 'a list of tuples; its members are the entries `classes[]...` below (codec.py:663)'),
-    'classes[].streams': _entry(SCRATCH, 'as `coder_streams.streams`, per shape class (codec.py:662)',
+    'classes': _entry(NOT_A_BUFFER, 'a list of tuples; its members are the entries `classes[]...` below (codec.py:679, 623)'),
+    'classes[].streams': _entry(SCRATCH, 'as `coder_streams.streams`, per shape class (codec.py:622)',
                                 get=lambda slot: [s.streams for s in _streams_of(slot)] if slot.coder_streams is None else []),
     'classes[].results': _entry(SCRATCH, _RESULT_ROWS, alias='results'),
-    'classes[].tiles': _entry(SCRATCH, 'views of `gathered` (codec.py:663)', alias='gathered'),
-    'classes[].rows': _entry(CONSTANT, 'views of the CODEC\'s `_tile_prob_row`, uploaded once (codec.py:852, 664): not the slot\'s bytes'),
-    'classes[].offsets': _entry(SCRATCH, 'views of `offsets` (codec.py:664)', alias='offsets'),
+    'classes[].tiles': _entry(SCRATCH, 'views of `gathered` (codec.py:679, 623)', alias='gathered'),
+    'classes[].rows': _entry(CONSTANT, 'views of the CODEC\'s `_tile_prob_row`, uploaded once (codec.py:868, 679): not the slot\'s bytes'),
+    'classes[].offsets': _entry(SCRATCH, 'views of `offsets` (codec.py:679, 624)', alias='offsets'),
     'coder_streams': _entry(NOT_A_BUFFER, 'a device.CoderStreams (codec.py:647; None with coding tiles); its members are the two entries below'),
     'coder_streams.streams': _entry(SCRATCH, 'binarise_kernel writes the bypass words it counts (coder_simd.hip:227, 233), emit_kernel the '
                                              'arithmetic-coded words as whole words; the decoder core loads 16-byte groups that hold stream '
@@ -138,75 +140,90 @@ SLOT = {
     'emit_host': _entry(NOT_A_BUFFER, 'the container\'s fixed parts, the capacity, and numpy views of pinned_payload and pinned_emit (codec.py:704)'),
 }
 
-# ---- codec._DecodeLane: the device side of one BatchDecoder slot -----------------------------------------------------------------
-_HEAD = ('a field of `head`: fetch_prefix copies head_bytes = ALL of the pinned head first (codec.py:1765), and plan_decode_step has written '
-         'every element of every field (codec.py:1393-1413)')
+# ---- codec._DecodeLane: the device side of one slot of BatchDecoder, BatchDecoder(coding_tile=...) and RegionDecoder --------------
+_HEAD = ('a field of `head`: fetch_prefix copies head_bytes = ALL of the pinned head first (codec.py:1876), and plan_decode_step has written '
+         'every element of every field (codec.py:1418-1442), plan_region_step of a RegionDecoder\'s (codec.py:2156-2173)')
+_REGION_HEAD = ('a field of a RegionDecoder\'s `head` (codec.py:1621; None otherwise): fetch_prefix copies ALL of the pinned head first '
+                '(codec.py:1876), and plan_region_step has written every element ')
 DECODE_LANE = {
-    'stream': _entry(NOT_A_BUFFER, 'the stream the lane\'s steps run on (codec.py:1521)'),
-    'head': _entry(CONTAINER, 'codec.py:1523: the fields of decode_head_layout, each on an 8-byte boundary, the block rounded up to 16',
-                   parts=('head_bits', 'prob_row', 'bin_widths', 'map_mean', 'table', 'payload_bytes'), max_gap=15),
+    'stream': _entry(NOT_A_BUFFER, 'the stream the lane\'s steps run on (codec.py:1609)'),
+    'head': _entry(CONTAINER, 'codec.py:1611: the fields of the decoder\'s head (decode_head_layout, region_head_layout), each on an 8-byte '
+                              'boundary, the block rounded up to 16 (codec.py:1306-1309)',
+                   parts=('head_bits', 'prob_row', 'placement', 'crop_origin', 'bin_widths', 'map_mean', 'table', 'payload_bytes'), max_gap=15),
     'head_bits': _entry(SCRATCH, _HEAD),
     'prob_row': _entry(SCRATCH, _HEAD),
+    'placement': _entry(SCRATCH, _REGION_HEAD + '(codec.py:2158, 2164)'),
+    'crop_origin': _entry(SCRATCH, _REGION_HEAD + '(codec.py:2159, 2165)'),
     'bin_widths': _entry(SCRATCH, _HEAD),
     'map_mean': _entry(SCRATCH, _HEAD),
     'table': _entry(SCRATCH, _HEAD),
     'payload_bytes': _entry(SCRATCH, _HEAD + '; fetch_prefix and the index clamp what it announces to the capacity (codec_decode.hip:17)'),
-    'head_bytes': _entry(CONSTANT, 'the size of the head, written at construction (codec.py:1535), read by fetch_prefix'),
-    'payload': _entry(SCRATCH, 'fetch_prefix copies the announced bytes (codec.py:1766); the unpack reads inside them (container.hip:27-30)'),
-    'status': _entry(CONTAINER, 'codec.py:1538: [results | index words]', parts=('results', 'index')),
-    'results': _entry(SCRATCH, 'rows 0-1: copied from head_bits (codec.py:1767); row 2: eae_hip_coder_decode_batch fills it with zeros '
+    'head_bytes': _entry(CONSTANT, 'the size of the head, written at construction (codec.py:1627), read by fetch_prefix'),
+    'payload': _entry(SCRATCH, 'fetch_prefix copies the announced bytes (codec.py:1877); the unpack reads inside them (container.hip:27-30)'),
+    'status': _entry(CONTAINER, 'codec.py:1631: [results | index words]', parts=('results', 'index')),
+    'results': _entry(SCRATCH, 'rows 0-1: copied from head_bits (codec.py:1878); row 2: eae_hip_coder_decode_batch fills it with zeros '
                                '(coder_simd.hip:1478); row 3 (stage) is written with every non-zero status (coder_device.hip:246-247) and '
-                               'read by the worker only next to one (codec.py:1496)'),
-    'index': _entry(SCRATCH, 'as `_Slot.index`: every word written by the index kernels (codec.py:1770, 1778)'),
-    'offsets': _entry(SCRATCH, 'as `_Slot.offsets` (codec.py:1770, 1778), in front of the unpack'),
-    'coder_streams': _entry(NOT_A_BUFFER, 'a device.CoderStreams (codec.py:1543; absent with coding tiles); its members are the two entries below'),
+                               'read by the worker only next to one (codec.py:1542)'),
+    'index': _entry(SCRATCH, 'as `_Slot.index`: every word written by the index kernels (codec.py:1897, 1905, 2246)'),
+    'offsets': _entry(SCRATCH, 'as `_Slot.offsets` (codec.py:1897, 1905, 2246), in front of the unpack'),
+    'coder_streams': _entry(NOT_A_BUFFER, 'a device.CoderStreams (codec.py:1637; None for a step in tiles); its members are the two entries below'),
     'coder_streams.streams': _entry(SCRATCH, 'the unpack writes the counted bytes of every piece (container.hip:24-30); the decoder core '
                                              'loads 16-byte groups that hold stream bits only and takes none beyond them (coder_simd.hip:585, '
                                              '610); debinarise_kernel masks the bypass words beyond the count (coder_simd.hip:821, 854)',
-                                    get=lambda lane: [s.streams for s in _streams_of(lane)] if hasattr(lane, 'coder_streams') else []),
+                                    get=lambda lane: [lane.coder_streams.streams] if lane.coder_streams is not None else []),
     'coder_streams.results': _entry(SCRATCH, _RESULT_ROWS, alias='results'),
     'workspace': _entry(SCRATCH, 'the decoder core writes the prefix bytes debinarise_kernel reads (coder_simd.hip:695, 740), debinarise_kernel '
                                  'or mark_kernel writes ndec (coder_simd.hip:785, 1387); nothing is read first'),
     'symbols': _entry(SCRATCH, 'debinarise_kernel (or the general kernel) writes every symbol of every coded map (coder_simd.hip:896). The maps '
                                'of an ABSENT image (prob_row -1) are left as they are and dequantised with bin width 0 and mean 0 '
-                               '(codec.py:1410-1411) into planes no ticket returns (codec.py:1501)'),
-    'decoded': _entry(SCRATCH, 'as `symbols`, tile-major (codec.py:1782-1783); the pad between two class runs is never read'),
-    'classes': _entry(NOT_A_BUFFER, 'a list of tuples; its members are the entries `classes[]...` below (codec.py:1556)'),
-    'classes[].streams': _entry(SCRATCH, 'as `coder_streams.streams`, per shape class (codec.py:1555)',
-                                get=lambda lane: [s.streams for s in _streams_of(lane)] if not hasattr(lane, 'coder_streams') else []),
+                               '(codec.py:1439-1440) into planes no ticket returns (codec.py:1694)'),
+    'decoded': _entry(SCRATCH, 'as `symbols`, tile-major (codec.py:1907-1908, 2248-2250); the pad between two class runs is never read, and '
+                               'an absent slot of a RegionDecoder (placement -1, codec.py:2158) is not placed'),
+    'classes': _entry(NOT_A_BUFFER, 'a list of tuples (None for whole maps); its members are the entries `classes[]...` below (codec.py:1644, 623)'),
+    'classes[].streams': _entry(SCRATCH, 'as `coder_streams.streams`, per shape class (codec.py:622)',
+                                get=lambda lane: [s.streams for s in _streams_of(lane)] if lane.coder_streams is None else []),
     'classes[].results': _entry(SCRATCH, _RESULT_ROWS, alias='results'),
-    'classes[].tiles': _entry(SCRATCH, 'views of `decoded` (codec.py:1556)', alias='decoded'),
-    'classes[].rows': _entry(SCRATCH, 'views of `prob_row` (codec.py:1557)', alias='prob_row'),
-    'classes[].offsets': _entry(SCRATCH, 'views of `offsets` (codec.py:1557)', alias='offsets'),
-    'shifted': _entry(SCRATCH, 'the dequantiser writes every latent of every image (codec.py:1773, 1783: every latent is in one tile)'),
+    'classes[].tiles': _entry(SCRATCH, 'views of `decoded` (codec.py:1644, 623)', alias='decoded'),
+    'classes[].rows': _entry(SCRATCH, 'views of `prob_row` (codec.py:1644, 623)', alias='prob_row'),
+    'classes[].offsets': _entry(SCRATCH, 'views of `offsets` (codec.py:1644, 624)', alias='offsets'),
+    'shifted': _entry(SCRATCH, 'the dequantiser writes every latent of every image (codec.py:1900, 1908: every latent is in one tile) and of '
+                               'every PRESENT crop\'s window (codec.py:2250); the window of an absent crop is synthesised as it is, into planes '
+                               'no crop is cut from for a ticket (codec.py:1697)'),
     'scratch': _entry(SCRATCH, 'eae_hip_decode zeroes its conv workspace and status word itself, by a kernel, at the head of every call '
                                '(model.hip:199); the activations are written before they are read'),
     'unfinished': _entry(SCRATCH, 'the status word inside `scratch` (device.py:191)', alias='scratch'),
 }
 
-# ---- codec._DecodeSlot: what one BatchDecoder step in flight owns beside its lane ------------------------------------------------
+# ---- codec._DecodeSlot: what one step in flight of the three resident decoders owns beside its lane -------------------------------
 DECODE_SLOT = {
-    'lane': _entry(NOT_A_BUFFER, 'the _DecodeLane (codec.py:1573): classified by DECODE_LANE'),
-    'pinned_head': _entry(SCRATCH, 'plan_decode_step writes every element of every field before the step is launched (codec.py:1393-1413); '
-                                   'the pad between fields is copied and never read'),
-    'pinned_payload': _entry(SCRATCH, 'plan_decode_step writes the bytes it announces (codec.py:1401, 1413); the device fetches those'),
-    'head_host': _entry(NOT_A_BUFFER, 'numpy view of pinned_head (codec.py:1576)'),
-    'payload_host': _entry(NOT_A_BUFFER, 'numpy view of pinned_payload (codec.py:1576)'),
-    'pinned_status': _entry(SCRATCH, 'publish_step copies all of the lane\'s `status` in front of the step counter (codec.py:1788)'),
-    'results_host': _entry(NOT_A_BUFFER, 'numpy view of pinned_status (codec.py:1578)'),
-    'index_host': _entry(NOT_A_BUFFER, 'numpy view of pinned_status (codec.py:1579)'),
-    'pinned_unfinished': _entry(SCRATCH, 'publish_to_host copies the scratch block\'s status word every step (codec.py:1787)'),
-    'unfinished_host': _entry(NOT_A_BUFFER, 'numpy view of pinned_unfinished (codec.py:1581)'),
-    'planes': _entry(SCRATCH, 'eae_hip_decode writes every pixel of every image of the step (codec.py:1784)'),
-    'pinned_rec': _entry(SCRATCH, 'publish_to_host copies all of `planes` (codec.py:1786)'),
-    'rec_host': _entry(NOT_A_BUFFER, 'numpy view of pinned_rec (codec.py:1584)'),
-    'seq_dev': _entry(CARRIED, 'step counter and publish_step\'s ticket word (codec.py:1585; misc.hip:133-138)'),
-    'pinned_seq': _entry(CARRIED, 'the published counter the worker compares with `count` (codec.py:1586, 1734)'),
-    'seq_host': _entry(NOT_A_BUFFER, 'numpy view of pinned_seq (codec.py:1587)'),
-    'count': _entry(CARRIED, 'how many times the host has submitted the slot (codec.py:1588, 1737): a Python int'),
-    'free': _entry(NOT_A_BUFFER, 'a threading.Event (codec.py:1589)'),
-    'graph': _entry(NOT_A_BUFFER, 'the torch.cuda.CUDAGraph of the slot\'s step; the captured step allocates nothing (codec.py:1762-1788 pass every '
-                                  'output in)'),
+    'lane': _entry(NOT_A_BUFFER, 'the _DecodeLane (codec.py:1660): classified by DECODE_LANE'),
+    'region': _entry(NOT_A_BUFFER, 'the crop size (rh, rw) of a RegionDecoder, None otherwise (codec.py:1661): a tuple'),
+    'pinned_head': _entry(SCRATCH, 'plan_decode_step / plan_region_step writes every element of every field before the step is launched '
+                                   '(codec.py:1418-1442, 2156-2173); the pad between fields is copied and never read'),
+    'pinned_payload': _entry(SCRATCH, 'plan_decode_step / plan_region_step writes the bytes it announces (codec.py:1430, 1442; 2173-2176); the '
+                                      'device fetches those'),
+    'head_host': _entry(NOT_A_BUFFER, 'numpy view of pinned_head (codec.py:1664)'),
+    'payload_host': _entry(NOT_A_BUFFER, 'numpy view of pinned_payload (codec.py:1664)'),
+    'pinned_status': _entry(SCRATCH, 'publish_step copies all of the lane\'s `status` in front of the step counter (codec.py:1883)'),
+    'results_host': _entry(NOT_A_BUFFER, 'numpy view of pinned_status (codec.py:1666)'),
+    'index_host': _entry(NOT_A_BUFFER, 'numpy view of pinned_status (codec.py:1667)'),
+    'pinned_unfinished': _entry(SCRATCH, 'publish_to_host copies the scratch block\'s status word every step (codec.py:1882)'),
+    'unfinished_host': _entry(NOT_A_BUFFER, 'numpy view of pinned_unfinished (codec.py:1669)'),
+    'planes': _entry(SCRATCH, 'eae_hip_decode writes every pixel of every image, or window, of the step (codec.py:1880)'),
+    'pinned_rec': _entry(SCRATCH, 'publish_to_host copies all of `planes` (codec.py:1913)'),
+    'rec_host': _entry(NOT_A_BUFFER, 'numpy view of pinned_rec (codec.py:1682)'),
+    'crops': _entry(SCRATCH, 'publish_crops writes every 16-byte word of it: the rh x rw pixels of every crop of the batch, an absent one '
+                             'from the origin plan_region_step left it (codec.py:2159), zeros behind the last (codec.py:2255; '
+                             'codec_decode.hip:98-134); the ticket takes the present crops\' (codec.py:1697)'),
+    'pinned_crops': _entry(SCRATCH, 'as `crops`, cut straight into pinned memory when the crops are fetched (codec.py:2255, 1679)'),
+    'crops_host': _entry(NOT_A_BUFFER, 'numpy view of pinned_crops (codec.py:1683)'),
+    'seq_dev': _entry(CARRIED, 'step counter and publish_step\'s ticket word (codec.py:1684; misc.hip:133-138)'),
+    'pinned_seq': _entry(CARRIED, 'the published counter the worker compares with `count` (codec.py:1685, 1837)'),
+    'seq_host': _entry(NOT_A_BUFFER, 'numpy view of pinned_seq (codec.py:1686)'),
+    'count': _entry(CARRIED, 'how many times the host has submitted the slot (codec.py:1687, 1840): a Python int'),
+    'free': _entry(NOT_A_BUFFER, 'a threading.Event (codec.py:1688)'),
+    'graph': _entry(NOT_A_BUFFER, 'the torch.cuda.CUDAGraph of the slot\'s step; the captured step allocates nothing (codec.py:1873-1913, '
+                                  '2243-2255 pass every output in)'),
 }
 
 for _table in (SLOT, DECODE_LANE):
@@ -219,9 +236,9 @@ MUST_BE_SCRATCH = {
     '_Slot': ('symbols', 'gathered', 'coder_streams.streams', 'classes[].streams', 'workspace', 'offsets', 'index', 'payload', 'exception_rows',
               'staging', 'graphs[1]', 'graphs[2]', 'graphs[3]', 'pinned_out', 'pinned_sse', 'pinned_payload', 'pinned_emit', 'pinned_rec',
               'pinned_symbols'),
-    '_DecodeLane': ('head_bits', 'prob_row', 'bin_widths', 'map_mean', 'table', 'payload_bytes', 'payload', 'results', 'index', 'offsets',
-                    'coder_streams.streams', 'classes[].streams', 'workspace', 'symbols', 'decoded', 'shifted', 'scratch'),
-    '_DecodeSlot': ('pinned_head', 'pinned_payload', 'pinned_status', 'pinned_unfinished', 'planes', 'pinned_rec'),
+    '_DecodeLane': ('head_bits', 'prob_row', 'placement', 'crop_origin', 'bin_widths', 'map_mean', 'table', 'payload_bytes', 'payload', 'results',
+                    'index', 'offsets', 'coder_streams.streams', 'classes[].streams', 'workspace', 'symbols', 'decoded', 'shifted', 'scratch'),
+    '_DecodeSlot': ('pinned_head', 'pinned_payload', 'pinned_status', 'pinned_unfinished', 'planes', 'pinned_rec', 'crops', 'pinned_crops'),
 }
 
 
@@ -252,7 +269,7 @@ def fill_bytes(tensor, byte):
 
 
 def owners(codec_or_decoder):
-    """[(object, table)] of every slot of a BatchCodec, or every slot and lane of a BatchDecoder."""
+    """[(object, table)] of every slot of a BatchCodec, or every slot and lane of a BatchDecoder or RegionDecoder."""
     out = []
     for slot in codec_or_decoder._slots:
         if hasattr(slot, 'lane'):

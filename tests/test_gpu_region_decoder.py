@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import guarded
+import slot_buffers
 
 pytestmark = pytest.mark.gpu
 
@@ -515,29 +516,14 @@ def test_refused_steps_and_lifetime(weights, guard):
 
 # ---- slot discipline -----------------------------------------------------------------------------------------------------------------------
 
-def _scratch(decoder):
-    """Every buffer a step must not depend on: it defines all of it that it later reads, before reading it (the classes of
-    tests/slot_buffers.py, for the region decoder's lane and slot). NOT among them: `head_bytes` and the decoder's static tables
-    (constants), `seq_dev` / `pinned_seq` (the step counter)."""
-    out = []
-    for slot in decoder._slots:
-        lane = slot.lane
-        out += [lane.head, lane.payload, lane.status, lane.offsets, lane.decoded, lane.workspace, lane.shifted, lane.scratch]
-        out += [streams.streams for (streams, _, _, _) in lane.classes]
-        out += [slot.pinned_head, slot.pinned_payload, slot.pinned_status, slot.pinned_unfinished, slot.planes]
-        out += [t for t in (slot.pinned_crops, slot.crops) if t is not None]
-    return out
-
-
 def _poison_between_steps(decoder, guard, poison):
+    """Every buffer a step must not depend on is filled with the poison: the SCRATCH entries of tests/slot_buffers.py for the lane and
+    the slot the region decoder shares with `BatchDecoder` (NOT among them: `head_bytes` and the decoder's static tables, constants;
+    `seq_dev` / `pinned_seq`, the step counter). `head` is filled field by field: the alignment gaps between its fields keep what
+    they held. No kernel reads them, and `check_tiling` bounds them by `max_gap=15` bytes."""
     decoder.drain()
     guard.check(keep=True)
-    total = 0
-    for tensor in _scratch(decoder):
-        tensor.view(torch.uint8).fill_(int(poison))
-        total += tensor.numel()*tensor.element_size()
-    torch.cuda.synchronize()
-    assert total > 0
+    assert slot_buffers.poison_scratch(decoder, poison) > 0
 
 
 @pytest.mark.parametrize('fetch', [True, False])
@@ -561,6 +547,10 @@ def test_steps_on_poisoned_slots(weights, case, fetch):
                      [(sources[0], 1) + places[2], (sources[1], 1) + places[2], (sources[0], 0) + places[3]]]
             with _decoder(weights, shape, tile, use_graphs=True, fetch_reconstruction=fetch) as decoder:
                 torch.cuda.synchronize()
+                if poison == POISONS[0]:
+                    # the classified parts cover the containers of every lane and slot: what is poisoned is all there is
+                    checked = [name for (owner, table) in slot_buffers.owners(decoder) for name in slot_buffers.check_tiling(owner, table)]
+                    assert 'head' in checked and 'status' in checked
                 _poison_between_steps(decoder, inner, poison)          # what construction left is no better than what a step leaves
                 values = []
                 for requests in steps:

@@ -1,7 +1,8 @@
-"""Every attribute of the resident codecs' slots (`codec._Slot`, `codec._DecodeLane`, `codec._DecodeSlot`) is classified in
-tests/slot_buffers.py: what a step may find in it when it starts. tests/test_gpu_codec_slots.py poisons the SCRATCH ones between the
-steps of `BatchCodec` and `BatchDecoder`; a buffer added to a slot without a word here would simply never be poisoned. CPU-only: it
-reads source text."""
+"""Every attribute of the resident codecs' slots (`codec._Slot`, and the `codec._DecodeLane` and `codec._DecodeSlot` that
+`BatchDecoder`, `BatchDecoder(coding_tile=...)` and `RegionDecoder` share) is classified in tests/slot_buffers.py: what a step may
+find in it when it starts. tests/test_gpu_codec_slots.py poisons the SCRATCH ones between the steps of `BatchCodec` and
+`BatchDecoder`, tests/test_gpu_region_decoder.py between those of `RegionDecoder`; a buffer added to a slot without a word here
+would simply never be poisoned. CPU-only: it reads source text."""
 import ast
 import os
 
@@ -76,8 +77,9 @@ def test_the_three_inits_parse():
     assert {'block', 'symbols', 'coder_streams', 'workspace', 'offsets', 'payload', 'staging', 'graphs', 'emit_host'} <= slot
     assert {'results', 'hist', 'overflow', 'flags', 'checks'} <= slot                  # a tuple target
     assert {'gathered', 'classes'} <= slot                                              # assigned as a pair
-    assert {'head', 'head_bits', 'status', 'decoded', 'classes', 'scratch', 'unfinished', 'stream'} <= assigned_attributes(source, '_DecodeLane')
-    assert {'lane', 'pinned_head', 'head_host', 'payload_host', 'planes', 'graph', 'count'} <= assigned_attributes(source, '_DecodeSlot')
+    assert {'head', 'head_bits', 'status', 'decoded', 'classes', 'scratch', 'unfinished', 'stream', 'placement', 'crop_origin'} <= \
+        assigned_attributes(source, '_DecodeLane')
+    assert {'lane', 'pinned_head', 'head_host', 'payload_host', 'planes', 'graph', 'count', 'crops'} <= assigned_attributes(source, '_DecodeSlot')
 
 
 def test_every_assigned_attribute_is_classified():
