@@ -2266,20 +2266,64 @@ class BudgetTicket(Ticket):
         raise RuntimeError('a BudgetCodec step has one rate point per image and one EAE1 blob holds one: use `image_containers()`')
 
     def image_containers(self):
-        """Blocks like `result()`; one single-image `EAE1` blob per image, byte for byte what `container.encode_images` writes for
-        that image at the point `result()['rate_point']` names. Raises `ContainerOverflow` like `Ticket.container()`."""
+        """Blocks like `result()`; one single-image `EAE1` blob per image (`EAT1` from a `TiledBudgetCodec`), byte for byte what
+        `container.encode_images` writes for that image at the point `result()['rate_point']` names. Raises `ContainerOverflow` like
+        `Ticket.container()`."""
         parts = self._parts()
         (learned, _, height, width, exception, ladder) = parts['head']
         (bits, rows, view) = (parts['bits'], parts['rows'], memoryview(parts['payload']))
         nb_maps = ladder.bin_widths_points.shape[1]
-        image_bytes = container_format._entry_bytes(bits.reshape(self.nb_images, nb_maps, 2))
+        per_image = bits.shape[0]//self.nb_images            # nb_maps, times the tiles of an image with a coding tile (payload order)
+        image_bytes = container_format._entry_bytes(bits.reshape(self.nb_images, per_image//nb_maps, nb_maps, 2)).sum(axis=1)
         stops = numpy.cumsum(image_bytes)
         blobs = []
         for (i, k) in enumerate(parts['rate_point'].tolist()):
             blobs.append(container_format.assemble_blob(learned, 1, height, width, exception, ladder.bin_widths_points[k], ladder.map_mean,
                                                         ladder.binary_probabilities_points[k], rows[i:i + 1] if exception >= 0 else rows[:0],
-                                                        bits[i*nb_maps:(i + 1)*nb_maps], view[int(stops[i] - image_bytes[i]):int(stops[i])])[0])
+                                                        bits[i*per_image:(i + 1)*per_image], view[int(stops[i] - image_bytes[i]):int(stops[i])],
+                                                        coding_tile=parts['coding_tile'])[0])
         return blobs
+
+
+def _ladder_accumulators(counts_shape, nb_points, length, device):
+    """The ladder's accumulators of a budget slot, zeroed by one launch at the head of every step: (accum = [bypass bits int64 |
+    histograms int32 | range errors int32], and its three views). counts_shape: (N, K, 128), or (N, K, T, 128) per coding tile."""
+    nb_bits = 1
+    for extent in counts_shape:
+        nb_bits *= extent
+    nb_bins = nb_bits*(length + 1)
+    accum = torch.zeros(2*nb_bits + nb_bins + nb_points, dtype=torch.int32, device=device)
+    return (accum, accum[:2*nb_bits].view(torch.int64).view(counts_shape), accum[2*nb_bits:2*nb_bits + nb_bins].view(tuple(counts_shape) + (length + 1,)),
+            accum[2*nb_bits + nb_bins:])
+
+
+def _budget_slot_blocks(codec):
+    """What `_BudgetSlot` and `_TiledBudgetSlot` hold alike: the step's budgets, the choice and the coder's table, on the device and
+    in pinned memory -> (pinned_budgets, budgets_host, budgets, budgets_nbytes, select, upper, point, flags, pinned_select,
+    select_host, table, points_table, exception_rows, pinned_rows, rows_host)."""
+    (batch_size, nb_maps, device, ladder) = (codec.batch_size, codec.nb_maps, codec.device, codec.ladder)
+    (nb_points, length) = (ladder.nb_points, ladder.truncated_unary_length)
+    # the step's budgets: written by `BudgetCodec._stage` into pinned memory, fetched by a kernel inside the step's chain
+    padded = batch_size + batch_size % 2                       # `device.fetch_prefix` copies multiples of 16 bytes
+    pinned_budgets = torch.zeros(padded, dtype=torch.int64).pin_memory()
+    budgets = torch.zeros(padded, dtype=torch.int64, device=device)
+    budgets_nbytes = torch.full((1,), 8*padded, dtype=torch.int64, device=device)
+    # what the selection leaves for the host: [upper int64 N x K | point int32 N | flags int32 N]
+    select = torch.zeros(2*batch_size*nb_points + 2*batch_size, dtype=torch.int32, device=device)
+    upper = select[:2*batch_size*nb_points].view(torch.int64).view(batch_size, nb_points)
+    point = select[2*batch_size*nb_points:2*batch_size*nb_points + batch_size]
+    flags = select[2*batch_size*nb_points + batch_size:]
+    pinned_select = torch.zeros(select.numel(), dtype=torch.int32).pin_memory()
+    (upper_host, point_host, flags_host) = torch.split(pinned_select, [2*batch_size*nb_points, batch_size, batch_size])
+    # what the result worker reads (`_BudgetWorker._finish`)
+    select_host = (upper_host.view(torch.int64).view(batch_size, nb_points).numpy(), point_host.numpy(), flags_host.numpy())
+    # the coder's table: [the K x 128 rows of the ladder | one row per image for its exception map]
+    table = torch.zeros((nb_points*nb_maps + batch_size, length), dtype=torch.float64, device=device)
+    points_table = table[:nb_points*nb_maps]
+    points_table.copy_(torch.from_numpy(ladder.binary_probabilities_points.reshape(nb_points*nb_maps, length)))
+    pinned_rows = torch.zeros((batch_size, length), dtype=torch.float64).pin_memory()
+    return (pinned_budgets, pinned_budgets.numpy(), budgets, budgets_nbytes, select, upper, point, flags, pinned_select, select_host, table,
+            points_table, table[nb_points*nb_maps:], pinned_rows, pinned_rows.numpy())
 
 
 class _BudgetSlot(object):
@@ -2290,37 +2334,14 @@ class _BudgetSlot(object):
                  'pinned_rows', 'rows_host')
 
     def __init__(self, codec):
-        (batch_size, nb_maps, device, ladder) = (codec.batch_size, codec.nb_maps, codec.device, codec.ladder)
-        (nb_points, length) = (ladder.nb_points, ladder.truncated_unary_length)
-        # the ladder's accumulators, zeroed by one launch at the head of every step: [bypass bits int64 | histograms int32 | range errors int32]
-        (nb_bits, nb_bins) = (batch_size*nb_points*nb_maps, batch_size*nb_points*nb_maps*(length + 1))
-        self.accum = torch.zeros(2*nb_bits + nb_bins + nb_points, dtype=torch.int32, device=device)
-        self.bypass_bits = self.accum[:2*nb_bits].view(torch.int64).view(batch_size, nb_points, nb_maps)
-        self.hist = self.accum[2*nb_bits:2*nb_bits + nb_bins].view(batch_size, nb_points, nb_maps, length + 1)
-        self.range_errors = self.accum[2*nb_bits + nb_bins:]
-        # the step's budgets: written by `BudgetCodec._stage` into pinned memory, fetched by a kernel inside the step's chain
-        padded = batch_size + batch_size % 2                       # `device.fetch_prefix` copies multiples of 16 bytes
-        self.pinned_budgets = torch.zeros(padded, dtype=torch.int64).pin_memory()
-        self.budgets_host = self.pinned_budgets.numpy()
-        self.budgets = torch.zeros(padded, dtype=torch.int64, device=device)
-        self.budgets_nbytes = torch.full((1,), 8*padded, dtype=torch.int64, device=device)
-        # what `device.ladder_select` leaves for the host: [upper int64 N x K | point int32 N | flags int32 N]
-        self.select = torch.zeros(2*batch_size*nb_points + 2*batch_size, dtype=torch.int32, device=device)
-        self.upper = self.select[:2*batch_size*nb_points].view(torch.int64).view(batch_size, nb_points)
-        self.point = self.select[2*batch_size*nb_points:2*batch_size*nb_points + batch_size]
-        self.flags = self.select[2*batch_size*nb_points + batch_size:]
-        self.prob_row = torch.zeros((batch_size, nb_maps), dtype=torch.int32, device=device)
-        self.pinned_select = torch.zeros(self.select.numel(), dtype=torch.int32).pin_memory()
-        (upper_host, point_host, flags_host) = torch.split(self.pinned_select, [2*batch_size*nb_points, batch_size, batch_size])
-        # the coder's table: [the K x 128 rows of the ladder | one row per image for its exception map]
-        self.table = torch.zeros((nb_points*nb_maps + batch_size, length), dtype=torch.float64, device=device)
-        self.points_table = self.table[:nb_points*nb_maps]
-        self.points_table.copy_(torch.from_numpy(ladder.binary_probabilities_points.reshape(nb_points*nb_maps, length)))
-        self.exception_rows = self.table[nb_points*nb_maps:]
-        self.pinned_rows = torch.zeros((batch_size, length), dtype=torch.float64).pin_memory()
-        self.rows_host = self.pinned_rows.numpy()
-        # what the result worker reads (`_BudgetWorker._finish`)
-        self.select_host = (upper_host.view(torch.int64).view(batch_size, nb_points).numpy(), point_host.numpy(), flags_host.numpy())
+        (batch_size, nb_maps, ladder) = (codec.batch_size, codec.nb_maps, codec.ladder)
+        (self.accum, self.bypass_bits, self.hist, self.range_errors) = _ladder_accumulators(
+            (batch_size, ladder.nb_points, nb_maps), ladder.nb_points, ladder.truncated_unary_length, codec.device)
+        (self.pinned_budgets, self.budgets_host, self.budgets, self.budgets_nbytes, self.select, self.upper, self.point, self.flags,
+         self.pinned_select, self.select_host, self.table, self.points_table, self.exception_rows, self.pinned_rows,
+         self.rows_host) = _budget_slot_blocks(codec)
+        # the coder's row of every map of the step, chosen by `device.ladder_select`
+        self.prob_row = torch.zeros((batch_size, nb_maps), dtype=torch.int32, device=codec.device)
 
 
 class _BudgetHead(object):
@@ -2356,6 +2377,8 @@ class BudgetCodec(BatchCodec):
     """`BatchCodec` with a rate point per image, chosen inside the step, on the device, so that the image's blob fits a byte budget
     (DESIGN.md section 19): "N bytes per image" as a property of a step of the resident codec."""
     (_ticket_class, _worker_class) = (BudgetTicket, _BudgetWorker)
+    # what `TiledBudgetCodec` flips: whether `coding_tile` is taken, and the class of the per-step state beyond `_Slot`
+    (_takes_coding_tile, _budget_slot_class) = (False, _BudgetSlot)
 
     def __init__(self, variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, budget_bytes=None, **batch_codec_options):
         """ladder: a `ratecontrol.RateLadder`, finest point first, of at most `device.ladder_max_points(L)` points. budget_bytes: the
@@ -2377,7 +2400,7 @@ class BudgetCodec(BatchCodec):
         options = dict(batch_codec_options)
         if not options.pop('emit_container', True):
             raise ValueError('`BudgetCodec` always emits containers: the budget is that of the image\'s blob.')
-        if options.get('coding_tile') is not None:
+        if options.get('coding_tile') is not None and not self._takes_coding_tile:
             raise ValueError('`BudgetCodec` does not take `coding_tile`: the bounds are those of whole maps (EAE1).')
         if options.get('fuse_latent'):
             raise ValueError('`BudgetCodec` does not take `fuse_latent`: the point is chosen between conv_3 and the quantiser.')
@@ -2395,13 +2418,17 @@ class BudgetCodec(BatchCodec):
                              '(`device.ladder_max_points`).'.format(ladder.nb_points, dev.ladder_max_points(length), length))
         self.ladder = ladder
         self._default_budgets = None if budget_bytes is None else self._budgets_of(budget_bytes, batch_size)
-        self._header_bytes = ratecontrol.header_bytes(ladder)
         # (the base class's own rate point, which no launch of this class reads, is the ladder's first)
         super(BudgetCodec, self).__init__(variables, are_bin_widths_learned, ladder.bin_widths_points[0], ladder.map_mean,
                                           ladder.binary_probabilities_points[0], ladder.idx_map_exception, batch_size, h_in, w_in,
                                           emit_container=True, **options)
         try:
             to_device = lambda array: torch.from_numpy(numpy.ascontiguousarray(array)).to(self.device)
+            self._header_bytes = ratecontrol.header_bytes(ladder, h_in, w_in, self.coding_tile)
+            if self._tile_layout is not None:
+                # `device.ladder_select_tiles`: the image of every (image, tile) entry in the run order the coder takes them in
+                tiled = self._tile_layout
+                self._entry_image = to_device(numpy.array([tiled['entries'][p][0] for p in tiled['payload_entry'].tolist()], dtype=numpy.int32))
             self._bin_widths_points = to_device(ladder.bin_widths_points)
             # (32-bit words: torch has no arithmetic on uint32, and none is asked of it)
             self._fixed_costs = to_device(ratecontrol.fixed_costs(ladder).view(numpy.int32))
@@ -2409,7 +2436,7 @@ class BudgetCodec(BatchCodec):
             self._budget_slots = {}
             fixed = (bool(are_bin_widths_learned), 1, h_in, w_in, self.idx_map_exception, ladder)
             for slot in self._slots:
-                budget_slot = _BudgetSlot(self)
+                budget_slot = self._budget_slot_class(self)
                 self._budget_slots[id(slot)] = budget_slot
                 slot.emit_host = (_BudgetHead(fixed, budget_slot, self._header_bytes),) + slot.emit_host[1:]
             self._staged = None
@@ -2456,22 +2483,16 @@ class BudgetCodec(BatchCodec):
         v = enc.v
         d = self.decoder.v
         budget = self._budget_slots[id(slot)]
-        length = self.truncated_unary_length
-        budget.accum.zero_()                              # the ladder's accumulators: the head of the step
+        budget.accum.zero_()                             # the ladder's accumulators: the head of the step
         gdn_1 = hook('conv1_gdn1', lambda: dev.conv9x9s4_u8(luminances_uint8, enc.w1, v['encoder/biases_1'], enc.g[1], v['encoder/beta_1']))
         ws = slot.conv_ws
         gdn_2 = hook('conv2_gdn2', lambda: dev.conv5x5s2(gdn_1, enc.w2, v['encoder/biases_2'], dev.NORM_GDN, enc.g[2], v['encoder/beta_2'], workspace=ws))
         y = hook('conv3', lambda: dev.conv5x5s2(gdn_2, enc.w3, v['encoder/biases_3'], dev.NORM_NONE, workspace=ws))
         if not self.learned:
             y = hook('gdn3', lambda: dev.gdn(y, enc.g[3], v['encoder/beta_3']))
-        hook('ladder', lambda: dev.ladder_histograms(y, self._bin_widths_points, self.map_mean, length,
-                                                     out=(budget.hist, budget.bypass_bits, budget.range_errors)))
+        hook('ladder', lambda: self._launch_ladder(y, budget))
         dev.fetch_prefix(budget.pinned_budgets, budget.budgets, budget.budgets_nbytes)
-        hook('select', lambda: dev.ladder_select(budget.hist, budget.bypass_bits, self._fixed_costs, self._log2_tables, self.idx_map_exception,
-                                                 self._header_bytes, self.map_size, budget.budgets[:self.batch_size],
-                                                 self.ladder.nb_points*self.nb_maps,
-                                                 out={'point': budget.point, 'prob_row': budget.prob_row, 'upper': budget.upper,
-                                                      'flags': budget.flags}))
+        hook('select', lambda: self._launch_select(budget))
         igdn_out = None if self.learned else (self.decoder.g[4], d['decoder/beta_4'])
         q = hook('latent', lambda: dev.latent_quantize_rows(y, self._bin_widths_points, budget.point, self.map_mean, igdn_out=igdn_out,
                                                             want_shifted=self.learned, want_symbols=True, want_flags=True,
@@ -2483,6 +2504,15 @@ class BudgetCodec(BatchCodec):
             first = 4*self._n_streams
             dev.publish_to_host(slot.out[first:], slot.pinned_out[first:])
         return q['shifted'] if self.learned else q['t']
+
+    def _launch_ladder(self, y, budget):
+        dev.ladder_histograms(y, self._bin_widths_points, self.map_mean, self.truncated_unary_length,
+                              out=(budget.hist, budget.bypass_bits, budget.range_errors))
+
+    def _launch_select(self, budget):
+        dev.ladder_select(budget.hist, budget.bypass_bits, self._fixed_costs, self._log2_tables, self.idx_map_exception, self._header_bytes,
+                          self.map_size, budget.budgets[:self.batch_size], self.ladder.nb_points*self.nb_maps,
+                          out={'point': budget.point, 'prob_row': budget.prob_row, 'upper': budget.upper, 'flags': budget.flags})
 
     def _launch_coder(self, slot, hook=_no_hook):
         """`BatchCodec._launch_coder` over the table of every point's rows with the rows `ladder_select` chose, and the publication
@@ -2498,9 +2528,86 @@ class BudgetCodec(BatchCodec):
                                                             workspace=slot.workspace))
         dev.coder_index_streams(slot.coder_streams, self.nb_maps, self.container_capacity_bytes, offsets=slot.offsets, index=slot.index)
         dev.coder_pack_indexed(slot.coder_streams, slot.offsets, slot.index, slot.payload)
+        self._publish_coder_side(slot, budget)
+
+    def _publish_coder_side(self, slot, budget):
+        """The payload's prefix, the index words, the choice and the exception rows into pinned memory, then the step counter."""
         dev.publish_prefix(slot.payload, slot.pinned_payload, slot.payload_bytes)
         dev.publish_to_host(slot.emit_tail, slot.pinned_emit)
         dev.publish_to_host(budget.select, budget.pinned_select)
         if self.idx_map_exception >= 0:
             dev.publish_to_host(budget.exception_rows, budget.pinned_rows)
         dev.publish_step(slot.out, slot.pinned_out, 4*self._n_streams, *slot.coder_seq)
+
+
+# ---- the same for tile-indexed containers: counts, bounds and streams per coding tile (DESIGN.md section 20) ------------------------
+
+class _TiledBudgetSlot(object):
+    """What one `TiledBudgetCodec` step in flight owns beyond its `_Slot`: `_BudgetSlot`'s state with the ladder's accumulators per
+    coding tile and the coder's rows per stream of the step. Made once; tests/tiled_budget_slot_buffers.py says what a step may find
+    in every attribute when it starts. The accumulators take N K T 128 (L + 1) 4 bytes per slot (and an eleventh of that for the
+    bypass bits): 7.3 MB at 24 Kodak images, K = 9 and tiles of 16, 29 MB at tiles of 8."""
+    __slots__ = ('accum', 'hist', 'bypass_bits', 'range_errors', 'pinned_budgets', 'budgets_host', 'budgets', 'budgets_nbytes', 'select',
+                 'upper', 'point', 'flags', 'prob_row', 'class_rows', 'pinned_select', 'select_host', 'table', 'points_table',
+                 'exception_rows', 'pinned_rows', 'rows_host')
+
+    def __init__(self, codec):
+        (batch_size, nb_maps, ladder, tiled) = (codec.batch_size, codec.nb_maps, codec.ladder, codec._tile_layout)
+        (self.accum, self.bypass_bits, self.hist, self.range_errors) = _ladder_accumulators(
+            (batch_size, ladder.nb_points, tiled['nb_tiles'], nb_maps), ladder.nb_points, ladder.truncated_unary_length, codec.device)
+        (self.pinned_budgets, self.budgets_host, self.budgets, self.budgets_nbytes, self.select, self.upper, self.point, self.flags,
+         self.pinned_select, self.select_host, self.table, self.points_table, self.exception_rows, self.pinned_rows,
+         self.rows_host) = _budget_slot_blocks(codec)
+        # the coder's row of every stream of the step in RUN order, chosen by `device.ladder_select_tiles`, and every shape class's run
+        self.prob_row = torch.zeros(tiled['n_streams'], dtype=torch.int32, device=codec.device)
+        self.class_rows = [self.prob_row[first:first + count*nb_maps] for (_, count, first, _) in tiled['runs']]
+
+
+class TiledBudgetCodec(BudgetCodec):
+    """`BudgetCodec` for tile-indexed containers: a byte budget per image whose blob is the single-image `EAT1`
+    blob `container.encode_images(..., coding_tile=coding_tile)` writes, so that crops come out of it (`container.decode_region`,
+    `RegionDecoder`) and its serial chains are a tile long."""
+    (_takes_coding_tile, _budget_slot_class) = (True, _TiledBudgetSlot)
+
+    def __init__(self, variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, coding_tile, budget_bytes=None, **batch_codec_options):
+        """coding_tile: (th, tw) in latents, clamped to the latent plane, as `BatchCodec(coding_tile=...)` takes it; everything else
+        as `BudgetCodec`. Refused in front of every allocation: `fuse_latent`, a coder other than 'device', `coder_chunks` > 1, a
+        ladder longer than `device.ladder_max_points(L)`, and `batch_size` times the tiles of an image beyond 65535.
+        The step counts per (image, point, tile, map) (`device.ladder_histograms_tiles`), bounds every image's `EAT1` blob at every
+        point with every tile stream's own closing bits and byte padding (`device.ladder_select_tiles`:
+        ratecontrol.upper_bounds_fixed_tiles) and codes the tiles with the rows of the image's point. `Ticket.result()` has
+        `BudgetCodec`'s keys, 'coder_bits' summed over an image's tiles; `Ticket.image_containers()[i]` is byte for byte
+        `container.encode_images(image i, ..., coding_tile=coding_tile)` at `rate_point[i]`; `Ticket.container()` raises."""
+        coding_tile = container_format._positive_pair(coding_tile, '`coding_tile`')
+        super(TiledBudgetCodec, self).__init__(variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, budget_bytes=budget_bytes,
+                                               coding_tile=coding_tile, **batch_codec_options)
+
+    def _launch_ladder(self, y, budget):
+        plane = y.view(self.batch_size, self.h_in//csts.STRIDE_PROD, self.w_in//csts.STRIDE_PROD, self.nb_maps)
+        dev.ladder_histograms_tiles(plane, self._bin_widths_points, self.coding_tile, self.map_mean, self.truncated_unary_length,
+                                    out=(budget.hist, budget.bypass_bits, budget.range_errors))
+
+    def _launch_select(self, budget):
+        dev.ladder_select_tiles(budget.hist, budget.bypass_bits, self._fixed_costs, self._log2_tables, self.idx_map_exception,
+                                self._header_bytes, self.map_size, budget.budgets[:self.batch_size], self._entry_image,
+                                self.ladder.nb_points*self.nb_maps,
+                                out={'point': budget.point, 'prob_row': budget.prob_row, 'upper': budget.upper, 'flags': budget.flags})
+
+    def _launch_coder(self, slot, hook=_no_hook):
+        """`BatchCodec._launch_coder` in tiles over the table of every point's rows: every shape class with its run of the rows
+        `ladder_select_tiles` chose, then the index, one pack per class and the publication of the choice, on the current stream."""
+        budget = self._budget_slots[id(slot)]
+        length = self.truncated_unary_length
+        if self.idx_map_exception >= 0:
+            dev.exception_rows(slot.hist, slot.overflow, self.map_size, length, out=budget.exception_rows)
+        if slot.gathered.data_ptr() != slot.symbols.data_ptr():
+            dev.tile_symbols_gather(slot.symbols, slot.gathered, self._tile_plan, self._tile_plan_host, self.h_in//csts.STRIDE_PROD,
+                                    self.w_in//csts.STRIDE_PROD)
+        for ((streams, tiles, _, _), rows) in zip(slot.classes, budget.class_rows):
+            hook('coder_encode', lambda: dev.coder_encode_batch(tiles, budget.table, rows, length, out=streams, workspace=slot.workspace))
+            hook('coder_decode', lambda: dev.coder_decode_batch(streams, budget.table, rows, expected=tiles, workspace=slot.workspace))
+        dev.coder_index_tiles(slot.results[0], slot.results[1], self._tile_table, self.nb_maps, self._tile_layout['nb_tiles'],
+                              self.container_capacity_bytes, offsets=slot.offsets, index=slot.index)
+        for (streams, _, _, offsets) in slot.classes:
+            dev.coder_pack_indexed(streams, offsets, slot.index, slot.payload)
+        self._publish_coder_side(slot, budget)

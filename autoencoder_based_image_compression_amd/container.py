@@ -60,6 +60,7 @@ _HEADER = struct.Struct('<4sHHIIIHBBi')
 TILE_MAGIC = b'EAT1'
 TILE_VERSION = 1
 _TILE_HEADER = struct.Struct('<4sHHIIIHBBiHH')
+TILES_PER_CALL = 64            # (image, tile) entries the coder takes per group by default: bounds its streams and workspace
 
 
 def _exception_rows(symbols_planar, idx_map_exception, truncated_unary_length):
@@ -174,7 +175,7 @@ def assemble_image_blobs(are_bin_widths_learned, nb_images, height, width, idx_m
 
 
 def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_probabilities, idx_map_exception=-1, tile=None,
-                  coding_tile=None, tiles_per_call=64):
+                  coding_tile=None, tiles_per_call=TILES_PER_CALL):
     """uint8 (N, H, W) or (N, H, W, 1) luminance images -> (blob bytes, info dict).
 
     encoder: pipeline.DeviceEncoder of the model; bin_widths_test float32 (128,) (the trained bin widths times the
@@ -221,7 +222,7 @@ def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_p
     return _encode_entries(symbols, fields, nb_images if coding_tile is None else tiles_per_call)
 
 
-def encode_images_to_budget(luminances_uint8, encoder, ladder, budget_bytes, tile=None):
+def encode_images_to_budget(luminances_uint8, encoder, ladder, budget_bytes, tile=None, coding_tile=None):
     """uint8 (N, H, W) or (N, H, W, 1) luminance images -> (blobs, info): every image compressed into at most `budget_bytes` bytes
     (a scalar, or one value per image) at the first rate point of `ladder` (ratecontrol.RateLadder, finest first) at which it fits.
 
@@ -235,8 +236,11 @@ def encode_images_to_budget(luminances_uint8, encoder, ladder, budget_bytes, til
     points coded for the image; 'fits' bool (N,); 'upper_bound_misses': points whose upper bound was within the budget and whose
     blob was not (expected 0: the allowances of ratecontrol.py are measured, not proven).
     An image whose symbols leave int16 at every point raises the AssertionError of `encode_images`.
-    tile=(th, tw): as in `encode_images`. Not in this function: coding tiles (EAT1: a tile's termination and byte padding need
-    counts per tile), and codec.BatchCodec, which takes one rate point per codec (codec.BudgetCodec chooses one per image inside
+    tile=(th, tw): as in `encode_images`.
+    coding_tile=(th, tw) latents: single-image EAT1 blobs instead, byte for byte `encode_images(..., coding_tile=coding_tile)[0]` at
+    the image's point. A tile's termination and byte padding need counts per tile: the one pass is
+    `device.ladder_histograms_tiles`, the bounds those of `ratecontrol.blob_byte_bounds(..., coding_tile)`.
+    Not in this function: codec.BatchCodec, which takes one rate point per codec (codec.BudgetCodec chooses one per image inside
     the step, on the upper bound alone: DESIGN.md section 19)."""
     from . import ratecontrol
     images = numpy.ascontiguousarray(luminances_uint8)
@@ -255,10 +259,19 @@ def encode_images_to_budget(luminances_uint8, encoder, ladder, budget_bytes, til
     y = encoder(torch.from_numpy(images).to(device), tile=tile)
     mean = torch.from_numpy(ladder.map_mean).to(device)
     bin_widths_points = torch.from_numpy(ladder.bin_widths_points).to(device)
-    (hist, bypass_bits, _) = dev.ladder_histograms(y, bin_widths_points, mean, length)
-    (hist, bypass_bits) = (hist.cpu().numpy(), bypass_bits.cpu().numpy())
-    (lower, upper) = ratecontrol.blob_byte_bounds(hist, bypass_bits, ladder, height, width)
-    valid = ratecontrol.valid_points(hist, (height//csts.STRIDE_PROD)*(width//csts.STRIDE_PROD))
+    map_size = (height//csts.STRIDE_PROD)*(width//csts.STRIDE_PROD)
+    if coding_tile is None:
+        (hist, bypass_bits, _) = dev.ladder_histograms(y, bin_widths_points, mean, length)
+        (hist, bypass_bits) = (hist.cpu().numpy(), bypass_bits.cpu().numpy())
+        (lower, upper) = ratecontrol.blob_byte_bounds(hist, bypass_bits, ladder, height, width)
+        valid = ratecontrol.valid_points(hist, map_size)
+    else:
+        coding_tile = _clamped_coding_tile(coding_tile, height, width)
+        plane = y.view(nb_images, height//csts.STRIDE_PROD, width//csts.STRIDE_PROD, -1)
+        (hist, bypass_bits, _) = dev.ladder_histograms_tiles(plane, bin_widths_points, coding_tile, mean, length)
+        (hist, bypass_bits) = (hist.cpu().numpy(), bypass_bits.cpu().numpy())
+        (lower, upper) = ratecontrol.blob_byte_bounds(hist, bypass_bits, ladder, height, width, coding_tile)
+        valid = ratecontrol.valid_points(hist.astype(numpy.int64).sum(axis=2), map_size)
     coded = {}
 
     def size_of(i, k):
@@ -268,8 +281,8 @@ def encode_images_to_budget(luminances_uint8, encoder, ladder, budget_bytes, til
         e = ladder.idx_map_exception
         rows = _exception_rows(q['symbols'], e, length) if e >= 0 else numpy.zeros((0, length), dtype=numpy.float64)
         fields = _fields(encoder.are_bin_widths_learned, 1, height, width, e, ladder.bin_widths_points[k], ladder.map_mean,
-                         ladder.binary_probabilities_points[k], rows)
-        coded[(i, k)] = _encode_entries(q['symbols'], fields, 1)[0]
+                         ladder.binary_probabilities_points[k], rows, coding_tile)
+        coded[(i, k)] = _encode_entries(q['symbols'], fields, 1 if coding_tile is None else TILES_PER_CALL)[0]
         return len(coded[(i, k)])
 
     info = ratecontrol.select_rate_points(lower, upper, valid, budgets, size_of)
@@ -375,7 +388,7 @@ def _require_kind(header, decoder):
         raise ValueError('The container was written by the other kind of model (learned / fixed bin widths).')
 
 
-def decode_images(blob, decoder, tile=None, tiles_per_call=64):
+def decode_images(blob, decoder, tile=None, tiles_per_call=TILES_PER_CALL):
     """blob + pipeline.DeviceDecoder of the model -> uint8 (N, H, W) reconstructions (BT.601 range, tools.py:61-93).
     tile=(th, tw): run the synthesis transform through windows (pipeline.DeviceDecoder.__call__): same reconstruction.
     EAT1 blobs are decoded in groups of `tiles_per_call` coding tiles, scattered and dequantised into the latent plane; the whole
@@ -705,7 +718,7 @@ def _all_entries(header, blob):
     return plan['entries'], [view[a:b] for (a, b) in plan['ranges']]
 
 
-def decode_tile_symbols(blob, device='cuda', tiles_per_call=64):
+def decode_tile_symbols(blob, device='cuda', tiles_per_call=TILES_PER_CALL):
     """An EAT1 (or EAE1) blob -> (header, symbols): symbols[i][t] = int16 [128, rows, cols] (device) of image i, coding tile t
     (row-major; an EAE1 blob has one tile per map), arithmetic decoding only."""
     header = read_header(blob)
@@ -722,7 +735,7 @@ def decode_tile_symbols(blob, device='cuda', tiles_per_call=64):
     return header, out
 
 
-def decode_region(source, decoder, region, images=None, tile=None, tiles_per_call=64):
+def decode_region(source, decoder, region, images=None, tile=None, tiles_per_call=TILES_PER_CALL):
     """The pixels region = (y0, x0, height, width) of `images` (indices, default all) -> uint8 [N_sel, height, width], equal to
     decode_images(...)[images, y0:y0 + height, x0:x0 + width]. `source`: a bytes-like blob or a seekable binary file object, of
     which only the header and the byte ranges region_plan names are read (fetch_region). Only the coding tiles that meet the

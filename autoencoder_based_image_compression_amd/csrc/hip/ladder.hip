@@ -21,6 +21,25 @@
 // bit count and two LDS adds: about 40 vector instructions per (latent, point), 26 M wave-instructions at K = 9 over 1024 SIMDs,
 // 45 us and more at four cycles each. The divisions bind, not the HBM read. Measured (profiles/rate_ladder.md): 22 / 38 / 84 us at
 // K = 1 / 3 / 9, 7.7 us per point.
+//
+// Tiles (eae_hip_ladder_histograms_tiles). The same counts per coding tile of th x tw latents: hist
+// [N][K][T][128][L + 1], bypass_bits [N][K][T][128], T tiles row-major. The LDS array and the lane-is-a-channel layout stay; what
+// changes is which pixels a block owns: tw consecutive pixels per row over th rows, walked in the tile's raster order, four pixels
+// at a time. A block's LDS holds ONE set of counts (60 KB at K = 9), so a block serves one tile at a time and flushes K (L + 1) 128
+// words per tile it touches. The launcher decides per shape:
+//   * fewer tiles than two blocks per compute unit (24 images, tiles of 16: 144 tiles for 512 blocks): a tile is cut into chunks of
+//     whole pixel rows of the block, as many as fill the grid, none below LADDER_MIN_PIXELS -- three chunks of 88 / 88 / 80 pixels
+//     there, 432 blocks, a flush per 85 pixels where the whole-map kernel flushes per 76;
+//   * that many tiles or more (tiles of 8: 576): whole tiles, dealt evenly to two blocks per compute unit, a block flushing after
+//     each and finding its arrays zero again (the flush clears what it adds). 64 pixels per flush is the floor of the whole-map
+//     kernel too; below it (edge tiles, tiles of 4) the flush leads: 12.7 K LDS words read per tile at K = 9, L = 10 whatever the
+//     tile holds, though only the non-zero ones become atomics.
+// Bound: the divisions, as above -- the same 40 vector instructions per (latent, point); the flush adds K (L + 1) 128 / 512 = 25
+// LDS reads per thread and tile. Zeroing the accumulators is the caller's: N K T 128 (L + 1) 4 bytes, 7.3 MB at 24 Kodak images
+// with tiles of 16, 29 MB with tiles of 8. Measured (profiles/tiled_budget_codec.md; 24 x 32 x 48 latents, K = 9, L = 10, device
+// events, median of 30): 96.9 us with tiles of 16 against 82.5 us for ladder_kernel on the same latents (1.18), 140.3 us with tiles
+// of 8 (1.70): 576 tiles on 512 blocks leave 64 blocks a second tile, 128 pixels where ladder_kernel's block counts 76 -- a second
+// round of work, not the flush. Zeroing 8.6 / 34.5 MB of accumulators: 7.2 / 9.5 us.
 #include "common.h"
 
 namespace {
@@ -29,6 +48,28 @@ constexpr int LADDER_THREADS = LADDER_ROWS * EAE_C;
 constexpr int LADDER_LDS_BYTES = 64 * 1024;         // what one block may ask for
 constexpr int LADDER_MIN_PIXELS = 64;
 constexpr int LADDER_MAX_PIXELS = 1 << 20;          // 34 bypass bits per symbol at most: a block's sums fit 32 bits
+
+// One latent (already centred) of channel c at the K points: its bin and its bypass bits into the block's LDS arrays.
+__device__ __forceinline__ void count_latent(float centered, int c, int k_points, int length, const float* widths, unsigned int* bins,
+                                             unsigned int* bits, unsigned int* __restrict__ range_errors) {
+    const int nb = length + 1;
+#pragma unroll 2
+    for (int k = 0; k < k_points; ++k) {
+        const float bw = widths[k * EAE_C + c];
+        const float r = round_half_even(centered / bw);
+        const float cq = bw * r;
+        const float rs = round_half_even(cq / bw);              // compression.py:142: from cq / bw again, not from r
+        if (!(fabsf(rs) < 32768.f)) {                           // tools.py:130-132: no bin, no bits (rare: straight to memory)
+            if (range_errors) atomicAdd(&range_errors[k], 1u);
+            continue;
+        }
+        const int a = (int)fabsf(rs);
+        atomicAdd(&bins[(k * nb + min(a, length)) * EAE_C + c], 1u);
+        unsigned int b = a != 0 ? 1u : 0u;                      // the sign
+        if (a >= length) b += 2u * (31u - (unsigned int)__clz(a - length + 1)) + 1u;   // Exp-Golomb order 0 of |s| - L
+        if (b) atomicAdd(&bits[k * EAE_C + c], b);
+    }
+}
 
 __global__ __launch_bounds__(LADDER_THREADS) void ladder_kernel(const float* __restrict__ y, const float* __restrict__ map_mean,
                                                                 const float* __restrict__ bin_widths_points, int k_points, int length,
@@ -49,25 +90,8 @@ __global__ __launch_bounds__(LADDER_THREADS) void ladder_kernel(const float* __r
     const int p0 = chunk * pixels;
     const int p1 = min(p0 + pixels, hw);
     const float* yc = y + (size_t)img * hw * EAE_C + c;
-    for (int pix = p0 + row; pix < p1; pix += LADDER_ROWS) {
-        const float centered = yc[(size_t)pix * EAE_C] - m;
-#pragma unroll 2
-        for (int k = 0; k < k_points; ++k) {
-            const float bw = widths[k * EAE_C + c];
-            const float r = round_half_even(centered / bw);
-            const float cq = bw * r;
-            const float rs = round_half_even(cq / bw);              // compression.py:142: from cq / bw again, not from r
-            if (!(fabsf(rs) < 32768.f)) {                           // tools.py:130-132: no bin, no bits (rare: straight to memory)
-                if (range_errors) atomicAdd(&range_errors[k], 1u);
-                continue;
-            }
-            const int a = (int)fabsf(rs);
-            atomicAdd(&bins[(k * nb + min(a, length)) * EAE_C + c], 1u);
-            unsigned int b = a != 0 ? 1u : 0u;                      // the sign
-            if (a >= length) b += 2u * (31u - (unsigned int)__clz(a - length + 1)) + 1u;   // Exp-Golomb order 0 of |s| - L
-            if (b) atomicAdd(&bits[k * EAE_C + c], b);
-        }
-    }
+    for (int pix = p0 + row; pix < p1; pix += LADDER_ROWS)
+        count_latent(yc[(size_t)pix * EAE_C] - m, c, k_points, length, widths, bins, bits, range_errors);
     __syncthreads();
     // flush in the outputs' order, [K][128][L + 1] and [K][128] of this image: consecutive lanes, consecutive addresses
     const int per_point = EAE_C * nb;
@@ -82,6 +106,68 @@ __global__ __launch_bounds__(LADDER_THREADS) void ladder_kernel(const float* __r
         unsigned long long* bb = bypass_bits + (size_t)img * k_points * EAE_C;
         for (int g = tid; g < k_points * EAE_C; g += LADDER_THREADS)
             if (bits[g]) atomicAdd(&bb[g], (unsigned long long)bits[g]);
+    }
+}
+
+// The same counts per coding tile (file header, "Tiles"). An ITEM is chunk `item % cpt` of entry `item / cpt` = image * T + tile:
+// the pixels [chunk * per, (chunk + 1) * per) of the tile's raster (rows x cols of it, cols consecutive pixels per row; an edge
+// tile is smaller and may leave its last chunks empty). A block takes the items [items * b / blocks, items * (b + 1) / blocks)
+// one after the other and flushes after each: the LDS arrays are zero again when the next one starts.
+__global__ __launch_bounds__(LADDER_THREADS) void ladder_tiles_kernel(
+    const float* __restrict__ y, const float* __restrict__ map_mean, const float* __restrict__ bin_widths_points, int k_points, int length,
+    unsigned int* __restrict__ hist, unsigned long long* __restrict__ bypass_bits, unsigned int* __restrict__ range_errors, int h, int w,
+    int th, int tw, int tiles_x, int nb_tiles, int cpt, int per, long items) {
+    extern __shared__ unsigned int lds[];
+    const int nb = length + 1;
+    unsigned int* bins = lds;                                        // [K][L + 1][128]
+    unsigned int* bits = bins + k_points * nb * EAE_C;               // [K][128]
+    float* widths = reinterpret_cast<float*>(bits + k_points * EAE_C);   // [K][128]
+    const int tid = threadIdx.x;
+    const int c = tid & (EAE_C - 1), row = tid >> 7;
+    for (int i = tid; i < k_points * (nb + 1) * EAE_C; i += LADDER_THREADS) lds[i] = 0u;
+    for (int i = tid; i < k_points * EAE_C; i += LADDER_THREADS) widths[i] = bin_widths_points[i];
+    __syncthreads();
+    const float m = map_mean ? map_mean[c] : 0.f;
+    const int per_point = EAE_C * nb;
+    const long first = items * (long)blockIdx.x / (long)gridDim.x, last = items * ((long)blockIdx.x + 1) / (long)gridDim.x;
+    for (long item = first; item < last; ++item) {
+        const int chunk = (int)(item % cpt);
+        const long entry = item / cpt;
+        const int tile = (int)(entry % nb_tiles);
+        const long img = entry / nb_tiles;
+        const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+        const int r0 = ty * th, c0 = tx * tw;
+        const int rows = min(th, h - r0), cols = min(tw, w - c0);
+        const int q0 = chunk * per, q1 = min(q0 + per, rows * cols);
+        if (q0 >= q1) continue;                                      // (the whole block: nothing was counted, nothing to flush)
+        const float* yc = y + (size_t)img * h * w * EAE_C + c;
+        int q = q0 + row;
+        int r = q / cols, col = q - r * cols;
+        for (; q < q1; q += LADDER_ROWS) {
+            count_latent(yc[((size_t)(r0 + r) * w + c0 + col) * EAE_C] - m, c, k_points, length, widths, bins, bits, range_errors);
+            col += LADDER_ROWS;
+            while (col >= cols) { col -= cols; ++r; }
+        }
+        __syncthreads();
+        // flush in the outputs' order, [K][T][128][L + 1] and [K][T][128] of this image, and leave zeros behind
+        for (int g = tid; g < k_points * per_point; g += LADDER_THREADS) {
+            const int k = g / per_point, rem = g - k * per_point;
+            const int ch = rem / nb, bin = rem - ch * nb;
+            const unsigned int v = bins[(k * nb + bin) * EAE_C + ch];
+            if (v) {
+                atomicAdd(&hist[(((size_t)img * k_points + k) * nb_tiles + tile) * per_point + rem], v);
+                bins[(k * nb + bin) * EAE_C + ch] = 0u;
+            }
+        }
+        for (int g = tid; g < k_points * EAE_C; g += LADDER_THREADS) {
+            const unsigned int v = bits[g];
+            if (v) {
+                const int k = g >> 7, ch = g & (EAE_C - 1);
+                if (bypass_bits) atomicAdd(&bypass_bits[(((size_t)img * k_points + k) * nb_tiles + tile) * EAE_C + ch], (unsigned long long)v);
+                bits[g] = 0u;
+            }
+        }
+        __syncthreads();
     }
 }
 }  // namespace
@@ -110,6 +196,40 @@ extern "C" int eae_hip_ladder_histograms(const float* y, const float* map_mean, 
     hipLaunchKernelGGL(ladder_kernel, dim3((unsigned)(n * chunks)), dim3(LADDER_THREADS), lds_bytes, (hipStream_t)stream, y, map_mean,
                        bin_widths_points, k_points, length, hist, reinterpret_cast<unsigned long long*>(bypass_bits), range_errors, hw,
                        (int)chunks, pixels);
+    EAE_HIP_CHECK_LAUNCH();
+    return EAE_HIP_OK;
+}
+
+extern "C" int eae_hip_ladder_histograms_tiles(const float* y, const float* map_mean, const float* bin_widths_points, int k_points,
+                                               int length, uint32_t* hist, uint64_t* bypass_bits, uint32_t* range_errors, int n, int h,
+                                               int w, int th, int tw, void* stream) {
+    if (!y || !bin_widths_points || !hist || n <= 0 || h <= 0 || w <= 0 || th <= 0 || tw <= 0) return EAE_HIP_BAD_ARGUMENT;
+    if (length < 1 || length > 255 || k_points < 1 || k_points > eae_hip_ladder_max_points(length)) return EAE_HIP_BAD_ARGUMENT;
+    if ((long)h * w > 0x3FFFFFFFL) return EAE_HIP_BAD_SHAPE;       // chunk * per, past the last chunk of a tile, stays an int
+    th = th < h ? th : h;                            // container._clamped_coding_tile
+    tw = tw < w ? tw : w;
+    const long tiles_x = (w + tw - 1) / tw, nb_tiles = (long)((h + th - 1) / th) * tiles_x;
+    const long entries = (long)n * nb_tiles;
+    if (entries > 0x7FFFFFFFL) return EAE_HIP_BAD_SHAPE;
+    // Chunks per tile: as many as bring the grid to two blocks per compute unit, none below LADDER_MIN_PIXELS pixels (a whole
+    // number of pixel rows each) or above LADDER_MAX_PIXELS; with that many tiles or more, whole tiles, several per block.
+    int cus = eae_compute_units();
+    if (cus <= 0) cus = 256;
+    const long tile_pixels = (long)th * tw;
+    long cpt = 2L * cus / entries;
+    const long most = (tile_pixels + LADDER_MIN_PIXELS - 1) / LADDER_MIN_PIXELS, least = (tile_pixels + LADDER_MAX_PIXELS - 1) / LADDER_MAX_PIXELS;
+    if (cpt > most) cpt = most;
+    if (cpt < least) cpt = least;
+    int per = (int)((tile_pixels + cpt - 1) / cpt);
+    per = (per + LADDER_ROWS - 1) / LADDER_ROWS * LADDER_ROWS;
+    cpt = (tile_pixels + per - 1) / per;
+    const long items = entries * cpt;
+    if (items > 0x7FFFFFFFL) return EAE_HIP_BAD_SHAPE;
+    const long blocks = items < 2L * cus ? items : 2L * cus;
+    const size_t lds_bytes = (size_t)k_points * (length + 3) * EAE_C * 4;
+    hipLaunchKernelGGL(ladder_tiles_kernel, dim3((unsigned)blocks), dim3(LADDER_THREADS), lds_bytes, (hipStream_t)stream, y, map_mean,
+                       bin_widths_points, k_points, length, hist, reinterpret_cast<unsigned long long*>(bypass_bits), range_errors, h, w, th,
+                       tw, (int)tiles_x, (int)nb_tiles, (int)cpt, per, items);
     EAE_HIP_CHECK_LAUNCH();
     return EAE_HIP_OK;
 }

@@ -593,6 +593,143 @@ def ladder_histograms(y, bin_widths_points, map_mean=None, length=10, out=None):
     return out
 
 
+def _ladder_point_tiles_by_passes(y, bin_widths, map_mean, length, tiles):
+    """One rate point of `ladder_histograms_tiles` without its kernel: the symbols of `quantize_maps` folded per tile on the host ->
+    numpy (hist int64 [N, T, 128, L + 1], bypass bits int64 [N, T, 128], range errors). A point with range errors, whose int16
+    symbols have wrapped, is counted from the quantiser's float32 expressions instead (`_ladder_point_by_passes`). y [N, h, w, 128];
+    tiles: the rows of `container.coding_tile_grid`."""
+    import numpy
+    (n, h, w, c) = y.shape
+    nb_tiles = tiles.shape[0]
+    q = quantize_maps(y, bin_widths, map_mean, want_symbols=True)
+    range_errors = int(q['checks'][0].item())
+    if range_errors:
+        host = y.reshape(n, -1, c).cpu().numpy()
+        bw = bin_widths.cpu().numpy()
+        centered = host - (map_mean.cpu().numpy() if map_mean is not None else numpy.float32(0.))
+        with numpy.errstate(all='ignore'):
+            rs = numpy.abs(numpy.rint(bw*numpy.rint(centered/bw)/bw))
+            good = rs < numpy.float32(32768.)
+        magnitudes = numpy.where(good, rs, 0.).astype(numpy.int64)
+    else:
+        magnitudes = numpy.abs(q['symbols'].cpu().numpy().astype(numpy.int64)).transpose(0, 2, 1)          # [N, hw, 128]
+        good = numpy.ones(magnitudes.shape, dtype=bool)
+    (good, magnitudes) = (good.reshape(n, h, w, c), magnitudes.reshape(n, h, w, c))
+    clipped = numpy.minimum(magnitudes, length)
+    bits = _bypass_bits_of_magnitudes(magnitudes, length)*good
+    hist = numpy.zeros((n, nb_tiles, c, length + 1), dtype=numpy.int64)
+    bypass = numpy.zeros((n, nb_tiles, c), dtype=numpy.int64)
+    for (t, (r0, c0, rows, cols, _)) in enumerate(tiles.tolist()):
+        window = (slice(None), slice(r0, r0 + rows), slice(c0, c0 + cols))
+        for b in range(length + 1):
+            hist[:, t, :, b] = (good[window] & (clipped[window] == b)).sum(axis=(1, 2))
+        bypass[:, t] = bits[window].sum(axis=(1, 2))
+    return hist, bypass, range_errors
+
+
+def ladder_histograms_tiles(y, bin_widths_points, coding_tile, map_mean=None, length=10, out=None):
+    """`ladder_histograms` per coding tile (include/eae_hip.h: eae_hip_ladder_histograms_tiles). y float32
+    [N, h, w, 128]; coding_tile=(th, tw) latents, clamped to the plane as `container.encode_images` clamps it; the T tiles are those
+    of `container.coding_tile_grid(h, w, coding_tile)`, row-major -> (hist int32 [N, K, T, 128, L + 1], bypass_bits int64
+    [N, K, T, 128], range_errors int32 [K]). Summed over T they are `ladder_histograms`' on the same input.
+    A ladder longer than `ladder_max_points(length)` takes several launches; at a length for which not one point fits a launch the
+    same arrays are folded on the host from `quantize_maps` symbols. out: that triple, preallocated, to ACCUMULATE into."""
+    if y.dim() != 4 or y.shape[-1] != NB_MAPS or y.dtype != torch.float32:
+        raise HipError('y must be float32 [N, h, w, 128]')
+    (n, h, w, c) = y.shape
+    d = y.device
+    length = int(length)
+    if bin_widths_points.dtype != torch.float32 or bin_widths_points.dim() != 2 or bin_widths_points.shape[1] != NB_MAPS:
+        raise HipError('bin_widths_points must be float32 [K, 128]')
+    if map_mean is not None and (map_mean.dtype != torch.float32 or map_mean.numel() != NB_MAPS):
+        raise HipError('map_mean must be float32 of 128 elements')
+    if length < 1 or length > 255:
+        raise ValueError('The truncated unary length does not belong to [1, 255].')
+    from . import container                       # (it imports this module; both are loaded by the time anything is called)
+    (th, tw) = container._positive_pair(coding_tile, '`coding_tile`')
+    (th, tw) = (min(th, h), min(tw, w))
+    (tiles, _) = container.coding_tile_grid(h, w, (th, tw))
+    nb_tiles = tiles.shape[0]
+    k_points = bin_widths_points.shape[0]
+    if k_points < 1:
+        raise ValueError('A ladder has at least one rate point.')
+
+    def buffers(points, errors=None):
+        return (torch.zeros((n, points, nb_tiles, c, length + 1), dtype=torch.int32, device=d),
+                torch.zeros((n, points, nb_tiles, c), dtype=torch.int64, device=d),
+                torch.zeros(points, dtype=torch.int32, device=d) if errors is None else errors)
+
+    if out is None:
+        out = buffers(k_points)
+    (hist, bypass_bits, range_errors) = out
+    if (hist.dtype, bypass_bits.dtype, range_errors.dtype) != (torch.int32, torch.int64, torch.int32) \
+            or tuple(hist.shape) != (n, k_points, nb_tiles, c, length + 1) or tuple(bypass_bits.shape) != (n, k_points, nb_tiles, c) \
+            or tuple(range_errors.shape) != (k_points,):
+        raise HipError('`out` must be (int32 [N, K, T, 128, L + 1], int64 [N, K, T, 128], int32 [K])')
+    most = ladder_max_points(length)
+    if most == 0:
+        for k in range(k_points):
+            (hist_k, bits_k, errors_k) = _ladder_point_tiles_by_passes(y, bin_widths_points[k].contiguous(), map_mean, length, tiles)
+            hist[:, k] += torch.from_numpy(hist_k).to(d).to(torch.int32)
+            bypass_bits[:, k] += torch.from_numpy(bits_k).to(d)
+            range_errors[k] += errors_k
+        return out
+    whole = k_points <= most
+    for k0 in range(0, k_points, most):
+        k1 = min(k0 + most, k_points)
+        # a launch writes [N][its points][...]: a part of a longer ladder gets buffers of its own, added into the whole afterwards
+        part = out if whole else buffers(k1 - k0, range_errors[k0:k1])
+        _check(_native.hip().eae_hip_ladder_histograms_tiles(_p(y), _p(map_mean), _p(bin_widths_points[k0:k1]), k1 - k0, length,
+                                                             _p(part[0]), _p(part[1]), _p(part[2]), n, h, w, th, tw, _stream(y)),
+               'eae_hip_ladder_histograms_tiles')
+        if not whole:
+            hist[:, k0:k1] += part[0]
+            bypass_bits[:, k0:k1] += part[1]
+    return out
+
+
+def ladder_select_tiles(hist, bypass_bits, fixed_costs, log2_tables, idx_map_exception, header_bytes, map_size, budgets, entry_image,
+                        exception_row_base, out=None):
+    """`ladder_select` for single-image EAT1 blobs (include/eae_hip.h: eae_hip_ladder_select_tiles; the host rule is
+    ratecontrol.upper_bounds_fixed_tiles + valid_points on the counts summed over the tiles + select_by_upper_bound). hist int32
+    [N, K, T, 128, L + 1] and bypass_bits int64 [N, K, T, 128] as `ladder_histograms_tiles` leaves them; map_size: symbols of a WHOLE
+    map; header_bytes: ratecontrol.header_bytes(ladder, height, width, coding_tile); entry_image int32 [entries] on the device: the
+    image of every (image, tile) entry in the order the coder takes them (`codec.coding_tile_layout`'s run order). The other
+    arguments as `ladder_select`. -> dict: 'point' int32 [N], 'prob_row' int32 [entries, 128], 'upper' int64 [N, K], 'flags' int32
+    [N]. out: that dict, preallocated; every element is written."""
+    if hist.dim() != 5 or hist.shape[3] != NB_MAPS or hist.dtype != torch.int32:
+        raise HipError('hist must be int32 [N, K, T, 128, L + 1]')
+    (n, k_points, nb_tiles, _, nb) = hist.shape
+    length = nb - 1
+    d = hist.device
+    if bypass_bits.dtype != torch.int64 or tuple(bypass_bits.shape) != (n, k_points, nb_tiles, NB_MAPS):
+        raise HipError('bypass_bits must be int64 [N, K, T, 128]')
+    if fixed_costs.element_size() != 4 or fixed_costs.is_floating_point() or fixed_costs.numel() != k_points*NB_MAPS*length*2:
+        raise HipError('fixed_costs must hold K x 128 x L x 2 32-bit words')
+    map_size = int(map_size)
+    if log2_tables is not None and (log2_tables.element_size() != 4 or log2_tables.is_floating_point()
+                                    or log2_tables.numel() != 2*(map_size + 1)):
+        raise HipError('log2_tables must hold 2 x (map_size + 1) 32-bit words')
+    if budgets.dtype != torch.int64 or budgets.numel() != n:
+        raise HipError('budgets must be int64 [N]')
+    if entry_image.dtype != torch.int32 or entry_image.dim() != 1 or entry_image.numel() < 1:
+        raise HipError('entry_image must be int32 [entries]')
+    entries = entry_image.numel()
+    if out is None:
+        out = {'point': torch.empty(n, dtype=torch.int32, device=d), 'prob_row': torch.empty((entries, NB_MAPS), dtype=torch.int32, device=d),
+               'upper': torch.empty((n, k_points), dtype=torch.int64, device=d), 'flags': torch.empty(n, dtype=torch.int32, device=d)}
+    for (name, dtype, count) in (('point', torch.int32, n), ('prob_row', torch.int32, entries*NB_MAPS), ('upper', torch.int64, n*k_points),
+                                 ('flags', torch.int32, n)):
+        if out[name].dtype != dtype or out[name].numel() != count:
+            raise HipError('`out[{0!r}]` must hold {1} elements of {2}'.format(name, count, dtype))
+    _check(_native.hip().eae_hip_ladder_select_tiles(_p(hist), _p(bypass_bits), _p(fixed_costs), _p(log2_tables), k_points, length,
+                                                     int(idx_map_exception), int(header_bytes), map_size, nb_tiles, _p(budgets),
+                                                     _p(entry_image), entries, int(exception_row_base), _p(out['point']),
+                                                     _p(out['prob_row']), _p(out['upper']), _p(out['flags']), n, _stream(hist)),
+           'eae_hip_ladder_select_tiles')
+    return out
+
+
 def ladder_select(hist, bypass_bits, fixed_costs, log2_tables, idx_map_exception, header_bytes, map_size, budgets, exception_row_base,
                   out=None):
     """The rate point of every image for its byte budget, on the device (include/eae_hip.h: eae_hip_ladder_select; the host rule is

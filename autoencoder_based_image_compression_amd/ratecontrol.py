@@ -38,6 +38,7 @@ ALLOWANCE_HIGH = 3
 INTERVAL_SHARE_EXCESS = 2.**-14
 
 _FIXED_HEADER_BYTES = 28          # container._HEADER.size: 'EAE1', version, flags, sizes, L, exception map index
+_TILE_FIELD_BYTES = 4             # container._TILE_HEADER.size - container._HEADER.size: the coding tile of an EAT1 blob, two u16
 
 
 class RateLadder(object):
@@ -139,19 +140,69 @@ def _decisions_and_tables(hist, bypass_bits, ladder):
     return zeros, ones, tables, bypass_bits
 
 
-def header_bytes(ladder):
-    """Bytes in front of the payload of a single-image EAE1 blob written at a point of the ladder (container.py, layout)."""
+def nb_coding_tiles(height, width, coding_tile):
+    """(tiles of a height x width image cut by coding_tile=(th, tw) latents, the tile clamped to the latent plane): the grid of
+    `container.coding_tile_grid`, counted."""
+    if height < 1 or width < 1 or height % 16 != 0 or width % 16 != 0:
+        raise ValueError('The image sizes are not positive multiples of 16.')
+    (th, tw) = (int(coding_tile[0]), int(coding_tile[1]))
+    if th < 1 or tw < 1:
+        raise ValueError('`coding_tile` must be a pair of positive integers.')
+    (h, w) = (height//16, width//16)
+    (th, tw) = (min(th, h), min(tw, w))
+    return (-(-h//th))*(-(-w//tw)), (th, tw)
+
+
+def header_bytes(ladder, height=None, width=None, coding_tile=None):
+    """Bytes in front of the payload of a single-image EAE1 blob written at a point of the ladder (container.py, layout); with
+    coding_tile=(th, tw) latents, of the single-image EAT1 blob of a height x width image: the same fields, the tile, and the index
+    u32 [T][128][2]."""
     length = ladder.truncated_unary_length
-    return _FIXED_HEADER_BYTES + 8*NB_MAPS + 8*NB_MAPS*length + (8*length if ladder.idx_map_exception >= 0 else 0) + 8*NB_MAPS
+    common = _FIXED_HEADER_BYTES + 8*NB_MAPS + 8*NB_MAPS*length + (8*length if ladder.idx_map_exception >= 0 else 0)
+    if coding_tile is None:
+        return common + 8*NB_MAPS
+    if height is None or width is None:
+        raise ValueError('The header of an EAT1 blob depends on the image sizes.')
+    return common + _TILE_FIELD_BYTES + 8*NB_MAPS*nb_coding_tiles(height, width, coding_tile)[0]
 
 
-def blob_byte_bounds(hist, bypass_bits, ladder, height, width):
+def _check_counts_tiles(hist, bypass_bits, ladder):
+    hist = numpy.asarray(hist)
+    bypass_bits = numpy.asarray(bypass_bits)
+    if hist.ndim != 5 or hist.shape[1] != ladder.nb_points or hist.shape[3:] != (NB_MAPS, ladder.truncated_unary_length + 1):
+        raise ValueError('`hist` must be (N, K, T, {}, L + 1) for the K points and the L of the ladder.'.format(NB_MAPS))
+    if bypass_bits.shape != hist.shape[:4]:
+        raise ValueError('`bypass_bits` must be (N, K, T, {}).'.format(NB_MAPS))
+    return hist.astype(numpy.int64), bypass_bits.astype(numpy.int64)
+
+
+def blob_byte_bounds(hist, bypass_bits, ladder, height, width, coding_tile=None):
     """(lower, upper), int64 (N, K): bounds on the size of the single-image EAE1 blob `container.encode_images` would write for
     every image at every point. The header is exact; every map adds its bypass stream, ceil(bits / 8) bytes, exact, and its
     arithmetic-coded stream, between floor(`floor_bits`) - ALLOWANCE_LOW and ceil(`ideal_bits`) + ALLOWANCE_HIGH bits, each rounded up
     to a byte (on a table fitted to the data the two costs are a few bits apart: the comment at ALLOWANCE_LOW).
     height, width: of the images (the histograms must count their (height / 16) * (width / 16) symbols per map, except at a point
-    with range errors, which `valid_points` tells apart)."""
+    with range errors, which `valid_points` tells apart).
+    coding_tile=(th, tw) latents: of the single-image EAT1 blob instead, from the counts per tile `device.ladder_histograms_tiles`
+    leaves, hist (N, K, T, 128, L + 1) and bypass_bits (N, K, T, 128). Every (tile, map) is a pair of streams of its own, so the
+    same costs and the same allowances apply per tile stream (a tile is a map of 1 to 16,384 symbols: what the allowances were
+    measured on); the exception map's row is the one its WHOLE-map counts give, as the blob carries one per image."""
+    if coding_tile is not None:
+        (hist, bypass_bits) = _check_counts_tiles(hist, bypass_bits, ladder)
+        (nb_tiles, _) = nb_coding_tiles(height, width, coding_tile)
+        if hist.shape[2] != nb_tiles:
+            raise ValueError('The histograms are not those of the {} coding tiles of the image.'.format(nb_tiles))
+        if int(hist.sum(axis=(2, -1)).max()) > (height//16)*(width//16):
+            raise ValueError('The histograms count more symbols than a map of a {} x {} image holds.'.format(height, width))
+        (zeros, ones) = decision_counts(hist)                                       # (N, K, T, 128, L)
+        tables = numpy.broadcast_to(ladder.binary_probabilities_points[None, :, None], zeros.shape).copy()
+        e = ladder.idx_map_exception
+        if e >= 0:
+            tables[:, :, :, e] = probabilities_from_counts(zeros[:, :, :, e].sum(axis=2), ones[:, :, :, e].sum(axis=2))[:, :, None]
+        fixed = header_bytes(ladder, height, width, coding_tile) + ((bypass_bits + 7)//8).sum(axis=(-1, -2))
+        low_bits = numpy.maximum(numpy.floor(floor_bits(zeros, ones, tables)).astype(numpy.int64) - ALLOWANCE_LOW, 0)
+        high_bits = numpy.ceil(ideal_bits(zeros, ones, tables)).astype(numpy.int64) + ALLOWANCE_HIGH
+        return fixed + ((low_bits + 7)//8).sum(axis=(-1, -2)), fixed + ((high_bits + 7)//8).sum(axis=(-1, -2))
     (zeros, ones, tables, bypass_bits) = _decisions_and_tables(hist, bypass_bits, ladder)
     if height < 1 or width < 1 or height % 16 != 0 or width % 16 != 0:
         raise ValueError('The image sizes are not positive multiples of 16.')
@@ -274,6 +325,38 @@ def upper_bounds_fixed(hist, bypass_bits, ladder, map_size):
     bits = (fp + (FIXED_ONE - 1)) >> FIXED_SHIFT
     stream_bytes = (bits + (ALLOWANCE_HIGH + 7))//8
     return header_bytes(ladder) + (stream_bytes + (bypass_bits + 7)//8).sum(axis=-1)
+
+
+def upper_bounds_fixed_tiles(hist, bypass_bits, ladder, map_size, header_bytes):
+    """int64 (N, K): `upper_bounds_fixed` for the single-image EAT1 blob, from the counts per coding tile hist (N, K, T, 128, L + 1)
+    and bypass_bits (N, K, T, 128) (`device.ladder_histograms_tiles`); what `eae_hip_ladder_select_tiles` computes, integers only.
+    map_size: symbols of a WHOLE map; header_bytes: `header_bytes(ladder, height, width, coding_tile)`.
+    Per (image, point, tile, map), fp = sum over the decisions of z * c0 + o * c1 (`fixed_costs`) on the tile's own counts; the
+    stream takes ((fp + 2^20 - 1) >> 20) + ALLOWANCE_HIGH bits, rounded up to a byte, the tile's bypass stream ceil(bits / 8) bytes.
+    The exception map keeps ONE row per image, measured on the whole map: with Z, O the whole-map counts of a
+    decision (the sums over the tiles) and T_ = Z + O, a tile's z zeros and o ones of it cost z * (Lceil[T_] - Lfloor[Z]) + o *
+    (Lceil[T_] - Lfloor[O]), o * C99 when Z == 0, z * C99 when O == 0 -- over the tiles that is `upper_bounds_fixed`'s whole-map
+    cost T_ * Lceil[T_] - Z * Lfloor[Z] - O * Lfloor[O].
+    Never below `blob_byte_bounds(..., coding_tile)[1]` and at most a byte per stream above it while map_size * L <= 2^19."""
+    (hist, bypass_bits) = _check_counts_tiles(hist, bypass_bits, ladder)
+    map_size = int(map_size)
+    (zeros, ones) = decision_counts(hist)                                                  # (N, K, T, 128, L)
+    if int(hist.sum(axis=(2, -1)).max()) > map_size:
+        raise ValueError('The histograms count more symbols than a map of {} holds.'.format(map_size))
+    costs = fixed_costs(ladder).astype(numpy.int64)
+    fp = (zeros*costs[None, :, None, :, :, 0] + ones*costs[None, :, None, :, :, 1]).sum(axis=-1)     # (N, K, T, 128)
+    e = ladder.idx_map_exception
+    if e >= 0:
+        tables = log2_tables(map_size).astype(numpy.int64)
+        (z, o) = (zeros[:, :, :, e], ones[:, :, :, e])                                    # (N, K, T, L)
+        (whole_z, whole_o) = (z.sum(axis=2), o.sum(axis=2))                               # (N, K, L)
+        total = tables[0][whole_z + whole_o]
+        cost_zero = numpy.where(whole_z == 0, 0, numpy.where(whole_o == 0, C99, total - tables[1][whole_z]))
+        cost_one = numpy.where(whole_z == 0, C99, numpy.where(whole_o == 0, 0, total - tables[1][whole_o]))
+        fp[:, :, :, e] = (z*cost_zero[:, :, None] + o*cost_one[:, :, None]).sum(axis=-1)
+    bits = (fp + (FIXED_ONE - 1)) >> FIXED_SHIFT
+    stream_bytes = (bits + (ALLOWANCE_HIGH + 7))//8
+    return int(header_bytes) + (stream_bytes + (bypass_bits + 7)//8).sum(axis=(-1, -2))
 
 
 def select_by_upper_bound(upper, valid, budgets):

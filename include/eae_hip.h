@@ -358,6 +358,16 @@ int eae_hip_symbol_histograms_strided(const int16_t* symbols_planar, uint32_t* h
 int eae_hip_ladder_histograms(const float* y, const float* map_mean, const float* bin_widths_points, int k_points, int length,
                               uint32_t* hist, uint64_t* bypass_bits, uint32_t* range_errors, int n, int hw, void* stream);
 int eae_hip_ladder_max_points(int length);
+/* The same counts per coding tile: y [N][h * w][128] is a plane of h x w latents per image, the tile th x tw
+ * latents, clamped to the plane; T = ceil(h / th) * ceil(w / tw) tiles, row-major, edge tiles smaller (container.coding_tile_grid).
+ *   hist uint32 [N][K][T][128][L + 1], bypass_bits uint64 [N][K][T][128] (nullable), range_errors uint32 [K] (nullable)
+ * Symbols, bins, bits and range errors are eae_hip_ladder_histograms'; all three are ACCUMULATED into, and summed over T they are that
+ * function's outputs on the same input. k_points and length as there. NULL y / bin_widths_points / hist, non-positive n, h, w, th or
+ * tw -> EAE_HIP_BAD_ARGUMENT; h * w >= 2^30, or n * T times the chunks a tile is cut into (tile pixels / 64 at the most) >= 2^31 ->
+ * EAE_HIP_BAD_SHAPE. One launch, at most two blocks per compute unit. */
+int eae_hip_ladder_histograms_tiles(const float* y, const float* map_mean, const float* bin_widths_points, int k_points, int length,
+                                    uint32_t* hist, uint64_t* bypass_bits, uint32_t* range_errors, int n, int h, int w, int th, int tw,
+                                    void* stream);
 
 /* ---- a rate point per image, on the device (csrc/hip/budget.hip; ratecontrol.py) ------------------------
  * eae_hip_ladder_select: the point of every image of a batch for its byte budget, from what eae_hip_ladder_histograms left. Integer
@@ -393,6 +403,25 @@ int eae_hip_ladder_select(const uint32_t* hist, const uint64_t* bypass_bits, con
 int eae_hip_latent_quantize_rows(const float* y, const float* map_mean, const float* bin_widths_points, const int32_t* point, int k_points,
                                  const float* gamma_out_packed, const float* beta_out, float* shifted_out, float* t_out,
                                  int16_t* symbols_planar, uint32_t* nonzero_flags, uint32_t* checks, int n, int hw, void* stream);
+/* eae_hip_ladder_select for single-image EAT1 blobs, from what eae_hip_ladder_histograms_tiles left: hist
+ * uint32 [N][K][T][128][L + 1], bypass_bits uint64 [N][K][T][128], T = nb_tiles. Equal, element for element, to
+ * ratecontrol.upper_bounds_fixed_tiles + valid_points (on the counts summed over T) + select_by_upper_bound. Every (tile, map) is a
+ * pair of streams of its own: bytes = (((fp + 2^20 - 1) >> 20) + 3 + 7) / 8 + (bypass + 7) / 8 per tile, fp from the tile's counts.
+ * The exception map keeps ONE row per image, measured on the whole map: with Z, O its whole-map counts of a decision (summed over
+ * the tiles inside, before any tile is priced), a tile's z zeros and o ones cost z (Lceil[Z + O] - Lfloor[Z]) + o (Lceil[Z + O] -
+ * Lfloor[O]); o C99 when Z is 0, z C99 when O is 0. map_size: symbols of a WHOLE map (sizes log2_tables and the validity of a
+ * point); header_bytes: ratecontrol.header_bytes(..., coding_tile); fixed_costs, log2_tables, budgets, exception_row_base, upper,
+ * point, flags as eae_hip_ladder_select.
+ *   entry_image int32 [n_entries], device memory: the image of every entry (image, tile) in the order the coder takes them (the
+ *                          run order of codec.coding_tile_layout); a value outside [0, N) is clamped
+ *   prob_row int32 [n_entries][128]: point[image] * 128 + m; exception_row_base + image for the exception map
+ * Every element of every output is written by every call. Argument checks as eae_hip_ladder_select, and NULL entry_image, nb_tiles or
+ * n_entries < 1 -> EAE_HIP_BAD_ARGUMENT; nb_tiles > map_size, K T 128 (L + 1) or n_entries 128 >= 2^31 -> EAE_HIP_BAD_SHAPE. Two
+ * launches: one block per image, then prob_row. */
+int eae_hip_ladder_select_tiles(const uint32_t* hist, const uint64_t* bypass_bits, const uint32_t* fixed_costs, const uint32_t* log2_tables,
+                                int k_points, int length, int idx_map_exception, int64_t header_bytes, int map_size, int nb_tiles,
+                                const int64_t* budgets, const int32_t* entry_image, int n_entries, int exception_row_base, int32_t* point,
+                                int32_t* prob_row, int64_t* upper, uint32_t* flags, int n, void* stream);
 
 /* ---- lossless coder on the device: one feature map per lane --------------------------------------------------------
  * Replaces the per-map compress_lossless loop of lossless/compression.py:76-81 (and, underneath it,
