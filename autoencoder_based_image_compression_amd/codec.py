@@ -2297,10 +2297,11 @@ def _ladder_accumulators(counts_shape, nb_points, length, device):
             accum[2*nb_bits + nb_bins:])
 
 
-def _budget_slot_blocks(codec):
-    """What `_BudgetSlot` and `_TiledBudgetSlot` hold alike: the step's budgets, the choice and the coder's table, on the device and
-    in pinned memory -> (pinned_budgets, budgets_host, budgets, budgets_nbytes, select, upper, point, flags, pinned_select,
-    select_host, table, points_table, exception_rows, pinned_rows, rows_host)."""
+def _budget_slot_blocks(codec, extra_words=0):
+    """What `_BudgetSlot`, `_TiledBudgetSlot` and `_QualitySlot` hold alike: the step's budgets, the choice and the coder's table, on
+    the device and in pinned memory -> (pinned_budgets, budgets_host, budgets, budgets_nbytes, select, upper, point, flags,
+    pinned_select, select_host, table, points_table, exception_rows, pinned_rows, rows_host). extra_words: 32-bit words behind `flags`
+    in `select` and `pinned_select`, on an 8-byte boundary, for what a slot publishes together with the selection."""
     (batch_size, nb_maps, device, ladder) = (codec.batch_size, codec.nb_maps, codec.device, codec.ladder)
     (nb_points, length) = (ladder.nb_points, ladder.truncated_unary_length)
     # the step's budgets: written by `BudgetCodec._stage` into pinned memory, fetched by a kernel inside the step's chain
@@ -2309,12 +2310,12 @@ def _budget_slot_blocks(codec):
     budgets = torch.zeros(padded, dtype=torch.int64, device=device)
     budgets_nbytes = torch.full((1,), 8*padded, dtype=torch.int64, device=device)
     # what the selection leaves for the host: [upper int64 N x K | point int32 N | flags int32 N]
-    select = torch.zeros(2*batch_size*nb_points + 2*batch_size, dtype=torch.int32, device=device)
+    select = torch.zeros(2*batch_size*nb_points + 2*batch_size + extra_words, dtype=torch.int32, device=device)
     upper = select[:2*batch_size*nb_points].view(torch.int64).view(batch_size, nb_points)
     point = select[2*batch_size*nb_points:2*batch_size*nb_points + batch_size]
-    flags = select[2*batch_size*nb_points + batch_size:]
+    flags = select[2*batch_size*nb_points + batch_size:2*batch_size*nb_points + 2*batch_size]
     pinned_select = torch.zeros(select.numel(), dtype=torch.int32).pin_memory()
-    (upper_host, point_host, flags_host) = torch.split(pinned_select, [2*batch_size*nb_points, batch_size, batch_size])
+    (upper_host, point_host, flags_host, _) = torch.split(pinned_select, [2*batch_size*nb_points, batch_size, batch_size, extra_words])
     # what the result worker reads (`_BudgetWorker._finish`)
     select_host = (upper_host.view(torch.int64).view(batch_size, nb_points).numpy(), point_host.numpy(), flags_host.numpy())
     # the coder's table: [the K x 128 rows of the ladder | one row per image for its exception map]
@@ -2479,10 +2480,14 @@ class BudgetCodec(BatchCodec):
         """conv1+GDN1 -> conv2+GDN2 -> conv3 -> gdn_3 -> the ladder's histograms -> the step's budgets -> the point of every image
         -> the quantiser with every image's own bin widths (+ inverse_gdn_4) -> exception-map histograms, on the current stream.
         Everything that varies from step to step travels through device memory: no argument of any launch depends on it."""
+        budget = self._budget_slots[id(slot)]
+        y = self._launch_selection(luminances_uint8, slot, budget, hook)
+        return self._launch_quantiser(y, slot, budget, hook)
+
+    def _launch_selection(self, luminances_uint8, slot, budget, hook):
+        """`_launch_analysis` up to the point of every image; returns the latents the quantiser sees."""
         enc = self.encoder
         v = enc.v
-        d = self.decoder.v
-        budget = self._budget_slots[id(slot)]
         budget.accum.zero_()                             # the ladder's accumulators: the head of the step
         gdn_1 = hook('conv1_gdn1', lambda: dev.conv9x9s4_u8(luminances_uint8, enc.w1, v['encoder/biases_1'], enc.g[1], v['encoder/beta_1']))
         ws = slot.conv_ws
@@ -2493,6 +2498,11 @@ class BudgetCodec(BatchCodec):
         hook('ladder', lambda: self._launch_ladder(y, budget))
         dev.fetch_prefix(budget.pinned_budgets, budget.budgets, budget.budgets_nbytes)
         hook('select', lambda: self._launch_select(budget))
+        return y
+
+    def _launch_quantiser(self, y, slot, budget, hook):
+        """`_launch_analysis` from the quantiser on, at `budget.point`; returns the synthesis transform's input."""
+        d = self.decoder.v
         igdn_out = None if self.learned else (self.decoder.g[4], d['decoder/beta_4'])
         q = hook('latent', lambda: dev.latent_quantize_rows(y, self._bin_widths_points, budget.point, self.map_mean, igdn_out=igdn_out,
                                                             want_shifted=self.learned, want_symbols=True, want_flags=True,
@@ -2611,3 +2621,192 @@ class TiledBudgetCodec(BudgetCodec):
         for (streams, _, _, offsets) in slot.classes:
             dev.coder_pack_indexed(streams, offsets, slot.index, slot.payload)
         self._publish_coder_side(slot, budget)
+
+
+# ---- a PSNR floor per image, searched on the device ----------------------------------------------------------
+
+class _QualitySlot(object):
+    """What one `QualityCodec` step in flight owns beyond its `_Slot`: `_BudgetSlot`'s state -- its `point` is called `first` here,
+    the finest point the search may take --, the step's thresholds, the bisection's state and trace behind the selection in `select`
+    (published with it), the accumulator and the latent buffer of the probes. Made once; tests/quality_slot_buffers.py says what a
+    step may find in every attribute when it starts."""
+    __slots__ = ('accum', 'hist', 'bypass_bits', 'range_errors', 'pinned_budgets', 'budgets_host', 'budgets', 'budgets_nbytes', 'select',
+                 'upper', 'first', 'flags', 'prob_row', 'pinned_select', 'select_host', 'table', 'points_table', 'exception_rows',
+                 'pinned_rows', 'rows_host', 'pinned_max_sse', 'max_sse_host', 'max_sse', 'max_sse_nbytes', 'trace_sse', 'point', 'met',
+                 'state', 'trace_point', 'search_host', 'probe_acc', 'probe_latent')
+
+    def __init__(self, codec):
+        (batch_size, nb_maps, ladder, device) = (codec.batch_size, codec.nb_maps, codec.ladder, codec.device)
+        nb_rounds = codec.nb_rounds
+        (self.accum, self.bypass_bits, self.hist, self.range_errors) = _ladder_accumulators(
+            (batch_size, ladder.nb_points, nb_maps), ladder.nb_points, ladder.truncated_unary_length, device)
+        # behind [upper | first | flags]: [trace_sse int64 N x R | point int32 N | met int32 N | state int32 N x 2 | trace_point int32 N x R]
+        layout = [2*batch_size*nb_rounds, batch_size, batch_size, 2*batch_size, batch_size*nb_rounds]
+        (self.pinned_budgets, self.budgets_host, self.budgets, self.budgets_nbytes, self.select, self.upper, self.first, self.flags,
+         self.pinned_select, self.select_host, self.table, self.points_table, self.exception_rows, self.pinned_rows,
+         self.rows_host) = _budget_slot_blocks(codec, extra_words=sum(layout))
+        own = self.select.numel() - sum(layout)
+        (trace_sse, self.point, self.met, state, trace_point) = torch.split(self.select[own:], layout)
+        self.trace_sse = trace_sse.view(torch.int64).view(batch_size, nb_rounds)
+        self.state = state.view(batch_size, 2)
+        self.trace_point = trace_point.view(batch_size, nb_rounds)
+        (trace_sse, point, met, state, trace_point) = torch.split(self.pinned_select[own:], layout)
+        # what the result worker reads (`_QualityWorker._finish`): (point, met, trace_point, trace_sse)
+        self.search_host = (point.numpy(), met.numpy(), trace_point.view(batch_size, nb_rounds).numpy(),
+                            trace_sse.view(torch.int64).view(batch_size, nb_rounds).numpy())
+        # the step's thresholds: written by `QualityCodec._stage` into pinned memory, fetched by a kernel inside the step's chain
+        padded = batch_size + batch_size % 2                       # `device.fetch_prefix` copies multiples of 16 bytes
+        self.pinned_max_sse = torch.zeros(padded, dtype=torch.int64).pin_memory()
+        self.max_sse_host = self.pinned_max_sse.numpy()
+        self.max_sse = torch.zeros(padded, dtype=torch.int64, device=device)
+        self.max_sse_nbytes = torch.full((1,), 8*padded, dtype=torch.int64, device=device)
+        # the coder's row of every map of the step: `device.ladder_select`'s, then every round's of `device.quality_search`
+        self.prob_row = torch.zeros((batch_size, nb_maps), dtype=torch.int32, device=device)
+        # what a probe's `tconv9x9s4_luma` adds its squared errors into, and what its quantiser writes for its synthesis pass
+        self.probe_acc = torch.zeros(batch_size, dtype=torch.int64, device=device)
+        self.probe_latent = torch.empty((batch_size, codec.h_in//csts.STRIDE_PROD, codec.w_in//csts.STRIDE_PROD, nb_maps), dtype=torch.float32,
+                                        device=device)
+
+
+class _QualityWorker(_Worker):
+    """The result worker of `QualityCodec`."""
+
+    def _finish(self, job):
+        """The step's search out of the slot's pinned blocks into the ticket, while the slot is still the step's."""
+        (ticket, head) = (job.ticket, job.emit[0])
+        quality = head.budget_slot
+        (upper, first, _) = quality.select_host
+        (point, met, trace_point, trace_sse) = quality.search_host
+        n = ticket.nb_images
+        budgets = quality.budgets_host[:n].copy()
+        rate_point = point[:n].astype(numpy.int64)
+        upper = upper[:n].copy()
+        blob_bytes = head.header_bytes + ticket._values['container_bytes']
+        ticket._values.update({'rate_point': rate_point, 'first_point': first[:n].astype(numpy.int64), 'met': (met[:n] & 1) != 0,
+                               'max_sse': quality.max_sse_host[:n].copy(), 'probe_points': trace_point[:n].astype(numpy.int64),
+                               'probe_sse': trace_sse[:n].copy(), 'upper_bound_bytes': upper, 'budget_bytes': budgets,
+                               'blob_bytes': blob_bytes, 'promised': upper[numpy.arange(n), rate_point] <= budgets,
+                               'fits': blob_bytes <= budgets})
+        parts = ticket._container_parts
+        parts['head'] = head.fixed
+        parts['rate_point'] = rate_point
+        if self.idx_map_exception >= 0:
+            parts['rows'] = head.budget_slot.rows_host.copy()
+
+
+class QualityCodec(BudgetCodec):
+    """`BudgetCodec` with the rate point of every image found inside the step, on the device, so that the image keeps a PSNR floor at
+    the smallest size the ladder allows: "this much quality per image" as a property of a step of the
+    resident codec."""
+    (_ticket_class, _worker_class) = (BudgetTicket, _QualityWorker)
+    (_takes_coding_tile, _budget_slot_class) = (False, _QualitySlot)
+    NO_BUDGET = 1 << 62            # what a step without a budget stages: every valid point's bound is within it
+
+    def __init__(self, variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, target_psnr=None, max_sse=None, budget_bytes=None,
+                 **batch_codec_options):
+        """ladder, batch_codec_options: as `BudgetCodec`; `coding_tile`, `fuse_latent`, a coder other than 'device' and `coder_chunks`
+        > 1 are refused. target_psnr (dB) or max_sse (the largest squared error against the input, an integer): the threshold of a
+        `submit` that names none, a scalar or one value per image, at most one of the two; target_psnr becomes
+        `ratecontrol.max_sse_for_psnr(target_psnr, h_in*w_in)`. budget_bytes: the budget of a `submit` that names none; None: no budget.
+        Per image the step bisects the ladder, in `ratecontrol.quality_rounds(K)` rounds, for the COARSEST point whose squared error
+        against the input is within the threshold (`ratecontrol.select_by_quality`; the squared error is assumed not to decrease along
+        the ladder, which is not checked), starting from the point `BudgetCodec` takes for the budget -- without a budget the first
+        point whose symbols fit int16 --: quality is met at the smallest size, inside the budget where there is one. An image whose
+        finest allowed point misses the threshold is coded at that point and reported in 'met'. A round quantises every image at its
+        probe point, runs the synthesis transform and takes the exact squared error; the point finally taken is then quantised, coded
+        and synthesised as in `BudgetCodec`.
+        `Ticket.result()` has `BudgetCodec`'s keys and 'met' bool (N,), 'max_sse' int64 (N,), 'probe_points' and 'probe_sse' int64
+        (N, R) (what every round probed and found) and 'first_point' int64 (N,) (the finest point the search could take);
+        'rate_point' is the point taken, 'promised' says upper_bound_bytes[i, rate_point[i]] <= budget, 'budget_bytes' is 2^62
+        without a budget. `Ticket.image_containers()[i]` is byte for byte `container.encode_images` of image i at its point;
+        `Ticket.container()` raises."""
+        from . import ratecontrol
+        if not isinstance(ladder, ratecontrol.RateLadder):
+            raise TypeError('`ladder` is not a `ratecontrol.RateLadder`.')
+        # refused in front of every allocation
+        if batch_codec_options.get('coding_tile') is not None:
+            raise ValueError('`QualityCodec` does not take `coding_tile`: the coder\'s rows per stream would need the run order of '
+                             '`device.ladder_select_tiles`.')
+        self.nb_rounds = ratecontrol.quality_rounds(ladder.nb_points)
+        self._nb_pixels = h_in*w_in
+        self._default_max_sse = self._max_sse_of(target_psnr, max_sse, batch_size)
+        super(QualityCodec, self).__init__(variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, budget_bytes=budget_bytes,
+                                           **batch_codec_options)
+
+    def _max_sse_of(self, target_psnr, max_sse, batch_size):
+        """The thresholds of a step as int64 (batch_size,), from one of the two ways to name them; None when neither is given."""
+        from . import ratecontrol
+        if target_psnr is not None and max_sse is not None:
+            raise ValueError('give `target_psnr` or `max_sse`, not both.')
+        if target_psnr is not None:
+            targets = numpy.asarray(target_psnr, dtype=numpy.float64)
+            if targets.ndim > 1 or (targets.ndim == 1 and targets.shape[0] != batch_size):
+                raise ValueError('`target_psnr` must be a number or one number per image.')
+            max_sse = ratecontrol.max_sse_for_psnr(targets, self._nb_pixels)
+        if max_sse is None:
+            return None
+        thresholds = numpy.asarray(max_sse)
+        if thresholds.dtype.kind not in 'iu' or thresholds.ndim > 1 or (thresholds.ndim == 1 and thresholds.shape[0] != batch_size):
+            raise ValueError('`max_sse` must be an integer or one integer per image.')
+        return numpy.ascontiguousarray(numpy.broadcast_to(thresholds.astype(numpy.int64), (batch_size,)))
+
+    def submit(self, luminances_uint8, target_psnr=None, max_sse=None, budget_bytes=None):
+        """`BatchCodec.submit` with the step's thresholds (`target_psnr` or `max_sse`, a scalar or one value per image; neither: the
+        constructor's) and budgets (None: the constructor's `budget_bytes`; none there either: no budget)."""
+        if target_psnr is None and max_sse is None:
+            thresholds = self._default_max_sse
+            if thresholds is None:
+                raise ValueError('neither `target_psnr` nor `max_sse`, and the codec was built without a default.')
+        else:
+            thresholds = self._max_sse_of(target_psnr, max_sse, self.batch_size)
+        budgets = self._default_budgets if budget_bytes is None else self._budgets_of(budget_bytes, self.batch_size)
+        if budgets is None:
+            budgets = numpy.full(self.batch_size, self.NO_BUDGET, dtype=numpy.int64)
+        self._staged = (budgets, thresholds)
+        try:
+            return BatchCodec.submit(self, luminances_uint8)
+        finally:
+            self._staged = None
+
+    def _stage(self, slot):
+        """The step's budgets and thresholds into the slot's pinned blocks (the slot is this step's: `_submit` has claimed it)."""
+        quality = self._budget_slots[id(slot)]
+        (quality.budgets_host[:self.batch_size], quality.max_sse_host[:self.batch_size]) = self._staged
+
+    def _launch_select(self, budget):
+        dev.ladder_select(budget.hist, budget.bypass_bits, self._fixed_costs, self._log2_tables, self.idx_map_exception, self._header_bytes,
+                          self.map_size, budget.budgets[:self.batch_size], self.ladder.nb_points*self.nb_maps,
+                          out={'point': budget.first, 'prob_row': budget.prob_row, 'upper': budget.upper, 'flags': budget.flags})
+
+    def _launch_round(self, quality, round):
+        dev.quality_search(quality.first, quality.max_sse[:self.batch_size], quality.state, quality.probe_acc, quality.point, quality.prob_row,
+                           quality.trace_point, quality.trace_sse, quality.met, self.ladder.nb_points, round, self.idx_map_exception,
+                           self.ladder.nb_points*self.nb_maps)
+
+    def _launch_analysis(self, luminances_uint8, slot, hook):
+        """`BudgetCodec._launch_analysis` with the search between the point for the budget and the quantiser: ... -> the point of every
+        image for its budget (`first`) -> the step's thresholds -> round 0 -> R times [the quantiser at every image's probe point (no
+        symbols, flags or checks) -> tconv1+IGDN5 -> tconv2+IGDN6 -> tconv3 + BT.601 cast + squared error against the input -> round
+        r] -> the quantiser at the point taken -> exception-map histograms, on the current stream. A linear chain whose launches
+        and arguments are the same every step: the rounds differ by a scalar, the step's contents travel through device memory."""
+        quality = self._budget_slots[id(slot)]
+        y = self._launch_selection(luminances_uint8, slot, quality, hook)
+        dev.fetch_prefix(quality.pinned_max_sse, quality.max_sse, quality.max_sse_nbytes)
+        hook('search', lambda: self._launch_round(quality, 0))
+        dec = self.decoder
+        d = dec.v
+        ws = slot.conv_ws                         # the slot's: its error word, collected behind the synthesis side, covers the probes
+        igdn_out = None if self.learned else (dec.g[4], d['decoder/beta_4'])
+        (out_shifted, out_t) = (quality.probe_latent, None) if self.learned else (None, quality.probe_latent)
+        for r in range(1, self.nb_rounds + 1):
+            hook('probe_latent', lambda: dev.latent_quantize_rows(y, self._bin_widths_points, quality.point, self.map_mean, igdn_out=igdn_out,
+                                                                  want_shifted=self.learned, want_symbols=False, want_checks=False,
+                                                                  out_shifted=out_shifted, out_t=out_t))
+            t = hook('probe_tconv1_igdn5', lambda: dev.tconv5x5s2(quality.probe_latent, dec.w4, d['decoder/biases_4'], dev.NORM_IGDN, dec.g[5],
+                                                                  d['decoder/beta_5'], workspace=ws))
+            t = hook('probe_tconv2_igdn6', lambda: dev.tconv5x5s2(t, dec.w5, d['decoder/biases_5'], dev.NORM_IGDN, dec.g[6], d['decoder/beta_6'],
+                                                                  workspace=ws))
+            hook('probe_tconv3', lambda: dev.tconv9x9s4_luma(t, dec.w6, want_f32=False, want_u8=False, ref_u8=luminances_uint8,
+                                                             sse=quality.probe_acc))
+            hook('search', lambda: self._launch_round(quality, r))
+        return self._launch_quantiser(y, slot, quality, hook)

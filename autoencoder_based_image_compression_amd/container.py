@@ -290,6 +290,82 @@ def encode_images_to_budget(luminances_uint8, encoder, ladder, budget_bytes, til
     return [coded[(i, int(info['rate_point'][i]))] for i in range(nb_images)], info
 
 
+def encode_images_to_quality(luminances_uint8, encoder, decoder, ladder, target_psnr=None, max_sse=None, budget_bytes=None):
+    """uint8 (N, H, W) or (N, H, W, 1) luminance images -> (blobs, info): every image at the COARSEST rate point of `ladder`
+    (ratecontrol.RateLadder, finest first) that keeps its PSNR at `target_psnr` dB or better -- its squared error against the input
+    within `max_sse`; give one of the two, a scalar or one value per image. The synchronous sibling of `encode_images_to_budget`
+    and the host loop `codec.QualityCodec` runs on the device.
+
+    One analysis transform; then per image the bisection of ratecontrol.select_by_quality, a point's squared error found by
+    quantising at it, decoding with `decoder` (pipeline.DeviceDecoder of the model) and `device.sse_u8`; only the point taken is
+    coded. budget_bytes (a scalar or one value per image): the search starts at the point `ratecontrol.select_by_upper_bound` takes
+    for the budget on `ratecontrol.upper_bounds_fixed`, the rule of `codec.BudgetCodec`, and goes to the coarsest; None: at the first
+    point whose symbols fit int16. The squared error is assumed not to decrease along the ladder (select_by_quality).
+    blobs: one single-image EAE1 blob per image, byte for byte `encode_images(images[i:i + 1], encoder, bin_widths_k, map_mean,
+    table_k, idx_map_exception)[0]` for its point k.
+    info: 'rate_point' int64 (N,), 'met' bool (N,), 'probe_points' and 'probe_sse' int64 (N, R) (select_by_quality's), 'max_sse'
+    int64 (N,), 'first_point' int64 (N,), 'blob_bytes' int64 (N,), 'upper_bound_bytes' int64 (N, K)."""
+    from . import ratecontrol
+    images = numpy.ascontiguousarray(luminances_uint8)
+    if images.dtype != numpy.uint8:
+        raise TypeError('`luminances_uint8.dtype` is not equal to `numpy.uint8`.')
+    if images.ndim == 4:
+        images = images[:, :, :, 0]
+    if not isinstance(ladder, ratecontrol.RateLadder):
+        raise TypeError('`ladder` is not a `ratecontrol.RateLadder`.')
+    (nb_images, height, width) = images.shape
+    if (target_psnr is None) == (max_sse is None):
+        raise ValueError('give `target_psnr` or `max_sse`, one of the two.')
+    if target_psnr is not None:
+        max_sse = ratecontrol.max_sse_for_psnr(numpy.asarray(target_psnr, dtype=numpy.float64), height*width)
+    thresholds = numpy.asarray(max_sse)
+    if thresholds.dtype.kind not in 'iu' or thresholds.ndim > 1 or (thresholds.ndim == 1 and thresholds.shape[0] != nb_images):
+        raise ValueError('`target_psnr` / `max_sse` must be a scalar or one value per image (`max_sse` an integer).')
+    thresholds = numpy.ascontiguousarray(numpy.broadcast_to(thresholds.astype(numpy.int64), (nb_images,)))
+    (nb_points, length) = (ladder.nb_points, ladder.truncated_unary_length)
+    device = encoder.device
+    references = torch.from_numpy(images).to(device)
+    y = encoder(references)
+    mean = torch.from_numpy(ladder.map_mean).to(device)
+    bin_widths_points = torch.from_numpy(ladder.bin_widths_points).to(device)
+    map_size = (height//csts.STRIDE_PROD)*(width//csts.STRIDE_PROD)
+    (hist, bypass_bits, _) = dev.ladder_histograms(y, bin_widths_points, mean, length)
+    (hist, bypass_bits) = (hist.cpu().numpy(), bypass_bits.cpu().numpy())
+    upper = ratecontrol.upper_bounds_fixed(hist, bypass_bits, ladder, map_size)
+    budgets = 1 << 62 if budget_bytes is None else budget_bytes
+    (first, _) = ratecontrol.select_by_upper_bound(upper, ratecontrol.valid_points(hist, map_size), budgets)
+
+    rounds = ratecontrol.quality_rounds(nb_points)
+    info = {'rate_point': numpy.zeros(nb_images, dtype=numpy.int64), 'met': numpy.zeros(nb_images, dtype=bool),
+            'probe_points': numpy.zeros((nb_images, rounds), dtype=numpy.int64), 'probe_sse': numpy.zeros((nb_images, rounds), dtype=numpy.int64),
+            'max_sse': thresholds, 'first_point': first, 'blob_bytes': numpy.zeros(nb_images, dtype=numpy.int64), 'upper_bound_bytes': upper}
+    e = ladder.idx_map_exception
+    blobs = []
+    for i in range(nb_images):
+        known = {}
+
+        def sse_of(k):
+            if k not in known:
+                q = dev.quantize_maps(y[i:i + 1], bin_widths_points[k], mean, want_shifted=True)
+                (_, decoded, _) = decoder(q['shifted'])
+                known[k] = int(dev.sse_u8(decoded, references[i:i + 1]).item())
+            return known[k]
+
+        (k, info['met'][i], info['probe_points'][i], info['probe_sse'][i]) = ratecontrol.bisect_by_quality(sse_of, nb_points, int(first[i]),
+                                                                                                           int(thresholds[i]))
+        info['rate_point'][i] = k
+        # the coding stage of `encode_images` on the latents at hand (as `encode_images_to_budget` codes a point)
+        q = dev.quantize_maps(y[i:i + 1], bin_widths_points[k], mean, want_symbols=True)
+        if int(q['checks'][0].item()) != 0:
+            raise AssertionError('The rounded array elements cannot be represented as 16-bit signed integers.')
+        rows = _exception_rows(q['symbols'], e, length) if e >= 0 else numpy.zeros((0, length), dtype=numpy.float64)
+        fields = _fields(encoder.are_bin_widths_learned, 1, height, width, e, ladder.bin_widths_points[k], ladder.map_mean,
+                         ladder.binary_probabilities_points[k], rows)
+        blobs.append(_encode_entries(q['symbols'], fields, 1)[0])
+        info['blob_bytes'][i] = len(blobs[i])
+    return blobs, info
+
+
 def _fixed_header(fixed, total_length):
     """Checks the fixed part of the header of either format (`fixed`: the first bytes of the blob or file, `total_length`: the length
     of all of it) -> (fields, bytes of the fixed part, bytes of the whole header). Everything that sizes a read or an allocation is

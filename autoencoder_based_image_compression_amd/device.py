@@ -767,13 +767,35 @@ def ladder_select(hist, bypass_bits, fixed_costs, log2_tables, idx_map_exception
     return out
 
 
+def quality_search(first, max_sse, state, probe_acc, point, prob_row, trace_point, trace_sse, flags, k_points, round, idx_map_exception,
+                   exception_row_base):
+    """One round of the bisection for a PSNR floor per image, on the device (include/eae_hip.h: eae_hip_quality_search; the host rule
+    is ratecontrol.select_by_quality). All tensors are preallocated device memory: first int32 [N], max_sse int64 [N], state int32
+    [N, 2], probe_acc int64 [N] (what `tconv9x9s4_luma` adds the probe's squared errors into), point int32 [N], prob_row int32
+    [N, 128], trace_point int32 [N, R], trace_sse int64 [N, R], flags int32 [N], R = ratecontrol.quality_rounds(k_points). round:
+    0..R, the only argument that differs between the R + 1 calls of a step."""
+    n = first.numel()
+    nb_rounds = int(k_points).bit_length()
+    for (name, t, dtype, count) in (('first', first, torch.int32, n), ('max_sse', max_sse, torch.int64, n), ('state', state, torch.int32, 2*n),
+                                    ('probe_acc', probe_acc, torch.int64, n), ('point', point, torch.int32, n),
+                                    ('prob_row', prob_row, torch.int32, n*NB_MAPS), ('trace_point', trace_point, torch.int32, n*nb_rounds),
+                                    ('trace_sse', trace_sse, torch.int64, n*nb_rounds), ('flags', flags, torch.int32, n)):
+        if t.dtype != dtype or t.numel() != count:
+            raise HipError('`{0}` must hold {1} elements of {2}'.format(name, count, dtype))
+    _check(_native.hip().eae_hip_quality_search(_p(first), _p(max_sse), _p(state), _p(probe_acc), _p(point), _p(prob_row), _p(trace_point),
+                                                _p(trace_sse), _p(flags), int(k_points), nb_rounds, int(round), int(idx_map_exception),
+                                                int(exception_row_base), n, _stream(first)), 'eae_hip_quality_search')
+
+
 def latent_quantize_rows(y, bin_widths_points, point, map_mean=None, igdn_out=None, want_shifted=False, want_symbols=True,
-                         want_flags=False, out_symbols=None, out_flags=None, out_checks=None):
+                         want_flags=False, out_symbols=None, out_flags=None, out_checks=None, want_checks=True, out_shifted=None,
+                         out_t=None):
     """The quantiser half of `latent_stage` with one row of bin widths per image (include/eae_hip.h: eae_hip_latent_quantize_rows):
     y [N, h, w, 128] (or [N, hw, 128]) are the latents after gdn_3, image i is quantised with bin_widths_points[point[i]] (float32
     [K, 128]; point int32 [N] on the device, clamped to [0, K)). Returns `latent_stage`'s dict without 'y'; image i's part equals
     `latent_stage(y[i:i + 1], bin_widths_points[point[i]], map_mean, gdn_in=None, igdn_out=igdn_out)` bit for bit. out_* buffers:
-    preallocated, flags / checks already zeroed (see quantize_maps)."""
+    preallocated, flags / checks already zeroed (see quantize_maps). want_checks=False: no check is counted ('checks': None).
+    out_shifted / out_t: preallocated float32 outputs of y's size (a probe of `codec.QualityCodec` owns its latent buffer)."""
     n = y.shape[0]
     c = y.shape[-1]
     hw = y.numel()//(n*c)
@@ -786,16 +808,19 @@ def latent_quantize_rows(y, bin_widths_points, point, map_mean=None, igdn_out=No
         raise HipError('point must be int32 [N]')
     if map_mean is not None and (map_mean.dtype != torch.float32 or map_mean.numel() != NB_MAPS):
         raise HipError('map_mean must be float32 of 128 elements')
-    shifted = torch.empty_like(y) if want_shifted else None
-    t = torch.empty_like(y) if igdn_out is not None else None
+    for (name, out) in (('out_shifted', out_shifted), ('out_t', out_t)):
+        if out is not None and (out.dtype != torch.float32 or out.numel() != y.numel()):
+            raise HipError('`{0}` must be a float32 tensor of the size of y'.format(name))
+    shifted = (out_shifted if out_shifted is not None else torch.empty_like(y)) if want_shifted else None
+    t = (out_t if out_t is not None else torch.empty_like(y)) if igdn_out is not None else None
     symbols = (out_symbols if out_symbols is not None else torch.empty((n, c, hw), dtype=torch.int16, device=d)) if want_symbols else None
     if symbols is not None and (symbols.dtype != torch.int16 or symbols.numel() != n*c*hw):
         raise TypeError('`out_symbols` must be an int16 tensor of N x C x hw elements.')
     flags = (out_flags if out_flags is not None else torch.zeros((n, c), dtype=torch.int32, device=d)) if want_flags else None
     if flags is not None and flags.numel() != n*c:
         raise HipError('`out_flags` must hold N x 128 words')
-    checks = out_checks if out_checks is not None else torch.zeros(3, dtype=torch.int32, device=d)
-    if checks.numel() < 3:
+    checks = (out_checks if out_checks is not None else torch.zeros(3, dtype=torch.int32, device=d)) if want_checks else None
+    if checks is not None and checks.numel() < 3:
         raise HipError('`out_checks` must hold three words')
     (g_out, b_out) = igdn_out if igdn_out is not None else (None, None)
     _check(_native.hip().eae_hip_latent_quantize_rows(_p(y), _p(map_mean), _p(bin_widths_points), _p(point), bin_widths_points.shape[0],

@@ -2,7 +2,9 @@
 (DESIGN.md section 18). Host side, numpy only; the one device call is `device.ladder_histograms`, made by the callers
 (`container.encode_images_to_budget`, `kodak.lossless.stats.compute_binary_probabilities_ladder`), which hand its outputs in here
 as numpy arrays. The second half of the file is the rule of `codec.BudgetCodec`: the same upper bound in integer
-arithmetic, which `eae_hip_ladder_select` restates on the device element for element, and the choice on that bound alone.
+arithmetic, which `eae_hip_ladder_select` restates on the device element for element, and the choice on that bound alone. The end of
+the file is the rule of `codec.QualityCodec`: a PSNR floor as an integer bound on the squared error, and the
+bisection of the ladder for the coarsest point that keeps it, which `eae_hip_quality_search` restates round by round.
 
 A rate point is a pair: 128 bin widths and a table of binary probabilities (the reference walks nine, `multipliers` of
 reconstructing_eae_kodak.py, and learns a point's cost by quantising and coding at it). The coder's cost is a function of the
@@ -383,3 +385,100 @@ def select_by_upper_bound(upper, valid, budgets):
         promised[i] = fitting.size != 0
         rate_point[i] = fitting[0] if fitting.size else candidates[-1]
     return rate_point, promised
+
+
+# ---- the rule of `codec.QualityCodec`: the coarsest point per image that keeps a PSNR floor, in integers -----
+# PSNR >= T is sse <= max_sse for an integer max_sse the host derives once per threshold (`max_sse_for_psnr`); the search itself
+# compares integers only, so the device (`eae_hip_quality_search`) reaches the choice below element for element.
+MAX_SSE_SATURATION = 1 << 62      # where `max_sse_for_psnr` stops: no image has a squared error near it (255^2 per pixel)
+
+
+def _psnr_meets(sse, nb_pixels, target_psnr):
+    """`tls.psnr_from_sse(sse, nb_pixels) >= target_psnr`, a squared error of 0 meeting every target (psnr_from_sse raises there)."""
+    from .kodak.tools import tools as tls
+    return sse == 0 or bool(tls.psnr_from_sse(sse, nb_pixels) >= target_psnr)
+
+
+def max_sse_for_psnr(target_psnr, nb_pixels):
+    """The largest integer s >= 0 with `tls.psnr_from_sse(s, nb_pixels) >= target_psnr`, int64; s = 0 meets every target. Scalars
+    or arrays (broadcast against each other). The closed form floor(255^2 nb_pixels 10^(-T / 10)) is only the start: s is stepped
+    by one until psnr_from_sse, in the float64 expression it has, meets the target at s and misses it at s + 1, so that `sse <= s` and
+    `psnr_from_sse(sse) >= T` are the same statement for every integer sse. Saturates at MAX_SSE_SATURATION = 2^62 (a target no
+    image can miss). A target that is not finite raises ValueError; one that only s = 0 meets gives 0."""
+    targets = numpy.asarray(target_psnr, dtype=numpy.float64)
+    pixels = numpy.asarray(nb_pixels)
+    if not numpy.isfinite(targets).all():
+        raise ValueError('`target_psnr` is not finite.')
+    if pixels.dtype.kind not in 'iu' or (pixels < 1).any():
+        raise ValueError('`nb_pixels` must be a positive integer.')
+    (targets, pixels) = numpy.broadcast_arrays(targets, pixels)
+    out = numpy.zeros(targets.shape, dtype=numpy.int64)
+    for index in numpy.ndindex(targets.shape):
+        (target, n) = (float(targets[index]), int(pixels[index]))
+        estimate = (255.**2)*n*(10.**(-target/10.))
+        s = MAX_SSE_SATURATION if estimate >= MAX_SSE_SATURATION else int(numpy.floor(estimate))
+        while s > 0 and not _psnr_meets(s, n, target):
+            s -= 1
+        while s < MAX_SSE_SATURATION and _psnr_meets(s + 1, n, target):
+            s += 1
+        out[index] = s
+    return out if out.ndim else out[()]
+
+
+def quality_rounds(nb_points):
+    """ceil(log2(nb_points + 1)): the rounds after which a bisection over nb_points + 1 outcomes (each point, or none) has one left,
+    whatever the data: 1, 2, 2, 3, 3, 3, 3, 4, ... and 4 for the reference's nine points."""
+    nb_points = int(nb_points)
+    if nb_points < 1:
+        raise ValueError('`nb_points` must be at least 1.')
+    return nb_points.bit_length()
+
+
+def select_by_quality(sse, first, max_sse):
+    """-> (point int64 (N,), met bool (N,), probe_points int64 (N, R), probe_sse int64 (N, R)), R = quality_rounds(K).
+    sse int64 (N, K): the squared error of image i at point k; first int64 (N,): the finest point the search may take; max_sse int64
+    (N,). Per image a bisection of exactly R rounds from (L, R) = (first - 1, K): a round with R - L > 1 (live) probes mid = (L + R)
+    >> 1 and sets L = mid if sse[mid] <= max_sse, else R = mid; a round that is not live probes max(L, first) and changes nothing;
+    every round records the point it probed and its sse. At the end point = L and met if L >= first, else point = first, not met.
+    MONOTONICITY IS ASSUMED AND NOT CHECKED. Where sse is non-decreasing in k (points are ordered finest first), point is the
+    coarsest point >= first with sse <= max_sse -- the smallest blob that keeps the floor --, or `first`, not met, when not even the
+    finest allowed point keeps it. On a table that is not monotone the result is the bisection's own outcome: a point >= first
+    that was probed and met the threshold (a coarser one that meets it too may exist), or `first`, not met, although some point
+    the search did not probe would have met it."""
+    sse = numpy.asarray(sse)
+    first = numpy.asarray(first)
+    max_sse = numpy.asarray(max_sse)
+    if sse.ndim != 2 or sse.shape[1] < 1 or sse.dtype.kind not in 'iu':
+        raise ValueError('`sse` must be an integer array (N, K) with K >= 1.')
+    (nb_images, nb_points) = sse.shape
+    if first.shape != (nb_images,) or max_sse.shape != (nb_images,) or first.dtype.kind not in 'iu' or max_sse.dtype.kind not in 'iu':
+        raise ValueError('`first` and `max_sse` must be integer arrays (N,).')
+    if nb_images and (first.min() < 0 or first.max() >= nb_points):
+        raise ValueError('`first` does not belong to [0, K).')
+    nb_rounds = quality_rounds(nb_points)
+    point = numpy.zeros(nb_images, dtype=numpy.int64)
+    met = numpy.zeros(nb_images, dtype=bool)
+    probe_points = numpy.zeros((nb_images, nb_rounds), dtype=numpy.int64)
+    probe_sse = numpy.zeros((nb_images, nb_rounds), dtype=numpy.int64)
+    for i in range(nb_images):
+        (point[i], met[i], probe_points[i], probe_sse[i]) = bisect_by_quality(lambda k: int(sse[i, k]), nb_points, int(first[i]), int(max_sse[i]))
+    return point, met, probe_points, probe_sse
+
+
+def bisect_by_quality(sse_of, nb_points, first, max_sse):
+    """`select_by_quality` for one image whose squared error at point k is sse_of(k), asked for the points probed only (a point may
+    be asked for more than once) -> (point, met, probed points, their sse), the last two lists of quality_rounds(nb_points)."""
+    (low, high) = (first - 1, nb_points)
+    (points, values) = ([], [])
+    for _ in range(quality_rounds(nb_points)):
+        live = high - low > 1
+        probed = (low + high) >> 1 if live else max(low, first)
+        value = int(sse_of(probed))
+        points.append(probed)
+        values.append(value)
+        if live:
+            if value <= max_sse:
+                low = probed
+            else:
+                high = probed
+    return (low, True, points, values) if low >= first else (first, False, points, values)

@@ -423,6 +423,33 @@ int eae_hip_ladder_select_tiles(const uint32_t* hist, const uint64_t* bypass_bit
                                 const int64_t* budgets, const int32_t* entry_image, int n_entries, int exception_row_base, int32_t* point,
                                 int32_t* prob_row, int64_t* upper, uint32_t* flags, int n, void* stream);
 
+/* ---- a PSNR floor per image, searched on the device (csrc/hip/quality.hip; ratecontrol.py) ---------------
+ * eae_hip_quality_search: ONE round of the bisection that finds, per image, the coarsest rate point >= first whose squared error
+ * against the input is at most max_sse. Integer arithmetic only; after round nb_rounds it equals, element for element,
+ * ratecontrol.select_by_quality. A step calls it nb_rounds + 1 times, round = 0, 1, .., nb_rounds, and between round r - 1 and
+ * round r quantises every image at point[i] (eae_hip_latent_quantize_rows), synthesises it and adds its squared error into
+ * probe_acc[i] (eae_hip_tconv9x9s4_luma's sse). Every argument but `round` is the same in every call and none depends on the data.
+ *   first int32 [N]          the finest point the search may take (eae_hip_ladder_select's point); clamped to [0, K)
+ *   max_sse int64 [N]        the threshold: ratecontrol.max_sse_for_psnr
+ *   state int32 [N][2]       (L, R) of the bisection: points <= L met the threshold, points >= R did not
+ *   probe_acc uint64 [N]     the squared error of the point the previous round left in `point`; zeroed by every round
+ *   point int32 [N]          the point to quantise next: the next probe, after the last round the chosen point
+ *   prob_row int32 [N][128]  point * 128 + m; exception_row_base + i for the exception map (as eae_hip_ladder_select)
+ *   trace_point int32 [N][nb_rounds], trace_sse int64 [N][nb_rounds]   what round r probed and found, in column r - 1
+ *   flags uint32 [N]         bit 0: met (the chosen point's squared error was within max_sse); 0 before the last round
+ * Round 0: (L, R) = (first - 1, K); every element of the trace = -1. Round r >= 1: with mid the point round r - 1 left, column
+ * r - 1 of the trace = (mid, probe_acc); when R - L > 1 (a LIVE round), L = mid if probe_acc <= max_sse, else R = mid. Every round
+ * then leaves the next point -- (L + R) >> 1 when R - L > 1, else max(L, first), which moves nothing -- and after round nb_rounds
+ * point = L and met = 1 if L >= first, else point = first and met = 0. Round 0 writes every element of every output; a later
+ * round writes state, probe_acc, point, prob_row, flags and its column of the trace.
+ * nb_rounds must be ceil(log2(k_points + 1)) (ratecontrol.quality_rounds): the interval is then one point wide whatever the data.
+ * A NULL pointer, k_points < 1, another nb_rounds, round outside [0, nb_rounds], idx_map_exception >= 128, a negative
+ * exception_row_base, n <= 0, a 64-bit array not 8-byte aligned -> EAE_HIP_BAD_ARGUMENT; n > 65535 -> EAE_HIP_BAD_SHAPE; both
+ * before any launch. One launch, one block per image: 11 to 12 us at 24 images (profiles/quality_codec.md). */
+int eae_hip_quality_search(const int32_t* first, const int64_t* max_sse, int32_t* state, uint64_t* probe_acc, int32_t* point,
+                           int32_t* prob_row, int32_t* trace_point, int64_t* trace_sse, uint32_t* flags, int k_points, int nb_rounds,
+                           int round, int idx_map_exception, int exception_row_base, int n, void* stream);
+
 /* ---- lossless coder on the device: one feature map per lane --------------------------------------------------------
  * Replaces the per-map compress_lossless loop of lossless/compression.py:76-81 (and, underneath it,
  * lossless/c++/source/compression.cpp:3-65) for a whole batch of images whose symbols are already in HBM
