@@ -2724,7 +2724,7 @@ class QualityCodec(BudgetCodec):
         if not isinstance(ladder, ratecontrol.RateLadder):
             raise TypeError('`ladder` is not a `ratecontrol.RateLadder`.')
         # refused in front of every allocation
-        if batch_codec_options.get('coding_tile') is not None:
+        if batch_codec_options.get('coding_tile') is not None and not self._takes_coding_tile:
             raise ValueError('`QualityCodec` does not take `coding_tile`: the coder\'s rows per stream would need the run order of '
                              '`device.ladder_select_tiles`.')
         self.nb_rounds = ratecontrol.quality_rounds(ladder.nb_points)
@@ -2810,3 +2810,107 @@ class QualityCodec(BudgetCodec):
                                                              sse=quality.probe_acc))
             hook('search', lambda: self._launch_round(quality, r))
         return self._launch_quantiser(y, slot, quality, hook)
+
+
+# ---- the same for tile-indexed containers: the search's rows per stream, in the coder's run order -----------
+
+def tile_prob_rows(layout, points, idx_map_exception=-1, exception_row_base=None):
+    """The coder's row of every stream of a step in coding tiles whose image i is coded at `points[i]`, in the run order of `layout`
+    (`coding_tile_layout`'s dict): what `device.quality_search_tiles` writes. Map m of run-order entry e, an (image, tile), takes row
+    points[image]*128 + m; the exception map takes `exception_row_base + image` (None: behind the K = max(points) + 1 points'
+    rows). -> int32 [n_streams]. With every point 0 it is `layout['prob_row']`."""
+    nb_maps = csts.NB_MAPS_3
+    points = numpy.asarray(points, dtype=numpy.int64)
+    if exception_row_base is None:
+        exception_row_base = (int(points.max()) + 1)*nb_maps
+    images = numpy.array([layout['entries'][p][0] for p in layout['payload_entry'].tolist()], dtype=numpy.int64)
+    rows = points[images][:, None]*nb_maps + numpy.arange(nb_maps, dtype=numpy.int64)[None, :]
+    if idx_map_exception >= 0:
+        rows[:, idx_map_exception] = exception_row_base + images
+    return rows.reshape(-1).astype(numpy.int32)
+
+
+class _TiledQualitySlot(object):
+    """What one `TiledQualityCodec` step in flight owns beyond its `_Slot`: `_QualitySlot`'s state with the ladder's accumulators per
+    coding tile and the coder's rows per stream of the step, as in `_TiledBudgetSlot`. Made once;
+    tests/tiled_quality_slot_buffers.py says what a step may find in every attribute when it starts."""
+    __slots__ = ('accum', 'hist', 'bypass_bits', 'range_errors', 'pinned_budgets', 'budgets_host', 'budgets', 'budgets_nbytes', 'select',
+                 'upper', 'first', 'flags', 'prob_row', 'class_rows', 'pinned_select', 'select_host', 'table', 'points_table',
+                 'exception_rows', 'pinned_rows', 'rows_host', 'pinned_max_sse', 'max_sse_host', 'max_sse', 'max_sse_nbytes', 'trace_sse',
+                 'point', 'met', 'state', 'trace_point', 'search_host', 'probe_acc', 'probe_latent')
+
+    def __init__(self, codec):
+        (batch_size, nb_maps, ladder, device, tiled) = (codec.batch_size, codec.nb_maps, codec.ladder, codec.device, codec._tile_layout)
+        nb_rounds = codec.nb_rounds
+        (self.accum, self.bypass_bits, self.hist, self.range_errors) = _ladder_accumulators(
+            (batch_size, ladder.nb_points, tiled['nb_tiles'], nb_maps), ladder.nb_points, ladder.truncated_unary_length, device)
+        # behind [upper | first | flags]: [trace_sse int64 N x R | point int32 N | met int32 N | state int32 N x 2 | trace_point int32 N x R]
+        layout = [2*batch_size*nb_rounds, batch_size, batch_size, 2*batch_size, batch_size*nb_rounds]
+        (self.pinned_budgets, self.budgets_host, self.budgets, self.budgets_nbytes, self.select, self.upper, self.first, self.flags,
+         self.pinned_select, self.select_host, self.table, self.points_table, self.exception_rows, self.pinned_rows,
+         self.rows_host) = _budget_slot_blocks(codec, extra_words=sum(layout))
+        own = self.select.numel() - sum(layout)
+        (trace_sse, self.point, self.met, state, trace_point) = torch.split(self.select[own:], layout)
+        self.trace_sse = trace_sse.view(torch.int64).view(batch_size, nb_rounds)
+        self.state = state.view(batch_size, 2)
+        self.trace_point = trace_point.view(batch_size, nb_rounds)
+        (trace_sse, point, met, state, trace_point) = torch.split(self.pinned_select[own:], layout)
+        # what the result worker reads (`_QualityWorker._finish`): (point, met, trace_point, trace_sse)
+        self.search_host = (point.numpy(), met.numpy(), trace_point.view(batch_size, nb_rounds).numpy(),
+                            trace_sse.view(torch.int64).view(batch_size, nb_rounds).numpy())
+        # the step's thresholds: written by `QualityCodec._stage` into pinned memory, fetched by a kernel inside the step's chain
+        padded = batch_size + batch_size % 2                       # `device.fetch_prefix` copies multiples of 16 bytes
+        self.pinned_max_sse = torch.zeros(padded, dtype=torch.int64).pin_memory()
+        self.max_sse_host = self.pinned_max_sse.numpy()
+        self.max_sse = torch.zeros(padded, dtype=torch.int64, device=device)
+        self.max_sse_nbytes = torch.full((1,), 8*padded, dtype=torch.int64, device=device)
+        # the coder's row of every stream of the step in RUN order: `device.ladder_select_tiles`', then every round's of
+        # `device.quality_search_tiles`, and every shape class's run
+        self.prob_row = torch.zeros(tiled['n_streams'], dtype=torch.int32, device=device)
+        self.class_rows = [self.prob_row[first:first + count*nb_maps] for (_, count, first, _) in tiled['runs']]
+        # what a probe's `tconv9x9s4_luma` adds its squared errors into, and what its quantiser writes for its synthesis pass
+        self.probe_acc = torch.zeros(batch_size, dtype=torch.int64, device=device)
+        self.probe_latent = torch.empty((batch_size, codec.h_in//csts.STRIDE_PROD, codec.w_in//csts.STRIDE_PROD, nb_maps), dtype=torch.float32,
+                                        device=device)
+
+
+class TiledQualityCodec(QualityCodec):
+    """`QualityCodec` for tile-indexed containers: a PSNR floor per image whose blob is the single-image `EAT1`
+    blob `container.encode_images(..., coding_tile=coding_tile)` writes, so that crops come out of it (`container.decode_region`,
+    `RegionDecoder`) and its serial chains are a tile long."""
+    (_takes_coding_tile, _budget_slot_class) = (True, _TiledQualitySlot)
+
+    def __init__(self, variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, coding_tile, target_psnr=None, max_sse=None,
+                 budget_bytes=None, **batch_codec_options):
+        """coding_tile: (th, tw) in latents, clamped to the latent plane, as `BatchCodec(coding_tile=...)` takes it; everything else
+        as `QualityCodec`. Refused in front of every allocation: what `QualityCodec` and `TiledBudgetCodec` refuse.
+        The step is `QualityCodec`'s with the tiled pieces of `TiledBudgetCodec`: the counts per (image, point, tile, map), the
+        bounds of every image's `EAT1` blob for the finest point the search may take, the search -- a point's squared error does not
+        depend on the coding tile: the probes are `QualityCodec`'s --, every round leaving the coder's rows per stream of the step
+        (`device.quality_search_tiles`), and the coder in tiles. `Ticket.result()` has `QualityCodec`'s keys, 'coder_bits' summed over
+        an image's tiles, 'upper_bound_bytes' the `EAT1` bounds; `Ticket.image_containers()[i]` is byte for byte
+        `container.encode_images(image i, ..., coding_tile=coding_tile)` at `rate_point[i]`; `Ticket.container()` raises."""
+        coding_tile = container_format._positive_pair(coding_tile, '`coding_tile`')
+        super(TiledQualityCodec, self).__init__(variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, target_psnr=target_psnr,
+                                                max_sse=max_sse, budget_bytes=budget_bytes, coding_tile=coding_tile, **batch_codec_options)
+        try:
+            # `device.quality_search_tiles`: where the coder takes every (image, tile) entry from, in payload order
+            self._run_entry = torch.from_numpy(self._tile_layout['run_entry'].astype(numpy.int32)).to(self.device)
+        except BaseException:
+            self.close()
+            raise
+
+    _launch_ladder = TiledBudgetCodec._launch_ladder
+    _launch_coder = TiledBudgetCodec._launch_coder
+
+    def _launch_select(self, budget):
+        dev.ladder_select_tiles(budget.hist, budget.bypass_bits, self._fixed_costs, self._log2_tables, self.idx_map_exception,
+                                self._header_bytes, self.map_size, budget.budgets[:self.batch_size], self._entry_image,
+                                self.ladder.nb_points*self.nb_maps,
+                                out={'point': budget.first, 'prob_row': budget.prob_row, 'upper': budget.upper, 'flags': budget.flags})
+
+    def _launch_round(self, quality, round):
+        dev.quality_search_tiles(quality.first, quality.max_sse[:self.batch_size], quality.state, quality.probe_acc, quality.point,
+                                 quality.prob_row, quality.trace_point, quality.trace_sse, quality.met, self._run_entry,
+                                 self._tile_layout['nb_tiles'], self.ladder.nb_points, round, self.idx_map_exception,
+                                 self.ladder.nb_points*self.nb_maps)

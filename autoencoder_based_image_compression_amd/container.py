@@ -290,7 +290,7 @@ def encode_images_to_budget(luminances_uint8, encoder, ladder, budget_bytes, til
     return [coded[(i, int(info['rate_point'][i]))] for i in range(nb_images)], info
 
 
-def encode_images_to_quality(luminances_uint8, encoder, decoder, ladder, target_psnr=None, max_sse=None, budget_bytes=None):
+def encode_images_to_quality(luminances_uint8, encoder, decoder, ladder, target_psnr=None, max_sse=None, budget_bytes=None, coding_tile=None):
     """uint8 (N, H, W) or (N, H, W, 1) luminance images -> (blobs, info): every image at the COARSEST rate point of `ladder`
     (ratecontrol.RateLadder, finest first) that keeps its PSNR at `target_psnr` dB or better -- its squared error against the input
     within `max_sse`; give one of the two, a scalar or one value per image. The synchronous sibling of `encode_images_to_budget`
@@ -304,7 +304,11 @@ def encode_images_to_quality(luminances_uint8, encoder, decoder, ladder, target_
     blobs: one single-image EAE1 blob per image, byte for byte `encode_images(images[i:i + 1], encoder, bin_widths_k, map_mean,
     table_k, idx_map_exception)[0]` for its point k.
     info: 'rate_point' int64 (N,), 'met' bool (N,), 'probe_points' and 'probe_sse' int64 (N, R) (select_by_quality's), 'max_sse'
-    int64 (N,), 'first_point' int64 (N,), 'blob_bytes' int64 (N,), 'upper_bound_bytes' int64 (N, K)."""
+    int64 (N,), 'first_point' int64 (N,), 'blob_bytes' int64 (N,), 'upper_bound_bytes' int64 (N, K).
+    coding_tile=(th, tw) latents: single-image EAT1 blobs instead, byte for byte `encode_images(..., coding_tile=coding_tile)[0]` at
+    the image's point, and the host loop of `codec.TiledQualityCodec`. The search is the same -- a point's
+    squared error does not depend on the coding tile --; the budget's point comes from the counts per tile
+    (`device.ladder_histograms_tiles`) and `ratecontrol.upper_bounds_fixed_tiles`, the rule of `codec.TiledBudgetCodec`."""
     from . import ratecontrol
     images = numpy.ascontiguousarray(luminances_uint8)
     if images.dtype != numpy.uint8:
@@ -329,11 +333,21 @@ def encode_images_to_quality(luminances_uint8, encoder, decoder, ladder, target_
     mean = torch.from_numpy(ladder.map_mean).to(device)
     bin_widths_points = torch.from_numpy(ladder.bin_widths_points).to(device)
     map_size = (height//csts.STRIDE_PROD)*(width//csts.STRIDE_PROD)
-    (hist, bypass_bits, _) = dev.ladder_histograms(y, bin_widths_points, mean, length)
-    (hist, bypass_bits) = (hist.cpu().numpy(), bypass_bits.cpu().numpy())
-    upper = ratecontrol.upper_bounds_fixed(hist, bypass_bits, ladder, map_size)
+    if coding_tile is None:
+        (hist, bypass_bits, _) = dev.ladder_histograms(y, bin_widths_points, mean, length)
+        (hist, bypass_bits) = (hist.cpu().numpy(), bypass_bits.cpu().numpy())
+        upper = ratecontrol.upper_bounds_fixed(hist, bypass_bits, ladder, map_size)
+        valid = ratecontrol.valid_points(hist, map_size)
+    else:
+        coding_tile = _clamped_coding_tile(coding_tile, height, width)
+        plane = y.view(nb_images, height//csts.STRIDE_PROD, width//csts.STRIDE_PROD, -1)
+        (hist, bypass_bits, _) = dev.ladder_histograms_tiles(plane, bin_widths_points, coding_tile, mean, length)
+        (hist, bypass_bits) = (hist.cpu().numpy(), bypass_bits.cpu().numpy())
+        upper = ratecontrol.upper_bounds_fixed_tiles(hist, bypass_bits, ladder, map_size,
+                                                     ratecontrol.header_bytes(ladder, height, width, coding_tile))
+        valid = ratecontrol.valid_points(hist.astype(numpy.int64).sum(axis=2), map_size)
     budgets = 1 << 62 if budget_bytes is None else budget_bytes
-    (first, _) = ratecontrol.select_by_upper_bound(upper, ratecontrol.valid_points(hist, map_size), budgets)
+    (first, _) = ratecontrol.select_by_upper_bound(upper, valid, budgets)
 
     rounds = ratecontrol.quality_rounds(nb_points)
     info = {'rate_point': numpy.zeros(nb_images, dtype=numpy.int64), 'met': numpy.zeros(nb_images, dtype=bool),
@@ -360,8 +374,8 @@ def encode_images_to_quality(luminances_uint8, encoder, decoder, ladder, target_
             raise AssertionError('The rounded array elements cannot be represented as 16-bit signed integers.')
         rows = _exception_rows(q['symbols'], e, length) if e >= 0 else numpy.zeros((0, length), dtype=numpy.float64)
         fields = _fields(encoder.are_bin_widths_learned, 1, height, width, e, ladder.bin_widths_points[k], ladder.map_mean,
-                         ladder.binary_probabilities_points[k], rows)
-        blobs.append(_encode_entries(q['symbols'], fields, 1)[0])
+                         ladder.binary_probabilities_points[k], rows, coding_tile)
+        blobs.append(_encode_entries(q['symbols'], fields, 1 if coding_tile is None else TILES_PER_CALL)[0])
         info['blob_bytes'][i] = len(blobs[i])
     return blobs, info
 

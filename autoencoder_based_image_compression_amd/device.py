@@ -787,6 +787,27 @@ def quality_search(first, max_sse, state, probe_acc, point, prob_row, trace_poin
                                                 int(exception_row_base), n, _stream(first)), 'eae_hip_quality_search')
 
 
+def quality_search_tiles(first, max_sse, state, probe_acc, point, prob_row, trace_point, trace_sse, flags, run_entry, nb_tiles, k_points,
+                         round, idx_map_exception, exception_row_base):
+    """`quality_search` for a step in coding tiles (include/eae_hip.h: eae_hip_quality_search_tiles; the rows are
+    `codec.tile_prob_rows`). run_entry int32 [N * nb_tiles] on the device: `codec.coding_tile_layout`'s 'run_entry'; prob_row int32
+    [N * nb_tiles, 128], written in that layout's run order. Everything else as `quality_search`."""
+    n = first.numel()
+    nb_tiles = int(nb_tiles)
+    nb_rounds = int(k_points).bit_length()
+    for (name, t, dtype, count) in (('first', first, torch.int32, n), ('max_sse', max_sse, torch.int64, n), ('state', state, torch.int32, 2*n),
+                                    ('probe_acc', probe_acc, torch.int64, n), ('point', point, torch.int32, n),
+                                    ('prob_row', prob_row, torch.int32, n*nb_tiles*NB_MAPS),
+                                    ('trace_point', trace_point, torch.int32, n*nb_rounds), ('trace_sse', trace_sse, torch.int64, n*nb_rounds),
+                                    ('flags', flags, torch.int32, n), ('run_entry', run_entry, torch.int32, n*nb_tiles)):
+        if t.dtype != dtype or t.numel() != count:
+            raise HipError('`{0}` must hold {1} elements of {2}'.format(name, count, dtype))
+    _check(_native.hip().eae_hip_quality_search_tiles(_p(first), _p(max_sse), _p(state), _p(probe_acc), _p(point), _p(prob_row),
+                                                      _p(trace_point), _p(trace_sse), _p(flags), _p(run_entry), nb_tiles, int(k_points),
+                                                      nb_rounds, int(round), int(idx_map_exception), int(exception_row_base), n,
+                                                      _stream(first)), 'eae_hip_quality_search_tiles')
+
+
 def latent_quantize_rows(y, bin_widths_points, point, map_mean=None, igdn_out=None, want_shifted=False, want_symbols=True,
                          want_flags=False, out_symbols=None, out_flags=None, out_checks=None, want_checks=True, out_shifted=None,
                          out_t=None):

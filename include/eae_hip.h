@@ -449,6 +449,20 @@ int eae_hip_ladder_select_tiles(const uint32_t* hist, const uint64_t* bypass_bit
 int eae_hip_quality_search(const int32_t* first, const int64_t* max_sse, int32_t* state, uint64_t* probe_acc, int32_t* point,
                            int32_t* prob_row, int32_t* trace_point, int64_t* trace_sse, uint32_t* flags, int k_points, int nb_rounds,
                            int round, int idx_map_exception, int exception_row_base, int n, void* stream);
+/* eae_hip_quality_search for a step in coding tiles (codec.TiledQualityCodec): the same round, state, trace and
+ * arguments, with the coder's rows written per stream of the step, where the coder takes them from.
+ *   run_entry int32 [N * nb_tiles], device memory: the run-order index (codec.coding_tile_layout) of every entry (image, tile), in
+ *                          payload order (image, then tile); an entry whose value lies outside [0, N * nb_tiles) is skipped
+ *   prob_row int32 [N * nb_tiles][128]: for run-order entry e of image i, prob_row[e][m] = point[i] * 128 + m; exception_row_base + i
+ *                          for the exception map (as eae_hip_ladder_select_tiles)
+ * With nb_tiles == 1 and run_entry the identity every word equals eae_hip_quality_search's. Argument checks as
+ * eae_hip_quality_search, and NULL run_entry or nb_tiles < 1 -> EAE_HIP_BAD_ARGUMENT; n * nb_tiles > 65535 -> EAE_HIP_BAD_SHAPE;
+ * before any launch. One launch, one block per image, which walks the image's own tiles: no block reads what another block of the
+ * same launch writes. */
+int eae_hip_quality_search_tiles(const int32_t* first, const int64_t* max_sse, int32_t* state, uint64_t* probe_acc, int32_t* point,
+                                 int32_t* prob_row, int32_t* trace_point, int64_t* trace_sse, uint32_t* flags, const int32_t* run_entry,
+                                 int nb_tiles, int k_points, int nb_rounds, int round, int idx_map_exception, int exception_row_base,
+                                 int n, void* stream);
 
 /* ---- lossless coder on the device: one feature map per lane --------------------------------------------------------
  * Replaces the per-map compress_lossless loop of lossless/compression.py:76-81 (and, underneath it,
