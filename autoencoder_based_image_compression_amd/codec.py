@@ -728,7 +728,7 @@ class BatchCodec(object):
                  batch_size, h_in, w_in, device='cuda', nb_in_flight=None, keep_reconstruction=False, launch_hook=None,
                  coder='device', host_coder_threads=0, hist_radius=2047, nb_transform_streams=1, use_graphs=False,
                  time_coder=False, fuse_latent=False, fetch_reconstruction=False, coder_chunks=None, one_stream_steps=False,
-                 emit_container=False, container_capacity_bytes=None, coding_tile=None):
+                 emit_container=False, container_capacity_bytes=None, coding_tile=None, rdo_lambda=None):
         """coder: 'device' (the coder kernels on side streams), 'host' (ONE device -> host copy of the symbols per batch, then
         the host C-ABI coder `eae_coder_compress_maps` on `host_coder_threads` threads: the shape BASELINE.json sketches) or
         'none' (transforms only; the bit counts come back as zeros).
@@ -771,9 +771,24 @@ class BatchCodec(object):
         `container.encode_images(..., coding_tile=(th, tw))` writes, so `container.decode_region` reads a crop out of them. The tile
         is clamped to the latent plane. 'coder_bits' sums an image's tiles (every tile's streams pay their own termination, so it is
         larger than without tiles); 'sse', 'nb_deads' and 'exception_bits' do not change. The serial chains are then a tile long
-        instead of a map. At most 65,535 (image, tile) pairs per step; not with `coder_chunks`."""
+        instead of a map. At most 65,535 (image, tile) pairs per step; not with `coder_chunks`.
+        rdo_lambda: None, or a non-negative float in squared latent units per bit: the step's symbols are chosen by the
+        rate-distortion optimised quantiser instead of by nearest rounding: conv_3, gdn_3 as a launch of its
+        own, then `device.latent_quantize_rdo` with `ratecontrol.rdo_thresholds` of this rate point. Everything behind the symbols is
+        unchanged and `result()` has the same keys; the containers are byte for byte `container.encode_images(..., rdo_lambda=...)`.
+        0.0 gives the results of None. Not with `fuse_latent` or the host coder."""
         if coder not in ('device', 'host', 'none'):
             raise ValueError('`coder` is neither "device" nor "host" nor "none".')
+        self.rdo_lambda = None
+        if rdo_lambda is not None:
+            # refused in front of every allocation
+            if fuse_latent:
+                raise ValueError('`rdo_lambda` does not go with `fuse_latent`: the fused latent stage rounds to the nearest symbol.')
+            if coder == 'host':
+                raise ValueError('`rdo_lambda` needs the coder on the device (or none).')
+            self.rdo_lambda = float(rdo_lambda)
+            if not numpy.isfinite(self.rdo_lambda) or self.rdo_lambda < 0.:
+                raise ValueError('`rdo_lambda` must be a finite number that is not negative.')
         if use_graphs and coder == 'host':
             raise ValueError('`use_graphs` needs the coder on the device (or none).')
         if h_in % csts.STRIDE_PROD != 0 or w_in % csts.STRIDE_PROD != 0:
@@ -832,6 +847,13 @@ class BatchCodec(object):
         self.bin_widths = torch.from_numpy(bin_widths_host).to(self.device)
         self.map_mean = torch.from_numpy(map_mean_host).to(self.device)
         self.probabilities = torch.from_numpy(probabilities).to(self.device)
+        if self.rdo_lambda is not None:
+            # what `device.latent_quantize_rdo` takes beyond the latents: one rate point, which every image takes
+            from . import ratecontrol
+            self._rdo_bin_widths = self.bin_widths.reshape(1, self.nb_maps)
+            self._rdo_thresholds = torch.from_numpy(ratecontrol.rdo_thresholds(bin_widths_host[None], probabilities[None], self.rdo_lambda,
+                                                                               self.idx_map_exception)).to(self.device)
+            self._rdo_point = torch.zeros(batch_size, dtype=torch.int32, device=self.device)
         prob_row = torch.arange(self.nb_maps, dtype=torch.int32).repeat(batch_size)
         if self.idx_map_exception >= 0:
             prob_row[self.idx_map_exception::self.nb_maps] = -1        # costed from its histogram (compression.py:68-75)
@@ -1174,6 +1196,15 @@ class BatchCodec(object):
             q = hook('conv3', lambda: dev.conv5x5s2_latent(gdn_2, enc.w3, v['encoder/biases_3'], self.bin_widths, self.map_mean, gdn_in=gdn_in,
                                                            igdn_out=igdn_out, want_flags=True, out_symbols=slot.symbols,
                                                            out_flags=slot.flags, out_checks=slot.checks[:3], workspace=ws))
+        elif self.rdo_lambda is not None:
+            # conv_3 -> gdn_3 as its own launch -> the quantiser that weighs every symbol's bits against its error (+ inverse_gdn_4)
+            y = hook('conv3', lambda: dev.conv5x5s2(gdn_2, enc.w3, v['encoder/biases_3'], dev.NORM_NONE, workspace=ws))
+            if not self.learned:
+                y = hook('gdn3', lambda: dev.gdn(y, enc.g[3], v['encoder/beta_3']))
+            q = hook('latent', lambda: dev.latent_quantize_rdo(y, self._rdo_bin_widths, self._rdo_thresholds, self._rdo_point,
+                                                               self.truncated_unary_length, self.map_mean, igdn_out=igdn_out,
+                                                               want_shifted=self.learned, want_symbols=True, want_flags=True,
+                                                               out_symbols=slot.symbols, out_flags=slot.flags, out_checks=slot.checks[:3]))
         else:
             y_raw = hook('conv3', lambda: dev.conv5x5s2(gdn_2, enc.w3, v['encoder/biases_3'], dev.NORM_NONE, workspace=ws))
             # gdn_3 -> centre / quantise / symbols / dead-map flags -> de-centre -> inverse_gdn_4: one pass over the latents
@@ -2405,6 +2436,8 @@ class BudgetCodec(BatchCodec):
             raise ValueError('`BudgetCodec` does not take `coding_tile`: the bounds are those of whole maps (EAE1).')
         if options.get('fuse_latent'):
             raise ValueError('`BudgetCodec` does not take `fuse_latent`: the point is chosen between conv_3 and the quantiser.')
+        if options.get('rdo_lambda') is not None:
+            raise ValueError('The rate-control codecs do not take `rdo_lambda`: their byte bounds and probes are those of nearest rounding.')
         if options.get('coder', 'device') != 'device':
             raise ValueError('`BudgetCodec` needs the coder on the device.')
         chunks = options.get('coder_chunks')

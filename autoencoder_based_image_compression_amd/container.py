@@ -175,7 +175,7 @@ def assemble_image_blobs(are_bin_widths_learned, nb_images, height, width, idx_m
 
 
 def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_probabilities, idx_map_exception=-1, tile=None,
-                  coding_tile=None, tiles_per_call=TILES_PER_CALL):
+                  coding_tile=None, tiles_per_call=TILES_PER_CALL, rdo_lambda=None):
     """uint8 (N, H, W) or (N, H, W, 1) luminance images -> (blob bytes, info dict).
 
     encoder: pipeline.DeviceEncoder of the model; bin_widths_test float32 (128,) (the trained bin widths times the
@@ -186,6 +186,10 @@ def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_p
     coding_tile=(th, tw) latents: write the tile-indexed format EAT1 (module docstring) instead of EAE1. The coder runs on groups
     of `tiles_per_call` (image, tile) pairs, so its streams and workspace are bounded by one group whatever the image size.
     info then also holds 'tile_bits' uint32 (N, nb_tiles, 128, 2). EAE1 is one tile per map, coded as one group.
+    rdo_lambda: None, or a non-negative float in squared latent units per bit: the symbols are chosen by the rate-distortion
+    optimised quantiser (device.latent_quantize_rdo with ratecontrol.rdo_thresholds of this rate point)
+    instead of by nearest rounding. The blob is an ordinary one, every decoder reads it; the exception map's row is measured on the
+    symbols chosen. 0.0 gives the bytes of None.
     """
     images = numpy.ascontiguousarray(luminances_uint8)
     if images.dtype != numpy.uint8:
@@ -205,8 +209,17 @@ def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_p
         coding_tile = _positive_pair(coding_tile, '`coding_tile`')
         tiles_per_call = _positive_int(tiles_per_call, '`tiles_per_call`')
     device = encoder.device
+    thresholds = None
+    if rdo_lambda is not None:
+        from . import ratecontrol
+        thresholds = ratecontrol.rdo_thresholds(bin_widths[None], probabilities[None], rdo_lambda, idx_map_exception)
     y = encoder(torch.from_numpy(images).to(device), tile=tile)
-    q = dev.quantize_maps(y, torch.from_numpy(bin_widths).to(device), torch.from_numpy(mean).to(device), want_symbols=True)
+    if thresholds is None:
+        q = dev.quantize_maps(y, torch.from_numpy(bin_widths).to(device), torch.from_numpy(mean).to(device), want_symbols=True)
+    else:
+        q = dev.latent_quantize_rdo(y, torch.from_numpy(bin_widths[None]).to(device), torch.from_numpy(thresholds).to(device),
+                                    torch.zeros(nb_images, dtype=torch.int32, device=device), truncated_unary_length,
+                                    torch.from_numpy(mean).to(device), want_symbols=True)
     if int(q['checks'][0].item()) != 0:
         raise AssertionError('The rounded array elements cannot be represented as 16-bit signed integers.')
     symbols = q['symbols']                                              # [N, 128, map_size] int16, stays in HBM

@@ -482,3 +482,82 @@ def bisect_by_quality(sse_of, nb_points, first, max_sse):
             else:
                 high = probed
     return (low, True, points, values) if low >= first else (first, False, points, values)
+
+
+# ---- the rule of the rate-distortion optimised quantiser --------------------------------------------------------
+# Nearest rounding fixes the symbols before the coder's tables are looked at. Here a latent whose nearest symbol has magnitude a >= 1
+# is coded at a - 1 instead when the squared error that adds, (2 u + 1) bw^2 with u = |x| - a in [-1/2, 1/2], is below rdo_lambda times
+# the bits the coder's static table says it saves. The host forms one threshold per (map, magnitude), `rdo_thresholds`; the device
+# (`eae_hip_latent_quantize_rdo`) and `rdo_quantize_numpy` compare 2 u + 1 against it in float32, element for element the same.
+RDO_MAGNITUDES = 16               # the magnitudes 1 .. 16 have a threshold; a larger one is never lowered
+
+
+def magnitude_bits(binary_probabilities):
+    """float64 (..., L) -> float64 (..., L + 1): B(a), the bits the coder spends on a symbol of magnitude a = 0 .. L under the static
+    table p, p[i] the probability that decision i of the truncated unary prefix is 0: -log2(1 - p[i]) for every decision i < min(a, L)
+    that is a one, -log2 p[a] for the closing zero when a < L, the Exp-Golomb suffix of a - L when a >= L (2 floor(log2(a - L + 1))
+    + 1 bits, as eae_hip_ladder_histograms counts it: 1 bit at a = L), and the sign bit when a > 0."""
+    p = numpy.asarray(binary_probabilities, dtype=numpy.float64)
+    if p.ndim < 1 or p.shape[-1] < 1:
+        raise ValueError('`binary_probabilities` must be (..., L) with L >= 1.')
+    length = p.shape[-1]
+    ones = numpy.concatenate([numpy.zeros(p.shape[:-1] + (1,)), numpy.cumsum(-numpy.log2(1. - p), axis=-1)], axis=-1)   # i < a
+    bits = ones.copy()
+    bits[..., :length] += -numpy.log2(p)
+    bits[..., length] += 1.                                # Exp-Golomb order 0 of a - L = 0
+    bits[..., 1:] += 1.                                    # the sign
+    return bits
+
+
+def rdo_thresholds(bin_widths, binary_probabilities, rdo_lambda, idx_map_exception=-1):
+    """float32 (..., 128, RDO_MAGNITUDES): T[c][a - 1] = rdo_lambda (B(a) - B(a - 1)) / bw[c]^2 for a = 1 .. min(L, 16), formed in
+    float64 and cast; 0 where a step saves nothing (B(a) <= B(a - 1)), in the columns beyond min(L, 16), in the whole row of the
+    exception map (its probability row is measured on the image's own symbols: a price taken from it would move the symbols it is
+    measured on) and everywhere at rdo_lambda = 0. bin_widths float32 (..., 128), binary_probabilities float64 (..., 128, L): one
+    point, or (K, 128) and (K, 128, L) for a ladder. rdo_lambda: squared latent units per bit; negative or not finite: ValueError."""
+    rdo_lambda = float(rdo_lambda)
+    if not numpy.isfinite(rdo_lambda) or rdo_lambda < 0.:
+        raise ValueError('`rdo_lambda` must be a finite number that is not negative.')
+    bw = numpy.asarray(bin_widths, dtype=numpy.float64)
+    p = numpy.asarray(binary_probabilities, dtype=numpy.float64)
+    if bw.ndim < 1 or bw.shape[-1] != NB_MAPS or p.shape[:-1] != bw.shape or p.shape[-1] < 1:
+        raise ValueError('`bin_widths` must be (..., {0}) and `binary_probabilities` (..., {0}, L).'.format(NB_MAPS))
+    used = min(p.shape[-1], RDO_MAGNITUDES)
+    thresholds = numpy.zeros(bw.shape + (RDO_MAGNITUDES,), dtype=numpy.float32)
+    if rdo_lambda == 0.:
+        return thresholds
+    bits = magnitude_bits(p)
+    saved = (bits[..., 1:] - bits[..., :-1])[..., :used]
+    with numpy.errstate(over='ignore'):
+        thresholds[..., :used] = numpy.where(saved > 0., rdo_lambda*saved/(bw*bw)[..., None], 0.).astype(numpy.float32)
+    if 0 <= idx_map_exception < NB_MAPS:
+        thresholds[..., int(idx_map_exception), :] = 0.
+    return thresholds
+
+
+def rdo_quantize_numpy(y, bin_widths, map_mean, thresholds, truncated_unary_length):
+    """The choice `eae_hip_latent_quantize_rdo` makes, in numpy float32, statement for statement: y float32 (..., 128) (channels
+    last), bin_widths and map_mean float32 (128,) (map_mean None: zeros), thresholds float32 (128, RDO_MAGNITUDES) -> r float32
+    of y's shape, the symbol of every latent as a float (what the device multiplies by the bin width).
+    centered = y - m; x = centered / bw; r = round_half_even(x); a = |r|; u = |x| - a; where a >= 1 and a <= min(L, 16) -- tested
+    in float, so that a NaN, an infinity or a huge a is left alone -- and 2 u + 1 < thresholds[c][a - 1], r = r - copysign(1, r)."""
+    f32 = numpy.float32
+    y = numpy.asarray(y)
+    bw = numpy.asarray(bin_widths)
+    mean = numpy.zeros(NB_MAPS, dtype=f32) if map_mean is None else numpy.asarray(map_mean)
+    thresholds = numpy.asarray(thresholds)
+    if y.dtype != f32 or bw.dtype != f32 or mean.dtype != f32 or thresholds.dtype != f32:
+        raise TypeError('`y`, `bin_widths`, `map_mean` and `thresholds` must be float32.')
+    if y.shape[-1] != NB_MAPS or bw.shape != (NB_MAPS,) or mean.shape != (NB_MAPS,) or thresholds.shape != (NB_MAPS, RDO_MAGNITUDES):
+        raise ValueError('`y` must be (..., {0}), `bin_widths` and `map_mean` ({0},), `thresholds` ({0}, {1}).'.format(NB_MAPS, RDO_MAGNITUDES))
+    amax = f32(min(int(truncated_unary_length), RDO_MAGNITUDES))
+    with numpy.errstate(invalid='ignore', over='ignore'):
+        centered = y - mean
+        x = centered/bw
+        r = numpy.rint(x)
+        a = numpy.abs(r)
+        u = numpy.abs(x) - a
+        eligible = (a >= f32(1.)) & (a <= amax)
+        column = numpy.where(eligible, a, f32(1.)).astype(numpy.int64) - 1
+        lower = eligible & (f32(2.)*u + f32(1.) < thresholds[numpy.arange(NB_MAPS), column])
+        return numpy.where(lower, r - numpy.copysign(f32(1.), r), r).astype(f32)

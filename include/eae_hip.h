@@ -464,6 +464,22 @@ int eae_hip_quality_search_tiles(const int32_t* first, const int64_t* max_sse, i
                                  int nb_tiles, int k_points, int nb_rounds, int round, int idx_map_exception, int exception_row_base,
                                  int n, void* stream);
 
+/* ---- rate-distortion optimised quantiser (csrc/hip/rdoq.hip; ratecontrol.py) -----------------------------
+ * eae_hip_latent_quantize_rdo: eae_hip_latent_quantize_rows with one more input, thresholds_points float32 [K][128][16]
+ * (ratecontrol.rdo_thresholds; image i takes row clamp(point[i], 0, K - 1) of it as of bin_widths_points), and `length`, the
+ * truncated unary length L. Per latent, in IEEE float32: centered = y - mean; x = centered / bw; r = round_half_even(x); a = |r|;
+ * u = |x| - a; if a >= 1 && a <= min(L, 16) (tested in float: a NaN, an infinity or a huge a never indexes the table) and
+ * 2 u + 1 < thresholds[k][c][(int)a - 1], then r = r - copysign(1, r): the symbol one step nearer zero. From that r on every
+ * statement, output, check and flag is eae_hip_latent_quantize_rows': cq = bw r, the symbol round_half_even(cq / bw), shifted_out,
+ * t_out = inverse_gdn_4(shifted). Equal to ratecontrol.rdo_quantize_numpy element for element; with a table of zeros (the
+ * comparison is strict) equal to eae_hip_latent_quantize_rows bit for bit. The decoder is unchanged: the symbols are ordinary ones.
+ * Refusals as eae_hip_latent_quantize_rows, and a NULL or not 16-byte aligned thresholds_points or length outside [1, 255] ->
+ * EAE_HIP_BAD_ARGUMENT, before any launch. One launch. */
+int eae_hip_latent_quantize_rdo(const float* y, const float* map_mean, const float* bin_widths_points, const float* thresholds_points,
+                                const int32_t* point, int k_points, int length, const float* gamma_out_packed, const float* beta_out,
+                                float* shifted_out, float* t_out, int16_t* symbols_planar, uint32_t* nonzero_flags, uint32_t* checks,
+                                int n, int hw, void* stream);
+
 /* ---- lossless coder on the device: one feature map per lane --------------------------------------------------------
  * Replaces the per-map compress_lossless loop of lossless/compression.py:76-81 (and, underneath it,
  * lossless/c++/source/compression.cpp:3-65) for a whole batch of images whose symbols are already in HBM
