@@ -1222,16 +1222,22 @@ class BatchCodec(object):
             dev.publish_to_host(slot.out[first:], slot.pinned_out[first:])
         return q['shifted'] if self.learned else q['t']
 
+    def _coder_table(self, slot):
+        """What the step's coder runs on -> (the probability table, the rows of it the streams take: one tensor for whole maps, one per
+        shape class of `slot.classes` with a coding tile, where the exception maps' rows of the table go: None without a container)."""
+        if not self.emit_container:
+            return (self.probabilities, self.prob_row, None)
+        rows = self._emit_prob_row if self.coding_tile is None else [rows for (_, _, rows, _) in slot.classes]
+        return (slot.table, rows, slot.exception_rows)
+
     def _launch_coder(self, slot, hook=_no_hook):
         """The lossless coder over the slot's symbols (encode every map, decode it back, compare) and the publication of the
         slot's result block, on the current stream."""
         symbols = slot.symbols_2d
-        (table, prob_row) = (self.probabilities, self.prob_row)
-        if self.emit_container:
-            (table, prob_row) = (slot.table, self._emit_prob_row)
-            if self.idx_map_exception >= 0:
-                # the histograms are final since the analysis side and are zeroed only by this side's `publish_step` below
-                dev.exception_rows(slot.hist, slot.overflow, self.map_size, self.truncated_unary_length, out=slot.exception_rows)
+        (table, prob_row, exception_rows) = self._coder_table(slot)
+        if exception_rows is not None and self.idx_map_exception >= 0:
+            # the histograms are final since the analysis side and are zeroed only by this side's `publish_step`
+            dev.exception_rows(slot.hist, slot.overflow, self.map_size, self.truncated_unary_length, out=exception_rows)
         if self.coding_tile is not None:
             # (image, tile) entries instead of whole maps (DESIGN.md section 15): the symbols tile-major, one coder batch per shape
             # class, then the index over all of them and one pack per class into the one payload
@@ -1239,16 +1245,14 @@ class BatchCodec(object):
             if slot.gathered.data_ptr() != slot.symbols.data_ptr():
                 dev.tile_symbols_gather(slot.symbols, slot.gathered, self._tile_plan, self._tile_plan_host, self.h_in//csts.STRIDE_PROD,
                                         self.w_in//csts.STRIDE_PROD)
-            for (streams, tiles, rows, _) in slot.classes:
+            for ((streams, tiles, _, _), rows) in zip(slot.classes, prob_row):
                 hook('coder_encode', lambda: dev.coder_encode_batch(tiles, table, rows, length, out=streams, workspace=slot.workspace))
                 hook('coder_decode', lambda: dev.coder_decode_batch(streams, table, rows, expected=tiles, workspace=slot.workspace))
             dev.coder_index_tiles(slot.results[0], slot.results[1], self._tile_table, self.nb_maps, self._tile_layout['nb_tiles'],
                                   self.container_capacity_bytes, offsets=slot.offsets, index=slot.index)
             for (streams, _, _, offsets) in slot.classes:
                 dev.coder_pack_indexed(streams, offsets, slot.index, slot.payload)
-            dev.publish_prefix(slot.payload, slot.pinned_payload, slot.payload_bytes)
-            dev.publish_to_host(slot.emit_tail, slot.pinned_emit)
-            dev.publish_step(slot.out, slot.pinned_out, 4*self._n_streams, *slot.coder_seq)
+            self._publish_coder_side(slot)
             return
         if self.coder == 'device' and self.coder_chunks > 1:
             hook('coder_roundtrip', lambda: dev.coder_roundtrip_trailing(symbols, table, prob_row, self.truncated_unary_length,
@@ -1263,12 +1267,19 @@ class BatchCodec(object):
         else:
             slot.results.zero_()
         if self.emit_container:
-            # offsets and sizes from the bit counts, the streams packed, the packed bytes and the index words into pinned memory: all in
-            # front of the step counter's publication, so whoever sees the counter finds the payload on the host
+            # offsets and sizes from the bit counts, then the streams packed
             dev.coder_index_streams(slot.coder_streams, self.nb_maps, self.container_capacity_bytes, offsets=slot.offsets, index=slot.index)
             dev.coder_pack_indexed(slot.coder_streams, slot.offsets, slot.index, slot.payload)
+        self._publish_coder_side(slot)
+
+    def _publish_coder_side(self, slot, beside=()):
+        """With a container, the payload's prefix and the index words into pinned memory; `beside`: (device block, pinned block) pairs
+        a subclass publishes with them; then the step counter: all in front of it, so whoever sees the counter finds them on the host."""
+        if self.emit_container:
             dev.publish_prefix(slot.payload, slot.pinned_payload, slot.payload_bytes)
             dev.publish_to_host(slot.emit_tail, slot.pinned_emit)
+        for (block, pinned) in beside:
+            dev.publish_to_host(block, pinned)
         dev.publish_step(slot.out, slot.pinned_out, 4*self._n_streams, *slot.coder_seq)
 
     def _launch_synthesis_head(self, latents, slot, hook):
@@ -2316,64 +2327,66 @@ class BudgetTicket(Ticket):
         return blobs
 
 
-def _ladder_accumulators(counts_shape, nb_points, length, device):
-    """The ladder's accumulators of a budget slot, zeroed by one launch at the head of every step: (accum = [bypass bits int64 |
-    histograms int32 | range errors int32], and its three views). counts_shape: (N, K, 128), or (N, K, T, 128) per coding tile."""
-    nb_bits = 1
-    for extent in counts_shape:
-        nb_bits *= extent
-    nb_bins = nb_bits*(length + 1)
-    accum = torch.zeros(2*nb_bits + nb_bins + nb_points, dtype=torch.int32, device=device)
-    return (accum, accum[:2*nb_bits].view(torch.int64).view(counts_shape), accum[2*nb_bits:2*nb_bits + nb_bins].view(tuple(counts_shape) + (length + 1,)),
-            accum[2*nb_bits + nb_bins:])
-
-
-def _budget_slot_blocks(codec, extra_words=0):
-    """What `_BudgetSlot`, `_TiledBudgetSlot` and `_QualitySlot` hold alike: the step's budgets, the choice and the coder's table, on
-    the device and in pinned memory -> (pinned_budgets, budgets_host, budgets, budgets_nbytes, select, upper, point, flags,
-    pinned_select, select_host, table, points_table, exception_rows, pinned_rows, rows_host). extra_words: 32-bit words behind `flags`
-    in `select` and `pinned_select`, on an 8-byte boundary, for what a slot publishes together with the selection."""
-    (batch_size, nb_maps, device, ladder) = (codec.batch_size, codec.nb_maps, codec.device, codec.ladder)
-    (nb_points, length) = (ladder.nb_points, ladder.truncated_unary_length)
-    # the step's budgets: written by `BudgetCodec._stage` into pinned memory, fetched by a kernel inside the step's chain
+def _staged_block(batch_size, device):
+    """One int64 per image that `_stage` writes into pinned memory and a kernel inside the step's chain fetches -> (the pinned block,
+    its numpy view, the device's copy, the block's size in bytes on the device, as `device.fetch_prefix` takes it)."""
     padded = batch_size + batch_size % 2                       # `device.fetch_prefix` copies multiples of 16 bytes
-    pinned_budgets = torch.zeros(padded, dtype=torch.int64).pin_memory()
-    budgets = torch.zeros(padded, dtype=torch.int64, device=device)
-    budgets_nbytes = torch.full((1,), 8*padded, dtype=torch.int64, device=device)
-    # what the selection leaves for the host: [upper int64 N x K | point int32 N | flags int32 N]
-    select = torch.zeros(2*batch_size*nb_points + 2*batch_size + extra_words, dtype=torch.int32, device=device)
-    upper = select[:2*batch_size*nb_points].view(torch.int64).view(batch_size, nb_points)
-    point = select[2*batch_size*nb_points:2*batch_size*nb_points + batch_size]
-    flags = select[2*batch_size*nb_points + batch_size:2*batch_size*nb_points + 2*batch_size]
-    pinned_select = torch.zeros(select.numel(), dtype=torch.int32).pin_memory()
-    (upper_host, point_host, flags_host, _) = torch.split(pinned_select, [2*batch_size*nb_points, batch_size, batch_size, extra_words])
-    # what the result worker reads (`_BudgetWorker._finish`)
-    select_host = (upper_host.view(torch.int64).view(batch_size, nb_points).numpy(), point_host.numpy(), flags_host.numpy())
-    # the coder's table: [the K x 128 rows of the ladder | one row per image for its exception map]
-    table = torch.zeros((nb_points*nb_maps + batch_size, length), dtype=torch.float64, device=device)
-    points_table = table[:nb_points*nb_maps]
-    points_table.copy_(torch.from_numpy(ladder.binary_probabilities_points.reshape(nb_points*nb_maps, length)))
-    pinned_rows = torch.zeros((batch_size, length), dtype=torch.float64).pin_memory()
-    return (pinned_budgets, pinned_budgets.numpy(), budgets, budgets_nbytes, select, upper, point, flags, pinned_select, select_host, table,
-            points_table, table[nb_points*nb_maps:], pinned_rows, pinned_rows.numpy())
+    pinned = torch.zeros(padded, dtype=torch.int64).pin_memory()
+    return (pinned, pinned.numpy(), torch.zeros(padded, dtype=torch.int64, device=device),
+            torch.full((1,), 8*padded, dtype=torch.int64, device=device))
 
 
 class _BudgetSlot(object):
-    """What one `BudgetCodec` step in flight owns beyond its `_Slot`. Made once; tests/budget_slot_buffers.py says what a step may
-    find in every attribute when it starts."""
+    """What one `BudgetCodec` step in flight owns beyond its `_Slot`, and the base of what the other rate-control codecs' steps own:
+    the ladder's accumulators, the step's budgets, the choice and the coder's table, on the device and in pinned memory. Made once;
+    tests/budget_slot_buffers.py says what a step may find in every attribute when it starts."""
     __slots__ = ('accum', 'hist', 'bypass_bits', 'range_errors', 'pinned_budgets', 'budgets_host', 'budgets', 'budgets_nbytes', 'select',
                  'upper', 'point', 'flags', 'prob_row', 'pinned_select', 'select_host', 'table', 'points_table', 'exception_rows',
                  'pinned_rows', 'rows_host')
 
-    def __init__(self, codec):
-        (batch_size, nb_maps, ladder) = (codec.batch_size, codec.nb_maps, codec.ladder)
-        (self.accum, self.bypass_bits, self.hist, self.range_errors) = _ladder_accumulators(
-            (batch_size, ladder.nb_points, nb_maps), ladder.nb_points, ladder.truncated_unary_length, codec.device)
-        (self.pinned_budgets, self.budgets_host, self.budgets, self.budgets_nbytes, self.select, self.upper, self.point, self.flags,
-         self.pinned_select, self.select_host, self.table, self.points_table, self.exception_rows, self.pinned_rows,
-         self.rows_host) = _budget_slot_blocks(codec)
-        # the coder's row of every map of the step, chosen by `device.ladder_select`
-        self.prob_row = torch.zeros((batch_size, nb_maps), dtype=torch.int32, device=codec.device)
+    def __init__(self, codec, extra_words=0):
+        """extra_words: 32-bit words behind `flags` in `select` and `pinned_select`, on an 8-byte boundary, for what a subclass
+        publishes together with the selection."""
+        (batch_size, nb_maps, device, ladder) = (codec.batch_size, codec.nb_maps, codec.device, codec.ladder)
+        (nb_points, length) = (ladder.nb_points, ladder.truncated_unary_length)
+        (counts_shape, rows_shape) = self._shapes(codec)
+        # the ladder's accumulators, zeroed by one launch at the head of every step: [bypass bits int64 | histograms int32 | range
+        # errors int32]
+        nb_bits = int(numpy.prod(counts_shape))
+        nb_bins = nb_bits*(length + 1)
+        self.accum = torch.zeros(2*nb_bits + nb_bins + nb_points, dtype=torch.int32, device=device)
+        (bypass_bits, hist, self.range_errors) = torch.split(self.accum, [2*nb_bits, nb_bins, nb_points])
+        self.bypass_bits = bypass_bits.view(torch.int64).view(counts_shape)
+        self.hist = hist.view(counts_shape + (length + 1,))
+        # the step's budgets (`BudgetCodec._stage`)
+        (self.pinned_budgets, self.budgets_host, self.budgets, self.budgets_nbytes) = _staged_block(batch_size, device)
+        # what the selection leaves for the host: [upper int64 N x K | point int32 N | flags int32 N | the subclass's words]
+        layout = [2*batch_size*nb_points, batch_size, batch_size, extra_words]
+        self.select = torch.zeros(sum(layout), dtype=torch.int32, device=device)
+        (upper, self.point, self.flags, _) = torch.split(self.select, layout)
+        self.upper = upper.view(torch.int64).view(batch_size, nb_points)
+        self.pinned_select = torch.zeros(sum(layout), dtype=torch.int32).pin_memory()
+        (upper, point, flags, _) = torch.split(self.pinned_select, layout)
+        # what the result worker reads (`_BudgetWorker._finish`)
+        self.select_host = (upper.view(torch.int64).view(batch_size, nb_points).numpy(), point.numpy(), flags.numpy())
+        # the coder's table: [the K x 128 rows of the ladder | one row per image for its exception map]
+        self.table = torch.zeros((nb_points*nb_maps + batch_size, length), dtype=torch.float64, device=device)
+        (self.points_table, self.exception_rows) = (self.table[:nb_points*nb_maps], self.table[nb_points*nb_maps:])
+        self.points_table.copy_(torch.from_numpy(ladder.binary_probabilities_points.reshape(nb_points*nb_maps, length)))
+        self.pinned_rows = torch.zeros((batch_size, length), dtype=torch.float64).pin_memory()
+        self.rows_host = self.pinned_rows.numpy()
+        # the coder's row of every stream of the step, chosen by `device.ladder_select` or `device.ladder_select_tiles`
+        self.prob_row = torch.zeros(rows_shape, dtype=torch.int32, device=device)
+
+    @staticmethod
+    def _shapes(codec):
+        """(the shape of the ladder's counts, the shape of `prob_row`): here one count and one row per (image, [point,] map)."""
+        return ((codec.batch_size, codec.ladder.nb_points, codec.nb_maps), (codec.batch_size, codec.nb_maps))
+
+    @property
+    def selected(self):
+        """The block `device.ladder_select` writes every image's point into."""
+        return self.point
 
 
 class _BudgetHead(object):
@@ -2409,8 +2422,10 @@ class BudgetCodec(BatchCodec):
     """`BatchCodec` with a rate point per image, chosen inside the step, on the device, so that the image's blob fits a byte budget
     (DESIGN.md section 19): "N bytes per image" as a property of a step of the resident codec."""
     (_ticket_class, _worker_class) = (BudgetTicket, _BudgetWorker)
-    # what `TiledBudgetCodec` flips: whether `coding_tile` is taken, and the class of the per-step state beyond `_Slot`
+    # what the subclasses flip: whether `coding_tile` is taken (and in what words it is refused), and the class of the per-step state
+    # beyond `_Slot`
     (_takes_coding_tile, _budget_slot_class) = (False, _BudgetSlot)
+    _no_coding_tile = '`BudgetCodec` does not take `coding_tile`: the bounds are those of whole maps (EAE1).'
 
     def __init__(self, variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, budget_bytes=None, **batch_codec_options):
         """ladder: a `ratecontrol.RateLadder`, finest point first, of at most `device.ladder_max_points(L)` points. budget_bytes: the
@@ -2433,7 +2448,7 @@ class BudgetCodec(BatchCodec):
         if not options.pop('emit_container', True):
             raise ValueError('`BudgetCodec` always emits containers: the budget is that of the image\'s blob.')
         if options.get('coding_tile') is not None and not self._takes_coding_tile:
-            raise ValueError('`BudgetCodec` does not take `coding_tile`: the bounds are those of whole maps (EAE1).')
+            raise ValueError(self._no_coding_tile)
         if options.get('fuse_latent'):
             raise ValueError('`BudgetCodec` does not take `fuse_latent`: the point is chosen between conv_3 and the quantiser.')
         if options.get('rdo_lambda') is not None:
@@ -2488,10 +2503,18 @@ class BudgetCodec(BatchCodec):
     def submit(self, luminances_uint8, budget_bytes=None):
         """`BatchCodec.submit` with the step's budgets: a scalar or one value per image, bytes of the image's whole blob (header
         included); None: the constructor's `budget_bytes`."""
-        budgets = self._default_budgets if budget_bytes is None else self._budgets_of(budget_bytes, self.batch_size)
+        budgets = self._budgets_for(budget_bytes)
         if budgets is None:
             raise ValueError('no `budget_bytes`, and the codec was built without a default.')
-        self._staged = budgets
+        return self._submit_staged(luminances_uint8, (budgets,))
+
+    def _budgets_for(self, budget_bytes):
+        """The budgets of a step as int64 (batch_size,): those it names, else the constructor's; None when there are none."""
+        return self._default_budgets if budget_bytes is None else self._budgets_of(budget_bytes, self.batch_size)
+
+    def _submit_staged(self, luminances_uint8, staged):
+        """`BatchCodec.submit` of a step whose `_stage` finds `staged`, one int64 (batch_size,) per pinned block it fills."""
+        self._staged = staged
         try:
             return super(BudgetCodec, self).submit(luminances_uint8)
         finally:
@@ -2499,7 +2522,7 @@ class BudgetCodec(BatchCodec):
 
     def _stage(self, slot):
         """The step's budgets into the slot's pinned block (the slot is this step's: `_submit` has claimed it)."""
-        self._budget_slots[id(slot)].budgets_host[:self.batch_size] = self._staged
+        self._budget_slots[id(slot)].budgets_host[:self.batch_size] = self._staged[0]
 
     def _launch_step(self, luminances_uint8, slot, index, ticket, coded):
         self._stage(slot)
@@ -2555,62 +2578,74 @@ class BudgetCodec(BatchCodec):
     def _launch_select(self, budget):
         dev.ladder_select(budget.hist, budget.bypass_bits, self._fixed_costs, self._log2_tables, self.idx_map_exception, self._header_bytes,
                           self.map_size, budget.budgets[:self.batch_size], self.ladder.nb_points*self.nb_maps,
-                          out={'point': budget.point, 'prob_row': budget.prob_row, 'upper': budget.upper, 'flags': budget.flags})
+                          out={'point': budget.selected, 'prob_row': budget.prob_row, 'upper': budget.upper, 'flags': budget.flags})
 
-    def _launch_coder(self, slot, hook=_no_hook):
-        """`BatchCodec._launch_coder` over the table of every point's rows with the rows `ladder_select` chose, and the publication
-        of the choice, on the current stream."""
+    def _coder_table(self, slot):
+        """The table of every point's rows, the rows `ladder_select` chose and the table's own exception rows."""
         budget = self._budget_slots[id(slot)]
-        symbols = slot.symbols_2d
-        prob_row = budget.prob_row.view(-1)
-        if self.idx_map_exception >= 0:
-            dev.exception_rows(slot.hist, slot.overflow, self.map_size, self.truncated_unary_length, out=budget.exception_rows)
-        hook('coder_encode', lambda: dev.coder_encode_batch(symbols, budget.table, prob_row, self.truncated_unary_length,
-                                                            out=slot.coder_streams, workspace=slot.workspace))
-        hook('coder_decode', lambda: dev.coder_decode_batch(slot.coder_streams, budget.table, prob_row, expected=symbols,
-                                                            workspace=slot.workspace))
-        dev.coder_index_streams(slot.coder_streams, self.nb_maps, self.container_capacity_bytes, offsets=slot.offsets, index=slot.index)
-        dev.coder_pack_indexed(slot.coder_streams, slot.offsets, slot.index, slot.payload)
-        self._publish_coder_side(slot, budget)
+        return (budget.table, budget.prob_row.view(-1), budget.exception_rows)
 
-    def _publish_coder_side(self, slot, budget):
-        """The payload's prefix, the index words, the choice and the exception rows into pinned memory, then the step counter."""
-        dev.publish_prefix(slot.payload, slot.pinned_payload, slot.payload_bytes)
-        dev.publish_to_host(slot.emit_tail, slot.pinned_emit)
-        dev.publish_to_host(budget.select, budget.pinned_select)
-        if self.idx_map_exception >= 0:
-            dev.publish_to_host(budget.exception_rows, budget.pinned_rows)
-        dev.publish_step(slot.out, slot.pinned_out, 4*self._n_streams, *slot.coder_seq)
+    def _publish_coder_side(self, slot):
+        """`BatchCodec._publish_coder_side` with the choice, and with an exception map its rows, beside the payload and the index."""
+        budget = self._budget_slots[id(slot)]
+        rows = ((budget.exception_rows, budget.pinned_rows),) if self.idx_map_exception >= 0 else ()
+        super(BudgetCodec, self)._publish_coder_side(slot, ((budget.select, budget.pinned_select),) + rows)
 
 
 # ---- the same for tile-indexed containers: counts, bounds and streams per coding tile (DESIGN.md section 20) ------------------------
 
-class _TiledBudgetSlot(object):
-    """What one `TiledBudgetCodec` step in flight owns beyond its `_Slot`: `_BudgetSlot`'s state with the ladder's accumulators per
-    coding tile and the coder's rows per stream of the step. Made once; tests/tiled_budget_slot_buffers.py says what a step may find
-    in every attribute when it starts. The accumulators take N K T 128 (L + 1) 4 bytes per slot (and an eleventh of that for the
-    bypass bits): 7.3 MB at 24 Kodak images, K = 9 and tiles of 16, 29 MB at tiles of 8."""
-    __slots__ = ('accum', 'hist', 'bypass_bits', 'range_errors', 'pinned_budgets', 'budgets_host', 'budgets', 'budgets_nbytes', 'select',
-                 'upper', 'point', 'flags', 'prob_row', 'class_rows', 'pinned_select', 'select_host', 'table', 'points_table',
-                 'exception_rows', 'pinned_rows', 'rows_host')
+class _TiledRows(object):
+    """What makes a `_BudgetSlot` or a `_QualitySlot` the one of a codec with a coding tile (in front of it among the bases): the
+    ladder's accumulators per coding tile and the coder's rows per stream of the step."""
+    __slots__ = ()              # (`class_rows` is a slot of the two classes below: two bases that both add slots do not combine)
 
     def __init__(self, codec):
-        (batch_size, nb_maps, ladder, tiled) = (codec.batch_size, codec.nb_maps, codec.ladder, codec._tile_layout)
-        (self.accum, self.bypass_bits, self.hist, self.range_errors) = _ladder_accumulators(
-            (batch_size, ladder.nb_points, tiled['nb_tiles'], nb_maps), ladder.nb_points, ladder.truncated_unary_length, codec.device)
-        (self.pinned_budgets, self.budgets_host, self.budgets, self.budgets_nbytes, self.select, self.upper, self.point, self.flags,
-         self.pinned_select, self.select_host, self.table, self.points_table, self.exception_rows, self.pinned_rows,
-         self.rows_host) = _budget_slot_blocks(codec)
-        # the coder's row of every stream of the step in RUN order, chosen by `device.ladder_select_tiles`, and every shape class's run
-        self.prob_row = torch.zeros(tiled['n_streams'], dtype=torch.int32, device=codec.device)
-        self.class_rows = [self.prob_row[first:first + count*nb_maps] for (_, count, first, _) in tiled['runs']]
+        super(_TiledRows, self).__init__(codec)
+        # `prob_row` holds the rows in RUN order (`device.ladder_select_tiles`): every shape class's run of them
+        self.class_rows = [self.prob_row[first:first + count*codec.nb_maps] for (_, count, first, _) in codec._tile_layout['runs']]
+
+    @staticmethod
+    def _shapes(codec):
+        tiled = codec._tile_layout
+        return ((codec.batch_size, codec.ladder.nb_points, tiled['nb_tiles'], codec.nb_maps), (tiled['n_streams'],))
 
 
-class TiledBudgetCodec(BudgetCodec):
+class _TiledBudgetSlot(_TiledRows, _BudgetSlot):
+    """What one `TiledBudgetCodec` step in flight owns beyond its `_Slot`: `_BudgetSlot`'s state with `_TiledRows`' shapes. Made once;
+    tests/tiled_budget_slot_buffers.py says what a step may find in every attribute when it starts. The accumulators take
+    N K T 128 (L + 1) 4 bytes per slot (and an eleventh of that for the bypass bits): 7.3 MB at 24 Kodak images, K = 9 and tiles of
+    16, 29 MB at tiles of 8."""
+    __slots__ = ('class_rows',)
+
+
+class _TiledRateControl(object):
+    """The tiled pieces of a rate-control step, in front of `BudgetCodec` or `QualityCodec` among the bases: the counts and the
+    bounds per coding tile, and the coder's rows per shape class."""
+    _takes_coding_tile = True
+
+    def _launch_ladder(self, y, budget):
+        plane = y.view(self.batch_size, self.h_in//csts.STRIDE_PROD, self.w_in//csts.STRIDE_PROD, self.nb_maps)
+        dev.ladder_histograms_tiles(plane, self._bin_widths_points, self.coding_tile, self.map_mean, self.truncated_unary_length,
+                                    out=(budget.hist, budget.bypass_bits, budget.range_errors))
+
+    def _launch_select(self, budget):
+        dev.ladder_select_tiles(budget.hist, budget.bypass_bits, self._fixed_costs, self._log2_tables, self.idx_map_exception,
+                                self._header_bytes, self.map_size, budget.budgets[:self.batch_size], self._entry_image,
+                                self.ladder.nb_points*self.nb_maps,
+                                out={'point': budget.selected, 'prob_row': budget.prob_row, 'upper': budget.upper, 'flags': budget.flags})
+
+    def _coder_table(self, slot):
+        """The table of every point's rows, every shape class's run of the rows `ladder_select_tiles` chose and the table's own
+        exception rows."""
+        budget = self._budget_slots[id(slot)]
+        return (budget.table, budget.class_rows, budget.exception_rows)
+
+
+class TiledBudgetCodec(_TiledRateControl, BudgetCodec):
     """`BudgetCodec` for tile-indexed containers: a byte budget per image whose blob is the single-image `EAT1`
     blob `container.encode_images(..., coding_tile=coding_tile)` writes, so that crops come out of it (`container.decode_region`,
     `RegionDecoder`) and its serial chains are a tile long."""
-    (_takes_coding_tile, _budget_slot_class) = (True, _TiledBudgetSlot)
+    _budget_slot_class = _TiledBudgetSlot
 
     def __init__(self, variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, coding_tile, budget_bytes=None, **batch_codec_options):
         """coding_tile: (th, tw) in latents, clamped to the latent plane, as `BatchCodec(coding_tile=...)` takes it; everything else
@@ -2625,106 +2660,61 @@ class TiledBudgetCodec(BudgetCodec):
         super(TiledBudgetCodec, self).__init__(variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, budget_bytes=budget_bytes,
                                                coding_tile=coding_tile, **batch_codec_options)
 
-    def _launch_ladder(self, y, budget):
-        plane = y.view(self.batch_size, self.h_in//csts.STRIDE_PROD, self.w_in//csts.STRIDE_PROD, self.nb_maps)
-        dev.ladder_histograms_tiles(plane, self._bin_widths_points, self.coding_tile, self.map_mean, self.truncated_unary_length,
-                                    out=(budget.hist, budget.bypass_bits, budget.range_errors))
-
-    def _launch_select(self, budget):
-        dev.ladder_select_tiles(budget.hist, budget.bypass_bits, self._fixed_costs, self._log2_tables, self.idx_map_exception,
-                                self._header_bytes, self.map_size, budget.budgets[:self.batch_size], self._entry_image,
-                                self.ladder.nb_points*self.nb_maps,
-                                out={'point': budget.point, 'prob_row': budget.prob_row, 'upper': budget.upper, 'flags': budget.flags})
-
-    def _launch_coder(self, slot, hook=_no_hook):
-        """`BatchCodec._launch_coder` in tiles over the table of every point's rows: every shape class with its run of the rows
-        `ladder_select_tiles` chose, then the index, one pack per class and the publication of the choice, on the current stream."""
-        budget = self._budget_slots[id(slot)]
-        length = self.truncated_unary_length
-        if self.idx_map_exception >= 0:
-            dev.exception_rows(slot.hist, slot.overflow, self.map_size, length, out=budget.exception_rows)
-        if slot.gathered.data_ptr() != slot.symbols.data_ptr():
-            dev.tile_symbols_gather(slot.symbols, slot.gathered, self._tile_plan, self._tile_plan_host, self.h_in//csts.STRIDE_PROD,
-                                    self.w_in//csts.STRIDE_PROD)
-        for ((streams, tiles, _, _), rows) in zip(slot.classes, budget.class_rows):
-            hook('coder_encode', lambda: dev.coder_encode_batch(tiles, budget.table, rows, length, out=streams, workspace=slot.workspace))
-            hook('coder_decode', lambda: dev.coder_decode_batch(streams, budget.table, rows, expected=tiles, workspace=slot.workspace))
-        dev.coder_index_tiles(slot.results[0], slot.results[1], self._tile_table, self.nb_maps, self._tile_layout['nb_tiles'],
-                              self.container_capacity_bytes, offsets=slot.offsets, index=slot.index)
-        for (streams, _, _, offsets) in slot.classes:
-            dev.coder_pack_indexed(streams, offsets, slot.index, slot.payload)
-        self._publish_coder_side(slot, budget)
-
 
 # ---- a PSNR floor per image, searched on the device (DESIGN.md section 21) ----------------------------------------------------------
 
-class _QualitySlot(object):
+class _QualitySlot(_BudgetSlot):
     """What one `QualityCodec` step in flight owns beyond its `_Slot`: `_BudgetSlot`'s state -- its `point` is called `first` here,
     the finest point the search may take --, the step's thresholds, the bisection's state and trace behind the selection in `select`
     (published with it), the accumulator and the latent buffer of the probes. Made once; tests/quality_slot_buffers.py says what a
     step may find in every attribute when it starts."""
-    __slots__ = ('accum', 'hist', 'bypass_bits', 'range_errors', 'pinned_budgets', 'budgets_host', 'budgets', 'budgets_nbytes', 'select',
-                 'upper', 'first', 'flags', 'prob_row', 'pinned_select', 'select_host', 'table', 'points_table', 'exception_rows',
-                 'pinned_rows', 'rows_host', 'pinned_max_sse', 'max_sse_host', 'max_sse', 'max_sse_nbytes', 'trace_sse', 'point', 'met',
-                 'state', 'trace_point', 'search_host', 'probe_acc', 'probe_latent')
+    __slots__ = ('first', 'pinned_max_sse', 'max_sse_host', 'max_sse', 'max_sse_nbytes', 'trace_sse', 'met', 'state', 'trace_point',
+                 'search_host', 'probe_acc', 'probe_latent')
 
     def __init__(self, codec):
-        (batch_size, nb_maps, ladder, device) = (codec.batch_size, codec.nb_maps, codec.ladder, codec.device)
-        nb_rounds = codec.nb_rounds
-        (self.accum, self.bypass_bits, self.hist, self.range_errors) = _ladder_accumulators(
-            (batch_size, ladder.nb_points, nb_maps), ladder.nb_points, ladder.truncated_unary_length, device)
+        (batch_size, nb_rounds, device) = (codec.batch_size, codec.nb_rounds, codec.device)
         # behind [upper | first | flags]: [trace_sse int64 N x R | point int32 N | met int32 N | state int32 N x 2 | trace_point int32 N x R]
-        layout = [2*batch_size*nb_rounds, batch_size, batch_size, 2*batch_size, batch_size*nb_rounds]
-        (self.pinned_budgets, self.budgets_host, self.budgets, self.budgets_nbytes, self.select, self.upper, self.first, self.flags,
-         self.pinned_select, self.select_host, self.table, self.points_table, self.exception_rows, self.pinned_rows,
-         self.rows_host) = _budget_slot_blocks(codec, extra_words=sum(layout))
-        own = self.select.numel() - sum(layout)
-        (trace_sse, self.point, self.met, state, trace_point) = torch.split(self.select[own:], layout)
+        search = [2*batch_size*nb_rounds, batch_size, batch_size, 2*batch_size, batch_size*nb_rounds]
+        super(_QualitySlot, self).__init__(codec, extra_words=sum(search))
+        own = self.select.numel() - sum(search)
+        # what `device.ladder_select` writes keeps its place and gives its name to the search's own block: the point the step codes at
+        self.first = self.point
+        (trace_sse, self.point, self.met, state, trace_point) = torch.split(self.select[own:], search)
         self.trace_sse = trace_sse.view(torch.int64).view(batch_size, nb_rounds)
         self.state = state.view(batch_size, 2)
         self.trace_point = trace_point.view(batch_size, nb_rounds)
-        (trace_sse, point, met, state, trace_point) = torch.split(self.pinned_select[own:], layout)
+        (trace_sse, point, met, state, trace_point) = torch.split(self.pinned_select[own:], search)
         # what the result worker reads (`_QualityWorker._finish`): (point, met, trace_point, trace_sse)
         self.search_host = (point.numpy(), met.numpy(), trace_point.view(batch_size, nb_rounds).numpy(),
                             trace_sse.view(torch.int64).view(batch_size, nb_rounds).numpy())
-        # the step's thresholds: written by `QualityCodec._stage` into pinned memory, fetched by a kernel inside the step's chain
-        padded = batch_size + batch_size % 2                       # `device.fetch_prefix` copies multiples of 16 bytes
-        self.pinned_max_sse = torch.zeros(padded, dtype=torch.int64).pin_memory()
-        self.max_sse_host = self.pinned_max_sse.numpy()
-        self.max_sse = torch.zeros(padded, dtype=torch.int64, device=device)
-        self.max_sse_nbytes = torch.full((1,), 8*padded, dtype=torch.int64, device=device)
-        # the coder's row of every map of the step: `device.ladder_select`'s, then every round's of `device.quality_search`
-        self.prob_row = torch.zeros((batch_size, nb_maps), dtype=torch.int32, device=device)
+        # the step's thresholds (`QualityCodec._stage`)
+        (self.pinned_max_sse, self.max_sse_host, self.max_sse, self.max_sse_nbytes) = _staged_block(batch_size, device)
         # what a probe's `tconv9x9s4_luma` adds its squared errors into, and what its quantiser writes for its synthesis pass
         self.probe_acc = torch.zeros(batch_size, dtype=torch.int64, device=device)
-        self.probe_latent = torch.empty((batch_size, codec.h_in//csts.STRIDE_PROD, codec.w_in//csts.STRIDE_PROD, nb_maps), dtype=torch.float32,
-                                        device=device)
+        self.probe_latent = torch.empty((batch_size, codec.h_in//csts.STRIDE_PROD, codec.w_in//csts.STRIDE_PROD, codec.nb_maps),
+                                        dtype=torch.float32, device=device)
+
+    @property
+    def selected(self):
+        return self.first
 
 
-class _QualityWorker(_Worker):
+class _QualityWorker(_BudgetWorker):
     """The result worker of `QualityCodec`."""
 
     def _finish(self, job):
-        """The step's search out of the slot's pinned blocks into the ticket, while the slot is still the step's."""
-        (ticket, head) = (job.ticket, job.emit[0])
-        quality = head.budget_slot
-        (upper, first, _) = quality.select_host
+        """`_BudgetWorker._finish`, whose point is the finest the search could take, then the step's search out of the slot's pinned
+        blocks into the ticket."""
+        super(_QualityWorker, self)._finish(job)
+        (ticket, quality) = (job.ticket, job.emit[0].budget_slot)
         (point, met, trace_point, trace_sse) = quality.search_host
-        n = ticket.nb_images
-        budgets = quality.budgets_host[:n].copy()
+        (n, values) = (ticket.nb_images, ticket._values)
         rate_point = point[:n].astype(numpy.int64)
-        upper = upper[:n].copy()
-        blob_bytes = head.header_bytes + ticket._values['container_bytes']
-        ticket._values.update({'rate_point': rate_point, 'first_point': first[:n].astype(numpy.int64), 'met': (met[:n] & 1) != 0,
-                               'max_sse': quality.max_sse_host[:n].copy(), 'probe_points': trace_point[:n].astype(numpy.int64),
-                               'probe_sse': trace_sse[:n].copy(), 'upper_bound_bytes': upper, 'budget_bytes': budgets,
-                               'blob_bytes': blob_bytes, 'promised': upper[numpy.arange(n), rate_point] <= budgets,
-                               'fits': blob_bytes <= budgets})
-        parts = ticket._container_parts
-        parts['head'] = head.fixed
-        parts['rate_point'] = rate_point
-        if self.idx_map_exception >= 0:
-            parts['rows'] = head.budget_slot.rows_host.copy()
+        values.update({'rate_point': rate_point, 'first_point': values['rate_point'], 'met': (met[:n] & 1) != 0,
+                       'max_sse': quality.max_sse_host[:n].copy(), 'probe_points': trace_point[:n].astype(numpy.int64),
+                       'probe_sse': trace_sse[:n].copy(),
+                       'promised': values['upper_bound_bytes'][numpy.arange(n), rate_point] <= values['budget_bytes']})
+        ticket._container_parts['rate_point'] = rate_point
 
 
 class QualityCodec(BudgetCodec):
@@ -2732,7 +2722,9 @@ class QualityCodec(BudgetCodec):
     the smallest size the ladder allows: "this much quality per image" as a property of a step of the
     resident codec."""
     (_ticket_class, _worker_class) = (BudgetTicket, _QualityWorker)
-    (_takes_coding_tile, _budget_slot_class) = (False, _QualitySlot)
+    _budget_slot_class = _QualitySlot
+    _no_coding_tile = ('`QualityCodec` does not take `coding_tile`: the coder\'s rows per stream would need the run order of '
+                       '`device.ladder_select_tiles`.')
     NO_BUDGET = 1 << 62            # what a step without a budget stages: every valid point's bound is within it
 
     def __init__(self, variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, target_psnr=None, max_sse=None, budget_bytes=None,
@@ -2753,18 +2745,17 @@ class QualityCodec(BudgetCodec):
         'rate_point' is the point taken, 'promised' says upper_bound_bytes[i, rate_point[i]] <= budget, 'budget_bytes' is 2^62
         without a budget. `Ticket.image_containers()[i]` is byte for byte `container.encode_images` of image i at its point;
         `Ticket.container()` raises."""
-        from . import ratecontrol
-        if not isinstance(ladder, ratecontrol.RateLadder):
-            raise TypeError('`ladder` is not a `ratecontrol.RateLadder`.')
-        # refused in front of every allocation
-        if batch_codec_options.get('coding_tile') is not None and not self._takes_coding_tile:
-            raise ValueError('`QualityCodec` does not take `coding_tile`: the coder\'s rows per stream would need the run order of '
-                             '`device.ladder_select_tiles`.')
-        self.nb_rounds = ratecontrol.quality_rounds(ladder.nb_points)
+        # refused in front of every allocation, as everything `BudgetCodec.__init__` refuses
         self._nb_pixels = h_in*w_in
         self._default_max_sse = self._max_sse_of(target_psnr, max_sse, batch_size)
         super(QualityCodec, self).__init__(variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, budget_bytes=budget_bytes,
                                            **batch_codec_options)
+
+    @property
+    def nb_rounds(self):
+        """The rounds of a step's bisection."""
+        from . import ratecontrol
+        return ratecontrol.quality_rounds(self.ladder.nb_points)
 
     def _max_sse_of(self, target_psnr, max_sse, batch_size):
         """The thresholds of a step as int64 (batch_size,), from one of the two ways to name them; None when neither is given."""
@@ -2792,24 +2783,15 @@ class QualityCodec(BudgetCodec):
                 raise ValueError('neither `target_psnr` nor `max_sse`, and the codec was built without a default.')
         else:
             thresholds = self._max_sse_of(target_psnr, max_sse, self.batch_size)
-        budgets = self._default_budgets if budget_bytes is None else self._budgets_of(budget_bytes, self.batch_size)
+        budgets = self._budgets_for(budget_bytes)
         if budgets is None:
             budgets = numpy.full(self.batch_size, self.NO_BUDGET, dtype=numpy.int64)
-        self._staged = (budgets, thresholds)
-        try:
-            return BatchCodec.submit(self, luminances_uint8)
-        finally:
-            self._staged = None
+        return self._submit_staged(luminances_uint8, (budgets, thresholds))
 
     def _stage(self, slot):
-        """The step's budgets and thresholds into the slot's pinned blocks (the slot is this step's: `_submit` has claimed it)."""
-        quality = self._budget_slots[id(slot)]
-        (quality.budgets_host[:self.batch_size], quality.max_sse_host[:self.batch_size]) = self._staged
-
-    def _launch_select(self, budget):
-        dev.ladder_select(budget.hist, budget.bypass_bits, self._fixed_costs, self._log2_tables, self.idx_map_exception, self._header_bytes,
-                          self.map_size, budget.budgets[:self.batch_size], self.ladder.nb_points*self.nb_maps,
-                          out={'point': budget.first, 'prob_row': budget.prob_row, 'upper': budget.upper, 'flags': budget.flags})
+        """`BudgetCodec._stage`, and the step's thresholds into their pinned block."""
+        super(QualityCodec, self)._stage(slot)
+        self._budget_slots[id(slot)].max_sse_host[:self.batch_size] = self._staged[1]
 
     def _launch_round(self, quality, round):
         dev.quality_search(quality.first, quality.max_sse[:self.batch_size], quality.state, quality.probe_acc, quality.point, quality.prob_row,
@@ -2863,55 +2845,18 @@ def tile_prob_rows(layout, points, idx_map_exception=-1, exception_row_base=None
     return rows.reshape(-1).astype(numpy.int32)
 
 
-class _TiledQualitySlot(object):
-    """What one `TiledQualityCodec` step in flight owns beyond its `_Slot`: `_QualitySlot`'s state with the ladder's accumulators per
-    coding tile and the coder's rows per stream of the step, as in `_TiledBudgetSlot`. Made once;
+class _TiledQualitySlot(_TiledRows, _QualitySlot):
+    """What one `TiledQualityCodec` step in flight owns beyond its `_Slot`: `_QualitySlot`'s state with `_TiledRows`' shapes, as
+    `_TiledBudgetSlot` is `_BudgetSlot`'s; every round of `device.quality_search_tiles` writes `prob_row` again. Made once;
     tests/tiled_quality_slot_buffers.py says what a step may find in every attribute when it starts."""
-    __slots__ = ('accum', 'hist', 'bypass_bits', 'range_errors', 'pinned_budgets', 'budgets_host', 'budgets', 'budgets_nbytes', 'select',
-                 'upper', 'first', 'flags', 'prob_row', 'class_rows', 'pinned_select', 'select_host', 'table', 'points_table',
-                 'exception_rows', 'pinned_rows', 'rows_host', 'pinned_max_sse', 'max_sse_host', 'max_sse', 'max_sse_nbytes', 'trace_sse',
-                 'point', 'met', 'state', 'trace_point', 'search_host', 'probe_acc', 'probe_latent')
-
-    def __init__(self, codec):
-        (batch_size, nb_maps, ladder, device, tiled) = (codec.batch_size, codec.nb_maps, codec.ladder, codec.device, codec._tile_layout)
-        nb_rounds = codec.nb_rounds
-        (self.accum, self.bypass_bits, self.hist, self.range_errors) = _ladder_accumulators(
-            (batch_size, ladder.nb_points, tiled['nb_tiles'], nb_maps), ladder.nb_points, ladder.truncated_unary_length, device)
-        # behind [upper | first | flags]: [trace_sse int64 N x R | point int32 N | met int32 N | state int32 N x 2 | trace_point int32 N x R]
-        layout = [2*batch_size*nb_rounds, batch_size, batch_size, 2*batch_size, batch_size*nb_rounds]
-        (self.pinned_budgets, self.budgets_host, self.budgets, self.budgets_nbytes, self.select, self.upper, self.first, self.flags,
-         self.pinned_select, self.select_host, self.table, self.points_table, self.exception_rows, self.pinned_rows,
-         self.rows_host) = _budget_slot_blocks(codec, extra_words=sum(layout))
-        own = self.select.numel() - sum(layout)
-        (trace_sse, self.point, self.met, state, trace_point) = torch.split(self.select[own:], layout)
-        self.trace_sse = trace_sse.view(torch.int64).view(batch_size, nb_rounds)
-        self.state = state.view(batch_size, 2)
-        self.trace_point = trace_point.view(batch_size, nb_rounds)
-        (trace_sse, point, met, state, trace_point) = torch.split(self.pinned_select[own:], layout)
-        # what the result worker reads (`_QualityWorker._finish`): (point, met, trace_point, trace_sse)
-        self.search_host = (point.numpy(), met.numpy(), trace_point.view(batch_size, nb_rounds).numpy(),
-                            trace_sse.view(torch.int64).view(batch_size, nb_rounds).numpy())
-        # the step's thresholds: written by `QualityCodec._stage` into pinned memory, fetched by a kernel inside the step's chain
-        padded = batch_size + batch_size % 2                       # `device.fetch_prefix` copies multiples of 16 bytes
-        self.pinned_max_sse = torch.zeros(padded, dtype=torch.int64).pin_memory()
-        self.max_sse_host = self.pinned_max_sse.numpy()
-        self.max_sse = torch.zeros(padded, dtype=torch.int64, device=device)
-        self.max_sse_nbytes = torch.full((1,), 8*padded, dtype=torch.int64, device=device)
-        # the coder's row of every stream of the step in RUN order: `device.ladder_select_tiles`', then every round's of
-        # `device.quality_search_tiles`, and every shape class's run
-        self.prob_row = torch.zeros(tiled['n_streams'], dtype=torch.int32, device=device)
-        self.class_rows = [self.prob_row[first:first + count*nb_maps] for (_, count, first, _) in tiled['runs']]
-        # what a probe's `tconv9x9s4_luma` adds its squared errors into, and what its quantiser writes for its synthesis pass
-        self.probe_acc = torch.zeros(batch_size, dtype=torch.int64, device=device)
-        self.probe_latent = torch.empty((batch_size, codec.h_in//csts.STRIDE_PROD, codec.w_in//csts.STRIDE_PROD, nb_maps), dtype=torch.float32,
-                                        device=device)
+    __slots__ = ('class_rows',)
 
 
-class TiledQualityCodec(QualityCodec):
+class TiledQualityCodec(_TiledRateControl, QualityCodec):
     """`QualityCodec` for tile-indexed containers: a PSNR floor per image whose blob is the single-image `EAT1`
     blob `container.encode_images(..., coding_tile=coding_tile)` writes, so that crops come out of it (`container.decode_region`,
     `RegionDecoder`) and its serial chains are a tile long."""
-    (_takes_coding_tile, _budget_slot_class) = (True, _TiledQualitySlot)
+    _budget_slot_class = _TiledQualitySlot
 
     def __init__(self, variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, coding_tile, target_psnr=None, max_sse=None,
                  budget_bytes=None, **batch_codec_options):
@@ -2932,15 +2877,6 @@ class TiledQualityCodec(QualityCodec):
         except BaseException:
             self.close()
             raise
-
-    _launch_ladder = TiledBudgetCodec._launch_ladder
-    _launch_coder = TiledBudgetCodec._launch_coder
-
-    def _launch_select(self, budget):
-        dev.ladder_select_tiles(budget.hist, budget.bypass_bits, self._fixed_costs, self._log2_tables, self.idx_map_exception,
-                                self._header_bytes, self.map_size, budget.budgets[:self.batch_size], self._entry_image,
-                                self.ladder.nb_points*self.nb_maps,
-                                out={'point': budget.first, 'prob_row': budget.prob_row, 'upper': budget.upper, 'flags': budget.flags})
 
     def _launch_round(self, quality, round):
         dev.quality_search_tiles(quality.first, quality.max_sse[:self.batch_size], quality.state, quality.probe_acc, quality.point,

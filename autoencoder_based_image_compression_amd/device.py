@@ -506,23 +506,31 @@ def _bypass_bits_of_magnitudes(magnitudes, length):
     return (magnitudes != 0).astype(numpy.int64) + numpy.where(magnitudes >= length, 2*nb_bits + 1, 0)
 
 
+def _wrapped_magnitudes(y, bin_widths, map_mean):
+    """|symbol| of y [N, ..., 128] at a rate point whose int16 symbols have wrapped, recounted on the host with the quantiser's float32
+    expressions (numpy divides and rounds as the kernels do) -> numpy (magnitudes int64 [N, hw, 128], 0 where the symbol does not fit
+    int16; good bool [N, hw, 128]: where it does)."""
+    import numpy
+    host = y.reshape(y.shape[0], -1, y.shape[-1]).cpu().numpy()
+    bw = bin_widths.cpu().numpy()
+    centered = host - (map_mean.cpu().numpy() if map_mean is not None else numpy.float32(0.))
+    with numpy.errstate(all='ignore'):
+        rs = numpy.abs(numpy.rint(bw*numpy.rint(centered/bw)/bw))
+        good = rs < numpy.float32(32768.)
+    return numpy.where(good, rs, 0.).astype(numpy.int64), good
+
+
 def _ladder_point_by_passes(y, bin_widths, map_mean, length):
     """One rate point by the route `stats.compute_binary_probabilities` takes: `quantize_maps`, `symbol_histograms`, a fold on the
     host -> numpy (hist int64 [N, 128, L + 1], bypass bits int64 [N, 128], range errors). A point with range errors, whose int16
-    symbols have wrapped, is recounted on the host with the quantiser's float32 expressions (numpy divides and rounds as the
-    kernels do), so that the arrays are `eae_hip_ladder_histograms`' in every case."""
+    symbols have wrapped, is recounted on the host with the quantiser's float32 expressions (`_wrapped_magnitudes`), so that the
+    arrays are `eae_hip_ladder_histograms`' in every case."""
     import numpy
     (n, c) = (y.shape[0], y.shape[-1])
     q = quantize_maps(y, bin_widths, map_mean, want_symbols=True)
     range_errors = int(q['checks'][0].item())
     if range_errors:
-        host = y.reshape(n, -1, c).cpu().numpy()
-        bw = bin_widths.cpu().numpy()
-        centered = host - (map_mean.cpu().numpy() if map_mean is not None else numpy.float32(0.))
-        with numpy.errstate(all='ignore'):
-            rs = numpy.abs(numpy.rint(bw*numpy.rint(centered/bw)/bw))
-            good = rs < numpy.float32(32768.)
-        magnitudes = numpy.where(good, rs, 0.).astype(numpy.int64)
+        (magnitudes, good) = _wrapped_magnitudes(y, bin_widths, map_mean)
         hist = numpy.zeros((n, c, length + 1), dtype=numpy.int64)
         for b in range(length + 1):
             hist[:, :, b] = (good & ((magnitudes == b) if b < length else (magnitudes >= length))).sum(axis=1)
@@ -540,63 +548,10 @@ def _ladder_point_by_passes(y, bin_widths, map_mean, length):
     return hist, bits, 0
 
 
-def ladder_histograms(y, bin_widths_points, map_mean=None, length=10, out=None):
-    """One pass over y [N, h, w, 128] (or [N, hw, 128]) for the K rate points bin_widths_points float32 [K, 128] (include/eae_hip.h,
-    rate ladder) -> (hist int32 [N, K, 128, L + 1]: |symbol| clipped at L = length; bypass_bits int64 [N, K, 128]: the exact length
-    of every map's bypass stream; range_errors int32 [K]: elements whose symbol does not fit int16, counted nowhere else).
-    A ladder longer than `ladder_max_points(length)` takes several launches. At a length for which not one point fits a launch
-    (large L) every point goes the route of `stats.compute_binary_probabilities` instead -- `quantize_maps`, `symbol_histograms`, a
-    fold on the host -- and the same arrays come back. out: that triple, preallocated, to ACCUMULATE into (the kernel adds)."""
-    n = y.shape[0]
-    c = y.shape[-1]
-    hw = y.numel()//(n*c)
-    d = y.device
-    length = int(length)
-    if c != NB_MAPS or y.dtype != torch.float32:
-        raise HipError('y must be float32 [N, ..., 128]')
-    if bin_widths_points.dtype != torch.float32 or bin_widths_points.dim() != 2 or bin_widths_points.shape[1] != NB_MAPS:
-        raise HipError('bin_widths_points must be float32 [K, 128]')
-    if map_mean is not None and (map_mean.dtype != torch.float32 or map_mean.numel() != NB_MAPS):
-        raise HipError('map_mean must be float32 of 128 elements')
-    if length < 1 or length > 255:
-        raise ValueError('The truncated unary length does not belong to [1, 255].')
-    k_points = bin_widths_points.shape[0]
-    if k_points < 1:
-        raise ValueError('A ladder has at least one rate point.')
-    if out is None:
-        out = (torch.zeros((n, k_points, c, length + 1), dtype=torch.int32, device=d),
-               torch.zeros((n, k_points, c), dtype=torch.int64, device=d), torch.zeros(k_points, dtype=torch.int32, device=d))
-    (hist, bypass_bits, range_errors) = out
-    if (hist.dtype, bypass_bits.dtype, range_errors.dtype) != (torch.int32, torch.int64, torch.int32) \
-            or tuple(hist.shape) != (n, k_points, c, length + 1) or tuple(bypass_bits.shape) != (n, k_points, c) \
-            or tuple(range_errors.shape) != (k_points,):
-        raise HipError('`out` must be (int32 [N, K, 128, L + 1], int64 [N, K, 128], int32 [K])')
-    most = ladder_max_points(length)
-    if most == 0:
-        for k in range(k_points):
-            (hist_k, bits_k, errors_k) = _ladder_point_by_passes(y, bin_widths_points[k].contiguous(), map_mean, length)
-            hist[:, k] += torch.from_numpy(hist_k).to(d).to(torch.int32)
-            bypass_bits[:, k] += torch.from_numpy(bits_k).to(d)
-            range_errors[k] += errors_k
-        return out
-    whole = k_points <= most
-    for k0 in range(0, k_points, most):
-        k1 = min(k0 + most, k_points)
-        # a launch writes [N][its points][...]: a part of a longer ladder gets buffers of its own, added into the whole afterwards
-        part = out if whole else (torch.zeros((n, k1 - k0, c, length + 1), dtype=torch.int32, device=d),
-                                  torch.zeros((n, k1 - k0, c), dtype=torch.int64, device=d), range_errors[k0:k1])
-        _check(_native.hip().eae_hip_ladder_histograms(_p(y), _p(map_mean), _p(bin_widths_points[k0:k1]), k1 - k0, length, _p(part[0]),
-                                                       _p(part[1]), _p(part[2]), n, hw, _stream(y)), 'eae_hip_ladder_histograms')
-        if not whole:
-            hist[:, k0:k1] += part[0]
-            bypass_bits[:, k0:k1] += part[1]
-    return out
-
-
 def _ladder_point_tiles_by_passes(y, bin_widths, map_mean, length, tiles):
     """One rate point of `ladder_histograms_tiles` without its kernel: the symbols of `quantize_maps` folded per tile on the host ->
     numpy (hist int64 [N, T, 128, L + 1], bypass bits int64 [N, T, 128], range errors). A point with range errors, whose int16
-    symbols have wrapped, is counted from the quantiser's float32 expressions instead (`_ladder_point_by_passes`). y [N, h, w, 128];
+    symbols have wrapped, is counted from the quantiser's float32 expressions instead (`_wrapped_magnitudes`). y [N, h, w, 128];
     tiles: the rows of `container.coding_tile_grid`."""
     import numpy
     (n, h, w, c) = y.shape
@@ -604,13 +559,7 @@ def _ladder_point_tiles_by_passes(y, bin_widths, map_mean, length, tiles):
     q = quantize_maps(y, bin_widths, map_mean, want_symbols=True)
     range_errors = int(q['checks'][0].item())
     if range_errors:
-        host = y.reshape(n, -1, c).cpu().numpy()
-        bw = bin_widths.cpu().numpy()
-        centered = host - (map_mean.cpu().numpy() if map_mean is not None else numpy.float32(0.))
-        with numpy.errstate(all='ignore'):
-            rs = numpy.abs(numpy.rint(bw*numpy.rint(centered/bw)/bw))
-            good = rs < numpy.float32(32768.)
-        magnitudes = numpy.where(good, rs, 0.).astype(numpy.int64)
+        (magnitudes, good) = _wrapped_magnitudes(y, bin_widths, map_mean)
     else:
         magnitudes = numpy.abs(q['symbols'].cpu().numpy().astype(numpy.int64)).transpose(0, 2, 1)          # [N, hw, 128]
         good = numpy.ones(magnitudes.shape, dtype=bool)
@@ -627,49 +576,41 @@ def _ladder_point_tiles_by_passes(y, bin_widths, map_mean, length, tiles):
     return hist, bypass, range_errors
 
 
-def ladder_histograms_tiles(y, bin_widths_points, coding_tile, map_mean=None, length=10, out=None):
-    """`ladder_histograms` per coding tile (include/eae_hip.h: eae_hip_ladder_histograms_tiles; DESIGN.md section 20). y float32
-    [N, h, w, 128]; coding_tile=(th, tw) latents, clamped to the plane as `container.encode_images` clamps it; the T tiles are those
-    of `container.coding_tile_grid(h, w, coding_tile)`, row-major -> (hist int32 [N, K, T, 128, L + 1], bypass_bits int64
-    [N, K, T, 128], range_errors int32 [K]). Summed over T they are `ladder_histograms`' on the same input.
-    A ladder longer than `ladder_max_points(length)` takes several launches; at a length for which not one point fits a launch the
-    same arrays are folded on the host from `quantize_maps` symbols. out: that triple, preallocated, to ACCUMULATE into."""
-    if y.dim() != 4 or y.shape[-1] != NB_MAPS or y.dtype != torch.float32:
-        raise HipError('y must be float32 [N, h, w, 128]')
-    (n, h, w, c) = y.shape
-    d = y.device
-    length = int(length)
+def _ladder_points_checked(bin_widths_points, map_mean, length):
+    """The argument checks `ladder_histograms` and `ladder_histograms_tiles` share, behind their own of y."""
     if bin_widths_points.dtype != torch.float32 or bin_widths_points.dim() != 2 or bin_widths_points.shape[1] != NB_MAPS:
         raise HipError('bin_widths_points must be float32 [K, 128]')
     if map_mean is not None and (map_mean.dtype != torch.float32 or map_mean.numel() != NB_MAPS):
         raise HipError('map_mean must be float32 of 128 elements')
     if length < 1 or length > 255:
         raise ValueError('The truncated unary length does not belong to [1, 255].')
-    from . import container                       # (it imports this module; both are loaded by the time anything is called)
-    (th, tw) = container._positive_pair(coding_tile, '`coding_tile`')
-    (th, tw) = (min(th, h), min(tw, w))
-    (tiles, _) = container.coding_tile_grid(h, w, (th, tw))
-    nb_tiles = tiles.shape[0]
+
+
+def _ladder_accumulate(y, bin_widths_points, length, out, group, launch, point_by_passes):
+    """What `ladder_histograms` (group = ()) and `ladder_histograms_tiles` (group = (T,)) do alike once their arguments are checked:
+    the counts are [N, K] + group + [128, ...]. launch(bin_widths_part, nb_points, hist, bypass_bits, range_errors): the native call
+    for some points of the ladder; point_by_passes(bin_widths): one point folded on the host, as `_ladder_point_by_passes`."""
+    (n, c, d) = (y.shape[0], y.shape[-1], y.device)
     k_points = bin_widths_points.shape[0]
     if k_points < 1:
         raise ValueError('A ladder has at least one rate point.')
 
     def buffers(points, errors=None):
-        return (torch.zeros((n, points, nb_tiles, c, length + 1), dtype=torch.int32, device=d),
-                torch.zeros((n, points, nb_tiles, c), dtype=torch.int64, device=d),
+        return (torch.zeros((n, points) + group + (c, length + 1), dtype=torch.int32, device=d),
+                torch.zeros((n, points) + group + (c,), dtype=torch.int64, device=d),
                 torch.zeros(points, dtype=torch.int32, device=d) if errors is None else errors)
 
     if out is None:
         out = buffers(k_points)
     (hist, bypass_bits, range_errors) = out
     if (hist.dtype, bypass_bits.dtype, range_errors.dtype) != (torch.int32, torch.int64, torch.int32) \
-            or tuple(hist.shape) != (n, k_points, nb_tiles, c, length + 1) or tuple(bypass_bits.shape) != (n, k_points, nb_tiles, c) \
+            or tuple(hist.shape) != (n, k_points) + group + (c, length + 1) or tuple(bypass_bits.shape) != (n, k_points) + group + (c,) \
             or tuple(range_errors.shape) != (k_points,):
-        raise HipError('`out` must be (int32 [N, K, T, 128, L + 1], int64 [N, K, T, 128], int32 [K])')
+        raise HipError('`out` must be (int32 [N, K, {0}128, L + 1], int64 [N, K, {0}128], int32 [K])'.format('T, ' if group else ''))
     most = ladder_max_points(length)
     if most == 0:
         for k in range(k_points):
-            (hist_k, bits_k, errors_k) = _ladder_point_tiles_by_passes(y, bin_widths_points[k].contiguous(), map_mean, length, tiles)
+            (hist_k, bits_k, errors_k) = point_by_passes(bin_widths_points[k].contiguous())
             hist[:, k] += torch.from_numpy(hist_k).to(d).to(torch.int32)
             bypass_bits[:, k] += torch.from_numpy(bits_k).to(d)
             range_errors[k] += errors_k
@@ -679,12 +620,89 @@ def ladder_histograms_tiles(y, bin_widths_points, coding_tile, map_mean=None, le
         k1 = min(k0 + most, k_points)
         # a launch writes [N][its points][...]: a part of a longer ladder gets buffers of its own, added into the whole afterwards
         part = out if whole else buffers(k1 - k0, range_errors[k0:k1])
-        _check(_native.hip().eae_hip_ladder_histograms_tiles(_p(y), _p(map_mean), _p(bin_widths_points[k0:k1]), k1 - k0, length,
-                                                             _p(part[0]), _p(part[1]), _p(part[2]), n, h, w, th, tw, _stream(y)),
-               'eae_hip_ladder_histograms_tiles')
+        launch(bin_widths_points[k0:k1], k1 - k0, *part)
         if not whole:
             hist[:, k0:k1] += part[0]
             bypass_bits[:, k0:k1] += part[1]
+    return out
+
+
+def ladder_histograms(y, bin_widths_points, map_mean=None, length=10, out=None):
+    """One pass over y [N, h, w, 128] (or [N, hw, 128]) for the K rate points bin_widths_points float32 [K, 128] (include/eae_hip.h,
+    rate ladder) -> (hist int32 [N, K, 128, L + 1]: |symbol| clipped at L = length; bypass_bits int64 [N, K, 128]: the exact length
+    of every map's bypass stream; range_errors int32 [K]: elements whose symbol does not fit int16, counted nowhere else).
+    A ladder longer than `ladder_max_points(length)` takes several launches. At a length for which not one point fits a launch
+    (large L) every point goes the route of `stats.compute_binary_probabilities` instead -- `quantize_maps`, `symbol_histograms`, a
+    fold on the host -- and the same arrays come back. out: that triple, preallocated, to ACCUMULATE into (the kernel adds)."""
+    n = y.shape[0]
+    c = y.shape[-1]
+    hw = y.numel()//(n*c)
+    length = int(length)
+    if c != NB_MAPS or y.dtype != torch.float32:
+        raise HipError('y must be float32 [N, ..., 128]')
+    _ladder_points_checked(bin_widths_points, map_mean, length)
+
+    def launch(bin_widths_part, nb_points, hist, bypass_bits, range_errors):
+        _check(_native.hip().eae_hip_ladder_histograms(_p(y), _p(map_mean), _p(bin_widths_part), nb_points, length, _p(hist),
+                                                       _p(bypass_bits), _p(range_errors), n, hw, _stream(y)), 'eae_hip_ladder_histograms')
+
+    return _ladder_accumulate(y, bin_widths_points, length, out, (), launch,
+                              lambda bin_widths: _ladder_point_by_passes(y, bin_widths, map_mean, length))
+
+
+def ladder_histograms_tiles(y, bin_widths_points, coding_tile, map_mean=None, length=10, out=None):
+    """`ladder_histograms` per coding tile (include/eae_hip.h: eae_hip_ladder_histograms_tiles; DESIGN.md section 20). y float32
+    [N, h, w, 128]; coding_tile=(th, tw) latents, clamped to the plane as `container.encode_images` clamps it; the T tiles are those
+    of `container.coding_tile_grid(h, w, coding_tile)`, row-major -> (hist int32 [N, K, T, 128, L + 1], bypass_bits int64
+    [N, K, T, 128], range_errors int32 [K]). Summed over T they are `ladder_histograms`' on the same input.
+    A ladder longer than `ladder_max_points(length)` takes several launches; at a length for which not one point fits a launch the
+    same arrays are folded on the host from `quantize_maps` symbols. out: that triple, preallocated, to ACCUMULATE into."""
+    if y.dim() != 4 or y.shape[-1] != NB_MAPS or y.dtype != torch.float32:
+        raise HipError('y must be float32 [N, h, w, 128]')
+    (n, h, w, _) = y.shape
+    length = int(length)
+    _ladder_points_checked(bin_widths_points, map_mean, length)
+    from . import container                       # (it imports this module; both are loaded by the time anything is called)
+    (th, tw) = container._positive_pair(coding_tile, '`coding_tile`')
+    (th, tw) = (min(th, h), min(tw, w))
+    (tiles, _) = container.coding_tile_grid(h, w, (th, tw))
+
+    def launch(bin_widths_part, nb_points, hist, bypass_bits, range_errors):
+        _check(_native.hip().eae_hip_ladder_histograms_tiles(_p(y), _p(map_mean), _p(bin_widths_part), nb_points, length, _p(hist),
+                                                             _p(bypass_bits), _p(range_errors), n, h, w, th, tw, _stream(y)),
+               'eae_hip_ladder_histograms_tiles')
+
+    return _ladder_accumulate(y, bin_widths_points, length, out, (tiles.shape[0],), launch,
+                              lambda bin_widths: _ladder_point_tiles_by_passes(y, bin_widths, map_mean, length, tiles))
+
+
+def _ladder_select_checked(hist, bypass_bits, fixed_costs, log2_tables, map_size, budgets, tiled):
+    """The argument checks `ladder_select` and `ladder_select_tiles` (tiled: counts per coding tile) share -> the shape of hist."""
+    group_names = 'T, ' if tiled else ''
+    if hist.dim() != (5 if tiled else 4) or hist.shape[-2] != NB_MAPS or hist.dtype != torch.int32:
+        raise HipError('hist must be int32 [N, K, {0}128, L + 1]'.format(group_names))
+    (n, k_points, length) = (hist.shape[0], hist.shape[1], hist.shape[-1] - 1)
+    if bypass_bits.dtype != torch.int64 or tuple(bypass_bits.shape) != tuple(hist.shape[:-1]):
+        raise HipError('bypass_bits must be int64 [N, K, {0}128]'.format(group_names))
+    if fixed_costs.element_size() != 4 or fixed_costs.is_floating_point() or fixed_costs.numel() != k_points*NB_MAPS*length*2:
+        raise HipError('fixed_costs must hold K x 128 x L x 2 32-bit words')
+    if log2_tables is not None and (log2_tables.element_size() != 4 or log2_tables.is_floating_point()
+                                    or log2_tables.numel() != 2*(map_size + 1)):
+        raise HipError('log2_tables must hold 2 x (map_size + 1) 32-bit words')
+    if budgets.dtype != torch.int64 or budgets.numel() != n:
+        raise HipError('budgets must be int64 [N]')
+    return tuple(hist.shape)
+
+
+def _ladder_select_out(out, n, k_points, rows, d):
+    """`out` of `ladder_select` and `ladder_select_tiles`, made where it is None and checked: `rows` rows of 128 in 'prob_row'."""
+    if out is None:
+        out = {'point': torch.empty(n, dtype=torch.int32, device=d), 'prob_row': torch.empty((rows, NB_MAPS), dtype=torch.int32, device=d),
+               'upper': torch.empty((n, k_points), dtype=torch.int64, device=d), 'flags': torch.empty(n, dtype=torch.int32, device=d)}
+    for (name, dtype, count) in (('point', torch.int32, n), ('prob_row', torch.int32, rows*NB_MAPS), ('upper', torch.int64, n*k_points),
+                                 ('flags', torch.int32, n)):
+        if out[name].dtype != dtype or out[name].numel() != count:
+            raise HipError('`out[{0!r}]` must hold {1} elements of {2}'.format(name, count, dtype))
     return out
 
 
@@ -697,32 +715,13 @@ def ladder_select_tiles(hist, bypass_bits, fixed_costs, log2_tables, idx_map_exc
     image of every (image, tile) entry in the order the coder takes them (`codec.coding_tile_layout`'s run order). The other
     arguments as `ladder_select`. -> dict: 'point' int32 [N], 'prob_row' int32 [entries, 128], 'upper' int64 [N, K], 'flags' int32
     [N]. out: that dict, preallocated; every element is written."""
-    if hist.dim() != 5 or hist.shape[3] != NB_MAPS or hist.dtype != torch.int32:
-        raise HipError('hist must be int32 [N, K, T, 128, L + 1]')
-    (n, k_points, nb_tiles, _, nb) = hist.shape
-    length = nb - 1
-    d = hist.device
-    if bypass_bits.dtype != torch.int64 or tuple(bypass_bits.shape) != (n, k_points, nb_tiles, NB_MAPS):
-        raise HipError('bypass_bits must be int64 [N, K, T, 128]')
-    if fixed_costs.element_size() != 4 or fixed_costs.is_floating_point() or fixed_costs.numel() != k_points*NB_MAPS*length*2:
-        raise HipError('fixed_costs must hold K x 128 x L x 2 32-bit words')
     map_size = int(map_size)
-    if log2_tables is not None and (log2_tables.element_size() != 4 or log2_tables.is_floating_point()
-                                    or log2_tables.numel() != 2*(map_size + 1)):
-        raise HipError('log2_tables must hold 2 x (map_size + 1) 32-bit words')
-    if budgets.dtype != torch.int64 or budgets.numel() != n:
-        raise HipError('budgets must be int64 [N]')
+    (n, k_points, nb_tiles, _, nb) = _ladder_select_checked(hist, bypass_bits, fixed_costs, log2_tables, map_size, budgets, True)
     if entry_image.dtype != torch.int32 or entry_image.dim() != 1 or entry_image.numel() < 1:
         raise HipError('entry_image must be int32 [entries]')
     entries = entry_image.numel()
-    if out is None:
-        out = {'point': torch.empty(n, dtype=torch.int32, device=d), 'prob_row': torch.empty((entries, NB_MAPS), dtype=torch.int32, device=d),
-               'upper': torch.empty((n, k_points), dtype=torch.int64, device=d), 'flags': torch.empty(n, dtype=torch.int32, device=d)}
-    for (name, dtype, count) in (('point', torch.int32, n), ('prob_row', torch.int32, entries*NB_MAPS), ('upper', torch.int64, n*k_points),
-                                 ('flags', torch.int32, n)):
-        if out[name].dtype != dtype or out[name].numel() != count:
-            raise HipError('`out[{0!r}]` must hold {1} elements of {2}'.format(name, count, dtype))
-    _check(_native.hip().eae_hip_ladder_select_tiles(_p(hist), _p(bypass_bits), _p(fixed_costs), _p(log2_tables), k_points, length,
+    out = _ladder_select_out(out, n, k_points, entries, hist.device)
+    _check(_native.hip().eae_hip_ladder_select_tiles(_p(hist), _p(bypass_bits), _p(fixed_costs), _p(log2_tables), k_points, nb - 1,
                                                      int(idx_map_exception), int(header_bytes), map_size, nb_tiles, _p(budgets),
                                                      _p(entry_image), entries, int(exception_row_base), _p(out['point']),
                                                      _p(out['prob_row']), _p(out['upper']), _p(out['flags']), n, _stream(hist)),
@@ -738,33 +737,28 @@ def ladder_select(hist, bypass_bits, fixed_costs, log2_tables, idx_map_exception
     [2, map_size + 1] (ratecontrol.log2_tables; None without an exception map), as device tensors of 32-bit words; budgets int64 [N]
     on the device. -> dict: 'point' int32 [N], 'prob_row' int32 [N, 128], 'upper' int64 [N, K], 'flags' int32 [N] (bit 0 promised,
     bit 1 no valid point). out: that dict, preallocated; every element is written."""
-    if hist.dim() != 4 or hist.shape[2] != NB_MAPS or hist.dtype != torch.int32:
-        raise HipError('hist must be int32 [N, K, 128, L + 1]')
-    (n, k_points, _, nb) = hist.shape
-    length = nb - 1
-    d = hist.device
-    if bypass_bits.dtype != torch.int64 or tuple(bypass_bits.shape) != (n, k_points, NB_MAPS):
-        raise HipError('bypass_bits must be int64 [N, K, 128]')
-    if fixed_costs.element_size() != 4 or fixed_costs.is_floating_point() or fixed_costs.numel() != k_points*NB_MAPS*length*2:
-        raise HipError('fixed_costs must hold K x 128 x L x 2 32-bit words')
     map_size = int(map_size)
-    if log2_tables is not None and (log2_tables.element_size() != 4 or log2_tables.is_floating_point()
-                                    or log2_tables.numel() != 2*(map_size + 1)):
-        raise HipError('log2_tables must hold 2 x (map_size + 1) 32-bit words')
-    if budgets.dtype != torch.int64 or budgets.numel() != n:
-        raise HipError('budgets must be int64 [N]')
-    if out is None:
-        out = {'point': torch.empty(n, dtype=torch.int32, device=d), 'prob_row': torch.empty((n, NB_MAPS), dtype=torch.int32, device=d),
-               'upper': torch.empty((n, k_points), dtype=torch.int64, device=d), 'flags': torch.empty(n, dtype=torch.int32, device=d)}
-    for (name, dtype, count) in (('point', torch.int32, n), ('prob_row', torch.int32, n*NB_MAPS), ('upper', torch.int64, n*k_points),
-                                 ('flags', torch.int32, n)):
-        if out[name].dtype != dtype or out[name].numel() != count:
-            raise HipError('`out[{0!r}]` must hold {1} elements of {2}'.format(name, count, dtype))
-    _check(_native.hip().eae_hip_ladder_select(_p(hist), _p(bypass_bits), _p(fixed_costs), _p(log2_tables), k_points, length,
+    (n, k_points, _, nb) = _ladder_select_checked(hist, bypass_bits, fixed_costs, log2_tables, map_size, budgets, False)
+    out = _ladder_select_out(out, n, k_points, n, hist.device)
+    _check(_native.hip().eae_hip_ladder_select(_p(hist), _p(bypass_bits), _p(fixed_costs), _p(log2_tables), k_points, nb - 1,
                                                int(idx_map_exception), int(header_bytes), map_size, _p(budgets), int(exception_row_base),
                                                _p(out['point']), _p(out['prob_row']), _p(out['upper']), _p(out['flags']), n,
                                                _stream(hist)), 'eae_hip_ladder_select')
     return out
+
+
+def _quality_search_checked(first, max_sse, state, probe_acc, point, prob_row, trace_point, trace_sse, flags, k_points, rows, more=()):
+    """The tensor table `quality_search` and `quality_search_tiles` share -> (N, R). rows: of 128 in `prob_row`; more: (name, tensor,
+    dtype, elements) entries behind it."""
+    n = first.numel()
+    nb_rounds = int(k_points).bit_length()
+    for (name, t, dtype, count) in (('first', first, torch.int32, n), ('max_sse', max_sse, torch.int64, n), ('state', state, torch.int32, 2*n),
+                                    ('probe_acc', probe_acc, torch.int64, n), ('point', point, torch.int32, n),
+                                    ('prob_row', prob_row, torch.int32, rows*NB_MAPS), ('trace_point', trace_point, torch.int32, n*nb_rounds),
+                                    ('trace_sse', trace_sse, torch.int64, n*nb_rounds), ('flags', flags, torch.int32, n)) + tuple(more):
+        if t.dtype != dtype or t.numel() != count:
+            raise HipError('`{0}` must hold {1} elements of {2}'.format(name, count, dtype))
+    return n, nb_rounds
 
 
 def quality_search(first, max_sse, state, probe_acc, point, prob_row, trace_point, trace_sse, flags, k_points, round, idx_map_exception,
@@ -774,14 +768,8 @@ def quality_search(first, max_sse, state, probe_acc, point, prob_row, trace_poin
     [N, 2], probe_acc int64 [N] (what `tconv9x9s4_luma` adds the probe's squared errors into), point int32 [N], prob_row int32
     [N, 128], trace_point int32 [N, R], trace_sse int64 [N, R], flags int32 [N], R = ratecontrol.quality_rounds(k_points). round:
     0..R, the only argument that differs between the R + 1 calls of a step."""
-    n = first.numel()
-    nb_rounds = int(k_points).bit_length()
-    for (name, t, dtype, count) in (('first', first, torch.int32, n), ('max_sse', max_sse, torch.int64, n), ('state', state, torch.int32, 2*n),
-                                    ('probe_acc', probe_acc, torch.int64, n), ('point', point, torch.int32, n),
-                                    ('prob_row', prob_row, torch.int32, n*NB_MAPS), ('trace_point', trace_point, torch.int32, n*nb_rounds),
-                                    ('trace_sse', trace_sse, torch.int64, n*nb_rounds), ('flags', flags, torch.int32, n)):
-        if t.dtype != dtype or t.numel() != count:
-            raise HipError('`{0}` must hold {1} elements of {2}'.format(name, count, dtype))
+    (n, nb_rounds) = _quality_search_checked(first, max_sse, state, probe_acc, point, prob_row, trace_point, trace_sse, flags, k_points,
+                                             first.numel())
     _check(_native.hip().eae_hip_quality_search(_p(first), _p(max_sse), _p(state), _p(probe_acc), _p(point), _p(prob_row), _p(trace_point),
                                                 _p(trace_sse), _p(flags), int(k_points), nb_rounds, int(round), int(idx_map_exception),
                                                 int(exception_row_base), n, _stream(first)), 'eae_hip_quality_search')
@@ -792,16 +780,9 @@ def quality_search_tiles(first, max_sse, state, probe_acc, point, prob_row, trac
     """`quality_search` for a step in coding tiles (include/eae_hip.h: eae_hip_quality_search_tiles; the rows are
     `codec.tile_prob_rows`). run_entry int32 [N * nb_tiles] on the device: `codec.coding_tile_layout`'s 'run_entry'; prob_row int32
     [N * nb_tiles, 128], written in that layout's run order. Everything else as `quality_search`."""
-    n = first.numel()
     nb_tiles = int(nb_tiles)
-    nb_rounds = int(k_points).bit_length()
-    for (name, t, dtype, count) in (('first', first, torch.int32, n), ('max_sse', max_sse, torch.int64, n), ('state', state, torch.int32, 2*n),
-                                    ('probe_acc', probe_acc, torch.int64, n), ('point', point, torch.int32, n),
-                                    ('prob_row', prob_row, torch.int32, n*nb_tiles*NB_MAPS),
-                                    ('trace_point', trace_point, torch.int32, n*nb_rounds), ('trace_sse', trace_sse, torch.int64, n*nb_rounds),
-                                    ('flags', flags, torch.int32, n), ('run_entry', run_entry, torch.int32, n*nb_tiles)):
-        if t.dtype != dtype or t.numel() != count:
-            raise HipError('`{0}` must hold {1} elements of {2}'.format(name, count, dtype))
+    (n, nb_rounds) = _quality_search_checked(first, max_sse, state, probe_acc, point, prob_row, trace_point, trace_sse, flags, k_points,
+                                             first.numel()*nb_tiles, [('run_entry', run_entry, torch.int32, first.numel()*nb_tiles)])
     _check(_native.hip().eae_hip_quality_search_tiles(_p(first), _p(max_sse), _p(state), _p(probe_acc), _p(point), _p(prob_row),
                                                       _p(trace_point), _p(trace_sse), _p(flags), _p(run_entry), nb_tiles, int(k_points),
                                                       nb_rounds, int(round), int(idx_map_exception), int(exception_row_base), n,

@@ -12,6 +12,7 @@ import numpy
 import pytest
 
 import budget_slot_buffers
+import ratecontrol_slot_buffers
 import slot_buffers
 from test_slot_inventory import _with_one_more_buffer, assigned_attributes
 
@@ -178,21 +179,10 @@ def test_every_attribute_of_the_budget_slot_is_classified():
 
 
 def test_every_entry_of_the_budget_slot_exists_and_says_why():
-    table = budget_slot_buffers.BUDGET_SLOT
-    assigned = assigned_attributes(_source(), '_BudgetSlot')
-    for (name, entry) in table.items():
-        assert slot_buffers.attribute_of(name) in assigned, (name, 'is classified but no longer assigned')
-        assert entry.cls in slot_buffers.CLASSES, name
-        assert entry.reason.strip() and any(c.isdigit() for c in entry.reason), (name, 'needs a reason that names a line')
-        if entry.cls == slot_buffers.CONTAINER:
-            assert entry.parts and all(part in table and table[part].cls != slot_buffers.CONTAINER for part in entry.parts), name
-        else:
-            assert entry.parts is None, name
-        assert entry.alias is None, name
-    for name in budget_slot_buffers.MUST_BE_SCRATCH:
-        assert table[name].cls == slot_buffers.SCRATCH, name
-    for name in ('budgets_nbytes', 'points_table'):
-        assert table[name].cls == slot_buffers.CONSTANT, name
+    # (a reason names a line or a step of DESIGN.md section 19's launch table: `needs_digit`)
+    ratecontrol_slot_buffers.check_entries(budget_slot_buffers.BUDGET_SLOT, assigned_attributes(_source(), '_BudgetSlot'),
+                                           budget_slot_buffers.MUST_BE_SCRATCH, ('budgets_nbytes', 'points_table'), needs_digit=True)
+    assert all(entry.alias is None for entry in budget_slot_buffers.BUDGET_SLOT.values())
 
 
 def test_an_unclassified_buffer_of_the_budget_slot_is_noticed():

@@ -9,6 +9,7 @@ import numpy
 import pytest
 
 import quality_slot_buffers
+import ratecontrol_slot_buffers
 import slot_buffers
 from test_slot_inventory import _with_one_more_buffer, assigned_attributes
 
@@ -166,20 +167,9 @@ def test_every_attribute_of_the_quality_slot_is_classified():
 
 def test_every_entry_of_the_quality_slot_exists_and_says_why():
     table = quality_slot_buffers.QUALITY_SLOT
-    assigned = assigned_attributes(_source(), '_QualitySlot')
-    for (name, entry) in table.items():
-        assert slot_buffers.attribute_of(name) in assigned, (name, 'is classified but no longer assigned')
-        assert entry.cls in slot_buffers.CLASSES, name
-        assert entry.reason.strip(), name
-        if entry.cls == slot_buffers.CONTAINER:
-            assert entry.parts and all(part in table and table[part].cls != slot_buffers.CONTAINER for part in entry.parts), name
-        else:
-            assert entry.parts is None, name
-        assert entry.alias is None, name
-    for name in quality_slot_buffers.MUST_BE_SCRATCH:
-        assert table[name].cls == slot_buffers.SCRATCH, name
-    for name in ('budgets_nbytes', 'max_sse_nbytes', 'points_table'):
-        assert table[name].cls == slot_buffers.CONSTANT, name
+    ratecontrol_slot_buffers.check_entries(table, assigned_attributes(_source(), '_QualitySlot'), quality_slot_buffers.MUST_BE_SCRATCH,
+                                           ('budgets_nbytes', 'max_sse_nbytes', 'points_table'))
+    assert all(entry.alias is None for entry in table.values())
     assert not any(entry.cls == slot_buffers.CARRIED for entry in table.values())       # a step depends on nothing the last one left
 
 

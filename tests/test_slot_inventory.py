@@ -17,12 +17,34 @@ def _source():
         return f.read()
 
 
+def _lineage(tree, class_name):
+    """The class's node and, behind it, those of its base classes defined in the same source, depth first in the order it names them
+    (which is the order Python looks `__init__` up in for the single and the mixin-in-front inheritance codec.py uses)."""
+    classes = {node.name: node for node in tree.body if isinstance(node, ast.ClassDef)}
+    if class_name not in classes:
+        raise AssertionError('codec.py has no class {0}'.format(class_name))
+    (order, stack) = ([], [class_name])
+    while stack:
+        node = classes[stack.pop(0)]
+        if node not in order:
+            order.append(node)
+            stack = [base.id for base in node.bases if isinstance(base, ast.Name) and base.id in classes] + stack
+    return order
+
+
+def _own_init(node):
+    for item in node.body:
+        if isinstance(item, ast.FunctionDef) and item.name == '__init__':
+            return item
+    return None
+
+
 def _init_of(tree, class_name):
-    for node in tree.body:
-        if isinstance(node, ast.ClassDef) and node.name == class_name:
-            for item in node.body:
-                if isinstance(item, ast.FunctionDef) and item.name == '__init__':
-                    return node, item
+    """(the class, the `__init__` an instance of it runs first: its own, else the first one along its bases)."""
+    lineage = _lineage(tree, class_name)
+    for node in lineage:
+        if _own_init(node) is not None:
+            return lineage[0], _own_init(node)
     raise AssertionError('codec.py has no {0}.__init__'.format(class_name))
 
 
@@ -38,18 +60,20 @@ def _self_targets(target):
 
 
 def assigned_attributes(source, class_name):
-    """Every attribute the class's `__init__` assigns (in any branch), and for a class with `__slots__` every slot."""
-    (node, init) = _init_of(ast.parse(source), class_name)
+    """Every attribute an instance of the class has: what its `__init__` and those of its base classes in the same source assign (in
+    any branch), and every name of their `__slots__`."""
     names = set()
-    for sub in ast.walk(init):
-        if isinstance(sub, ast.Assign):
-            for target in sub.targets:
-                names.update(_self_targets(target))
-        elif isinstance(sub, (ast.AugAssign, ast.AnnAssign)):
-            names.update(_self_targets(sub.target))
-    for item in node.body:
-        if isinstance(item, ast.Assign) and any(isinstance(t, ast.Name) and t.id == '__slots__' for t in item.targets):
-            names.update(ast.literal_eval(item.value))
+    for node in _lineage(ast.parse(source), class_name):
+        init = _own_init(node)
+        for sub in (ast.walk(init) if init is not None else ()):
+            if isinstance(sub, ast.Assign):
+                for target in sub.targets:
+                    names.update(_self_targets(target))
+            elif isinstance(sub, (ast.AugAssign, ast.AnnAssign)):
+                names.update(_self_targets(sub.target))
+        for item in node.body:
+            if isinstance(item, ast.Assign) and any(isinstance(t, ast.Name) and t.id == '__slots__' for t in item.targets):
+                names.update(ast.literal_eval(item.value))
     return names
 
 
@@ -63,7 +87,8 @@ def unclassified(source):
 
 
 def _with_one_more_buffer(source, class_name):
-    """`source` with `self.extra = torch.empty(...)` behind the last statement of the class's `__init__`."""
+    """`source` with `self.extra = torch.empty(...)` behind the last statement of the class's `__init__` (`_init_of`: its own, or the
+    one it inherits first)."""
     (_, init) = _init_of(ast.parse(source), class_name)
     last = init.body[-1]
     lines = source.split('\n')
@@ -124,3 +149,47 @@ def test_an_unclassified_buffer_is_noticed():
         grown = _with_one_more_buffer(source, class_name)
         assert grown != source and 'extra' in assigned_attributes(grown, class_name)
         assert unclassified(grown) == {k: (['extra'] if k == class_name else []) for k in slot_buffers.TABLES}, class_name
+
+
+# ---- the slot family of the rate-control codecs (tests/ratecontrol_slot_buffers.py) ------------------------------------------------
+
+FAMILY = ('_BudgetSlot', '_TiledBudgetSlot', '_QualitySlot', '_TiledQualitySlot')
+
+
+def _family_tables():
+    import ratecontrol_slot_buffers
+    return {'_BudgetSlot': ratecontrol_slot_buffers.slot_table(False, False), '_TiledBudgetSlot': ratecontrol_slot_buffers.slot_table(True, False),
+            '_QualitySlot': ratecontrol_slot_buffers.slot_table(False, True), '_TiledQualitySlot': ratecontrol_slot_buffers.slot_table(True, True)}
+
+
+def test_an_extra_buffer_of_a_family_member_shows_in_it_and_in_its_subclasses_only():
+    """The four slot classes are a hierarchy: one more buffer in an `__init__` is unclassified in every class whose instances run
+    that `__init__`, and nowhere else."""
+    source = _source()
+    tables = _family_tables()
+    for (grown_class, shows_in) in (('_BudgetSlot', FAMILY), ('_QualitySlot', ('_QualitySlot', '_TiledQualitySlot')),
+                                    ('_TiledRows', ('_TiledBudgetSlot', '_TiledQualitySlot')),
+                                    # (the two tiled classes have no `__init__` of their own: the mixin in front of their bases has it)
+                                    ('_TiledBudgetSlot', ('_TiledBudgetSlot', '_TiledQualitySlot')),
+                                    ('_TiledQualitySlot', ('_TiledBudgetSlot', '_TiledQualitySlot'))):
+        grown = _with_one_more_buffer(source, grown_class)
+        assert grown != source
+        for (class_name, table) in tables.items():
+            known = {slot_buffers.attribute_of(name) for name in table}
+            assert sorted(assigned_attributes(grown, class_name) - known) == (['extra'] if class_name in shows_in else []), (grown_class, class_name)
+            assert sorted(assigned_attributes(source, class_name) - known) == [], class_name
+        # and `_Slot` and the decoders' slots know nothing of it
+        assert unclassified(grown) == {k: [] for k in slot_buffers.TABLES}
+
+
+def test_no_family_member_lists_an_inherited_attribute_again():
+    """`__slots__` of a class names what that class adds: no name stands in the `__slots__` of two classes of one lineage. (The two
+    tiled classes are siblings and both add `class_rows`: Python does not combine two bases that both add slots.)"""
+    tree = ast.parse(_source())
+    for class_name in FAMILY:
+        seen = []
+        for node in _lineage(tree, class_name):
+            for item in node.body:
+                if isinstance(item, ast.Assign) and any(isinstance(t, ast.Name) and t.id == '__slots__' for t in item.targets):
+                    seen.extend(ast.literal_eval(item.value))
+        assert len(seen) == len(set(seen)), (class_name, sorted(name for name in set(seen) if seen.count(name) > 1))

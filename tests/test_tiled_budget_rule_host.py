@@ -245,24 +245,13 @@ def test_every_attribute_of_the_tiled_budget_slot_is_classified():
 
 
 def test_every_entry_of_the_tiled_budget_slot_exists_and_says_why():
-    import slot_buffers
+    import ratecontrol_slot_buffers
     import tiled_budget_slot_buffers
     from test_slot_inventory import assigned_attributes
     table = tiled_budget_slot_buffers.TILED_BUDGET_SLOT
-    assigned = assigned_attributes(_source(), '_TiledBudgetSlot')
-    for (name, entry) in table.items():
-        assert slot_buffers.attribute_of(name) in assigned, (name, 'is classified but no longer assigned')
-        assert entry.cls in slot_buffers.CLASSES, name
-        assert entry.reason.strip(), name
-        if entry.cls == slot_buffers.CONTAINER:
-            assert entry.parts and all(part in table and table[part].cls != slot_buffers.CONTAINER for part in entry.parts), name
-        else:
-            assert entry.parts is None, name
-        assert (entry.alias is None) == (name != 'class_rows'), name
-    for name in tiled_budget_slot_buffers.MUST_BE_SCRATCH:
-        assert table[name].cls == slot_buffers.SCRATCH, name
-    for name in ('budgets_nbytes', 'points_table'):
-        assert table[name].cls == slot_buffers.CONSTANT, name
+    ratecontrol_slot_buffers.check_entries(table, assigned_attributes(_source(), '_TiledBudgetSlot'), tiled_budget_slot_buffers.MUST_BE_SCRATCH,
+                                           ('budgets_nbytes', 'points_table'))
+    assert table['class_rows'].alias == 'prob_row'
 
 
 def test_an_unclassified_buffer_of_the_tiled_budget_slot_is_noticed():

@@ -7,6 +7,7 @@ import os
 
 import numpy
 
+import ratecontrol_slot_buffers
 import slot_buffers
 import tiled_quality_slot_buffers
 from test_slot_inventory import _with_one_more_buffer, assigned_attributes
@@ -89,20 +90,9 @@ def test_every_attribute_of_the_tiled_quality_slot_is_classified():
 
 def test_every_entry_of_the_tiled_quality_slot_exists_and_says_why():
     table = tiled_quality_slot_buffers.TILED_QUALITY_SLOT
-    assigned = assigned_attributes(_source(), '_TiledQualitySlot')
-    for (name, entry) in table.items():
-        assert slot_buffers.attribute_of(name) in assigned, (name, 'is classified but no longer assigned')
-        assert entry.cls in slot_buffers.CLASSES, name
-        assert entry.reason.strip(), name
-        if entry.cls == slot_buffers.CONTAINER:
-            assert entry.parts and all(part in table and table[part].cls != slot_buffers.CONTAINER for part in entry.parts), name
-        else:
-            assert entry.parts is None, name
-        assert (entry.alias is None) == (name != 'class_rows'), name
-    for name in tiled_quality_slot_buffers.MUST_BE_SCRATCH:
-        assert table[name].cls == slot_buffers.SCRATCH, name
-    for name in ('budgets_nbytes', 'max_sse_nbytes', 'points_table'):
-        assert table[name].cls == slot_buffers.CONSTANT, name
+    ratecontrol_slot_buffers.check_entries(table, assigned_attributes(_source(), '_TiledQualitySlot'), tiled_quality_slot_buffers.MUST_BE_SCRATCH,
+                                           ('budgets_nbytes', 'max_sse_nbytes', 'points_table'))
+    assert table['class_rows'].alias == 'prob_row'
     assert not any(entry.cls == slot_buffers.CARRIED for entry in table.values())       # a step depends on nothing the last one left
 
 
