@@ -9,7 +9,7 @@
 // (latent_quarter_kernel, the default), or of one wave (latent_wave_kernel); latent_kernel keeps 64 positions per block in
 // LDS -- and both 128 x 128 contractions run on the MFMA.
 // Arithmetic, operation by operation, is that of gdn.hip and quantize.hip (same helpers), so the results are the same bits.
-#include "latent_body.h"
+#include "quarter_body.h"
 
 #include <cstdlib>
 
@@ -169,9 +169,8 @@ __global__ __launch_bounds__(64) void latent_wave_kernel(const float* x, const f
 // channels, then they exchange through LDS, lane-private slots) but
 // accumulates, normalises, quantises and stores only its own 32 channels. 4.5 waves per SIMD, each a quarter as long: the
 // MFMAs of one overlap the vector work of the others. Same FMA chain per element, same statements: same bits.
-// x2[t][4 g + e]: the B operand of K-step kk = 16 t + 4 g + e, i.e. the squares of the tile in the order and lane placement the
-// MFMA wants them (squares_for_mfma below), all 128 channels; the wave accumulates its own channel tile w.
-// (quarter_denominator and squares_for_mfma: latent_body.h, shared with latent_rows.hip)
+// The body is quarter_body.h, shared with latent_rows.hip: here the bin widths are the one row in LDS, the quotient is rounded, and
+// gdn_3 goes first through the same exchange as inverse_gdn_4.
 template <bool GDN_IN, bool IGDN_OUT>
 __global__ __launch_bounds__(256) void latent_quarter_kernel(const float* x, const float* __restrict__ gamma_in,
                                                              const float* __restrict__ beta_in, const float* __restrict__ map_mean,
@@ -183,144 +182,25 @@ __global__ __launch_bounds__(256) void latent_quarter_kernel(const float* x, con
     __shared__ __attribute__((aligned(16))) float vec[4 * EAE_C];          // beta_in | beta_out | map_mean | bin_widths
     __shared__ __attribute__((aligned(16))) float xch[4 * 4 * 64 * 4];     // [channel tile][g][lane][4]: the exchange, 16 KB
     __shared__ unsigned int tally[4][3];
-    const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5, lj = lane & 31;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    if (tid < EAE_C) {
-        vec[tid] = GDN_IN ? beta_in[tid] : 0.f;
-        vec[EAE_C + tid] = IGDN_OUT ? beta_out[tid] : 0.f;
-        vec[2 * EAE_C + tid] = map_mean ? map_mean[tid] : 0.f;
-        vec[3 * EAE_C + tid] = bin_widths[tid];
+    const QuarterLane p = quarter_lane(rows, hw);
+    if (p.tid < EAE_C) {
+        vec[p.tid] = GDN_IN ? beta_in[p.tid] : 0.f;
+        vec[EAE_C + p.tid] = IGDN_OUT ? beta_out[p.tid] : 0.f;
+        vec[2 * EAE_C + p.tid] = map_mean ? map_mean[p.tid] : 0.f;
+        vec[3 * EAE_C + p.tid] = bin_widths[p.tid];
     }
-    const long row = (long)blockIdx.x * 32 + lj;
-    const bool valid = row < rows;
-    const long img = row / hw;
-    const int pix = (int)(row - img * hw);
-    const int cw = 32 * w + 4 * hi;                          // this lane's channels: cw + 8 g + q
-    const size_t obase = (size_t)(valid ? row : 0) * EAE_C + cw;
-    f32x16 own;                                              // [4 g + q]
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const float4 q = valid ? *reinterpret_cast<const float4*>(x + obase + 8 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
-        own[4 * g + 0] = q.x; own[4 * g + 1] = q.y; own[4 * g + 2] = q.z; own[4 * g + 3] = q.w;
-    }
-    float4* slot = reinterpret_cast<float4*>(xch) + lane;    // + (16 t + 4 g... ) * 64: [t][g][lane]
-    f32x16 full[4];
-#define EAE_Q_EXCHANGE()                                                                                                 \
-    {                                                                                                                    \
-        const f32x16 sq = squares_for_mfma(own);                                                                         \
-        _Pragma("unroll") for (int g = 0; g < 4; ++g)                                                                    \
-            slot[(4 * w + g) * 64] = make_float4(sq[4 * g], sq[4 * g + 1], sq[4 * g + 2], sq[4 * g + 3]);                \
-        __syncthreads();                                                                                                 \
-        _Pragma("unroll") for (int t = 0; t < 4; ++t)                                                                    \
-            _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                              \
-                const float4 q = slot[(4 * t + g) * 64];                                                                 \
-                full[t][4 * g + 0] = q.x; full[t][4 * g + 1] = q.y; full[t][4 * g + 2] = q.z; full[t][4 * g + 3] = q.w;  \
-            }                                                                                                            \
-    }
+    f32x16 own = quarter_load(x, p);                         // [4 g + q]
     if (GDN_IN) {
-        EAE_Q_EXCHANGE()
-        f32x16 d[1] = {quarter_denominator<8>(full, gamma_in, w, lane)};
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const float4 bt = *reinterpret_cast<const float4*>(vec + cw + 8 * g);
-            d[0][4 * g + 0] = d[0][4 * g + 0] + bt.x;
-            d[0][4 * g + 1] = d[0][4 * g + 1] + bt.y;
-            d[0][4 * g + 2] = d[0][4 * g + 2] + bt.z;
-            d[0][4 * g + 3] = d[0][4 * g + 3] + bt.w;
-        }
-        const f32x16 xn[1] = {own};
-        gdn_tile<1, false, false>(xn, d, [&](int, int g, float4 y) {
+        quarter_normalise<false>(own, xch, gamma_in, vec, p, [&](int, int g, float4 y) {
             own[4 * g + 0] = y.x; own[4 * g + 1] = y.y; own[4 * g + 2] = y.z; own[4 * g + 3] = y.w;
         });
     } else {
         __syncthreads();                                     // vec
     }
-    // the quantiser on this wave's 32 channels (quantize.hip, statement for statement). Planar symbols: the lanes of a
-    // half-wave write neighbouring pixels of one map; offsets are relative to the tile's first image so that 32 bits do
-    const long img0 = ((long)blockIdx.x * 32) / hw;
-    const bool one_image = __all(!valid || img == img0) != 0;
-    const __amdgpu_buffer_rsrc_t sym_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        symbols ? symbols + (size_t)img0 * EAE_C * hw : nullptr, 0, symbols ? 0x7FFFFFFF : 0, 0x00020000);
-    const int sym_lane = valid ? (int)((((img - img0) * EAE_C + 4 * hi) * hw + pix) * 2) : -1;     // bytes; -1: no store
-    unsigned int bad = 0, not_quantized = 0, altered = 0, flag_bits = 0;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const float4 m4 = *reinterpret_cast<const float4*>(vec + 2 * EAE_C + cw + 8 * g);
-        const float4 b4 = *reinterpret_cast<const float4*>(vec + 3 * EAE_C + cw + 8 * g);
-        const float mm[4] = {m4.x, m4.y, m4.z, m4.w}, bw[4] = {b4.x, b4.y, b4.z, b4.w};
-        float sh[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float yv = own[4 * g + q];
-            const float centered = yv - mm[q];
-            const float rr = round_half_even(centered / bw[q]);
-            const float cq = bw[q] * rr;
-            const float rs = round_half_even(cq / bw[q]);
-            sh[q] = cq + mm[q];
-            if (valid) {
-                if (!(fabsf(rs) < 32768.f)) bad++;
-                if (!(fabs((double)cq - (double)centered) < 1.5e-10)) not_quantized++;
-                if (!((float)(int16_t)(int)rs * bw[q] == centered)) altered++;
-            }
-            const bool nz = valid && cq != 0.f;
-            if (nonzero) {
-                if (one_image) {
-                    // one bit per channel of this tile: a half-wave's 32 positions share the channel
-                    const unsigned long long any = __ballot(nz);
-                    if ((unsigned int)any) flag_bits |= 1u << (8 * g + q);
-                    if ((unsigned int)(any >> 32)) flag_bits |= 1u << (8 * g + 4 + q);
-                } else if (nz) {
-                    nonzero[img * EAE_C + cw + 8 * g + q] = 1u;                      // benign race: every writer stores 1
-                }
-            }
-            if (symbols)
-                __builtin_amdgcn_raw_buffer_store_b16((short)(int16_t)(int)rs, sym_rsrc, sym_lane, (32 * w + 8 * g + q) * hw * 2, 0);
-        }
-        if (valid && y_out)
-            *reinterpret_cast<float4*>(y_out + obase + 8 * g) = make_float4(own[4 * g], own[4 * g + 1], own[4 * g + 2], own[4 * g + 3]);
-        if (valid && shifted_out) *reinterpret_cast<float4*>(shifted_out + obase + 8 * g) = make_float4(sh[0], sh[1], sh[2], sh[3]);
-        own[4 * g + 0] = sh[0]; own[4 * g + 1] = sh[1]; own[4 * g + 2] = sh[2]; own[4 * g + 3] = sh[3];
-    }
-    if (nonzero && one_image && lane < 32 && ((flag_bits >> lane) & 1u)) nonzero[img0 * EAE_C + 32 * w + lane] = 1u;
-#ifndef EAE_LATENT_NOCHECKS
-    if (checks) {
-        // one atomic per block and counter: all 4,608 waves adding to the same three words would queue behind each other in L2
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            bad += __shfl_down(bad, off, 64);
-            not_quantized += __shfl_down(not_quantized, off, 64);
-            altered += __shfl_down(altered, off, 64);
-        }
-        if (lane == 0) { tally[w][0] = bad; tally[w][1] = not_quantized; tally[w][2] = altered; }
-    }
-#endif
-    if (IGDN_OUT) {
-        if (GDN_IN) __syncthreads();                         // every wave has read the first exchange
-        EAE_Q_EXCHANGE()
-        f32x16 d[1] = {quarter_denominator<8>(full, gamma_out, w, lane)};
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const float4 bt = *reinterpret_cast<const float4*>(vec + EAE_C + cw + 8 * g);
-            d[0][4 * g + 0] = d[0][4 * g + 0] + bt.x;
-            d[0][4 * g + 1] = d[0][4 * g + 1] + bt.y;
-            d[0][4 * g + 2] = d[0][4 * g + 2] + bt.z;
-            d[0][4 * g + 3] = d[0][4 * g + 3] + bt.w;
-        }
-        const f32x16 xn[1] = {own};
-        gdn_tile<1, true, false>(xn, d, [&](int, int g, float4 y) {
-            if (valid) *reinterpret_cast<float4*>(t_out + obase + 8 * g) = y;
-        });
-    }
-#ifndef EAE_LATENT_NOCHECKS
-    if (checks) {
-        if (!IGDN_OUT) __syncthreads();                      // (with IGDN_OUT the second exchange's barrier came after the tally)
-        if (tid < 3) {
-            const unsigned int sum = tally[0][tid] + tally[1][tid] + tally[2][tid] + tally[3][tid];
-            if (sum) atomicAdd(&checks[tid], sum);
-        }
-    }
-#endif
-#undef EAE_Q_EXCHANGE
+    quarter_quantise<IGDN_OUT, GDN_IN>(
+        own, p, vec + 2 * EAE_C, vec + EAE_C, xch, tally, gamma_out, y_out, shifted_out, t_out, symbols, nonzero, checks, hw,
+        [&](int g) { return *reinterpret_cast<const float4*>(vec + 3 * EAE_C + p.cw + 8 * g); },
+        [](int, float centered, float bw) { return round_half_even(centered / bw); });
 }
 }  // namespace
 

@@ -157,7 +157,9 @@ __device__ __forceinline__ void wave_latent_body(f32x16 (&v)[4], const float* ve
 }
 
 
-// ---- four wavefronts per 32 positions (latent_quarter_kernel of latent.hip, latent_rows_kernel of latent_rows.hip) ------------
+// ---- four wavefronts per 32 positions (quarter_body.h: latent_quarter_kernel of latent.hip, the kernels of latent_rows.hip) ------
+// x2[t][4 g + e]: the B operand of K-step kk = 16 t + 4 g + e, i.e. the squares of the tile in the order and lane placement the
+// MFMA wants them (squares_for_mfma below), all 128 channels; the wave accumulates its own channel tile w.
 template <int RING>
 __device__ __forceinline__ f32x16 quarter_denominator(const f32x16 (&x2)[4], const float* __restrict__ gamma_packed, int w, int lane) {
     const int hi = lane >> 5, lj = lane & 31;

@@ -789,15 +789,10 @@ def quality_search_tiles(first, max_sse, state, probe_acc, point, prob_row, trac
                                                       _stream(first)), 'eae_hip_quality_search_tiles')
 
 
-def latent_quantize_rows(y, bin_widths_points, point, map_mean=None, igdn_out=None, want_shifted=False, want_symbols=True,
-                         want_flags=False, out_symbols=None, out_flags=None, out_checks=None, want_checks=True, out_shifted=None,
-                         out_t=None):
-    """The quantiser half of `latent_stage` with one row of bin widths per image (include/eae_hip.h: eae_hip_latent_quantize_rows):
-    y [N, h, w, 128] (or [N, hw, 128]) are the latents after gdn_3, image i is quantised with bin_widths_points[point[i]] (float32
-    [K, 128]; point int32 [N] on the device, clamped to [0, K)). Returns `latent_stage`'s dict without 'y'; image i's part equals
-    `latent_stage(y[i:i + 1], bin_widths_points[point[i]], map_mean, gdn_in=None, igdn_out=igdn_out)` bit for bit. out_* buffers:
-    preallocated, flags / checks already zeroed (see quantize_maps). want_checks=False: no check is counted ('checks': None).
-    out_shifted / out_t: preallocated float32 outputs of y's size (a probe of `codec.QualityCodec` owns its latent buffer)."""
+def _quantize_rows_checked(y, bin_widths_points, point, map_mean, igdn_out, want_shifted, want_symbols, want_flags, out_symbols, out_flags,
+                           out_checks, want_checks=True, out_shifted=None, out_t=None, thresholds_points=None):
+    """The input checks and the outputs of `latent_quantize_rows` and `latent_quantize_rdo` (thresholds_points: the latter's table).
+    Returns (n, hw, the dict both return)."""
     n = y.shape[0]
     c = y.shape[-1]
     hw = y.numel()//(n*c)
@@ -806,6 +801,9 @@ def latent_quantize_rows(y, bin_widths_points, point, map_mean=None, igdn_out=No
         raise HipError('y must be float32 [N, ..., 128]')
     if bin_widths_points.dtype != torch.float32 or bin_widths_points.dim() != 2 or bin_widths_points.shape[1] != NB_MAPS:
         raise HipError('bin_widths_points must be float32 [K, 128]')
+    if thresholds_points is not None and (thresholds_points.dtype != torch.float32 or
+                                          tuple(thresholds_points.shape) != (bin_widths_points.shape[0], NB_MAPS, 16)):
+        raise HipError('thresholds_points must be float32 [K, 128, 16]')
     if point.dtype != torch.int32 or point.numel() != n:
         raise HipError('point must be int32 [N]')
     if map_mean is not None and (map_mean.dtype != torch.float32 or map_mean.numel() != NB_MAPS):
@@ -824,11 +822,26 @@ def latent_quantize_rows(y, bin_widths_points, point, map_mean=None, igdn_out=No
     checks = (out_checks if out_checks is not None else torch.zeros(3, dtype=torch.int32, device=d)) if want_checks else None
     if checks is not None and checks.numel() < 3:
         raise HipError('`out_checks` must hold three words')
+    return n, hw, {'shifted': shifted, 't': t, 'symbols': symbols, 'nonzero_flags': flags, 'checks': checks}
+
+
+def latent_quantize_rows(y, bin_widths_points, point, map_mean=None, igdn_out=None, want_shifted=False, want_symbols=True,
+                         want_flags=False, out_symbols=None, out_flags=None, out_checks=None, want_checks=True, out_shifted=None,
+                         out_t=None):
+    """The quantiser half of `latent_stage` with one row of bin widths per image (include/eae_hip.h: eae_hip_latent_quantize_rows):
+    y [N, h, w, 128] (or [N, hw, 128]) are the latents after gdn_3, image i is quantised with bin_widths_points[point[i]] (float32
+    [K, 128]; point int32 [N] on the device, clamped to [0, K)). Returns `latent_stage`'s dict without 'y'; image i's part equals
+    `latent_stage(y[i:i + 1], bin_widths_points[point[i]], map_mean, gdn_in=None, igdn_out=igdn_out)` bit for bit. out_* buffers:
+    preallocated, flags / checks already zeroed (see quantize_maps). want_checks=False: no check is counted ('checks': None).
+    out_shifted / out_t: preallocated float32 outputs of y's size (a probe of `codec.QualityCodec` owns its latent buffer)."""
+    (n, hw, out) = _quantize_rows_checked(y, bin_widths_points, point, map_mean, igdn_out, want_shifted, want_symbols, want_flags, out_symbols,
+                                          out_flags, out_checks, want_checks, out_shifted, out_t)
     (g_out, b_out) = igdn_out if igdn_out is not None else (None, None)
     _check(_native.hip().eae_hip_latent_quantize_rows(_p(y), _p(map_mean), _p(bin_widths_points), _p(point), bin_widths_points.shape[0],
-                                                      _p(g_out), _p(b_out), _p(shifted), _p(t), _p(symbols), _p(flags), _p(checks), n, hw,
-                                                      _stream(y)), 'eae_hip_latent_quantize_rows')
-    return {'shifted': shifted, 't': t, 'symbols': symbols, 'nonzero_flags': flags, 'checks': checks}
+                                                      _p(g_out), _p(b_out), _p(out['shifted']), _p(out['t']), _p(out['symbols']),
+                                                      _p(out['nonzero_flags']), _p(out['checks']), n, hw, _stream(y)),
+           'eae_hip_latent_quantize_rows')
+    return out
 
 
 def latent_quantize_rdo(y, bin_widths_points, thresholds_points, point, truncated_unary_length, map_mean=None, igdn_out=None,
@@ -838,37 +851,14 @@ def latent_quantize_rdo(y, bin_widths_points, thresholds_points, point, truncate
     [K, 128, 16] (ratecontrol.rdo_thresholds), image i takes row point[i] of it as of bin_widths_points. A latent whose nearest
     symbol has magnitude a in [1, min(L, 16)] is coded one step nearer zero when 2 (|x| - a) + 1 < thresholds[k, c, a - 1].
     Returns `latent_quantize_rows`' dict; with thresholds of zeros, its bits."""
-    n = y.shape[0]
-    c = y.shape[-1]
-    hw = y.numel()//(n*c)
-    d = y.device
-    if c != NB_MAPS or y.dtype != torch.float32:
-        raise HipError('y must be float32 [N, ..., 128]')
-    if bin_widths_points.dtype != torch.float32 or bin_widths_points.dim() != 2 or bin_widths_points.shape[1] != NB_MAPS:
-        raise HipError('bin_widths_points must be float32 [K, 128]')
-    k_points = bin_widths_points.shape[0]
-    if thresholds_points.dtype != torch.float32 or tuple(thresholds_points.shape) != (k_points, NB_MAPS, 16):
-        raise HipError('thresholds_points must be float32 [K, 128, 16]')
-    if point.dtype != torch.int32 or point.numel() != n:
-        raise HipError('point must be int32 [N]')
-    if map_mean is not None and (map_mean.dtype != torch.float32 or map_mean.numel() != NB_MAPS):
-        raise HipError('map_mean must be float32 of 128 elements')
-    shifted = torch.empty_like(y) if want_shifted else None
-    t = torch.empty_like(y) if igdn_out is not None else None
-    symbols = (out_symbols if out_symbols is not None else torch.empty((n, c, hw), dtype=torch.int16, device=d)) if want_symbols else None
-    if symbols is not None and (symbols.dtype != torch.int16 or symbols.numel() != n*c*hw):
-        raise TypeError('`out_symbols` must be an int16 tensor of N x C x hw elements.')
-    flags = (out_flags if out_flags is not None else torch.zeros((n, c), dtype=torch.int32, device=d)) if want_flags else None
-    if flags is not None and flags.numel() != n*c:
-        raise HipError('`out_flags` must hold N x 128 words')
-    checks = out_checks if out_checks is not None else torch.zeros(3, dtype=torch.int32, device=d)
-    if checks.numel() < 3:
-        raise HipError('`out_checks` must hold three words')
+    (n, hw, out) = _quantize_rows_checked(y, bin_widths_points, point, map_mean, igdn_out, want_shifted, want_symbols, want_flags, out_symbols,
+                                          out_flags, out_checks, thresholds_points=thresholds_points)
     (g_out, b_out) = igdn_out if igdn_out is not None else (None, None)
-    _check(_native.hip().eae_hip_latent_quantize_rdo(_p(y), _p(map_mean), _p(bin_widths_points), _p(thresholds_points), _p(point), k_points,
-                                                     int(truncated_unary_length), _p(g_out), _p(b_out), _p(shifted), _p(t), _p(symbols),
-                                                     _p(flags), _p(checks), n, hw, _stream(y)), 'eae_hip_latent_quantize_rdo')
-    return {'shifted': shifted, 't': t, 'symbols': symbols, 'nonzero_flags': flags, 'checks': checks}
+    _check(_native.hip().eae_hip_latent_quantize_rdo(_p(y), _p(map_mean), _p(bin_widths_points), _p(thresholds_points), _p(point),
+                                                     bin_widths_points.shape[0], int(truncated_unary_length), _p(g_out), _p(b_out),
+                                                     _p(out['shifted']), _p(out['t']), _p(out['symbols']), _p(out['nonzero_flags']),
+                                                     _p(out['checks']), n, hw, _stream(y)), 'eae_hip_latent_quantize_rdo')
+    return out
 
 
 def cast_bt601(x):

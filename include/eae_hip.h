@@ -369,7 +369,7 @@ int eae_hip_ladder_histograms_tiles(const float* y, const float* map_mean, const
                                     uint32_t* hist, uint64_t* bypass_bits, uint32_t* range_errors, int n, int h, int w, int th, int tw,
                                     void* stream);
 
-/* ---- a rate point per image, on the device (csrc/hip/budget.hip; ratecontrol.py) ------------------------
+/* ---- a rate point per image, on the device (csrc/hip/budget.hip, latent_rows.hip; ratecontrol.py) -------
  * eae_hip_ladder_select: the point of every image of a batch for its byte budget, from what eae_hip_ladder_histograms left. Integer
  * arithmetic only; equal, element for element, to ratecontrol.upper_bounds_fixed + valid_points + select_by_upper_bound.
  *   hist uint32 [N][K][128][L + 1], bypass_bits uint64 [N][K][128]           as eae_hip_ladder_histograms leaves them
@@ -389,8 +389,8 @@ int eae_hip_ladder_histograms_tiles(const float* y, const float* map_mean, const
  * pointers, idx_map_exception >= 128 or >= 0 without log2_tables, a negative header_bytes / exception_row_base, n <= 0, 64-bit
  * arrays or fixed_costs not 8-byte aligned -> EAE_HIP_BAD_ARGUMENT, before any launch. One launch, one block per image.
  *
- * eae_hip_latent_quantize_rows: the quantiser half of eae_hip_latent_stage (no gdn_3: y [N][hw][128] are the latents the quantiser
- * sees) with one row of bin widths per image: image i takes bin_widths_points[clamp(point[i], 0, K - 1)] (float32 [K][128]; point
+ * eae_hip_latent_quantize_rows (latent_rows.hip): the quantiser half of eae_hip_latent_stage (no gdn_3: y [N][hw][128] are the
+ * latents the quantiser sees) with one row of bin widths per image: image i takes bin_widths_points[clamp(point[i], 0, K - 1)] (float32 [K][128]; point
  * int32 [N] in device memory, e.g. eae_hip_ladder_select's). Outputs as eae_hip_latent_stage: planar int16 symbols, dead-map
  * flags, the three checks (summed over the images; flags and checks are set / added to: the caller zeroes them), shifted_out
  * (nullable) and, with gamma_out_packed / beta_out, t_out = inverse_gdn_4(shifted). Image i's results are bit for bit
@@ -464,7 +464,7 @@ int eae_hip_quality_search_tiles(const int32_t* first, const int64_t* max_sse, i
                                  int nb_tiles, int k_points, int nb_rounds, int round, int idx_map_exception, int exception_row_base,
                                  int n, void* stream);
 
-/* ---- rate-distortion optimised quantiser (csrc/hip/rdoq.hip; ratecontrol.py) -----------------------------
+/* ---- rate-distortion optimised quantiser (csrc/hip/latent_rows.hip; ratecontrol.py) ----------------------
  * eae_hip_latent_quantize_rdo: eae_hip_latent_quantize_rows with one more input, thresholds_points float32 [K][128][16]
  * (ratecontrol.rdo_thresholds; image i takes row clamp(point[i], 0, K - 1) of it as of bin_widths_points), and `length`, the
  * truncated unary length L. Per latent, in IEEE float32: centered = y - mean; x = centered / bw; r = round_half_even(x); a = |r|;

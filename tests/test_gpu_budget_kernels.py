@@ -1,11 +1,12 @@
-"""The two launches of csrc/hip/budget.hip, on poisoned buffers between guard bands under both poisons (tests/guarded.py):
+"""The selection of csrc/hip/budget.hip and the quantiser of csrc/hip/latent_rows.hip that takes its points, on poisoned buffers between
+guard bands under both poisons (tests/guarded.py):
 
 * eae_hip_ladder_select (device.ladder_select) against the host rule it restates in integers -- ratecontrol.upper_bounds_fixed,
   valid_points, select_by_upper_bound --, element for element: on the histograms device.ladder_histograms leaves for random latents,
   and on synthetic histograms uploaded directly (maps of 16,384 symbols: the 64-bit sums; invalid points; the exception map's corner
   cases), with budgets at and one byte under every bound;
 * eae_hip_latent_quantize_rows (device.latent_quantize_rows) against device.latent_stage image by image, bit for bit: tiles of 32
-  positions that straddle two and three images, a ragged last tile, every image at another point.
+  positions that straddle two and three images, a ragged last tile, every image at another point; every optional output absent in turn.
 
 Every comparison is exact."""
 import functools
@@ -254,6 +255,27 @@ def test_the_points_matter(dev, guard):
     own = dev.latent_quantize_rows(y_d, bw_d, guard.upload(numpy.asarray(points, dtype=numpy.int32)), mean_d)
     first = dev.latent_quantize_rows(y_d, bw_d, guard.upload(numpy.zeros(n, dtype=numpy.int32)), mean_d)
     assert torch.equal(own['symbols'][1], first['symbols'][1]) and not torch.equal(own['symbols'][0], first['symbols'][0])
+
+
+@pytest.mark.parametrize('absent', ['shifted', 'symbols', 'nonzero_flags', 'checks'])
+@pytest.mark.parametrize('learned', [False, True], ids=['fixed', 'learned'])
+def test_latent_quantize_rows_every_optional_output_absent_in_turn(dev, guard, learned, absent):
+    """The null-output branches of the four-wave body (csrc/hip/quarter_body.h). n = 3, hw = 33: the tiles of 32 positions straddle
+    images (the per-lane flag path) or lie inside one (the packed path), and the last tile is ragged."""
+    import torch
+    (n, hw, k_points, points) = (3, 33, 3, (2, 0, 1))
+    (y, bw, mean, gamma, beta) = quantiser_inputs(n, hw, k_points, points)
+    (y_d, bw_d, mean_d, point_d) = (guard.upload(y), guard.upload(bw), guard.upload(mean), guard.upload(numpy.asarray(points, dtype=numpy.int32)))
+    igdn = None if learned else (dev.pack_gamma(guard.upload(gamma)), guard.upload(beta))
+    full = dev.latent_quantize_rows(y_d, bw_d, point_d, mean_d, igdn_out=igdn, want_shifted=True, want_symbols=True, want_flags=True,
+                                    want_checks=True)
+    part = dev.latent_quantize_rows(y_d, bw_d, point_d, mean_d, igdn_out=igdn, want_shifted=absent != 'shifted',
+                                    want_symbols=absent != 'symbols', want_flags=absent != 'nonzero_flags', want_checks=absent != 'checks')
+    assert part[absent] is None and (full['t'] is None) == learned
+    assert int(full['checks'][0]) == 1 and int(full['nonzero_flags'][:, 9].sum()) == 0 and int(full['nonzero_flags'].sum()) > n*100
+    for name in ('shifted', 't', 'symbols', 'nonzero_flags', 'checks'):
+        if name != absent and full[name] is not None:
+            assert torch.equal(part[name], full[name]), name
 
 
 def test_latent_quantize_rows_refuses_bad_arguments(dev, guard):

@@ -62,6 +62,33 @@ def test_latent_stage_equals_the_separate_kernels(shape, learned, form, launch_o
         assert torch.equal(f['t'], t)
 
 
+@pytest.mark.parametrize('absent', ['y', 'shifted', 'symbols', 'nonzero_flags'])
+@pytest.mark.parametrize('learned', [False, True])
+def test_quarter_form_every_optional_output_absent_in_turn(learned, absent, launch_options):
+    """The null-output branches of the four-wave body (csrc/hip/quarter_body.h). n = 3, hw = 33: the tiles of 32 positions straddle
+    images (the per-lane flag path) or lie inside one (the packed path), and the last tile is ragged."""
+    from autoencoder_based_image_compression_amd import device as dev
+    launch_options.setenv('EAE_HIP_LATENT', 'q')
+    rng = numpy.random.RandomState(33 + int(learned))
+    x = torch.from_numpy((rng.laplace(size=(3, 3, 11, 128))*rng.uniform(0.1, 6., size=128)).astype(numpy.float32)).cuda()
+    x[0, 0, 0, 5] = 1.e6                         # one symbol outside int16: checks[0]
+    x[:, :, :, 9] = 1e-3                         # a dead map after quantisation
+    gamma = torch.from_numpy(rng.uniform(2e-5, 0.01, size=(128, 128)).astype(numpy.float32)).cuda()
+    (b3, b4) = (torch.from_numpy(rng.uniform(0.5, 2., size=128).astype(numpy.float32)).cuda(),
+                torch.from_numpy(rng.uniform(0.5, 2., size=128).astype(numpy.float32)).cuda())
+    bw = torch.from_numpy(rng.uniform(0.4, 2., size=128).astype(numpy.float32)).cuda()
+    mean = torch.from_numpy(rng.normal(scale=0.2, size=128).astype(numpy.float32)).cuda()
+    norms = dict(gdn_in=None if learned else (dev.pack_gamma(gamma), b3), igdn_out=None if learned else (dev.pack_gamma(gamma*2.), b4))
+    full = dev.latent_stage(x, bw, mean, want_y=True, want_shifted=True, want_symbols=True, want_flags=True, **norms)
+    part = dev.latent_stage(x, bw, mean, want_y=absent != 'y', want_shifted=absent != 'shifted', want_symbols=absent != 'symbols',
+                            want_flags=absent != 'nonzero_flags', **norms)
+    assert part[absent] is None and (full['t'] is None) == learned
+    assert int(full['checks'][0]) >= int(learned) and int(full['nonzero_flags'][:, 9].sum()) == 0 and int(full['nonzero_flags'].sum()) > 3*64
+    for name in ('y', 'shifted', 't', 'symbols', 'nonzero_flags', 'checks'):
+        if name != absent and full[name] is not None:
+            assert torch.equal(part[name], full[name]), name
+
+
 def test_latent_stage_argument_checks():
     from autoencoder_based_image_compression_amd import _native
     lib = _native.hip()

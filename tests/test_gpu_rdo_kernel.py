@@ -1,4 +1,4 @@
-"""eae_hip_latent_quantize_rdo (csrc/hip/rdoq.hip, device.latent_quantize_rdo) on poisoned buffers between guard bands under both
+"""eae_hip_latent_quantize_rdo (csrc/hip/latent_rows.hip, device.latent_quantize_rdo) on poisoned buffers between guard bands under both
 poisons (tests/guarded.py). Every comparison is exact:
 
 * the choice of every symbol against ratecontrol.rdo_quantize_numpy, element for element;
