@@ -2428,7 +2428,11 @@ class BudgetCodec(BatchCodec):
     _no_coding_tile = '`BudgetCodec` does not take `coding_tile`: the bounds are those of whole maps (EAE1).'
 
     def __init__(self, variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, budget_bytes=None, **batch_codec_options):
-        """ladder: a `ratecontrol.RateLadder`, finest point first, of at most `device.ladder_max_points(L)` points. budget_bytes: the
+        """ladder: a `ratecontrol.RateLadder`, finest point first, of at most `device.ladder_max_points(L)` points. A ladder with a
+        price (`RateLadder(..., rdo_lambda=...)`) makes the step count, bound, probe and code the symbols of the
+        rate-distortion optimised quantiser: `Ticket.image_containers()[i]` is then `container.encode_images(..., rdo_lambda=
+        ladder.rdo_lambdas[k])` at the image's point k, everything else reads the same. The keyword `rdo_lambda` itself is refused:
+        the price belongs to the ladder. budget_bytes: the
         budget of a `submit` that names none (a scalar or one value per image). batch_codec_options: `BatchCodec`'s keyword arguments
         (device, nb_in_flight, keep_reconstruction, use_graphs, nb_transform_streams, one_stream_steps, hist_radius,
         container_capacity_bytes, ...); `emit_container` is always on; `coding_tile`, `fuse_latent`, a coder other than 'device' and
@@ -2452,7 +2456,8 @@ class BudgetCodec(BatchCodec):
         if options.get('fuse_latent'):
             raise ValueError('`BudgetCodec` does not take `fuse_latent`: the point is chosen between conv_3 and the quantiser.')
         if options.get('rdo_lambda') is not None:
-            raise ValueError('The rate-control codecs do not take `rdo_lambda`: their byte bounds and probes are those of nearest rounding.')
+            raise ValueError('The rate-control codecs do not take `rdo_lambda`: the price of a bit comes with the ladder '
+                             '(`ratecontrol.RateLadder(..., rdo_lambda=...)`), a point at a time.')
         if options.get('coder', 'device') != 'device':
             raise ValueError('`BudgetCodec` needs the coder on the device.')
         chunks = options.get('coder_chunks')
@@ -2479,6 +2484,12 @@ class BudgetCodec(BatchCodec):
                 tiled = self._tile_layout
                 self._entry_image = to_device(numpy.array([tiled['entries'][p][0] for p in tiled['payload_entry'].tolist()], dtype=numpy.int32))
             self._bin_widths_points = to_device(ladder.bin_widths_points)
+            # a ladder with a price (`RateLadder(rdo_lambda=...)`): the thresholds of its points in the
+            # quantiser's layout [K, 128, 16] and in the count's [K, 16, 128]; None: every launch is that of nearest rounding
+            self._rdo_thresholds_points = self._rdo_by_magnitude = None
+            if ladder.rdo_thresholds_points is not None:
+                self._rdo_thresholds_points = to_device(ladder.rdo_thresholds_points)
+                self._rdo_by_magnitude = dev.rdo_thresholds_by_magnitude(self._rdo_thresholds_points)
             # (32-bit words: torch has no arithmetic on uint32, and none is asked of it)
             self._fixed_costs = to_device(ratecontrol.fixed_costs(ladder).view(numpy.int32))
             self._log2_tables = to_device(ratecontrol.log2_tables(self.map_size).view(numpy.int32)) if self.idx_map_exception >= 0 else None
@@ -2560,9 +2571,9 @@ class BudgetCodec(BatchCodec):
         """`_launch_analysis` from the quantiser on, at `budget.point`; returns the synthesis transform's input."""
         d = self.decoder.v
         igdn_out = None if self.learned else (self.decoder.g[4], d['decoder/beta_4'])
-        q = hook('latent', lambda: dev.latent_quantize_rows(y, self._bin_widths_points, budget.point, self.map_mean, igdn_out=igdn_out,
-                                                            want_shifted=self.learned, want_symbols=True, want_flags=True,
-                                                            out_symbols=slot.symbols, out_flags=slot.flags, out_checks=slot.checks[:3]))
+        outputs = dict(igdn_out=igdn_out, want_shifted=self.learned, want_symbols=True, want_flags=True, out_symbols=slot.symbols,
+                       out_flags=slot.flags, out_checks=slot.checks[:3])
+        q = hook('latent', lambda: self._quantise_at(y, budget.point, **outputs))
         if self.idx_map_exception >= 0:
             dev.symbol_histograms(slot.symbols_2d, self.hist_radius, out=(slot.hist, slot.overflow),
                                   first_map=self.idx_map_exception, map_step=self.nb_maps, zero=False)
@@ -2571,9 +2582,21 @@ class BudgetCodec(BatchCodec):
             dev.publish_to_host(slot.out[first:], slot.pinned_out[first:])
         return q['shifted'] if self.learned else q['t']
 
+    def _quantise_at(self, y, point, **outputs):
+        """The quantiser with every image's own row (`point` int32 [N] on the device): `device.latent_quantize_rows`, or for a ladder
+        with a price `device.latent_quantize_rdo` with the thresholds of the same row."""
+        if self._rdo_thresholds_points is None:
+            return dev.latent_quantize_rows(y, self._bin_widths_points, point, self.map_mean, **outputs)
+        return dev.latent_quantize_rdo(y, self._bin_widths_points, self._rdo_thresholds_points, point, self.truncated_unary_length,
+                                       self.map_mean, **outputs)
+
     def _launch_ladder(self, y, budget):
-        dev.ladder_histograms(y, self._bin_widths_points, self.map_mean, self.truncated_unary_length,
-                              out=(budget.hist, budget.bypass_bits, budget.range_errors))
+        out = (budget.hist, budget.bypass_bits, budget.range_errors)
+        if self._rdo_thresholds_points is None:
+            dev.ladder_histograms(y, self._bin_widths_points, self.map_mean, self.truncated_unary_length, out=out)
+        else:                                            # the symbols counted are the symbols `_quantise_at` writes
+            dev.ladder_histograms_rdo(y, self._bin_widths_points, self._rdo_thresholds_points, self.map_mean, self.truncated_unary_length,
+                                      out=out, by_magnitude=self._rdo_by_magnitude)
 
     def _launch_select(self, budget):
         dev.ladder_select(budget.hist, budget.bypass_bits, self._fixed_costs, self._log2_tables, self.idx_map_exception, self._header_bytes,
@@ -2625,8 +2648,12 @@ class _TiledRateControl(object):
 
     def _launch_ladder(self, y, budget):
         plane = y.view(self.batch_size, self.h_in//csts.STRIDE_PROD, self.w_in//csts.STRIDE_PROD, self.nb_maps)
-        dev.ladder_histograms_tiles(plane, self._bin_widths_points, self.coding_tile, self.map_mean, self.truncated_unary_length,
-                                    out=(budget.hist, budget.bypass_bits, budget.range_errors))
+        out = (budget.hist, budget.bypass_bits, budget.range_errors)
+        if self._rdo_thresholds_points is None:
+            dev.ladder_histograms_tiles(plane, self._bin_widths_points, self.coding_tile, self.map_mean, self.truncated_unary_length, out=out)
+        else:
+            dev.ladder_histograms_rdo_tiles(plane, self._bin_widths_points, self._rdo_thresholds_points, self.coding_tile, self.map_mean,
+                                            self.truncated_unary_length, out=out, by_magnitude=self._rdo_by_magnitude)
 
     def _launch_select(self, budget):
         dev.ladder_select_tiles(budget.hist, budget.bypass_bits, self._fixed_costs, self._log2_tables, self.idx_map_exception,
@@ -2814,9 +2841,8 @@ class QualityCodec(BudgetCodec):
         igdn_out = None if self.learned else (dec.g[4], d['decoder/beta_4'])
         (out_shifted, out_t) = (quality.probe_latent, None) if self.learned else (None, quality.probe_latent)
         for r in range(1, self.nb_rounds + 1):
-            hook('probe_latent', lambda: dev.latent_quantize_rows(y, self._bin_widths_points, quality.point, self.map_mean, igdn_out=igdn_out,
-                                                                  want_shifted=self.learned, want_symbols=False, want_checks=False,
-                                                                  out_shifted=out_shifted, out_t=out_t))
+            hook('probe_latent', lambda: self._quantise_at(y, quality.point, igdn_out=igdn_out, want_shifted=self.learned, want_symbols=False,
+                                                           want_checks=False, out_shifted=out_shifted, out_t=out_t))
             t = hook('probe_tconv1_igdn5', lambda: dev.tconv5x5s2(quality.probe_latent, dec.w4, d['decoder/biases_4'], dev.NORM_IGDN, dec.g[5],
                                                                   d['decoder/beta_5'], workspace=ws))
             t = hook('probe_tconv2_igdn6', lambda: dev.tconv5x5s2(t, dec.w5, d['decoder/biases_5'], dev.NORM_IGDN, dec.g[6], d['decoder/beta_6'],

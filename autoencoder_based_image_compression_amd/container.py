@@ -235,6 +235,39 @@ def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_p
     return _encode_entries(symbols, fields, nb_images if coding_tile is None else tiles_per_call)
 
 
+class _LadderOnDevice(object):
+    """What `encode_images_to_budget` and `encode_images_to_quality` launch at the points of a ladder: the one pass of counts and the
+    quantiser at a point. A ladder with a price (`ratecontrol.RateLadder(..., rdo_lambda=...)`) takes the
+    rate-distortion optimised siblings of both, so that the symbols counted, probed and coded are the same."""
+
+    def __init__(self, ladder, device):
+        self.length = ladder.truncated_unary_length
+        self.mean = torch.from_numpy(ladder.map_mean).to(device)
+        self.bin_widths_points = torch.from_numpy(ladder.bin_widths_points).to(device)
+        self.thresholds_points = None
+        if ladder.rdo_thresholds_points is not None:
+            self.thresholds_points = torch.from_numpy(ladder.rdo_thresholds_points).to(device)
+
+    def histograms(self, y, coding_tile=None):
+        """(hist, bypass_bits) as numpy: `device.ladder_histograms[_rdo]`, with coding_tile `device.ladder_histograms[_rdo]_tiles` of
+        the plane y [N, h, w, 128]."""
+        if self.thresholds_points is None:
+            counts = (dev.ladder_histograms(y, self.bin_widths_points, self.mean, self.length) if coding_tile is None else
+                      dev.ladder_histograms_tiles(y, self.bin_widths_points, coding_tile, self.mean, self.length))
+        else:
+            counts = (dev.ladder_histograms_rdo(y, self.bin_widths_points, self.thresholds_points, self.mean, self.length)
+                      if coding_tile is None else
+                      dev.ladder_histograms_rdo_tiles(y, self.bin_widths_points, self.thresholds_points, coding_tile, self.mean, self.length))
+        return counts[0].cpu().numpy(), counts[1].cpu().numpy()
+
+    def quantize(self, y, k, **wanted):
+        """`device.quantize_maps(y, bin widths of point k, mean, **wanted)`, or `device.latent_quantize_rdo` at point k."""
+        if self.thresholds_points is None:
+            return dev.quantize_maps(y, self.bin_widths_points[k], self.mean, **wanted)
+        point = torch.full((y.shape[0],), int(k), dtype=torch.int32, device=y.device)
+        return dev.latent_quantize_rdo(y, self.bin_widths_points, self.thresholds_points, point, self.length, self.mean, **wanted)
+
+
 def encode_images_to_budget(luminances_uint8, encoder, ladder, budget_bytes, tile=None, coding_tile=None):
     """uint8 (N, H, W) or (N, H, W, 1) luminance images -> (blobs, info): every image compressed into at most `budget_bytes` bytes
     (a scalar, or one value per image) at the first rate point of `ladder` (ratecontrol.RateLadder, finest first) at which it fits.
@@ -253,6 +286,9 @@ def encode_images_to_budget(luminances_uint8, encoder, ladder, budget_bytes, til
     coding_tile=(th, tw) latents: single-image EAT1 blobs instead, byte for byte `encode_images(..., coding_tile=coding_tile)[0]` at
     the image's point. A tile's termination and byte padding need counts per tile: the one pass is
     `device.ladder_histograms_tiles`, the bounds those of `ratecontrol.blob_byte_bounds(..., coding_tile)`.
+    A ladder with a price (`ratecontrol.RateLadder(..., rdo_lambda=...)`): the counts, hence the bounds, and the
+    symbols coded are those of the rate-distortion optimised quantiser (`device.ladder_histograms_rdo[_tiles]`,
+    `device.latent_quantize_rdo`); the blobs are `encode_images(..., rdo_lambda=ladder.rdo_lambdas[k])`'s.
     Not in this function: codec.BatchCodec, which takes one rate point per codec (codec.BudgetCodec chooses one per image inside
     the step, on the upper bound alone: DESIGN.md section 19)."""
     from . import ratecontrol
@@ -270,25 +306,22 @@ def encode_images_to_budget(luminances_uint8, encoder, ladder, budget_bytes, til
     length = ladder.truncated_unary_length
     device = encoder.device
     y = encoder(torch.from_numpy(images).to(device), tile=tile)
-    mean = torch.from_numpy(ladder.map_mean).to(device)
-    bin_widths_points = torch.from_numpy(ladder.bin_widths_points).to(device)
+    points = _LadderOnDevice(ladder, device)
     map_size = (height//csts.STRIDE_PROD)*(width//csts.STRIDE_PROD)
     if coding_tile is None:
-        (hist, bypass_bits, _) = dev.ladder_histograms(y, bin_widths_points, mean, length)
-        (hist, bypass_bits) = (hist.cpu().numpy(), bypass_bits.cpu().numpy())
+        (hist, bypass_bits) = points.histograms(y)
         (lower, upper) = ratecontrol.blob_byte_bounds(hist, bypass_bits, ladder, height, width)
         valid = ratecontrol.valid_points(hist, map_size)
     else:
         coding_tile = _clamped_coding_tile(coding_tile, height, width)
         plane = y.view(nb_images, height//csts.STRIDE_PROD, width//csts.STRIDE_PROD, -1)
-        (hist, bypass_bits, _) = dev.ladder_histograms_tiles(plane, bin_widths_points, coding_tile, mean, length)
-        (hist, bypass_bits) = (hist.cpu().numpy(), bypass_bits.cpu().numpy())
+        (hist, bypass_bits) = points.histograms(plane, coding_tile)
         (lower, upper) = ratecontrol.blob_byte_bounds(hist, bypass_bits, ladder, height, width, coding_tile)
         valid = ratecontrol.valid_points(hist.astype(numpy.int64).sum(axis=2), map_size)
     coded = {}
 
     def size_of(i, k):
-        q = dev.quantize_maps(y[i:i + 1], bin_widths_points[k], mean, want_symbols=True)
+        q = points.quantize(y[i:i + 1], k, want_symbols=True)
         if int(q['checks'][0].item()) != 0:         # `valid` says it cannot happen: the same symbols were counted
             raise AssertionError('The rounded array elements cannot be represented as 16-bit signed integers.')
         e = ladder.idx_map_exception
@@ -321,7 +354,9 @@ def encode_images_to_quality(luminances_uint8, encoder, decoder, ladder, target_
     coding_tile=(th, tw) latents: single-image EAT1 blobs instead, byte for byte `encode_images(..., coding_tile=coding_tile)[0]` at
     the image's point, and the host loop of `codec.TiledQualityCodec`. The search is the same -- a point's
     squared error does not depend on the coding tile --; the budget's point comes from the counts per tile
-    (`device.ladder_histograms_tiles`) and `ratecontrol.upper_bounds_fixed_tiles`, the rule of `codec.TiledBudgetCodec`."""
+    (`device.ladder_histograms_tiles`) and `ratecontrol.upper_bounds_fixed_tiles`, the rule of `codec.TiledBudgetCodec`.
+    A ladder with a price (`ratecontrol.RateLadder(..., rdo_lambda=...)`): counts, probes and blobs are those of the rate-distortion
+    optimised quantiser, as in `encode_images_to_budget`."""
     from . import ratecontrol
     images = numpy.ascontiguousarray(luminances_uint8)
     if images.dtype != numpy.uint8:
@@ -343,19 +378,16 @@ def encode_images_to_quality(luminances_uint8, encoder, decoder, ladder, target_
     device = encoder.device
     references = torch.from_numpy(images).to(device)
     y = encoder(references)
-    mean = torch.from_numpy(ladder.map_mean).to(device)
-    bin_widths_points = torch.from_numpy(ladder.bin_widths_points).to(device)
+    points = _LadderOnDevice(ladder, device)
     map_size = (height//csts.STRIDE_PROD)*(width//csts.STRIDE_PROD)
     if coding_tile is None:
-        (hist, bypass_bits, _) = dev.ladder_histograms(y, bin_widths_points, mean, length)
-        (hist, bypass_bits) = (hist.cpu().numpy(), bypass_bits.cpu().numpy())
+        (hist, bypass_bits) = points.histograms(y)
         upper = ratecontrol.upper_bounds_fixed(hist, bypass_bits, ladder, map_size)
         valid = ratecontrol.valid_points(hist, map_size)
     else:
         coding_tile = _clamped_coding_tile(coding_tile, height, width)
         plane = y.view(nb_images, height//csts.STRIDE_PROD, width//csts.STRIDE_PROD, -1)
-        (hist, bypass_bits, _) = dev.ladder_histograms_tiles(plane, bin_widths_points, coding_tile, mean, length)
-        (hist, bypass_bits) = (hist.cpu().numpy(), bypass_bits.cpu().numpy())
+        (hist, bypass_bits) = points.histograms(plane, coding_tile)
         upper = ratecontrol.upper_bounds_fixed_tiles(hist, bypass_bits, ladder, map_size,
                                                      ratecontrol.header_bytes(ladder, height, width, coding_tile))
         valid = ratecontrol.valid_points(hist.astype(numpy.int64).sum(axis=2), map_size)
@@ -373,7 +405,7 @@ def encode_images_to_quality(luminances_uint8, encoder, decoder, ladder, target_
 
         def sse_of(k):
             if k not in known:
-                q = dev.quantize_maps(y[i:i + 1], bin_widths_points[k], mean, want_shifted=True)
+                q = points.quantize(y[i:i + 1], k, want_shifted=True)
                 (_, decoded, _) = decoder(q['shifted'])
                 known[k] = int(dev.sse_u8(decoded, references[i:i + 1]).item())
             return known[k]
@@ -382,7 +414,7 @@ def encode_images_to_quality(luminances_uint8, encoder, decoder, ladder, target_
                                                                                                            int(thresholds[i]))
         info['rate_point'][i] = k
         # the coding stage of `encode_images` on the latents at hand (as `encode_images_to_budget` codes a point)
-        q = dev.quantize_maps(y[i:i + 1], bin_widths_points[k], mean, want_symbols=True)
+        q = points.quantize(y[i:i + 1], k, want_symbols=True)
         if int(q['checks'][0].item()) != 0:
             raise AssertionError('The rounded array elements cannot be represented as 16-bit signed integers.')
         rows = _exception_rows(q['symbols'], e, length) if e >= 0 else numpy.zeros((0, length), dtype=numpy.float64)

@@ -40,6 +40,28 @@
 // events, median of 30): 96.9 us with tiles of 16 against 82.5 us for ladder_kernel on the same latents (1.18), 140.3 us with tiles
 // of 8 (1.70): 576 tiles on 512 blocks leave 64 blocks a second tile, 128 pixels where ladder_kernel's block counts 76 -- a second
 // round of work, not the flush. Zeroing 8.6 / 34.5 MB of accumulators: 7.2 / 9.5 us.
+//
+// RDO (eae_hip_ladder_histograms_rdo, eae_hip_ladder_histograms_rdo_tiles). The same counts of the symbols the
+// rate-distortion optimised quantiser chooses (latent_rows.hip, ratecontrol.rdo_quantize_numpy): before cq = bw r, an r of magnitude a
+// in [1, min(L, 16)] goes one step nearer zero where 2 u + 1 < T[k][c][a - 1], u = |x| - a. The two kernel bodies are templates over
+// what `ladder_round` is handed: NoRdo (nothing; ladder_kernel and ladder_tiles_kernel keep their signatures, their 660 and 1417
+// instructions -- the scalar prologue is scheduled in another order, the loops are the same -- and their LDS) or Rdo (the table and
+// min(L, 16)): no run-time branch in either instantiation, 33 VGPRs and no scratch in both whole-map kernels, 36 / 41 in the tiles'.
+// Where the thresholds live. A lane owns a channel here (in rdo_rows_kernel a half-wave shares one), so [K][128][16] would be a gather
+// of up to 64 rows of 64 bytes per load. Two designs:
+//   (a) a copy BY MAGNITUDE, [K][16][128], made once by the caller (device.rdo_thresholds_by_magnitude), read from memory: the lanes
+//       of a wave that hold the same magnitude read 256 contiguous bytes, a wave touches at most min(L, 16) such rows per point, the
+//       whole table is 74 KB at K = 9 (L2-resident), and only an eligible lane loads -- a wave without one (most waves at a coarse
+//       point) skips the instruction; the LDS budget, hence eae_hip_ladder_max_points, is the nearest-rounding kernels';
+//   (b) the rows [K][min(L, 16)][128] staged in LDS beside the bins, conflict-free like them: 106 KB per block at K = 9, L = 10. The
+//       device grants it (163,840 bytes of LDS per block on gfx950, read from its attributes), but a compute unit then holds ONE
+//       block where it holds two today, and this file's launchers size their grids for two.
+// (a) is what is built. Measured (profiles/rdo_ladder.md; 24 x 32 x 48 latents, K = 9, L = 10, lambda = 2 bw^2, device events,
+// median of 30): 103.8 us against 81.6 us for ladder_kernel on the same latents (1.27), 122.1 against 95.8 at tiles of 16 (1.28),
+// 188.7 against 140.8 at tiles of 8 (1.34) -- and the same times, within 1 us, with a table of zeros, where every load returns 0 and
+// nothing is lowered. So what the count pays is the rule's arithmetic per (latent, point) -- the quotient kept, |r|, u, two compares,
+// the row's address, the select and copysign: 742 instructions against 660 -- on a kernel its divisions already bind, not the table:
+// there is no load time for (b) to win back, and it would cost half the occupancy. (b) was therefore not built.
 #include "common.h"
 
 namespace {
@@ -49,14 +71,42 @@ constexpr int LADDER_LDS_BYTES = 64 * 1024;         // what one block may ask fo
 constexpr int LADDER_MIN_PIXELS = 64;
 constexpr int LADDER_MAX_PIXELS = 1 << 20;          // 34 bypass bits per symbol at most: a block's sums fit 32 bits
 
+constexpr int RDO_MAGNITUDES = 16;                  // ratecontrol.RDO_MAGNITUDES: the magnitudes 1 .. 16 have a threshold
+
+// What the rate-distortion optimised count knows beyond the nearest-rounding one (file header, "RDO"): the thresholds of the K
+// points by magnitude, [K][16][128], and min(L, 16) as a float. NoRdo is the nearest-rounding count's: nothing.
+struct NoRdo {};
+struct Rdo {
+    const float* __restrict__ thresholds;           // [K][RDO_MAGNITUDES][128], in memory
+    float amax;
+};
+
+// The r of one latent at point k: the nearest integer of the quotient ...
+__device__ __forceinline__ float ladder_round(NoRdo, float centered, float bw, int, int) { return round_half_even(centered / bw); }
+
+// ... or, statement for statement rdo_rows_kernel's and ratecontrol.rdo_quantize_numpy's, one step nearer zero where 2 u + 1 is below
+// the threshold of (k, c, a). Only an eligible lane loads (a in [1, amax], tested in float: a NaN, an infinity or a huge a never
+// becomes an index), so a wave without one -- most waves at a coarse point -- issues no load at all; t = 0 lowers nothing, 2 u + 1
+// being at least 0.
+__device__ __forceinline__ float ladder_round(Rdo rdo, float centered, float bw, int k, int c) {
+    const float x = centered / bw;
+    const float r = round_half_even(x);
+    const float a = fabsf(r);
+    const float u = fabsf(x) - a;
+    float t = 0.f;
+    if (a >= 1.f && a <= rdo.amax) t = rdo.thresholds[((size_t)k * RDO_MAGNITUDES + ((int)a - 1)) * EAE_C + c];
+    return 2.f * u + 1.f < t ? r - copysignf(1.f, r) : r;
+}
+
 // One latent (already centred) of channel c at the K points: its bin and its bypass bits into the block's LDS arrays.
-__device__ __forceinline__ void count_latent(float centered, int c, int k_points, int length, const float* widths, unsigned int* bins,
+template <class R>
+__device__ __forceinline__ void count_latent(R rdo, float centered, int c, int k_points, int length, const float* widths, unsigned int* bins,
                                              unsigned int* bits, unsigned int* __restrict__ range_errors) {
     const int nb = length + 1;
 #pragma unroll 2
     for (int k = 0; k < k_points; ++k) {
         const float bw = widths[k * EAE_C + c];
-        const float r = round_half_even(centered / bw);
+        const float r = ladder_round(rdo, centered, bw, k, c);
         const float cq = bw * r;
         const float rs = round_half_even(cq / bw);              // compression.py:142: from cq / bw again, not from r
         if (!(fabsf(rs) < 32768.f)) {                           // tools.py:130-132: no bin, no bits (rare: straight to memory)
@@ -71,10 +121,11 @@ __device__ __forceinline__ void count_latent(float centered, int c, int k_points
     }
 }
 
-__global__ __launch_bounds__(LADDER_THREADS) void ladder_kernel(const float* __restrict__ y, const float* __restrict__ map_mean,
-                                                                const float* __restrict__ bin_widths_points, int k_points, int length,
-                                                                unsigned int* __restrict__ hist, unsigned long long* __restrict__ bypass_bits,
-                                                                unsigned int* __restrict__ range_errors, int hw, int chunks, int pixels) {
+template <class R>
+__device__ __forceinline__ void ladder_body(R rdo, const float* __restrict__ y, const float* __restrict__ map_mean,
+                                            const float* __restrict__ bin_widths_points, int k_points, int length,
+                                            unsigned int* __restrict__ hist, unsigned long long* __restrict__ bypass_bits,
+                                            unsigned int* __restrict__ range_errors, int hw, int chunks, int pixels) {
     extern __shared__ unsigned int lds[];
     const int nb = length + 1;
     unsigned int* bins = lds;                                        // [K][L + 1][128]
@@ -91,7 +142,7 @@ __global__ __launch_bounds__(LADDER_THREADS) void ladder_kernel(const float* __r
     const int p1 = min(p0 + pixels, hw);
     const float* yc = y + (size_t)img * hw * EAE_C + c;
     for (int pix = p0 + row; pix < p1; pix += LADDER_ROWS)
-        count_latent(yc[(size_t)pix * EAE_C] - m, c, k_points, length, widths, bins, bits, range_errors);
+        count_latent(rdo, yc[(size_t)pix * EAE_C] - m, c, k_points, length, widths, bins, bits, range_errors);
     __syncthreads();
     // flush in the outputs' order, [K][128][L + 1] and [K][128] of this image: consecutive lanes, consecutive addresses
     const int per_point = EAE_C * nb;
@@ -109,14 +160,30 @@ __global__ __launch_bounds__(LADDER_THREADS) void ladder_kernel(const float* __r
     }
 }
 
+__global__ __launch_bounds__(LADDER_THREADS) void ladder_kernel(const float* __restrict__ y, const float* __restrict__ map_mean,
+                                                                const float* __restrict__ bin_widths_points, int k_points, int length,
+                                                                unsigned int* __restrict__ hist, unsigned long long* __restrict__ bypass_bits,
+                                                                unsigned int* __restrict__ range_errors, int hw, int chunks, int pixels) {
+    ladder_body(NoRdo{}, y, map_mean, bin_widths_points, k_points, length, hist, bypass_bits, range_errors, hw, chunks, pixels);
+}
+
+__global__ __launch_bounds__(LADDER_THREADS) void ladder_rdo_kernel(const float* __restrict__ y, const float* __restrict__ map_mean,
+                                                                    const float* __restrict__ bin_widths_points,
+                                                                    const float* __restrict__ thresholds, float amax, int k_points, int length,
+                                                                    unsigned int* __restrict__ hist, unsigned long long* __restrict__ bypass_bits,
+                                                                    unsigned int* __restrict__ range_errors, int hw, int chunks, int pixels) {
+    ladder_body(Rdo{thresholds, amax}, y, map_mean, bin_widths_points, k_points, length, hist, bypass_bits, range_errors, hw, chunks, pixels);
+}
+
 // The same counts per coding tile (file header, "Tiles"). An ITEM is chunk `item % cpt` of entry `item / cpt` = image * T + tile:
 // the pixels [chunk * per, (chunk + 1) * per) of the tile's raster (rows x cols of it, cols consecutive pixels per row; an edge
 // tile is smaller and may leave its last chunks empty). A block takes the items [items * b / blocks, items * (b + 1) / blocks)
 // one after the other and flushes after each: the LDS arrays are zero again when the next one starts.
-__global__ __launch_bounds__(LADDER_THREADS) void ladder_tiles_kernel(
-    const float* __restrict__ y, const float* __restrict__ map_mean, const float* __restrict__ bin_widths_points, int k_points, int length,
-    unsigned int* __restrict__ hist, unsigned long long* __restrict__ bypass_bits, unsigned int* __restrict__ range_errors, int h, int w,
-    int th, int tw, int tiles_x, int nb_tiles, int cpt, int per, long items) {
+template <class R>
+__device__ __forceinline__ void ladder_tiles_body(
+    R rdo, const float* __restrict__ y, const float* __restrict__ map_mean, const float* __restrict__ bin_widths_points, int k_points,
+    int length, unsigned int* __restrict__ hist, unsigned long long* __restrict__ bypass_bits, unsigned int* __restrict__ range_errors, int h,
+    int w, int th, int tw, int tiles_x, int nb_tiles, int cpt, int per, long items) {
     extern __shared__ unsigned int lds[];
     const int nb = length + 1;
     unsigned int* bins = lds;                                        // [K][L + 1][128]
@@ -144,7 +211,7 @@ __global__ __launch_bounds__(LADDER_THREADS) void ladder_tiles_kernel(
         int q = q0 + row;
         int r = q / cols, col = q - r * cols;
         for (; q < q1; q += LADDER_ROWS) {
-            count_latent(yc[((size_t)(r0 + r) * w + c0 + col) * EAE_C] - m, c, k_points, length, widths, bins, bits, range_errors);
+            count_latent(rdo, yc[((size_t)(r0 + r) * w + c0 + col) * EAE_C] - m, c, k_points, length, widths, bins, bits, range_errors);
             col += LADDER_ROWS;
             while (col >= cols) { col -= cols; ++r; }
         }
@@ -170,6 +237,24 @@ __global__ __launch_bounds__(LADDER_THREADS) void ladder_tiles_kernel(
         __syncthreads();
     }
 }
+
+__global__ __launch_bounds__(LADDER_THREADS) void ladder_tiles_kernel(
+    const float* __restrict__ y, const float* __restrict__ map_mean, const float* __restrict__ bin_widths_points, int k_points, int length,
+    unsigned int* __restrict__ hist, unsigned long long* __restrict__ bypass_bits, unsigned int* __restrict__ range_errors, int h, int w,
+    int th, int tw, int tiles_x, int nb_tiles, int cpt, int per, long items) {
+    ladder_tiles_body(NoRdo{}, y, map_mean, bin_widths_points, k_points, length, hist, bypass_bits, range_errors, h, w, th, tw, tiles_x,
+                      nb_tiles, cpt, per, items);
+}
+
+__global__ __launch_bounds__(LADDER_THREADS) void ladder_rdo_tiles_kernel(
+    const float* __restrict__ y, const float* __restrict__ map_mean, const float* __restrict__ bin_widths_points,
+    const float* __restrict__ thresholds, float amax, int k_points, int length, unsigned int* __restrict__ hist,
+    unsigned long long* __restrict__ bypass_bits, unsigned int* __restrict__ range_errors, int h, int w, int th, int tw, int tiles_x,
+    int nb_tiles, int cpt, int per, long items) {
+    ladder_tiles_body(Rdo{thresholds, amax}, y, map_mean, bin_widths_points, k_points, length, hist, bypass_bits, range_errors, h, w, th, tw,
+                      tiles_x, nb_tiles, cpt, per, items);
+}
+
 }  // namespace
 
 extern "C" int eae_hip_ladder_max_points(int length) {
@@ -177,8 +262,13 @@ extern "C" int eae_hip_ladder_max_points(int length) {
     return LADDER_LDS_BYTES / ((length + 3) * EAE_C * 4);
 }
 
-extern "C" int eae_hip_ladder_histograms(const float* y, const float* map_mean, const float* bin_widths_points, int k_points, int length,
-                                         uint32_t* hist, uint64_t* bypass_bits, uint32_t* range_errors, int n, int hw, void* stream) {
+namespace {
+inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+inline float rdo_amax(int length) { return (float)(length < RDO_MAGNITUDES ? length : RDO_MAGNITUDES); }
+
+// thresholds null: ladder_kernel; else ladder_rdo_kernel (the caller has checked the pointer)
+int launch_ladder(const float* y, const float* map_mean, const float* bin_widths_points, const float* thresholds, int k_points, int length,
+                  uint32_t* hist, uint64_t* bypass_bits, uint32_t* range_errors, int n, int hw, void* stream) {
     if (!y || !bin_widths_points || !hist || n <= 0 || hw <= 0) return EAE_HIP_BAD_ARGUMENT;
     if (length < 1 || length > 255 || k_points < 1 || k_points > eae_hip_ladder_max_points(length)) return EAE_HIP_BAD_ARGUMENT;
     // at most two blocks per compute unit, LADDER_MIN_PIXELS..LADDER_MAX_PIXELS pixels each, a whole number of pixel rows
@@ -193,16 +283,22 @@ extern "C" int eae_hip_ladder_histograms(const float* y, const float* map_mean, 
     chunks = ((long)hw + pixels - 1) / pixels;
     if ((long)n * chunks > 0x7FFFFFFFL) return EAE_HIP_BAD_SHAPE;
     const size_t lds_bytes = (size_t)k_points * (length + 3) * EAE_C * 4;
-    hipLaunchKernelGGL(ladder_kernel, dim3((unsigned)(n * chunks)), dim3(LADDER_THREADS), lds_bytes, (hipStream_t)stream, y, map_mean,
-                       bin_widths_points, k_points, length, hist, reinterpret_cast<unsigned long long*>(bypass_bits), range_errors, hw,
-                       (int)chunks, pixels);
+    const dim3 grid((unsigned)(n * chunks)), block(LADDER_THREADS);
+    unsigned long long* bypass = reinterpret_cast<unsigned long long*>(bypass_bits);
+    if (thresholds)
+        hipLaunchKernelGGL(ladder_rdo_kernel, grid, block, lds_bytes, (hipStream_t)stream, y, map_mean, bin_widths_points, thresholds,
+                           rdo_amax(length), k_points, length, hist, bypass, range_errors, hw, (int)chunks, pixels);
+    else
+        hipLaunchKernelGGL(ladder_kernel, grid, block, lds_bytes, (hipStream_t)stream, y, map_mean, bin_widths_points, k_points, length, hist,
+                           bypass, range_errors, hw, (int)chunks, pixels);
     EAE_HIP_CHECK_LAUNCH();
     return EAE_HIP_OK;
 }
 
-extern "C" int eae_hip_ladder_histograms_tiles(const float* y, const float* map_mean, const float* bin_widths_points, int k_points,
-                                               int length, uint32_t* hist, uint64_t* bypass_bits, uint32_t* range_errors, int n, int h,
-                                               int w, int th, int tw, void* stream) {
+// thresholds null: ladder_tiles_kernel; else ladder_rdo_tiles_kernel
+int launch_ladder_tiles(const float* y, const float* map_mean, const float* bin_widths_points, const float* thresholds, int k_points,
+                        int length, uint32_t* hist, uint64_t* bypass_bits, uint32_t* range_errors, int n, int h, int w, int th, int tw,
+                        void* stream) {
     if (!y || !bin_widths_points || !hist || n <= 0 || h <= 0 || w <= 0 || th <= 0 || tw <= 0) return EAE_HIP_BAD_ARGUMENT;
     if (length < 1 || length > 255 || k_points < 1 || k_points > eae_hip_ladder_max_points(length)) return EAE_HIP_BAD_ARGUMENT;
     if ((long)h * w > 0x3FFFFFFFL) return EAE_HIP_BAD_SHAPE;       // chunk * per, past the last chunk of a tile, stays an int
@@ -227,9 +323,45 @@ extern "C" int eae_hip_ladder_histograms_tiles(const float* y, const float* map_
     if (items > 0x7FFFFFFFL) return EAE_HIP_BAD_SHAPE;
     const long blocks = items < 2L * cus ? items : 2L * cus;
     const size_t lds_bytes = (size_t)k_points * (length + 3) * EAE_C * 4;
-    hipLaunchKernelGGL(ladder_tiles_kernel, dim3((unsigned)blocks), dim3(LADDER_THREADS), lds_bytes, (hipStream_t)stream, y, map_mean,
-                       bin_widths_points, k_points, length, hist, reinterpret_cast<unsigned long long*>(bypass_bits), range_errors, h, w, th,
-                       tw, (int)tiles_x, (int)nb_tiles, (int)cpt, per, items);
+    const dim3 grid((unsigned)blocks), block(LADDER_THREADS);
+    unsigned long long* bypass = reinterpret_cast<unsigned long long*>(bypass_bits);
+    if (thresholds)
+        hipLaunchKernelGGL(ladder_rdo_tiles_kernel, grid, block, lds_bytes, (hipStream_t)stream, y, map_mean, bin_widths_points, thresholds,
+                           rdo_amax(length), k_points, length, hist, bypass, range_errors, h, w, th, tw, (int)tiles_x, (int)nb_tiles, (int)cpt,
+                           per, items);
+    else
+        hipLaunchKernelGGL(ladder_tiles_kernel, grid, block, lds_bytes, (hipStream_t)stream, y, map_mean, bin_widths_points, k_points, length,
+                           hist, bypass, range_errors, h, w, th, tw, (int)tiles_x, (int)nb_tiles, (int)cpt, per, items);
     EAE_HIP_CHECK_LAUNCH();
     return EAE_HIP_OK;
+}
+}  // namespace
+
+extern "C" int eae_hip_ladder_histograms(const float* y, const float* map_mean, const float* bin_widths_points, int k_points, int length,
+                                         uint32_t* hist, uint64_t* bypass_bits, uint32_t* range_errors, int n, int hw, void* stream) {
+    return launch_ladder(y, map_mean, bin_widths_points, nullptr, k_points, length, hist, bypass_bits, range_errors, n, hw, stream);
+}
+
+extern "C" int eae_hip_ladder_histograms_tiles(const float* y, const float* map_mean, const float* bin_widths_points, int k_points,
+                                               int length, uint32_t* hist, uint64_t* bypass_bits, uint32_t* range_errors, int n, int h,
+                                               int w, int th, int tw, void* stream) {
+    return launch_ladder_tiles(y, map_mean, bin_widths_points, nullptr, k_points, length, hist, bypass_bits, range_errors, n, h, w, th, tw,
+                               stream);
+}
+
+extern "C" int eae_hip_ladder_histograms_rdo(const float* y, const float* map_mean, const float* bin_widths_points,
+                                             const float* thresholds_by_magnitude, int k_points, int length, uint32_t* hist,
+                                             uint64_t* bypass_bits, uint32_t* range_errors, int n, int hw, void* stream) {
+    if (!thresholds_by_magnitude || !aligned_to(thresholds_by_magnitude, 16)) return EAE_HIP_BAD_ARGUMENT;
+    return launch_ladder(y, map_mean, bin_widths_points, thresholds_by_magnitude, k_points, length, hist, bypass_bits, range_errors, n, hw,
+                         stream);
+}
+
+extern "C" int eae_hip_ladder_histograms_rdo_tiles(const float* y, const float* map_mean, const float* bin_widths_points,
+                                                   const float* thresholds_by_magnitude, int k_points, int length, uint32_t* hist,
+                                                   uint64_t* bypass_bits, uint32_t* range_errors, int n, int h, int w, int th, int tw,
+                                                   void* stream) {
+    if (!thresholds_by_magnitude || !aligned_to(thresholds_by_magnitude, 16)) return EAE_HIP_BAD_ARGUMENT;
+    return launch_ladder_tiles(y, map_mean, bin_widths_points, thresholds_by_magnitude, k_points, length, hist, bypass_bits, range_errors, n,
+                               h, w, th, tw, stream);
 }

@@ -506,31 +506,46 @@ def _bypass_bits_of_magnitudes(magnitudes, length):
     return (magnitudes != 0).astype(numpy.int64) + numpy.where(magnitudes >= length, 2*nb_bits + 1, 0)
 
 
-def _wrapped_magnitudes(y, bin_widths, map_mean):
+def _wrapped_magnitudes(y, bin_widths, map_mean, rdo=None):
     """|symbol| of y [N, ..., 128] at a rate point whose int16 symbols have wrapped, recounted on the host with the quantiser's float32
     expressions (numpy divides and rounds as the kernels do) -> numpy (magnitudes int64 [N, hw, 128], 0 where the symbol does not fit
-    int16; good bool [N, hw, 128]: where it does)."""
+    int16; good bool [N, hw, 128]: where it does). rdo: None, or (thresholds float32 [128, 16], length) of the rate-distortion
+    optimised quantiser (ratecontrol.rdo_quantize_numpy)."""
     import numpy
     host = y.reshape(y.shape[0], -1, y.shape[-1]).cpu().numpy()
     bw = bin_widths.cpu().numpy()
     centered = host - (map_mean.cpu().numpy() if map_mean is not None else numpy.float32(0.))
     with numpy.errstate(all='ignore'):
-        rs = numpy.abs(numpy.rint(bw*numpy.rint(centered/bw)/bw))
+        if rdo is None:
+            r = numpy.rint(centered/bw)
+        else:
+            from . import ratecontrol
+            r = ratecontrol.rdo_quantize_numpy(centered, bw, None, rdo[0].cpu().numpy(), rdo[1])
+        rs = numpy.abs(numpy.rint(bw*r/bw))
         good = rs < numpy.float32(32768.)
     return numpy.where(good, rs, 0.).astype(numpy.int64), good
 
 
-def _ladder_point_by_passes(y, bin_widths, map_mean, length):
+def _point_symbols(y, bin_widths, map_mean, rdo):
+    """The quantiser pass of `_ladder_point_by_passes` and `_ladder_point_tiles_by_passes`: `quantize_maps`, or with rdo =
+    (thresholds float32 [128, 16], length) `latent_quantize_rdo` at that one point."""
+    if rdo is None:
+        return quantize_maps(y, bin_widths, map_mean, want_symbols=True)
+    return latent_quantize_rdo(y, bin_widths.reshape(1, -1), rdo[0].reshape(1, NB_MAPS, 16).contiguous(),
+                               torch.zeros(y.shape[0], dtype=torch.int32, device=y.device), rdo[1], map_mean, want_symbols=True)
+
+
+def _ladder_point_by_passes(y, bin_widths, map_mean, length, rdo=None):
     """One rate point by the route `stats.compute_binary_probabilities` takes: `quantize_maps`, `symbol_histograms`, a fold on the
     host -> numpy (hist int64 [N, 128, L + 1], bypass bits int64 [N, 128], range errors). A point with range errors, whose int16
     symbols have wrapped, is recounted on the host with the quantiser's float32 expressions (`_wrapped_magnitudes`), so that the
     arrays are `eae_hip_ladder_histograms`' in every case."""
     import numpy
     (n, c) = (y.shape[0], y.shape[-1])
-    q = quantize_maps(y, bin_widths, map_mean, want_symbols=True)
+    q = _point_symbols(y, bin_widths, map_mean, rdo)
     range_errors = int(q['checks'][0].item())
     if range_errors:
-        (magnitudes, good) = _wrapped_magnitudes(y, bin_widths, map_mean)
+        (magnitudes, good) = _wrapped_magnitudes(y, bin_widths, map_mean, rdo)
         hist = numpy.zeros((n, c, length + 1), dtype=numpy.int64)
         for b in range(length + 1):
             hist[:, :, b] = (good & ((magnitudes == b) if b < length else (magnitudes >= length))).sum(axis=1)
@@ -548,7 +563,7 @@ def _ladder_point_by_passes(y, bin_widths, map_mean, length):
     return hist, bits, 0
 
 
-def _ladder_point_tiles_by_passes(y, bin_widths, map_mean, length, tiles):
+def _ladder_point_tiles_by_passes(y, bin_widths, map_mean, length, tiles, rdo=None):
     """One rate point of `ladder_histograms_tiles` without its kernel: the symbols of `quantize_maps` folded per tile on the host ->
     numpy (hist int64 [N, T, 128, L + 1], bypass bits int64 [N, T, 128], range errors). A point with range errors, whose int16
     symbols have wrapped, is counted from the quantiser's float32 expressions instead (`_wrapped_magnitudes`). y [N, h, w, 128];
@@ -556,10 +571,10 @@ def _ladder_point_tiles_by_passes(y, bin_widths, map_mean, length, tiles):
     import numpy
     (n, h, w, c) = y.shape
     nb_tiles = tiles.shape[0]
-    q = quantize_maps(y, bin_widths, map_mean, want_symbols=True)
+    q = _point_symbols(y, bin_widths, map_mean, rdo)
     range_errors = int(q['checks'][0].item())
     if range_errors:
-        (magnitudes, good) = _wrapped_magnitudes(y, bin_widths, map_mean)
+        (magnitudes, good) = _wrapped_magnitudes(y, bin_widths, map_mean, rdo)
     else:
         magnitudes = numpy.abs(q['symbols'].cpu().numpy().astype(numpy.int64)).transpose(0, 2, 1)          # [N, hw, 128]
         good = numpy.ones(magnitudes.shape, dtype=bool)
@@ -588,8 +603,8 @@ def _ladder_points_checked(bin_widths_points, map_mean, length):
 
 def _ladder_accumulate(y, bin_widths_points, length, out, group, launch, point_by_passes):
     """What `ladder_histograms` (group = ()) and `ladder_histograms_tiles` (group = (T,)) do alike once their arguments are checked:
-    the counts are [N, K] + group + [128, ...]. launch(bin_widths_part, nb_points, hist, bypass_bits, range_errors): the native call
-    for some points of the ladder; point_by_passes(bin_widths): one point folded on the host, as `_ladder_point_by_passes`."""
+    the counts are [N, K] + group + [128, ...]. launch(k0, k1, hist, bypass_bits, range_errors): the native call for the points
+    [k0, k1) of the ladder; point_by_passes(k): point k folded on the host, as `_ladder_point_by_passes`."""
     (n, c, d) = (y.shape[0], y.shape[-1], y.device)
     k_points = bin_widths_points.shape[0]
     if k_points < 1:
@@ -610,7 +625,7 @@ def _ladder_accumulate(y, bin_widths_points, length, out, group, launch, point_b
     most = ladder_max_points(length)
     if most == 0:
         for k in range(k_points):
-            (hist_k, bits_k, errors_k) = point_by_passes(bin_widths_points[k].contiguous())
+            (hist_k, bits_k, errors_k) = point_by_passes(k)
             hist[:, k] += torch.from_numpy(hist_k).to(d).to(torch.int32)
             bypass_bits[:, k] += torch.from_numpy(bits_k).to(d)
             range_errors[k] += errors_k
@@ -620,7 +635,7 @@ def _ladder_accumulate(y, bin_widths_points, length, out, group, launch, point_b
         k1 = min(k0 + most, k_points)
         # a launch writes [N][its points][...]: a part of a longer ladder gets buffers of its own, added into the whole afterwards
         part = out if whole else buffers(k1 - k0, range_errors[k0:k1])
-        launch(bin_widths_points[k0:k1], k1 - k0, *part)
+        launch(k0, k1, *part)
         if not whole:
             hist[:, k0:k1] += part[0]
             bypass_bits[:, k0:k1] += part[1]
@@ -642,12 +657,12 @@ def ladder_histograms(y, bin_widths_points, map_mean=None, length=10, out=None):
         raise HipError('y must be float32 [N, ..., 128]')
     _ladder_points_checked(bin_widths_points, map_mean, length)
 
-    def launch(bin_widths_part, nb_points, hist, bypass_bits, range_errors):
-        _check(_native.hip().eae_hip_ladder_histograms(_p(y), _p(map_mean), _p(bin_widths_part), nb_points, length, _p(hist),
+    def launch(k0, k1, hist, bypass_bits, range_errors):
+        _check(_native.hip().eae_hip_ladder_histograms(_p(y), _p(map_mean), _p(bin_widths_points[k0:k1]), k1 - k0, length, _p(hist),
                                                        _p(bypass_bits), _p(range_errors), n, hw, _stream(y)), 'eae_hip_ladder_histograms')
 
     return _ladder_accumulate(y, bin_widths_points, length, out, (), launch,
-                              lambda bin_widths: _ladder_point_by_passes(y, bin_widths, map_mean, length))
+                              lambda k: _ladder_point_by_passes(y, bin_widths_points[k].contiguous(), map_mean, length))
 
 
 def ladder_histograms_tiles(y, bin_widths_points, coding_tile, map_mean=None, length=10, out=None):
@@ -667,13 +682,85 @@ def ladder_histograms_tiles(y, bin_widths_points, coding_tile, map_mean=None, le
     (th, tw) = (min(th, h), min(tw, w))
     (tiles, _) = container.coding_tile_grid(h, w, (th, tw))
 
-    def launch(bin_widths_part, nb_points, hist, bypass_bits, range_errors):
-        _check(_native.hip().eae_hip_ladder_histograms_tiles(_p(y), _p(map_mean), _p(bin_widths_part), nb_points, length, _p(hist),
+    def launch(k0, k1, hist, bypass_bits, range_errors):
+        _check(_native.hip().eae_hip_ladder_histograms_tiles(_p(y), _p(map_mean), _p(bin_widths_points[k0:k1]), k1 - k0, length, _p(hist),
                                                              _p(bypass_bits), _p(range_errors), n, h, w, th, tw, _stream(y)),
                'eae_hip_ladder_histograms_tiles')
 
     return _ladder_accumulate(y, bin_widths_points, length, out, (tiles.shape[0],), launch,
-                              lambda bin_widths: _ladder_point_tiles_by_passes(y, bin_widths, map_mean, length, tiles))
+                              lambda k: _ladder_point_tiles_by_passes(y, bin_widths_points[k].contiguous(), map_mean, length, tiles))
+
+
+def rdo_thresholds_by_magnitude(thresholds_points):
+    """thresholds_points float32 [K, 128, 16] (ratecontrol.rdo_thresholds) -> the copy [K, 16, 128] `eae_hip_ladder_histograms_rdo`
+    reads (include/eae_hip.h): a codec makes it once and hands it to `ladder_histograms_rdo` with every call."""
+    if thresholds_points.dtype != torch.float32 or thresholds_points.dim() != 3 or tuple(thresholds_points.shape[1:]) != (NB_MAPS, 16):
+        raise HipError('thresholds_points must be float32 [K, 128, 16]')
+    return thresholds_points.transpose(1, 2).contiguous()
+
+
+def _ladder_thresholds_checked(bin_widths_points, thresholds_points, by_magnitude):
+    """The checks of the two tables of `ladder_histograms_rdo` and `ladder_histograms_rdo_tiles` -> the table by magnitude."""
+    k_points = bin_widths_points.shape[0]
+    if thresholds_points.dtype != torch.float32 or tuple(thresholds_points.shape) != (k_points, NB_MAPS, 16):
+        raise HipError('thresholds_points must be float32 [K, 128, 16]')
+    if by_magnitude is None:
+        return rdo_thresholds_by_magnitude(thresholds_points)
+    if by_magnitude.dtype != torch.float32 or tuple(by_magnitude.shape) != (k_points, 16, NB_MAPS) or not by_magnitude.is_contiguous():
+        raise HipError('by_magnitude must be a contiguous float32 [K, 16, 128]')
+    return by_magnitude
+
+
+def ladder_histograms_rdo(y, bin_widths_points, thresholds_points, map_mean=None, length=10, out=None, by_magnitude=None):
+    """`ladder_histograms` of the symbols the rate-distortion optimised quantiser chooses (include/eae_hip.h:
+    eae_hip_ladder_histograms_rdo; the rule is ratecontrol.rdo_quantize_numpy): thresholds_points float32
+    [K, 128, 16] (ratecontrol.rdo_thresholds of the K points). Point k of the result counts the symbols `latent_quantize_rdo` writes
+    with point == k; thresholds of zeros give `ladder_histograms`' words. by_magnitude: `rdo_thresholds_by_magnitude(
+    thresholds_points)`, made once by a caller that launches every step (None: made here, a transposition per call). Everything
+    else, `out` and the routes of a long ladder and of a large L included, as `ladder_histograms`."""
+    n = y.shape[0]
+    c = y.shape[-1]
+    hw = y.numel()//(n*c)
+    length = int(length)
+    if c != NB_MAPS or y.dtype != torch.float32:
+        raise HipError('y must be float32 [N, ..., 128]')
+    _ladder_points_checked(bin_widths_points, map_mean, length)
+    by_magnitude = _ladder_thresholds_checked(bin_widths_points, thresholds_points, by_magnitude)
+
+    def launch(k0, k1, hist, bypass_bits, range_errors):
+        _check(_native.hip().eae_hip_ladder_histograms_rdo(_p(y), _p(map_mean), _p(bin_widths_points[k0:k1]), _p(by_magnitude[k0:k1]),
+                                                           k1 - k0, length, _p(hist), _p(bypass_bits), _p(range_errors), n, hw,
+                                                           _stream(y)), 'eae_hip_ladder_histograms_rdo')
+
+    return _ladder_accumulate(y, bin_widths_points, length, out, (), launch,
+                              lambda k: _ladder_point_by_passes(y, bin_widths_points[k].contiguous(), map_mean, length,
+                                                                (thresholds_points[k], length)))
+
+
+def ladder_histograms_rdo_tiles(y, bin_widths_points, thresholds_points, coding_tile, map_mean=None, length=10, out=None,
+                                by_magnitude=None):
+    """`ladder_histograms_rdo` per coding tile, as `ladder_histograms_tiles` is `ladder_histograms`' (include/eae_hip.h:
+    eae_hip_ladder_histograms_rdo_tiles). y float32 [N, h, w, 128] -> (hist int32 [N, K, T, 128, L + 1], bypass_bits int64
+    [N, K, T, 128], range_errors int32 [K]); summed over T they are `ladder_histograms_rdo`'s on the same input."""
+    if y.dim() != 4 or y.shape[-1] != NB_MAPS or y.dtype != torch.float32:
+        raise HipError('y must be float32 [N, h, w, 128]')
+    (n, h, w, _) = y.shape
+    length = int(length)
+    _ladder_points_checked(bin_widths_points, map_mean, length)
+    by_magnitude = _ladder_thresholds_checked(bin_widths_points, thresholds_points, by_magnitude)
+    from . import container
+    (th, tw) = container._positive_pair(coding_tile, '`coding_tile`')
+    (th, tw) = (min(th, h), min(tw, w))
+    (tiles, _) = container.coding_tile_grid(h, w, (th, tw))
+
+    def launch(k0, k1, hist, bypass_bits, range_errors):
+        _check(_native.hip().eae_hip_ladder_histograms_rdo_tiles(_p(y), _p(map_mean), _p(bin_widths_points[k0:k1]), _p(by_magnitude[k0:k1]),
+                                                                 k1 - k0, length, _p(hist), _p(bypass_bits), _p(range_errors), n, h, w, th,
+                                                                 tw, _stream(y)), 'eae_hip_ladder_histograms_rdo_tiles')
+
+    return _ladder_accumulate(y, bin_widths_points, length, out, (tiles.shape[0],), launch,
+                              lambda k: _ladder_point_tiles_by_passes(y, bin_widths_points[k].contiguous(), map_mean, length, tiles,
+                                                                      (thresholds_points[k], length)))
 
 
 def _ladder_select_checked(hist, bypass_bits, fixed_costs, log2_tables, map_size, budgets, tiled):
@@ -845,14 +932,15 @@ def latent_quantize_rows(y, bin_widths_points, point, map_mean=None, igdn_out=No
 
 
 def latent_quantize_rdo(y, bin_widths_points, thresholds_points, point, truncated_unary_length, map_mean=None, igdn_out=None,
-                        want_shifted=False, want_symbols=True, want_flags=False, out_symbols=None, out_flags=None, out_checks=None):
+                        want_shifted=False, want_symbols=True, want_flags=False, out_symbols=None, out_flags=None, out_checks=None,
+                        want_checks=True, out_shifted=None, out_t=None):
     """`latent_quantize_rows` with the rate-distortion optimised choice of every symbol (include/eae_hip.h:
     eae_hip_latent_quantize_rdo; the rule is ratecontrol.rdo_quantize_numpy): thresholds_points float32
     [K, 128, 16] (ratecontrol.rdo_thresholds), image i takes row point[i] of it as of bin_widths_points. A latent whose nearest
     symbol has magnitude a in [1, min(L, 16)] is coded one step nearer zero when 2 (|x| - a) + 1 < thresholds[k, c, a - 1].
-    Returns `latent_quantize_rows`' dict; with thresholds of zeros, its bits."""
+    Returns `latent_quantize_rows`' dict; with thresholds of zeros, its bits. want_checks, out_shifted, out_t: as there."""
     (n, hw, out) = _quantize_rows_checked(y, bin_widths_points, point, map_mean, igdn_out, want_shifted, want_symbols, want_flags, out_symbols,
-                                          out_flags, out_checks, thresholds_points=thresholds_points)
+                                          out_flags, out_checks, want_checks, out_shifted, out_t, thresholds_points=thresholds_points)
     (g_out, b_out) = igdn_out if igdn_out is not None else (None, None)
     _check(_native.hip().eae_hip_latent_quantize_rdo(_p(y), _p(map_mean), _p(bin_widths_points), _p(thresholds_points), _p(point),
                                                      bin_widths_points.shape[0], int(truncated_unary_length), _p(g_out), _p(b_out),

@@ -46,9 +46,16 @@ _TILE_FIELD_BYTES = 4             # container._TILE_HEADER.size - container._HEA
 class RateLadder(object):
     """K rate points in the caller's order of preference, finest first (no monotonicity is assumed: the selection walks the order).
     bin_widths_points float32 (K, 128); binary_probabilities_points float64 (K, 128, L); map_mean float32 (128,); idx_map_exception:
-    the map coded with a probability row of its own (container.py), -1 for none."""
+    the map coded with a probability row of its own (container.py), -1 for none.
+    rdo_lambda: None, or the price of a bit at every point, in squared latent units per bit as `codec.BatchCodec(rdo_lambda=...)`
+    takes it (DESIGN.md sections 23 and 24): a non-negative finite number, or one per point, array-like (K,) -- c * bw_k**2 keeps the
+    price the same in bins at every point. A rate point is then 128 bin widths, a table and a price: the symbols of every point are
+    those of the rate-distortion optimised quantiser, and whatever chooses a point from this ladder counts, bounds and probes THOSE
+    symbols. `rdo_lambdas` float64 (K,) and `rdo_thresholds_points` float32 (K, 128, 16), row k `rdo_thresholds(bin_widths_points[k],
+    binary_probabilities_points[k], rdo_lambdas[k], idx_map_exception)`; both None without. 0.0 is a ladder with a price, of zero:
+    it takes every launch of one and gives the bytes of None."""
 
-    def __init__(self, bin_widths_points, binary_probabilities_points, map_mean, idx_map_exception=-1):
+    def __init__(self, bin_widths_points, binary_probabilities_points, map_mean, idx_map_exception=-1, rdo_lambda=None):
         for (name, array, dtype, ndim) in (('bin_widths_points', bin_widths_points, numpy.float32, 2),
                                            ('binary_probabilities_points', binary_probabilities_points, numpy.float64, 3),
                                            ('map_mean', map_mean, numpy.float32, 1)):
@@ -77,6 +84,23 @@ class RateLadder(object):
         self.idx_map_exception = int(idx_map_exception) if 0 <= idx_map_exception < nb_maps else -1
         self.nb_points = nb_points
         self.truncated_unary_length = length
+        self.rdo_lambdas = None
+        self.rdo_thresholds_points = None
+        if rdo_lambda is not None:
+            try:
+                lambdas = numpy.array(rdo_lambda, dtype=numpy.float64)
+            except (TypeError, ValueError):
+                raise ValueError('`rdo_lambda` must be None, a number or one number per point.')
+            if isinstance(rdo_lambda, (bool, numpy.bool_)) or lambdas.ndim > 1 or (lambdas.ndim == 1 and lambdas.shape[0] != nb_points):
+                raise ValueError('`rdo_lambda` must be None, a number or one number per point, (K,).')
+            lambdas = numpy.ascontiguousarray(numpy.broadcast_to(lambdas, (nb_points,)))
+            if not numpy.isfinite(lambdas).all() or (lambdas < 0.).any():
+                raise ValueError('`rdo_lambda` must be finite and not negative at every point.')
+            self.rdo_lambdas = lambdas
+            # (rdo_thresholds defined below: looked up when a ladder is made)
+            self.rdo_thresholds_points = numpy.ascontiguousarray(numpy.stack([
+                rdo_thresholds(self.bin_widths_points[k], self.binary_probabilities_points[k], lambdas[k], self.idx_map_exception)
+                for k in range(nb_points)]))
 
 
 def decision_counts(hist):

@@ -480,6 +480,35 @@ int eae_hip_latent_quantize_rdo(const float* y, const float* map_mean, const flo
                                 float* shifted_out, float* t_out, int16_t* symbols_planar, uint32_t* nonzero_flags, uint32_t* checks,
                                 int n, int hw, void* stream);
 
+/* ---- the ladder's counts of the rate-distortion optimised symbols (csrc/hip/ladder.hip; ratecontrol.py) --
+ * eae_hip_ladder_histograms_rdo: eae_hip_ladder_histograms with one more input, the thresholds of the K points, and with `length`
+ * deciding which magnitudes may be lowered. The table arrives BY MAGNITUDE, not in eae_hip_latent_quantize_rdo's layout:
+ *   thresholds_by_magnitude float32 [K][16][128]:  [k][a - 1][c] = ratecontrol.rdo_thresholds(...)[k][c][a - 1], the transposed copy
+ *                                                  of a ladder's (K, 128, 16) table (a lane of the kernel owns a channel: the lanes
+ *                                                  of a wave that hold the same magnitude read 256 contiguous bytes)
+ * Per latent and point k, in IEEE float32 with no contraction, statement for statement eae_hip_latent_quantize_rdo's rule
+ * (ratecontrol.rdo_quantize_numpy): centered = y - mean; x = centered / bw; r = round_half_even(x); a = |r|; u = |x| - a; if
+ * a >= 1 && a <= min(L, 16) (tested in float: a NaN, an infinity or a huge a never indexes the table) and
+ * 2 u + 1 < thresholds_by_magnitude[k][(int)a - 1][c], then r = r - copysign(1, r). From that r on every statement is
+ * eae_hip_ladder_histograms': cq = bw r; rs = round_half_even(cq / bw); the range check, the bin min(|rs|, L), the bypass bits.
+ *   - With thresholds all zero (the comparison is strict) every output word equals eae_hip_ladder_histograms' on the same input.
+ *   - For every k, hist[i][k] is the clipped histogram, and bypass_bits[i][k] the bypass length, of the symbols
+ *     eae_hip_latent_quantize_rdo writes for image i when point[i] == k (given the same table in its own layout).
+ * Outputs, accumulation, the limits on k_points and length and every refusal are eae_hip_ladder_histograms'; a NULL or not 16-byte
+ * aligned thresholds_by_magnitude -> EAE_HIP_BAD_ARGUMENT, before any launch. One launch, the LDS of eae_hip_ladder_histograms (the
+ * table stays in memory): eae_hip_ladder_max_points holds for both. */
+int eae_hip_ladder_histograms_rdo(const float* y, const float* map_mean, const float* bin_widths_points,
+                                  const float* thresholds_by_magnitude, int k_points, int length, uint32_t* hist, uint64_t* bypass_bits,
+                                  uint32_t* range_errors, int n, int hw, void* stream);
+/* The same per coding tile: eae_hip_ladder_histograms_tiles with thresholds_by_magnitude as above. hist uint32
+ * [N][K][T][128][L + 1], bypass_bits uint64 [N][K][T][128] (nullable), range_errors uint32 [K] (nullable), all ACCUMULATED into;
+ * summed over T they are eae_hip_ladder_histograms_rdo's outputs on the same input, and with thresholds all zero every word equals
+ * eae_hip_ladder_histograms_tiles'. Refusals as eae_hip_ladder_histograms_tiles, and a NULL or not 16-byte aligned
+ * thresholds_by_magnitude -> EAE_HIP_BAD_ARGUMENT, before any launch. One launch, at most two blocks per compute unit. */
+int eae_hip_ladder_histograms_rdo_tiles(const float* y, const float* map_mean, const float* bin_widths_points,
+                                        const float* thresholds_by_magnitude, int k_points, int length, uint32_t* hist,
+                                        uint64_t* bypass_bits, uint32_t* range_errors, int n, int h, int w, int th, int tw, void* stream);
+
 /* ---- lossless coder on the device: one feature map per lane --------------------------------------------------------
  * Replaces the per-map compress_lossless loop of lossless/compression.py:76-81 (and, underneath it,
  * lossless/c++/source/compression.cpp:3-65) for a whole batch of images whose symbols are already in HBM
