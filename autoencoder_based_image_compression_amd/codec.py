@@ -175,14 +175,14 @@ class Ticket(object):
         `BatchCodec(emit_container=True)`; before or after `result()`."""
         parts = self._parts()
         return container_format.assemble_blob(*(parts['head'] + (parts['rows'], parts['bits'], parts['payload'])),
-                                              coding_tile=parts['coding_tile'])[0]
+                                              coding_tile=parts['coding_tile'], image_size=parts.get('image_size'))[0]
 
     def image_containers(self):
         """Like `container()`: one single-image `EAE1` (`EAT1`) blob per image of the batch (the payload is image-major: slices of
         the batch's, each behind its own header)."""
         parts = self._parts()
         return container_format.assemble_image_blobs(*(parts['head'] + (parts['rows'], parts['bits'], parts['payload'])),
-                                                     coding_tile=parts['coding_tile'])
+                                                     coding_tile=parts['coding_tile'], image_size=parts.get('image_size'))
 
 
 class ContainerOverflow(RuntimeError):
@@ -355,6 +355,7 @@ class _StepWorker(threading.Thread):
 
 class _Worker(_StepWorker):
     """The result worker of `BatchCodec`."""
+    image_size = None       # of a codec that pads (`BatchCodec(pad=True)`): the real size its containers carry
 
     def __init__(self, map_size, nb_maps, host_probabilities, idx_map_exception, host_threads, coding_tile=None, payload_order=None):
         """coding_tile, payload_order: of a codec that codes in tiles (`coding_tile_layout`): the slot's results are in run order,
@@ -484,6 +485,7 @@ class _Worker(_StepWorker):
                 ticket._values['container_bytes'] = index[2:].astype(numpy.int64)
                 ticket._container_parts = {
                     'head': head, 'capacity': capacity, 'payload_bytes': payload_bytes, 'error': container_error, 'coding_tile': self.coding_tile,
+                    'image_size': self.image_size,
                     'rows': rows.copy() if self.idx_map_exception >= 0 else rows[:0].copy(),
                     'bits': numpy.stack([results[0], results[1]], axis=1).astype(numpy.uint32),
                     'payload': payload[:payload_bytes].tobytes() if int(index[1]) == 0 else None}
@@ -511,7 +513,7 @@ def default_nb_in_flight(h_in, w_in):
     images of 256x256 (maps of 256 symbols: short chains, short steps) lose 10 % with five against three; a 2048x2048 image
     has maps of 16,384 symbols and needs eight. Round 5, on the shorter chains of that round's cores (profiles/r05_coder_waves_per_block.log):
     six against five for Kodak-sized maps is equal within noise up to 2 bpp and 2 % ahead at 3.2 bpp (seven no better), so: six."""
-    map_size = (h_in//csts.STRIDE_PROD)*(w_in//csts.STRIDE_PROD)
+    map_size = (-(-h_in//csts.STRIDE_PROD))*(-(-w_in//csts.STRIDE_PROD))      # of the coded size (`BatchCodec(pad=True)`: any h_in, w_in)
     return int(min(8, 3 + map_size//512))
 
 
@@ -694,7 +696,7 @@ class _Slot(object):
         self.free.set()
         self.pinned_symbols = torch.empty((batch_size, nb_maps, codec.map_size), dtype=torch.int16).pin_memory() if codec.coder == 'host' else None
         self.staging = None          # device copy of a host batch (made at the slot's first host batch)
-        self.pinned_rec = (torch.empty((batch_size, codec.h_in, codec.w_in), dtype=torch.uint8).pin_memory()
+        self.pinned_rec = (torch.empty((batch_size, codec.h_image, codec.w_image), dtype=torch.uint8).pin_memory()
                            if codec.fetch_reconstruction else None)
         self.graphs = None           # (graphs, static input, latents, reconstruction) once captured (`BatchCodec._capture_all`)
         self.emit_host = None
@@ -728,7 +730,7 @@ class BatchCodec(object):
                  batch_size, h_in, w_in, device='cuda', nb_in_flight=None, keep_reconstruction=False, launch_hook=None,
                  coder='device', host_coder_threads=0, hist_radius=2047, nb_transform_streams=1, use_graphs=False,
                  time_coder=False, fuse_latent=False, fetch_reconstruction=False, coder_chunks=None, one_stream_steps=False,
-                 emit_container=False, container_capacity_bytes=None, coding_tile=None, rdo_lambda=None):
+                 emit_container=False, container_capacity_bytes=None, coding_tile=None, rdo_lambda=None, pad=False):
         """coder: 'device' (the coder kernels on side streams), 'host' (ONE device -> host copy of the symbols per batch, then
         the host C-ABI coder `eae_coder_compress_maps` on `host_coder_threads` threads: the shape BASELINE.json sketches) or
         'none' (transforms only; the bit counts come back as zeros).
@@ -776,9 +778,21 @@ class BatchCodec(object):
         rate-distortion optimised quantiser instead of by nearest rounding: conv_3, gdn_3 as a launch of its
         own, then `device.latent_quantize_rdo` with `ratecontrol.rdo_thresholds` of this rate point. Everything behind the symbols is
         unchanged and `result()` has the same keys; the containers are byte for byte `container.encode_images(..., rdo_lambda=...)`.
-        0.0 gives the results of None. Not with `fuse_latent` or the host coder."""
+        0.0 gives the results of None. Not with `fuse_latent` or the host coder.
+        pad: h_in x w_in is the REAL size of the images, any positive integers. `submit` takes
+        (batch_size, h_in, w_in); the step runs at the coded size -- both sides rounded up to multiples of 16 -- on the batch
+        extended by edge replication (`device.frame_pad_u8`, one launch in front of the analysis transform: on the graph path where the
+        batch is copied into the step's static input), in every mode above. `result()` has the same keys and, 'sse' apart, the values
+        of the same codec at the coded size on the numpy-edge-padded batch; 'sse' is over the real pixels (`device.frame_sse_u8`
+        behind transpose_conv_3, which then skips its fused error). The containers carry the real size in their `crop` byte: byte for
+        byte `container.encode_images(..., pad=True)`. `Ticket.reconstruction_uint8` / `reconstruction_host` are (batch_size, h_in,
+        w_in), the top-left of the coded planes. `h_in`, `w_in` of the codec are the coded size then, `h_image`, `w_image` the real."""
         if coder not in ('device', 'host', 'none'):
             raise ValueError('`coder` is neither "device" nor "host" nor "none".')
+        self.pad = bool(pad)
+        (self.h_image, self.w_image) = (h_in, w_in)
+        if self.pad:
+            (h_in, w_in) = container_format.coded_size(container_format._positive_int(h_in, '`h_in`'), container_format._positive_int(w_in, '`w_in`'))
         self.rdo_lambda = None
         if rdo_lambda is not None:
             # refused in front of every allocation
@@ -844,6 +858,9 @@ class BatchCodec(object):
         # the parts of a step's container that no step changes (container.assemble_blob's leading arguments)
         self._container_head = (bool(are_bin_widths_learned), batch_size, h_in, w_in, self.idx_map_exception, bin_widths_host.copy(),
                                 map_mean_host.copy(), probabilities.copy())
+        # with `pad`: the dense real-size copy of the batch a replayed step's squared error is taken against, one per slot, made at the
+        # capture (`_capture_all`) -- the codec's, not the slots': a slot holds what every mode needs
+        self._frame_references = None
         self.bin_widths = torch.from_numpy(bin_widths_host).to(self.device)
         self.map_mean = torch.from_numpy(map_mean_host).to(self.device)
         self.probabilities = torch.from_numpy(probabilities).to(self.device)
@@ -936,6 +953,8 @@ class BatchCodec(object):
         # last but one: a constructor that raised above has no worker yet, and `close()` has nothing to wait for
         self._worker = self._worker_class(self.map_size, self.nb_maps, probabilities if coder == 'host' else None, self.idx_map_exception,
                                host_coder_threads, self.coding_tile, self._tile_layout['payload_order'] if self._tile_layout else None)
+        if self.pad:
+            self._worker.image_size = (self.h_image, self.w_image)
         self._worker.start()
         # last: a constructor that raised above leaves nothing half-built behind for another codec's `_capture_all` to drain
         with _LIVE_LOCK:
@@ -947,7 +966,7 @@ class BatchCodec(object):
         stream of the codec's own (`Ticket.fed_event` is recorded behind the copy: leave the batch alone until then)."""
         if luminances_uint8.dtype != torch.uint8:
             raise TypeError('`luminances_uint8.dtype` is not equal to `torch.uint8`.')
-        if tuple(luminances_uint8.shape) != (self.batch_size, self.h_in, self.w_in):
+        if tuple(luminances_uint8.shape) != (self.batch_size, self.h_image, self.w_image):
             raise ValueError('`luminances_uint8.shape` is not (batch_size, h_in, w_in).')
         if self._worker.failed is not None:
             raise StepTimeout('this codec stopped taking batches: {0}'.format(self._worker.failed))
@@ -1016,6 +1035,8 @@ class BatchCodec(object):
             if not sequence_mode or self.keep_reconstruction:
                 ticket.decoded_event = torch.cuda.Event()
             reconstruction = (self._replay_step if replay else self._launch_step)(luminances_uint8, slot, index, ticket, coded)
+            if self.pad:
+                reconstruction = reconstruction[:, :self.h_image, :self.w_image]      # a view: the top-left of the coded planes
             if self.keep_reconstruction:
                 ticket.reconstruction_uint8 = reconstruction       # valid until this slot comes round again
             job = _Job(ticket, () if sequence_mode else (coded, ticket.decoded_event), slot.host_views, slot.pinned_symbols, slot.free,
@@ -1045,11 +1066,15 @@ class BatchCodec(object):
         # (`with torch.cuda.stream(...)` costs three device-index resolutions per entry and exit) and restored in the `finally`
         try:
             torch.cuda.set_stream(stream)
+            # (with `pad` the batch goes into the slot's real-size reference, and the pad kernel fills the static input from it)
+            batch_input = self._frame_references[index % self.nb_slots] if self.pad else static_input
             if luminances_uint8.device.type == 'cpu':
-                ticket.fed_event = self._feed(luminances_uint8, static_input)
+                ticket.fed_event = self._feed(luminances_uint8, batch_input)
             else:
                 stream.wait_stream(caller)
-                static_input.copy_(luminances_uint8, non_blocking=True)
+                batch_input.copy_(luminances_uint8, non_blocking=True)
+            if self.pad:
+                dev.frame_pad_u8(batch_input, out=static_input)
             graphs[0].replay()
             if self.one_stream_steps:
                 if coded is not None:                         # the whole step is graphs[0]: both of the worker's events behind it
@@ -1087,17 +1112,22 @@ class BatchCodec(object):
         for other in others:
             other.drain()
         torch.cuda.synchronize(self.device)
+        if self.pad:
+            self._frame_references = [torch.empty((self.batch_size, self.h_image, self.w_image), dtype=torch.uint8, device=self.device)
+                                      for _ in self._slots]
         for (number, slot) in enumerate(self._slots):
             # any of the codec's streams will do for the capture: a replay runs on the stream it is launched into, which
             # `_replay_step` picks from the submission index (slots and streams go round at different periods)
             stream = self._transform_streams[number % len(self._transform_streams)]
             coder_stream = self._streams[number % len(self._streams)] if self._streams else None
-            static_input = torch.empty(tuple(like.shape), dtype=torch.uint8, device=self.device)      # `like` may be a host batch
+            static_input = torch.empty((self.batch_size, self.h_in, self.w_in), dtype=torch.uint8, device=self.device)
+            # what the synthesis side takes its squared error against: the static input itself, with `pad` the real-size batch
+            reference = self._frame_references[number] if self.pad else static_input
             if self.one_stream_steps:
                 graphs = [torch.cuda.CUDAGraph()]
                 with torch.cuda.graph(graphs[0], stream=stream, capture_error_mode='thread_local'):
                     latents = self._launch_analysis(static_input, slot, _no_hook)
-                    reconstruction = self._launch_synthesis(latents, static_input, slot, _no_hook)
+                    reconstruction = self._launch_synthesis(latents, reference, slot, _no_hook)
                     self._launch_coder(slot)
                 slot.graphs = (graphs, static_input, latents, reconstruction)
                 continue
@@ -1109,7 +1139,7 @@ class BatchCodec(object):
             with torch.cuda.graph(graphs[1], stream=coder_stream, capture_error_mode='thread_local'):
                 self._launch_coder(slot)
             with torch.cuda.graph(graphs[2], stream=stream, capture_error_mode='thread_local'):
-                reconstruction = self._launch_synthesis(latents, static_input, slot, _no_hook, head_done=self._coder_behind_tconv1)
+                reconstruction = self._launch_synthesis(latents, reference, slot, _no_hook, head_done=self._coder_behind_tconv1)
             slot.graphs = (graphs, static_input, latents, reconstruction)
 
     def _launch_step(self, luminances_uint8, slot, index, ticket, coded):
@@ -1121,10 +1151,11 @@ class BatchCodec(object):
         if luminances_uint8.device.type == 'cpu':
             fresh = slot.staging is None
             if fresh:
-                slot.staging = torch.empty((self.batch_size, self.h_in, self.w_in), dtype=torch.uint8, device=self.device)
+                slot.staging = torch.empty((self.batch_size, self.h_image, self.w_image), dtype=torch.uint8, device=self.device)
             ticket.fed_event = self._feed(luminances_uint8, slot.staging, fresh)
             luminances_uint8 = slot.staging
-        latents = self._launch_analysis(luminances_uint8, slot, hook)
+        # with `pad` the transforms see the batch extended to the coded size (an allocator temporary), the squared error the batch itself
+        latents = self._launch_analysis(dev.frame_pad_u8(luminances_uint8) if self.pad else luminances_uint8, slot, hook)
         head_done = self._coder_behind_tconv1 and not self.one_stream_steps
         if head_done:
             latents = self._launch_synthesis_head(latents, slot, hook)
@@ -1291,14 +1322,20 @@ class BatchCodec(object):
 
     def _launch_synthesis(self, latents, luminances_uint8, slot, hook, head_done=False):
         """tconv1+IGDN5 -> tconv2+IGDN6 -> tconv3 + BT.601 cast + squared error against the input, and the publication of the
-        squared errors, on the current stream. Returns the uint8 reconstruction. head_done: `latents` is already tconv1's output."""
+        squared errors, on the current stream. Returns the uint8 reconstruction. head_done: `latents` is already tconv1's output.
+        luminances_uint8: what the error is taken against; with `pad` the real-size batch (the reconstruction is of the coded size)."""
         dec = self.decoder
         d = dec.v
         ws = slot.conv_ws
         t = latents if head_done else self._launch_synthesis_head(latents, slot, hook)
         t = hook('tconv2_igdn6', lambda: dev.tconv5x5s2(t, dec.w5, d['decoder/biases_5'], dev.NORM_IGDN, dec.g[6], d['decoder/beta_6'], workspace=ws))
-        (_, reconstruction, _) = hook('tconv3', lambda: dev.tconv9x9s4_luma(t, dec.w6, want_f32=False, want_u8=True, ref_u8=luminances_uint8,
-                                                                            sse=slot.sse[:self.batch_size]))
+        if self.pad:
+            # the error over the real pixels only: transpose_conv_3 without its fused error, then one launch over the top-left h x w
+            (_, reconstruction, _) = hook('tconv3', lambda: dev.tconv9x9s4_luma(t, dec.w6, want_f32=False, want_u8=True))
+            dev.frame_sse_u8(reconstruction, luminances_uint8, out=slot.sse[:self.batch_size])
+        else:
+            (_, reconstruction, _) = hook('tconv3', lambda: dev.tconv9x9s4_luma(t, dec.w6, want_f32=False, want_u8=True, ref_u8=luminances_uint8,
+                                                                                sse=slot.sse[:self.batch_size]))
         # every conv launch of this step (analysis side too: same stream, same workspace) is behind us: its error word, and a
         # clean workspace for the slot's next step
         dev.publish_step(slot.sse, slot.pinned_sse, 0, *slot.synthesis_seq, conv_ws=ws, error_word=slot.unfinished)
@@ -1382,7 +1419,7 @@ def decode_head_views(head, batch_size, nb_maps, truncated_unary_length, n_strea
 
 
 def plan_decode_step(blobs, batch_size, h_in, w_in, truncated_unary_length, are_bin_widths_learned, capacity, head, payload,
-                     nb_maps=csts.NB_MAPS_3, coding_tile=None, layout=None):
+                     nb_maps=csts.NB_MAPS_3, coding_tile=None, layout=None, image_size=None):
     """The host side of one `BatchDecoder` step; numpy only. blobs: one `EAE1` blob or a sequence of them, 1..batch_size images in
     all, in the order of the step's images. Every header is parsed and checked (`container.read_header`, then the decoder's own
     height, width, truncated unary length and model kind, the number of images, the payload against `capacity`) BEFORE a byte of
@@ -1398,6 +1435,8 @@ def plan_decode_step(blobs, batch_size, h_in, w_in, truncated_unary_length, are_
     The other fields and the payload are as without tiles: payload order is image-major, so blobs one behind the other are images one
     behind the other. layout: `coding_tile_layout(batch_size, h_in/16, w_in/16, coding_tile)` when the caller has it (it is the same
     for every step: its clamped tile is then the step's, and `coding_tile` is not looked at again), else it is computed here.
+    h_in, w_in: the CODED size. image_size: None, or the real (h, w) of a decoder that crops (`BatchDecoder(pad=True)`): every blob's
+    real size (its header's `crop` byte, container.py) must be that one -- without it the coded size, i.e. a crop of 0.
     -> (images, payload bytes)."""
     if isinstance(blobs, (bytes, bytearray, memoryview)):
         blobs = [blobs]
@@ -1418,6 +1457,11 @@ def plan_decode_step(blobs, batch_size, h_in, w_in, truncated_unary_length, are_
         if (header['height'], header['width']) != (h_in, w_in):
             raise ValueError('The container holds {0} x {1} images, the decoder was built for {2} x {3}.'.format(
                 header['height'], header['width'], h_in, w_in))
+        if (header['image_height'], header['image_width']) != ((h_in, w_in) if image_size is None else tuple(image_size)):
+            raise ValueError('The container holds images of {0} x {1} pixels inside its {2} x {3} planes (the `crop` byte of its header), '
+                             'the decoder {4}.'.format(header['image_height'], header['image_width'], h_in, w_in,
+                                                       'does not crop (`BatchDecoder(..., pad=True)` does)' if image_size is None else
+                                                       'was built for {0} x {1}'.format(*image_size)))
         if header['truncated_unary_length'] != truncated_unary_length:          # (`read_header` has refused anything but `nb_maps` maps)
             raise ValueError('The container was coded with a truncated unary length of {0}, the decoder was built for {1}.'.format(
                 header['truncated_unary_length'], truncated_unary_length))
@@ -1744,9 +1788,10 @@ class BatchDecoder(object):
     computes (same bytes), with every buffer made once, the host work of a step in `plan_decode_step`, and the step as one chain of
     launches on one of `nb_streams` private streams (one hipGraph per slot with `use_graphs`). DESIGN.md section 14. With
     `coding_tile`: the same for the tile-indexed `EAT1` containers of that coding tile (section 16)."""
+    (pad, image_size) = (False, None)      # `BatchDecoder(pad=True)`; a `RegionDecoder` never crops to a real size
 
     def __init__(self, variables, are_bin_widths_learned, batch_size, h_in, w_in, truncated_unary_length, device='cuda', nb_in_flight=None,
-                 nb_streams=None, use_graphs=False, payload_capacity_bytes=None, fetch_reconstruction=True, coding_tile=None):
+                 nb_streams=None, use_graphs=False, payload_capacity_bytes=None, fetch_reconstruction=True, coding_tile=None, pad=False):
         """nb_streams: consecutive steps go round that many private streams, so that one step's serial decoder core runs beside
         another step's synthesis transform. nb_in_flight: steps that may be pending at once (= slots: pinned buffers and planes).
         None: `DECODER_STREAMS` streams, or as many of them as the process's hardware queues allow (`stream_budget`; streams asked
@@ -1759,8 +1804,19 @@ class BatchDecoder(object):
         `BatchCodec(emit_container=True, coding_tile=(th, tw))` and `container.encode_images(..., coding_tile=(th, tw))` write --
         and nothing else: an `EAE1` blob or another tile is refused by `submit` (ValueError). Every (image, tile, map) is a pair of
         streams of its own, so the decoder core's serial chains are a tile long instead of a map. At most 65,535 (image, tile) pairs
-        per step. None: `EAE1` blobs only."""
+        per step. None: `EAE1` blobs only.
+        pad: h_in x w_in is the REAL size of the images, any positive integers: the decoder takes the blobs
+        whose coded size is that size rounded up to multiples of 16 and whose `crop` byte gives exactly it -- what
+        `container.encode_images(..., pad=True)` and `BatchCodec(..., pad=True)` write --, refuses every other (`plan_decode_step`), and
+        `result()` is uint8 (n, h_in, w_in), the top-left of the coded planes, cut by `device.publish_crops` at the end of the step
+        (into pinned memory with `fetch_reconstruction`). A decoder without `pad` refuses a blob whose `crop` is not 0."""
+        (self.pad, self.image_size) = (bool(pad), None)
+        if self.pad:
+            self.image_size = (container_format._positive_int(h_in, '`h_in`'), container_format._positive_int(w_in, '`w_in`'))
+            (h_in, w_in) = container_format.coded_size(*self.image_size)
         self._lay_out(batch_size, h_in, w_in, truncated_unary_length, payload_capacity_bytes, coding_tile)
+        if self.pad:
+            self.region = self.image_size          # what a slot cuts out of its planes for the ticket (`_DecodeSlot`), at the origin
         self._build(variables, are_bin_widths_learned, device, nb_in_flight, nb_streams, use_graphs, fetch_reconstruction)
 
     def _lay_out(self, batch_size, h_in, w_in, truncated_unary_length, payload_capacity_bytes, coding_tile):
@@ -1832,6 +1888,9 @@ class BatchDecoder(object):
             half_stride = numpy.array([dev.coder_stream_stride_bytes(int(tiled['tiles'][t, 2]*tiled['tiles'][t, 3]), self.truncated_unary_length)//2
                                        for (_, t) in tiled['entries']], dtype=numpy.int64)
             self._tile_table = torch.from_numpy(numpy.stack([tiled['run_entry'], half_stride], axis=1)).to(self.device)
+        if self.pad:
+            # `device.publish_crops`: every image's crop starts at (0, 0)
+            self._crop_origins = torch.zeros((self.batch_size, 2), dtype=torch.int32, device=self.device)
 
     def submit(self, blobs):
         """One `EAE1` blob of 1..batch_size images, or a sequence of `EAE1` blobs holding that many in all -> DecodeTicket
@@ -1896,7 +1955,7 @@ class BatchDecoder(object):
         Raises ValueError, with the slot untouched, for a step it refuses."""
         (nb_images, payload_bytes) = plan_decode_step(blobs, self.batch_size, self.h_in, self.w_in, self.truncated_unary_length, self.learned,
                                                       self.payload_capacity_bytes, slot.head_host, slot.payload_host, self.nb_maps,
-                                                      self.coding_tile, self._tile_layout)
+                                                      self.coding_tile, self._tile_layout, self.image_size)
         return nb_images, payload_bytes, self._image_ranges[:nb_images]
 
     def _capture_all(self):
@@ -1951,7 +2010,10 @@ class BatchDecoder(object):
 
     def _launch_output(self, slot):
         """The second half of a step, behind the synthesis transform: what the ticket returns reaches the host (if it is to)."""
-        if slot.pinned_rec is not None:
+        if self.pad:
+            (h, w) = self.image_size
+            dev.publish_crops(slot.planes, self._crop_origins, slot.pinned_crops if slot.pinned_crops is not None else slot.crops, h, w)
+        elif slot.pinned_rec is not None:
             dev.publish_to_host(slot.planes, slot.pinned_rec)
 
     def drain(self):
@@ -1999,6 +2061,10 @@ class RegionSource(object):
         (self.header, self._blob) = container_format._source_header(source)
         self._source = source
         header = self.header
+        if (header['image_height'], header['image_width']) != (header['height'], header['width']):
+            raise ValueError('The source holds images of {0} x {1} pixels inside {2} x {3} planes (the `crop` byte of its header): '
+                             '`RegionSource` / `RegionDecoder` do not crop to a real size; `container.decode_region` does.'.format(
+                                 header['image_height'], header['image_width'], header['height'], header['width']))
         (self.h_map, self.w_map) = (header['height']//csts.STRIDE_PROD, header['width']//csts.STRIDE_PROD)
         (tile, bits) = container_format._tile_layout(header)
         self.coding_tile = (min(tile[0], self.h_map), min(tile[1], self.w_map))          # clamped, as `coding_tile_grid` cuts the plane
@@ -2458,6 +2524,9 @@ class BudgetCodec(BatchCodec):
         if options.get('rdo_lambda') is not None:
             raise ValueError('The rate-control codecs do not take `rdo_lambda`: the price of a bit comes with the ladder '
                              '(`ratecontrol.RateLadder(..., rdo_lambda=...)`), a point at a time.')
+        if options.get('pad'):
+            raise ValueError('The rate-control codecs do not take `pad`: their bounds and probes are over the coded plane, and a PSNR floor '
+                             'would need the real pixel count (DESIGN.md section 25). `BatchCodec(..., pad=True)` pads.')
         if options.get('coder', 'device') != 'device':
             raise ValueError('`BudgetCodec` needs the coder on the device.')
         chunks = options.get('coder_chunks')

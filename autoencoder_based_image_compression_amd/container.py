@@ -10,7 +10,7 @@ The reconstruction is bit-identical to the in-memory path's (tests/test_containe
 
 Layout (little endian):
     magic 'EAE1' | version u16 | flags u16 (bit 0: learned bin widths) | nb_images u32 | height u32 | width u32 |
-    nb_maps u16 | L u8 | reserved u8 | idx_map_exception i32
+    nb_maps u16 | L u8 | crop u8 | idx_map_exception i32
     bin_widths f32[nb_maps] | map_mean f32[nb_maps] | binary_probabilities f64[nb_maps][L]
     exception_probabilities f64[nb_images][L]              (only when idx_map_exception >= 0)
     bit counts u32[nb_images * nb_maps][2]                 (arithmetic-coded stream, bypass stream)
@@ -25,7 +25,7 @@ map is cut into a plain grid of coding tiles of th x tw latents (edge tiles smal
 tile, map) is coded as its own pair of streams, the symbols of the tile in raster order. The probabilities are static, so a
 tile's stream costs its share of the whole map's bits plus its own termination and byte padding. The exception map keeps one
 probability row per image, measured on the whole map. Layout (little endian):
-    magic 'EAT1' | version u16 (= 1) | flags u16 | nb_images u32 | height u32 | width u32 | nb_maps u16 | L u8 | reserved u8 |
+    magic 'EAT1' | version u16 (= 1) | flags u16 | nb_images u32 | height u32 | width u32 | nb_maps u16 | L u8 | crop u8 |
     idx_map_exception i32 | coding_tile_h u16 | coding_tile_w u16                       (tile sides in latents)
     bin_widths f32[nb_maps] | map_mean f32[nb_maps] | binary_probabilities f64[nb_maps][L]
     exception_probabilities f64[nb_images][L]              (only when idx_map_exception >= 0)
@@ -39,6 +39,15 @@ One path serves both formats: EAE1 is the case coding tile = (h, w), one tile pe
 either magic and `_read_arrays` reads what follows (`read_header`, `fetch_region`); `_pack_header` writes it; `_encode_entries` codes
 and `_decode_entries` decodes groups of (image, tile) entries. An EAE1 blob is one group of whole maps, coded where the quantiser
 left the symbols.
+
+Images of any height and width. The transforms take sides that are multiples of 16, so an h x w image is
+coded at (H, W) = (h, w) rounded up to multiples of 16. `height` / `width` of both headers are that CODED size: latent planes, tile
+grids, header length, capacities and byte ranges all derive from them as before. Byte 23 of both fixed headers, `crop`, holds what a
+decoder cuts off: (H - h) << 4 | (W - w), two nibbles 0..15 (any value is valid: H, W >= 16). It was a reserved byte, written as 0
+and never read: crop == 0 is that blob, byte for byte, and there is no new version. `read_header` gives the real size as
+'image_height' / 'image_width'. How the encoder fills the H x W plane outside the image is its own business -- `encode_images(...,
+pad=True)` replicates the last row and column (device.frame_pad_u8) -- since a decoder only crops: `decode_images` returns h x w,
+and the regions of `decode_region` / `fetch_region` / `region_plan` are in real-image coordinates, inside h x w.
 """
 import math
 import numbers
@@ -96,9 +105,12 @@ def _raise_for_statuses(results):
 
 
 def _fields(are_bin_widths_learned, nb_images, height, width, idx_map_exception, bin_widths, map_mean, binary_probabilities,
-            exception_rows, coding_tile=None):
-    """The header of a blob to write, under `read_header`'s keys (no 'bits', no 'payload_offset'); EAT1 with a coding tile."""
-    fields = {'nb_images': nb_images, 'height': height, 'width': width, 'nb_maps': binary_probabilities.shape[0],
+            exception_rows, coding_tile=None, image_size=None):
+    """The header of a blob to write, under `read_header`'s keys (no 'bits', no 'payload_offset'); EAT1 with a coding tile.
+    height, width: the coded size; image_size: None, or the real (h, w) it is the coded size of (module docstring: `crop`)."""
+    (image_height, image_width) = (height, width) if image_size is None else _image_size(image_size, height, width)
+    fields = {'nb_images': nb_images, 'height': height, 'width': width, 'image_height': image_height, 'image_width': image_width,
+              'nb_maps': binary_probabilities.shape[0],
               'truncated_unary_length': binary_probabilities.shape[1], 'idx_map_exception': idx_map_exception,
               'are_bin_widths_learned': bool(are_bin_widths_learned), 'bin_widths': bin_widths, 'map_mean': map_mean,
               'binary_probabilities': binary_probabilities, 'exception_probabilities': exception_rows}
@@ -107,10 +119,24 @@ def _fields(are_bin_widths_learned, nb_images, height, width, idx_map_exception,
     return fields
 
 
+def coded_size(height, width):
+    """The size an image of height x width is coded at: both sides rounded up to multiples of 16 (module docstring)."""
+    return dev.coded_size(height, width)
+
+
+def _image_size(image_size, height, width):
+    """A real size (h, w) to write into a header of coded size height x width."""
+    image_size = _positive_pair(image_size, '`image_size`')
+    if coded_size(*image_size) != (height, width):
+        raise ValueError('{} x {} is not the coded size of a {} x {} image.'.format(height, width, *image_size))
+    return image_size
+
+
 def _pack_header(fields, bits):
     """Everything in front of the payload (module docstring), as bytes: what `read_header` parses. bits uint32, in payload order."""
+    crop = (fields['height'] - fields['image_height']) << 4 | (fields['width'] - fields['image_width'])
     common = (1 if fields['are_bin_widths_learned'] else 0, fields['nb_images'], fields['height'], fields['width'], fields['nb_maps'],
-              fields['truncated_unary_length'], 0, fields['idx_map_exception'])
+              fields['truncated_unary_length'], crop, fields['idx_map_exception'])
     if fields.get('format') == 'EAT1':
         head = _TILE_HEADER.pack(TILE_MAGIC, TILE_VERSION, *(common + tuple(fields['coding_tile'])))
     else:
@@ -130,13 +156,15 @@ def _clamped_coding_tile(coding_tile, height, width):
 
 
 def assemble_blob(are_bin_widths_learned, nb_images, height, width, idx_map_exception, bin_widths, map_mean, binary_probabilities,
-                  exception_rows, bits, payload, coding_tile=None):
+                  exception_rows, bits, payload, coding_tile=None, image_size=None):
     """The EAE1 blob (module docstring) from its parts -> (blob bytes, header bytes). bin_widths / map_mean float32 [nb_maps],
     binary_probabilities float64 [nb_maps, L], exception_rows float64 [nb_images, L] ([0, L] without an exception map), bits
     uint32 [nb_images*nb_maps, 2], payload bytes-like. What a `codec.Ticket` builds its containers with from the pinned blocks of
     its step; `encode_images` packs the same header.
     coding_tile=(th, tw) latents (clamped to the latent plane as `encode_images` clamps it): the EAT1 blob instead; bits uint32
-    [nb_images*nb_tiles*nb_maps, 2] in payload order (image -> tile, row-major -> map)."""
+    [nb_images*nb_tiles*nb_maps, 2] in payload order (image -> tile, row-major -> map).
+    height, width: the CODED size; image_size=(h, w): the real size it is the coded size of, written as the header's `crop` byte
+    (None: the coded size, crop 0)."""
     (nb_maps, truncated_unary_length) = binary_probabilities.shape
     nb_rows = nb_images if idx_map_exception >= 0 else 0
     nb_tiles = 1
@@ -152,12 +180,12 @@ def assemble_blob(are_bin_widths_learned, nb_images, height, width, idx_map_exce
     if len(payload) != int(_entry_bytes(bits.reshape(nb_images*nb_tiles, nb_maps, 2)).sum()):
         raise ValueError('The payload size does not match the bit counts.')
     header = _pack_header(_fields(are_bin_widths_learned, nb_images, height, width, idx_map_exception, bin_widths, map_mean,
-                                  binary_probabilities, exception_rows, coding_tile), bits)
+                                  binary_probabilities, exception_rows, coding_tile, image_size), bits)
     return (header + bytes(payload), len(header))
 
 
 def assemble_image_blobs(are_bin_widths_learned, nb_images, height, width, idx_map_exception, bin_widths, map_mean, binary_probabilities,
-                         exception_rows, bits, payload, coding_tile=None):
+                         exception_rows, bits, payload, coding_tile=None, image_size=None):
     """The parts of a batch's blob (`assemble_blob`) -> one single-image blob per image: the payload is image-major, so an image's
     blob is its slice of the bit counts, of the exception rows and of the payload behind a header of its own."""
     nb_maps = binary_probabilities.shape[0]
@@ -170,12 +198,12 @@ def assemble_image_blobs(are_bin_widths_learned, nb_images, height, width, idx_m
         rows = exception_rows[i:i + 1] if idx_map_exception >= 0 else exception_rows
         blobs.append(assemble_blob(are_bin_widths_learned, 1, height, width, idx_map_exception, bin_widths, map_mean, binary_probabilities,
                                    rows, bits[i*per_image:(i + 1)*per_image], view[int(stops[i] - image_bytes[i]):int(stops[i])],
-                                   coding_tile)[0])
+                                   coding_tile, image_size)[0])
     return blobs
 
 
 def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_probabilities, idx_map_exception=-1, tile=None,
-                  coding_tile=None, tiles_per_call=TILES_PER_CALL, rdo_lambda=None):
+                  coding_tile=None, tiles_per_call=TILES_PER_CALL, rdo_lambda=None, pad=False):
     """uint8 (N, H, W) or (N, H, W, 1) luminance images -> (blob bytes, info dict).
 
     encoder: pipeline.DeviceEncoder of the model; bin_widths_test float32 (128,) (the trained bin widths times the
@@ -190,6 +218,11 @@ def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_p
     optimised quantiser (device.latent_quantize_rdo with ratecontrol.rdo_thresholds of this rate point)
     instead of by nearest rounding. The blob is an ordinary one, every decoder reads it; the exception map's row is measured on the
     symbols chosen. 0.0 gives the bytes of None.
+    pad=True: images of any height and width (N, h, w). They are extended on the device to the coded size (module docstring) by
+    edge replication (device.frame_pad_u8) in front of the encoder, so everything above works unchanged behind it, and the real
+    size goes into the header's `crop` byte: the blob is that of the numpy-edge-padded images but for byte 23, and `decode_images`
+    returns (N, h, w). With sides that are multiples of 16 already the bytes are those of pad=False. Without `pad` such sizes go
+    on raising.
     """
     images = numpy.ascontiguousarray(luminances_uint8)
     if images.dtype != numpy.uint8:
@@ -213,7 +246,15 @@ def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_p
     if rdo_lambda is not None:
         from . import ratecontrol
         thresholds = ratecontrol.rdo_thresholds(bin_widths[None], probabilities[None], rdo_lambda, idx_map_exception)
-    y = encoder(torch.from_numpy(images).to(device), tile=tile)
+    image_size = None
+    luminances = torch.from_numpy(images).to(device)
+    if pad:
+        if nb_images < 1 or height < 1 or width < 1:
+            raise ValueError('`luminances_uint8` holds no pixel.')
+        image_size = (height, width)
+        (height, width) = coded_size(height, width)
+        luminances = dev.frame_pad_u8(luminances)
+    y = encoder(luminances, tile=tile)
     if thresholds is None:
         q = dev.quantize_maps(y, torch.from_numpy(bin_widths).to(device), torch.from_numpy(mean).to(device), want_symbols=True)
     else:
@@ -231,8 +272,15 @@ def encode_images(luminances_uint8, encoder, bin_widths_test, map_mean, binary_p
     if coding_tile is not None:
         coding_tile = _clamped_coding_tile(coding_tile, height, width)
     fields = _fields(encoder.are_bin_widths_learned, nb_images, height, width, idx_map_exception, bin_widths, mean, probabilities,
-                     exception_rows, coding_tile)
+                     exception_rows, coding_tile, image_size)
     return _encode_entries(symbols, fields, nb_images if coding_tile is None else tiles_per_call)
+
+
+def _require_multiples(height, width, what):
+    """The entry points that do not pad ("what is refused") say so."""
+    if height % csts.STRIDE_PROD != 0 or width % csts.STRIDE_PROD != 0:
+        raise ValueError('{} does not pad: {} x {} images are not multiples of {} (`encode_images(..., pad=True)` and '
+                         '`codec.BatchCodec(..., pad=True)` take any size).'.format(what, height, width, csts.STRIDE_PROD))
 
 
 class _LadderOnDevice(object):
@@ -300,6 +348,7 @@ def encode_images_to_budget(luminances_uint8, encoder, ladder, budget_bytes, til
     if not isinstance(ladder, ratecontrol.RateLadder):
         raise TypeError('`ladder` is not a `ratecontrol.RateLadder`.')
     (nb_images, height, width) = images.shape
+    _require_multiples(height, width, '`encode_images_to_budget`')
     budgets = numpy.asarray(budget_bytes)
     if budgets.ndim > 1 or (budgets.ndim == 1 and budgets.shape[0] != nb_images) or budgets.dtype.kind not in 'iuf':
         raise ValueError('`budget_bytes` must be a number or one number per image.')
@@ -366,6 +415,7 @@ def encode_images_to_quality(luminances_uint8, encoder, decoder, ladder, target_
     if not isinstance(ladder, ratecontrol.RateLadder):
         raise TypeError('`ladder` is not a `ratecontrol.RateLadder`.')
     (nb_images, height, width) = images.shape
+    _require_multiples(height, width, '`encode_images_to_quality`')
     if (target_psnr is None) == (max_sse is None):
         raise ValueError('give `target_psnr` or `max_sse`, one of the two.')
     if target_psnr is not None:
@@ -433,7 +483,7 @@ def _fixed_header(fixed, total_length):
     layout = _TILE_HEADER if tiled else _HEADER
     if len(fixed) < layout.size:
         raise ValueError('The container is truncated.')
-    (magic, version, flags, nb_images, height, width, nb_maps, length, _, idx_map_exception, *coding_tile) = layout.unpack_from(fixed, 0)
+    (magic, version, flags, nb_images, height, width, nb_maps, length, crop, idx_map_exception, *coding_tile) = layout.unpack_from(fixed, 0)
     if magic != (TILE_MAGIC if tiled else MAGIC):
         raise ValueError('The container does not start with the magic bytes.')
     if version != (TILE_VERSION if tiled else VERSION):
@@ -447,7 +497,9 @@ def _fixed_header(fixed, total_length):
         raise ValueError('The image sizes in the container are not positive multiples of {}.'.format(csts.STRIDE_PROD))
     if not -1 <= idx_map_exception < nb_maps:
         raise ValueError('The index of the exception map in the container is out of range.')
-    fields = {'nb_images': nb_images, 'height': height, 'width': width, 'nb_maps': nb_maps, 'truncated_unary_length': length,
+    # the real size: the coded one less the two nibbles of `crop` (module docstring); every value is valid, the sides are 16 at least
+    fields = {'nb_images': nb_images, 'height': height, 'width': width, 'image_height': height - (crop >> 4),
+              'image_width': width - (crop & 15), 'nb_maps': nb_maps, 'truncated_unary_length': length,
               'idx_map_exception': idx_map_exception, 'are_bin_widths_learned': bool(flags & 1)}
     if tiled:
         if min(coding_tile) < 1:
@@ -497,7 +549,8 @@ def _read_arrays(fields, pos, blob, total_length):
 def read_header(blob):
     """Parses everything in front of the payload. Raises ValueError on a malformed or truncated blob. 'bits' is uint32
     [nb_images*nb_maps, 2] for EAE1; an EAT1 blob gives the same keys, with 'bits' uint32 [nb_images, nb_tiles, nb_maps, 2], plus
-    'format' ('EAT1') and 'coding_tile' (th, tw)."""
+    'format' ('EAT1') and 'coding_tile' (th, tw). 'height' / 'width' are the coded size, 'image_height' / 'image_width' the real one
+    (module docstring: `crop`)."""
     (fields, pos, _) = _fixed_header(blob, len(blob))
     return _read_arrays(fields, pos, blob, len(blob))
 
@@ -524,13 +577,14 @@ def _require_kind(header, decoder):
 
 
 def decode_images(blob, decoder, tile=None, tiles_per_call=TILES_PER_CALL):
-    """blob + pipeline.DeviceDecoder of the model -> uint8 (N, H, W) reconstructions (BT.601 range, tools.py:61-93).
+    """blob + pipeline.DeviceDecoder of the model -> uint8 (N, H, W) reconstructions (BT.601 range, tools.py:61-93), of the real
+    size the header's `crop` byte gives: the top-left h x w of the coded planes.
     tile=(th, tw): run the synthesis transform through windows (pipeline.DeviceDecoder.__call__): same reconstruction.
     EAT1 blobs are decoded in groups of `tiles_per_call` coding tiles, scattered and dequantised into the latent plane; the whole
     maps of an EAE1 blob are one group, dequantised by `dequantize_maps`."""
     if bytes(blob[:4]) == TILE_MAGIC:
         header = read_header(blob)
-        return decode_region(blob, decoder, (0, 0, header['height'], header['width']), tile=tile, tiles_per_call=tiles_per_call)
+        return decode_region(blob, decoder, (0, 0, header['image_height'], header['image_width']), tile=tile, tiles_per_call=tiles_per_call)
     (header, symbols) = decode_symbols(blob, decoder.device)
     _require_kind(header, decoder)
     device = decoder.device
@@ -538,6 +592,8 @@ def decode_images(blob, decoder, tile=None, tiles_per_call=TILES_PER_CALL):
                                   torch.from_numpy(header['map_mean']).to(device))['shifted']
     (h_map, w_map) = (header['height']//csts.STRIDE_PROD, header['width']//csts.STRIDE_PROD)
     (_, reconstruction_uint8, _) = decoder(shifted.view(header['nb_images'], h_map, w_map, header['nb_maps']), tile=tile)
+    if (header['image_height'], header['image_width']) != (header['height'], header['width']):
+        reconstruction_uint8 = reconstruction_uint8[:, :header['image_height'], :header['image_width']]
     return reconstruction_uint8.cpu().numpy()
 
 
@@ -609,16 +665,18 @@ def region_plan(header, region, images=None):
     the region's pixels exactly. Returns a dict: 'sub_plane' (row0, row1, col0, col1) in latents,
     'images', 'tiles' (indices of the coding tiles that intersect the sub-plane, row-major), 'entries' [(image, tile)],
     'ranges' [(start, stop)] byte range of every entry in the blob, 'crop' (y, x, height, width) of the region in the
-    sub-plane's reconstruction, and 'header_bytes'. An EAE1 header is one tile per map."""
+    sub-plane's reconstruction, and 'header_bytes'. An EAE1 header is one tile per map. The region is in the coordinates of the real
+    image and lies inside it ('image_height' x 'image_width', module docstring: `crop`)."""
     (nb_images, height, width) = (header['nb_images'], header['height'], header['width'])
+    (image_height, image_width) = (header.get('image_height', height), header.get('image_width', width))
     if not isinstance(region, (tuple, list)) or len(region) != 4:
         raise ValueError('`region` must be (y0, x0, height, width).')
     for x in region:
         if not isinstance(x, numbers.Integral) or isinstance(x, bool):
             raise ValueError('`region` must be (y0, x0, height, width) in integers.')
     (y0, x0, rh, rw) = (int(x) for x in region)
-    if rh < 1 or rw < 1 or y0 < 0 or x0 < 0 or y0 + rh > height or x0 + rw > width:
-        raise ValueError('The region {} is empty or leaves the {} x {} image.'.format(tuple(region), height, width))
+    if rh < 1 or rw < 1 or y0 < 0 or x0 < 0 or y0 + rh > image_height or x0 + rw > image_width:
+        raise ValueError('The region {} is empty or leaves the {} x {} image.'.format(tuple(region), image_height, image_width))
     if images is None:
         images = list(range(nb_images))
     else:
@@ -848,7 +906,8 @@ def _decode_entries(header, entries, chunks, device, per_call, consume):
 
 def _all_entries(header, blob):
     """Every (image, tile) entry of a blob in payload order, and its payload bytes: (entries, chunks) for _decode_entries."""
-    plan = region_plan(header, (0, 0, header['height'], header['width']))
+    # the whole real image: its sub-plane is the whole latent plane (the coded size is the real one rounded up to the next 16)
+    plan = region_plan(header, (0, 0, header.get('image_height', header['height']), header.get('image_width', header['width'])))
     view = memoryview(blob).cast('B')
     return plan['entries'], [view[a:b] for (a, b) in plan['ranges']]
 

@@ -1514,6 +1514,47 @@ def publish_crops(planes, origins, dst, crop_h, crop_w):
                                                _stream(planes)), 'eae_hip_publish_crops')
 
 
+# ---- images of any height and width (include/eae_hip.h, csrc/hip/frame.hip) ------------------------------
+
+def coded_size(height, width):
+    """The size an image of height x width (any positive integers) is coded at: both sides rounded up to multiples of 16."""
+    return (-(-int(height)//16)*16, -(-int(width)//16)*16)
+
+
+def frame_pad_u8(images, out=None):
+    """uint8 [N, h, w], contiguous, in device or pinned host memory -> uint8 [N, H, W] (device) with (H, W) = coded_size(h, w), the
+    image extended by edge replication: numpy.pad(x, ((0, 0), (0, H - h), (0, W - w)), mode='edge'). One launch; `out`: the
+    preallocated result (a graph's static input)."""
+    if images.dtype != torch.uint8 or images.dim() != 3 or not images.is_contiguous() or not (images.is_cuda or images.is_pinned()):
+        raise HipError('images must be a contiguous uint8 [N, h, w] tensor in device or pinned host memory')
+    (n, h, w) = images.shape
+    (coded_h, coded_w) = coded_size(h, w)
+    if out is None:
+        device = images.device if images.is_cuda else torch.device('cuda', torch.cuda.current_device())
+        out = torch.empty((n, coded_h, coded_w), dtype=torch.uint8, device=device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (n, coded_h, coded_w):
+        raise HipError('`out` must be uint8 [N, H, W] of the coded size')
+    _check(_native.hip().eae_hip_frame_pad_u8(images.data_ptr(), _p(out), n, h, w, coded_h, coded_w, _stream(out)), 'eae_hip_frame_pad_u8')
+    return out
+
+
+def frame_sse_u8(reconstruction, reference, out=None):
+    """Squared error per image over the real pixels: reconstruction uint8 [N, H, W] at the coded size, reference uint8 [N, h, w] ->
+    int64 [N], sum over y < h, x < w of (reference - reconstruction)^2. `out`: int64 [N] to ADD into (the caller zeroes it)."""
+    if reconstruction.dtype != torch.uint8 or reference.dtype != torch.uint8 or reconstruction.dim() != 3 or reference.dim() != 3:
+        raise HipError('expected uint8 [N, H, W] and uint8 [N, h, w]')
+    (n, h, w) = reference.shape
+    if tuple(reconstruction.shape) != (n,) + coded_size(h, w):
+        raise HipError('the reconstruction does not have the coded size of the reference')
+    if out is None:
+        out = torch.zeros(n, dtype=torch.int64, device=reconstruction.device)
+    if out.dtype != torch.int64 or out.numel() != n:
+        raise HipError('`out` must hold one int64 per image')
+    _check(_native.hip().eae_hip_frame_sse_u8(_p(reconstruction), _p(reference), _p(out), n, h, w, reconstruction.shape[1],
+                                              reconstruction.shape[2], _stream(reconstruction)), 'eae_hip_frame_sse_u8')
+    return out
+
+
 # ---- SVHN float64 path (include/eae_hip.h, "SVHN path") -------------------------------------------------------------
 
 def svhn_dense(x, w, b, leaky_relu):

@@ -696,6 +696,23 @@ int eae_hip_dequantize_maps_rows(const int16_t* symbols_planar, const float* bin
 int eae_hip_publish_crops(const uint8_t* planes, int n, int H, int W, const int32_t* origins, int ch, int cw, void* dst,
                           uint64_t dst_capacity_bytes, void* stream);
 
+/* ---- images of any height and width (csrc/hip/frame.hip) --------------------------------------------
+ * An h x w image is coded as H x W = (h, w) rounded up to multiples of 16, extended by edge replication; a decoder crops
+ * (eae_hip_publish_crops at origin (0, 0)). Both entry points are one launch, asynchronous on `stream`, with no argument the host
+ * computes from the data: a step can be captured into a hipGraph. Planes are addressed with 64-bit offsets. NULL pointer or a
+ * non-positive size -> EAE_HIP_BAD_ARGUMENT; H x W not the coded size of h x w, or a misaligned dst / sse -> EAE_HIP_BAD_SHAPE;
+ * nothing is launched then.
+ * frame_pad_u8: src u8 [n][h][w] in device or pinned, device-mapped host memory, at ANY byte address (w odd, h * w odd: image 1
+ *   then starts misaligned) -> dst u8 [n][H][W] in device memory, 16-byte aligned:
+ *   dst[i][y][x] = src[i][min(y, h - 1)][min(x, w - 1)], the rows of numpy.pad(..., mode='edge'). Every store is one 16-byte word of
+ *   a destination row. Every load lies inside the n * h * w bytes of src: no aligned word that begins in front of them or ends
+ *   behind them is touched. With h == H and w == W it is a copy.
+ * frame_sse_u8: rec u8 [n][H][W], ref u8 [n][h][w] (device memory, any byte address), sse u64 [n], 8-byte aligned:
+ *   sse[i] += sum over y < h, x < w of (ref[i][y][x] - rec[i][y][x])^2, exact; the caller zeroes sse (as for eae_hip_sse_u8 and
+ *   eae_hip_tconv9x9s4_luma). The pixels of rec outside h x w are not read. */
+int eae_hip_frame_pad_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int H, int W, void* stream);
+int eae_hip_frame_sse_u8(const uint8_t* rec, const uint8_t* ref, uint64_t* sse, int n, int h, int w, int H, int W, void* stream);
+
 /* ==== TEST HOOKS (-DEAE_TEST_HOOKS): NOT exported by the product library lib/libeae_hip.so ====================================
  * Five entry points the test-suite needs and a deployment must not have (they change what later launches do, or only
  * exist to prove something about the kernels). Compiled into lib/libeae_hip_test.so only; tests/test_abi.py checks that
