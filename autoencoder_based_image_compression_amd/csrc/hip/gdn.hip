@@ -66,7 +66,9 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {     
 }
 // mode 0: every float whose bits lie in [first, last] through sqrt_mid and sqrtf. mode 1: `count` pseudo-random pairs (x, s) of the
 // range div_mid is guarded for -- every exponent of the range, random mantissas, both signs of x, plus the extreme mantissas at
-// every exponent pair -- through div_mid and `/`. out[0] += mismatches (bit patterns differ and not both NaN), out[1] = an example.
+// every exponent pair -- through div_mid and `/`. mode 2: the ONE pair (x, s) whose bits `first` carries (x in its high word, s in its
+// low word; count is 1) through div_mid and `/`, any operands at all: what tests/test_gpu_value_domain.py asks about the far side of
+// `gdn_tile`'s bounds. out[0] += mismatches (bit patterns differ and not both NaN), out[1] = an example.
 __global__ __launch_bounds__(256) void mid_forms_check_kernel(int mode, unsigned long long first, unsigned long long count,
                                                              unsigned long long seed, unsigned long long* out) {
     unsigned long long bad = 0, example = 0;
@@ -76,6 +78,11 @@ __global__ __launch_bounds__(256) void mid_forms_check_kernel(int mode, unsigned
             const unsigned int got = __float_as_uint(sqrt_mid(a)), want = __float_as_uint(sqrtf(a));
             const bool both_nan = (got & 0x7FFFFFFFu) > 0x7F800000u && (want & 0x7FFFFFFFu) > 0x7F800000u;
             if (got != want && !both_nan) { bad++; example = first + i; }
+        } else if (mode == 2) {
+            const float x = __uint_as_float((unsigned int)(first >> 32)), s = __uint_as_float((unsigned int)first);
+            const unsigned int got = __float_as_uint(div_mid(x, s)), want = __float_as_uint(x / s);
+            const bool both_nan = (got & 0x7FFFFFFFu) > 0x7F800000u && (want & 0x7FFFFFFFu) > 0x7F800000u;
+            if (got != want && !both_nan) { bad++; example = first; }
         } else {
             const unsigned long long h = mix64(seed + i), h2 = mix64(h);
             // exponents: x in [2^-60, 2^60], s in [2^-20, 2^40] (biased 67..187 and 107..167); the top of each range only with mantissa 0
@@ -97,8 +104,9 @@ __global__ __launch_bounds__(256) void mid_forms_check_kernel(int mode, unsigned
 }  // namespace
 
 extern "C" int eae_hip_debug_check_mid_forms(int mode, uint64_t first, uint64_t count, uint64_t seed, uint64_t* out2_device, void* stream) {
-    if ((mode != 0 && mode != 1) || !out2_device || count == 0) return EAE_HIP_BAD_ARGUMENT;
+    if ((mode != 0 && mode != 1 && mode != 2) || !out2_device || count == 0) return EAE_HIP_BAD_ARGUMENT;
     if (mode == 0 && first + count > (1ull << 32)) return EAE_HIP_BAD_ARGUMENT;
+    if (mode == 2 && count != 1) return EAE_HIP_BAD_ARGUMENT;
     hipLaunchKernelGGL(mid_forms_check_kernel, dim3(4096), dim3(256), 0, (hipStream_t)stream, mode, (unsigned long long)first,
                        (unsigned long long)count, (unsigned long long)seed, reinterpret_cast<unsigned long long*>(out2_device));
     EAE_HIP_CHECK_LAUNCH();

@@ -5,7 +5,9 @@
 // Formulation: output pixel (4p'+a, 4q'+b) receives kernel taps u = a + 2 - 4*dr,
 // v = b + 2 - 4*dc from the input sites (p'+dr, q'+dc), dr, dc in {-1, 0, +1}. So for a tile of input sites
 //     D[site][phase = 4a+b] = sum of X[site + (dr,dc)][ci] * Wp[(dr,dc)][ci][phase]
-// is a GEMM with N = 16 phases and K = 9 * 128, Wp holding zeros where 0 <= u,v <= 8 fails (x * 0 adds +0: exact).
+// is a GEMM with N = 16 phases and K = 9 * 128, Wp holding zeros where 0 <= u,v <= 8 fails (x * 0 adds +0: exact for every FINITE x;
+// an inf or NaN input turns the outputs of its whole 3 x 3 site neighbourhood into NaN, beyond the 9 x 9 of its taps: DESIGN.md
+// section 3, "Value domain").
 // K order = the oracle's: 32-channel block (outer), then (dr, dc) descending == (u, v) ascending, then the channel inside
 // the block. v_mfma_f32_16x16x4_f32 (A = sites x k, B = k x phases).
 //

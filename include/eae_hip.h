@@ -735,7 +735,8 @@ int eae_hip_debug_set_split_mute(int on);
 /* Proof harness of the normalisations' mid-range forms (csrc/hip/common.h: sqrt_mid, div_mid -- hipcc's correctly rounded sqrtf and
  * `/` without the scaling and fix-up steps that only extreme operands need). mode 0: every float with bits in [first, first + count)
  * through sqrt_mid and sqrtf; mode 1: `count` pseudo-random operand pairs of the guarded range (all exponents, random and extreme
- * mantissas) through div_mid and `/`. out2_device[0] += results whose bits differ, out2_device[1] = one such operand (pair). */
+ * mantissas) through div_mid and `/`; mode 2: the one pair (x, s) in `first` (bits of x in the high word, of s in the low word; count = 1),
+ * any operands at all, through div_mid and `/`. out2_device[0] += results whose bits differ, out2_device[1] = one such operand (pair). */
 int eae_hip_debug_check_mid_forms(int mode, uint64_t first, uint64_t count, uint64_t seed, uint64_t* out2_device, void* stream);
 /* What the last conv GEMM launch of the CALLING THREAD (eae_hip_conv5x5s2 / _tconv5x5s2, their _ws forms, eae_hip_conv5x5s2_latent)
  * launched, as the launcher wrote it down beside the launch itself -- not a second evaluation of its rules (tests/

@@ -26,6 +26,8 @@ def lib():
         _lib.orc_conv2d_transpose_same_col2im.argtypes = _lib.orc_conv2d_same.argtypes
         _lib.orc_gdn.restype = None
         _lib.orc_gdn.argtypes = [fp, ctypes.c_int64, ctypes.c_int, fp, fp, ctypes.c_int, fp]
+        _lib.orc_gdn_denominators.restype = None
+        _lib.orc_gdn_denominators.argtypes = [fp, ctypes.c_int64, ctypes.c_int, fp, fp, fp]
     return _lib
 
 
@@ -76,6 +78,17 @@ def gdn(x, gamma, beta, inverse=False):
     c = x.shape[-1]
     out = numpy.empty_like(x)
     lib().orc_gdn(_fp(x), x.size//c, c, _fp(gamma), _fp(beta), 1 if inverse else 0, _fp(out))
+    return out
+
+
+def gdn_denominators(x, gamma, beta):
+    """a = matmul(x**2, gamma) + beta as `gdn` forms it (the same chain, float32): the operand of its square root."""
+    x = _f32(x)
+    gamma = _f32(gamma)
+    beta = _f32(beta)
+    c = x.shape[-1]
+    out = numpy.empty_like(x)
+    lib().orc_gdn_denominators(_fp(x), x.size//c, c, _fp(gamma), _fp(beta), _fp(out))
     return out
 
 

@@ -217,6 +217,23 @@ void orc_gdn(const float* x, int64_t rows, int c, const float* gamma, const floa
     }
 }
 
+/* The denominators of orc_gdn by themselves, a[c] = (sum_k x[k]^2 * gamma[k][c]) + beta[c] in the same chain: what the value-domain
+ * tests (tests/value_domain_cases.py) assert their populations on. */
+void orc_gdn_denominators(const float* x, int64_t rows, int c, const float* gamma, const float* beta, float* out) {
+#pragma omp parallel for schedule(static)
+    for (int64_t r = 0; r < rows; ++r) {
+        const float* xr = x + (size_t)r * c;
+        float* d = out + (size_t)r * c;
+        for (int j = 0; j < c; ++j) d[j] = 0.f;
+        for (int kx = 0; kx < c; ++kx) {
+            const float x2 = xr[kx] * xr[kx];
+            const float* grow = gamma + (size_t)kx * c;
+            for (int j = 0; j < c; ++j) d[j] = fmaf(x2, grow[j], d[j]);
+        }
+        for (int j = 0; j < c; ++j) d[j] = d[j] + beta[j];
+    }
+}
+
 /* uint8 -> float32 with no offset and no scale (eae/batching.py:95). */
 void orc_u8_to_f32(const uint8_t* x, int64_t count, float* out) {
     for (int64_t i = 0; i < count; ++i) out[i] = (float)x[i];
