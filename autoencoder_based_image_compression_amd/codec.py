@@ -2978,3 +2978,251 @@ class TiledQualityCodec(_TiledRateControl, QualityCodec):
                                  quality.prob_row, quality.trace_point, quality.trace_sse, quality.met, self._run_entry,
                                  self._tile_layout['nb_tiles'], self.ladder.nb_points, round, self.idx_map_exception,
                                  self.ladder.nb_points*self.nb_maps)
+
+
+# ---- colour pictures: three planes through two luminance codecs ------------------------------------------------
+
+class ColourTicket(object):
+    """Handle on one submitted batch of colour pictures: the three plane tickets (`tickets`: Y, Cb, Cr) and what the colour layer adds."""
+
+    def __init__(self, tickets, image_size, step):
+        self.nb_images = tickets[0].nb_images
+        self.tickets = tuple(tickets)
+        self.image_size = image_size
+        self.reconstruction_rgb = None        # device tensor (N, h, w, 3): the merged pictures
+        self.reconstruction_host = None       # numpy uint8 (N, h, w, 3), a view of the colour slot's pinned buffer, with fetch_reconstruction,
+        #                                       after result(): the same pictures, written by a merge launch of their own straight into
+        #                                       pinned memory. Both are valid until the colour slot comes round (`ColourCodec.depth` submits
+        #                                       later); everything `result()` returns is the ticket's own and stays valid
+        self.fed_event = None                 # host input: recorded behind the host -> device copy (the caller's pinned batch may be
+        #                                       rewritten once it has completed)
+        self.merged_event = None              # recorded behind the merge and the publication of 'sse_rgb': wait for it on another stream
+        #                                       before reading `reconstruction_rgb` there
+        self._step = step
+        self._sse = None                      # 'sse_rgb', copied out of the colour slot's pinned words: by `result()`, or by the `submit`
+        #                                       that takes the slot for its next step (`_keep_sse`), whichever comes first
+        self._values = None
+
+    def _keep_sse(self):
+        """Behind `merged_event`: the step's squared errors leave the slot's pinned words for the ticket."""
+        if self._sse is None:
+            self._sse = self._step.sse_host.copy()
+
+    def result(self):
+        """Blocks until the three planes and the merge are through (and raises a plane's error as `Ticket.result()` does); every key of
+        `BatchCodec.result()` as an array (N, 3) in the order Y, Cb, Cr, and 'sse_rgb' int64 (N,): the squared error of the merged
+        picture against the input over its 3 h w samples. Only waits: everything was enqueued by `submit`. Valid at any later time, like
+        `Ticket.result()`: nothing it returns stays in a slot."""
+        if self._values is None:
+            results = [ticket.result() for ticket in self.tickets]
+            self.merged_event.synchronize()
+            values = {key: numpy.stack([r[key] for r in results], axis=1) for key in results[0]}
+            self._keep_sse()
+            values['sse_rgb'] = self._sse
+            if self._step.pinned_rgb is not None:
+                self.reconstruction_host = self._step.pinned_rgb.numpy()
+            self._values = values
+        return self._values
+
+    def container(self):
+        """The step as one `EAC1` blob (container.py): byte for byte `container.encode_colour_images` of the same pictures. Blocks and
+        raises like the three `Ticket.container()` it is made of (`ContainerOverflow` included). Needs `emit_container=True`."""
+        return container_format.assemble_colour_blob(self.image_size, *(ticket.container() for ticket in self.tickets))
+
+    def image_containers(self):
+        """Like `container()`: one `EAC1` blob per picture, made of the three single-image plane blobs."""
+        return [container_format.assemble_colour_blob(self.image_size, *blobs)
+                for blobs in zip(*(ticket.image_containers() for ticket in self.tickets))]
+
+
+class _ColourStep(object):
+    """What one colour step in flight owns beside the inner codecs' slots; `ColourCodec` goes round `depth` of them."""
+
+    def __init__(self, codec):
+        (n, h, w, device) = (codec.batch_size, codec.h, codec.w, codec.device)
+        (hc, wc) = (codec.hc, codec.wc)
+        self.rgb_in = torch.empty((n, h, w, 3), dtype=torch.uint8, device=device)          # the device copy of the batch: split from, compared with
+        self.planes = (torch.empty((n, h, w), dtype=torch.uint8, device=device), torch.empty((n, hc, wc), dtype=torch.uint8, device=device),
+                       torch.empty((n, hc, wc), dtype=torch.uint8, device=device))
+        self.pinned_rgb = torch.empty((n, h, w, 3), dtype=torch.uint8).pin_memory() if codec.fetch_reconstruction else None
+        self.rgb_out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=device)
+        self.sse = torch.zeros(n, dtype=torch.int64, device=device)
+        self.pinned_sse = torch.zeros(n, dtype=torch.int64).pin_memory()
+        self.sse_host = self.pinned_sse.numpy()
+        self.merged = None                    # the event behind the last merge that used this entry
+        self.ticket = None                    # that step's ticket, until the entry's next step has taken its squared errors out for it
+
+
+class ColourCodec(object):
+    """RGB pictures of any height and width through the luminance model, 4:2:0 (colour.py), pipelined: two `BatchCodec(pad=True,
+    keep_reconstruction=True)` of batch size `batch_size` -- `luma` at (h, w), `chroma` at (hc, wc) = ceil(h/2) x ceil(w/2) -- and,
+    around them, the split kernel, the merge kernel and rings of buffers of this class's own. Neither inner codec is modified.
+
+    A colour step is one step of `luma` and two consecutive steps of `chroma`, Cb then Cr; the three `Ticket.container()`s are the
+    three plane blobs of the step's `EAC1`. `submit` enqueues, in this order: the copy of the batch into the step's device buffer (a
+    pinned batch on a feed stream, `ColourTicket.fed_event` behind it), the split into the step's three plane buffers on the caller's
+    stream, the three inner submits, and, on a stream of this codec's own behind the three tickets' `decoded_event`s, the merge
+    (`device.colour_merge_420`) of the three kept reconstructions into the step's RGB output with the squared error against the device
+    copy of the input -- with `fetch_reconstruction` a second merge launch, of the picture alone, straight into the step's pinned
+    output --, then the publication of the errors and `merged_event`.
+
+    Ring depth. An inner slot's reconstruction is valid "until the slot comes round": the inner codecs order the reuse of a slot
+    against their own result worker, not against a merge on another stream. `luma` holds `luma.nb_slots` steps, `chroma`
+    `chroma.nb_slots` of which a colour step takes two consecutive ones, so the inner rings hold
+        depth = min(luma.nb_slots, chroma.nb_slots // 2)
+    colour steps: the plane of step i is overwritten by step i + luma.nb_slots at the earliest, Cb and Cr of step i (inner steps 2i,
+    2i + 1) by inner step 2i + chroma.nb_slots, which belongs to colour step i + chroma.nb_slots // 2 for either parity. `submit`
+    therefore waits on the host for the merge event of step i - depth before it enqueues anything of step i, and this class's own rings
+    (batch copies, plane buffers, RGB outputs, squared errors) are `depth` long: the same wait frees entry i % depth, and behind it
+    `submit` hands the entry's squared errors to the ticket of step i - depth, so a `ColourTicket.result()` collected at any later
+    time is its own step's. A configuration whose chroma codec cannot hold one colour step (depth 0) is refused. A `submit` that
+    raises half way (an inner codec's error) drains both inner codecs and the merge stream before it re-raises: whatever it did
+    enqueue is through, and the next step starts on idle rings whichever parity the chroma ring is left at.
+
+    chroma: None (Cb and Cr take the luminance rate point) or (bin_widths_test, map_mean, binary_probabilities, idx_map_exception).
+    batch_codec_options go to both inner codecs; chroma_options override them for `chroma` (`codec.product_mode(hc, wc)`). Unless
+    given there, the chroma codec's `nb_in_flight` is 2 * `luma.nb_in_flight` + 2 -- as many colour steps as `luma`'s slots hold --
+    cut to what `codec.stream_budget` leaves of it in this process, quietly, since nobody asked for the larger number: with 4 hardware
+    queues that is 2, and depth = 2. A value the caller gives is budgeted, and warned about, by `BatchCodec` as ever.
+    `fetch_reconstruction` is this codec's: the merged pictures in pinned memory as well. `pad` and `keep_reconstruction` are fixed."""
+
+    def __init__(self, variables, are_bin_widths_learned, bin_widths_test, map_mean, binary_probabilities, idx_map_exception, batch_size,
+                 h, w, chroma=None, chroma_options=None, **batch_codec_options):
+        (self.luma, self.chroma) = (None, None)
+        options = dict(batch_codec_options)
+        chroma_options = dict(chroma_options or {})
+        for fixed in ('pad', 'keep_reconstruction'):
+            if fixed in options or fixed in chroma_options:
+                raise ValueError('`{0}` is not an option of ColourCodec: its inner codecs run with {0}=True.'.format(fixed))
+        for shared in ('fetch_reconstruction', 'emit_container', 'device'):
+            if shared in chroma_options:
+                raise ValueError('`{0}` is the colour codec\'s, not the chroma codec\'s alone.'.format(shared))
+        self.fetch_reconstruction = bool(options.pop('fetch_reconstruction', False))
+        self.batch_size = container_format._positive_int(batch_size, '`batch_size`')
+        (self.h, self.w) = (container_format._positive_int(h, '`h`'), container_format._positive_int(w, '`w`'))
+        (self.hc, self.wc) = dev.chroma_size(self.h, self.w)
+        luma_point = (bin_widths_test, map_mean, binary_probabilities, idx_map_exception)
+        chroma_point = luma_point if chroma is None else tuple(chroma)
+        if len(chroma_point) != 4:
+            raise ValueError('`chroma` must be (bin_widths_test, map_mean, binary_probabilities, idx_map_exception).')
+        for_chroma = dict(options)
+        for_chroma.update(chroma_options)
+        self.emit_container = bool(options.get('emit_container', False))
+        try:
+            self.luma = BatchCodec(variables, are_bin_widths_learned, *luma_point, self.batch_size, self.h, self.w, pad=True,
+                                   keep_reconstruction=True, **options)
+            if chroma_options.get('nb_in_flight') is None:
+                # two inner steps per colour step: as many colour steps as the luminance codec's nb_in_flight + 2 slots hold, as far as
+                # this process's hardware queues go (the condition is `BatchCodec`'s own, so it finds nothing left to cut or to say)
+                wanted = 2*int(self.luma.nb_in_flight) + 2
+                if for_chroma.get('coder', 'device') == 'device' and not for_chroma.get('one_stream_steps') \
+                        and os.environ.get('EAE_IGNORE_HW_QUEUES') != '1':
+                    (_, wanted, _) = stream_budget(for_chroma.get('nb_transform_streams', 1), wanted)
+                for_chroma['nb_in_flight'] = wanted
+            self.chroma = BatchCodec(variables, are_bin_widths_learned, *chroma_point, self.batch_size, self.hc, self.wc, pad=True,
+                                     keep_reconstruction=True, **for_chroma)
+            self.device = self.luma.device
+            self.depth = min(self.luma.nb_slots, self.chroma.nb_slots//2)
+            if self.depth < 1:
+                raise ValueError('the chroma codec has {0} slot(s): it cannot hold the two steps (Cb, Cr) of one colour step.'.format(
+                    self.chroma.nb_slots))
+            self._steps = [_ColourStep(self) for _ in range(self.depth)]
+            self._merge_stream = torch.cuda.Stream(device=self.device)
+            self._feed_stream = None
+            self._index = 0
+        except BaseException:
+            self.close()
+            raise
+
+    def submit(self, rgb_uint8):
+        """uint8 tensor (batch_size, h, w, 3), on the device or in PINNED host memory -> ColourTicket. Everything is enqueued; the host
+        waits only for free inner slots and for the merge of the step `depth` submits ago (class docstring)."""
+        if rgb_uint8.dtype != torch.uint8:
+            raise TypeError('`rgb_uint8.dtype` is not equal to `torch.uint8`.')
+        if tuple(rgb_uint8.shape) != (self.batch_size, self.h, self.w, 3):
+            raise ValueError('`rgb_uint8.shape` is not (batch_size, h, w, 3).')
+        host = rgb_uint8.device.type == 'cpu'
+        if host and not rgb_uint8.is_pinned():
+            raise ValueError('a host batch must be in pinned memory (`torch.Tensor.pin_memory()`): its copy is asynchronous.')
+        step = self._steps[self._index % self.depth]
+        self._index += 1
+        if step.merged is not None:
+            # the merge that read this entry, and the inner reconstructions that come round with this step, is through
+            step.merged.synchronize()
+        if step.ticket is not None:
+            step.ticket._keep_sse()           # before this step's merge rewrites the entry's pinned words
+            step.ticket = None
+        try:
+            return self._enqueue(step, rgb_uint8, host)
+        except BaseException:
+            # part of the step may be enqueued (an inner submit raised): wait for all of it, so that the next step finds idle rings
+            step.merged = None
+            try:
+                self.drain()
+            except Exception:                 # the device itself is in trouble: the next submit will say so
+                pass
+            raise
+
+    def _enqueue(self, step, rgb_uint8, host):
+        """The launches of one colour step on ring entry `step` (class docstring) -> its ticket."""
+        fed = None
+        if host:
+            if self._feed_stream is None:
+                self._feed_stream = torch.cuda.Stream(device=self.device)
+            with torch.cuda.stream(self._feed_stream):
+                step.rgb_in.copy_(rgb_uint8, non_blocking=True)
+                fed = torch.cuda.Event()
+                fed.record()
+            torch.cuda.current_stream().wait_event(fed)
+        else:
+            step.rgb_in.copy_(rgb_uint8, non_blocking=True)
+        dev.colour_split_420(step.rgb_in, out=step.planes)
+        tickets = (self.luma.submit(step.planes[0]), self.chroma.submit(step.planes[1]), self.chroma.submit(step.planes[2]))
+        ticket = ColourTicket(tickets, (self.h, self.w), step)
+        ticket.fed_event = fed
+        with torch.cuda.stream(self._merge_stream):
+            for inner in tickets:
+                self._merge_stream.wait_event(inner.decoded_event)
+                inner.reconstruction_uint8.record_stream(self._merge_stream)
+            step.sse.zero_()
+            planes = tuple(inner.reconstruction_uint8 for inner in tickets)
+            dev.colour_merge_420(*planes, (self.h, self.w), out=step.rgb_out, reference=step.rgb_in, sse=step.sse)
+            if step.pinned_rgb is not None:
+                dev.colour_merge_420(*planes, (self.h, self.w), out=step.pinned_rgb)      # the picture alone, straight into pinned memory
+            step.pinned_sse.copy_(step.sse, non_blocking=True)
+            step.merged = torch.cuda.Event()
+            step.merged.record()
+        ticket.merged_event = step.merged
+        ticket.reconstruction_rgb = step.rgb_out
+        step.ticket = ticket
+        return ticket
+
+    def drain(self):
+        """Waits until every submitted batch is through, the merges included."""
+        for inner in (self.luma, self.chroma):
+            if inner is not None:
+                inner.drain()
+        if getattr(self, '_merge_stream', None) is not None:
+            self._merge_stream.synchronize()
+
+    def close(self):
+        """Waits for the pending batches and closes both inner codecs. Idempotent."""
+        try:
+            self.drain()
+        finally:
+            for inner in (self.luma, self.chroma):
+                if inner is not None:
+                    inner.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, traceback):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:      # interpreter shutdown: nothing left to report to
+            pass

@@ -48,6 +48,15 @@ and never read: crop == 0 is that blob, byte for byte, and there is no new versi
 'image_height' / 'image_width'. How the encoder fills the H x W plane outside the image is its own business -- `encode_images(...,
 pad=True)` replicates the last row and column (device.frame_pad_u8) -- since a decoder only crops: `decode_images` returns h x w,
 and the regions of `decode_region` / `fetch_region` / `region_plan` are in real-image coordinates, inside h x w.
+
+Colour pictures: EAC1 wraps the blobs of the three planes of 4:2:0 pictures (colour.py: Y at h x w, Cb and Cr
+at ceil(h/2) x ceil(w/2)), little endian like the others:
+    magic 'EAC1' | version u16 (= 1) | flags u16 (= 0) | nb_images u32 | image_height u32 | image_width u32 |
+    subsampling u8 (= 1: 4:2:0; every other value is reserved and refused) | reserved u8[3] (= 0) | plane_bytes u64[3]    (48 bytes)
+    Y blob | Cb blob | Cr blob
+Each plane blob is byte for byte what `encode_images(plane, ..., pad=True)` writes -- EAE1 or EAT1 with its own `crop` byte, rate
+point and tables --, so every decoder above reads a plane of a colour file unchanged (`split_colour_blob`). `read_header` and
+`decode_images` raise on an EAC1 blob as on any unknown magic: `read_colour_header`, `decode_colour_images` read it.
 """
 import math
 import numbers
@@ -56,6 +65,7 @@ import struct
 import numpy
 import torch
 
+from . import colour as colour_rules
 from . import device as dev
 from . import pipeline
 from .kodak.eae.graph import constants as csts
@@ -953,3 +963,121 @@ def decode_region(source, decoder, region, images=None, tile=None, tiles_per_cal
     (_, reconstruction, _) = decoder(shifted, tile=tile)
     (y, x, rh, rw) = plan['crop']
     return reconstruction[:, y:y + rh, x:x + rw].cpu().numpy()
+
+
+# ---- colour pictures: EAC1, three plane blobs behind one header (module docstring) -------------------------------
+
+COLOUR_MAGIC = b'EAC1'
+COLOUR_VERSION = 1
+SUBSAMPLING_420 = 1            # the only value written and read; the others are reserved for 4:4:4 / 4:2:2 and refused
+_COLOUR_HEADER = struct.Struct('<4sHHIIIB3s3Q')
+_PLANE_NAMES = ('y', 'cb', 'cr')
+
+
+def _plane_sizes(image_size):
+    (h, w) = image_size
+    chroma = colour_rules.chroma_size(h, w)
+    return ((h, w), chroma, chroma)
+
+
+def _check_planes(nb_images, image_size, plane_blobs):
+    """Every plane blob must be an EAE1 / EAT1 blob of `nb_images` images (None: of the luminance blob's count) of its plane's real
+    size -> the image count. Only the fixed part of each header is looked at: `decode_images` checks the rest when it reads a plane."""
+    for (name, size, blob) in zip(_PLANE_NAMES, _plane_sizes(image_size), plane_blobs):
+        (fields, _, _) = _fixed_header(blob, len(blob))
+        if nb_images is None:
+            nb_images = fields['nb_images']
+        if fields['nb_images'] != nb_images:
+            raise ValueError('The {0} plane holds {1} images, not {2}.'.format(name, fields['nb_images'], nb_images))
+        if (fields['image_height'], fields['image_width']) != size:
+            raise ValueError('The {0} plane of a {1} x {2} picture is {3} x {4}, not {5} x {6}.'.format(
+                name, image_size[0], image_size[1], size[0], size[1], fields['image_height'], fields['image_width']))
+    return nb_images
+
+
+def assemble_colour_blob(image_size, y_blob, cb_blob, cr_blob):
+    """The EAC1 blob (module docstring) of pictures of image_size = (h, w) from the blobs of their three planes, each what
+    `encode_images(plane, ..., pad=True)` writes. Raises ValueError when the planes' image counts differ or their real sizes are not
+    (h, w), (hc, wc), (hc, wc)."""
+    image_size = _positive_pair(image_size, '`image_size`')
+    blobs = tuple(bytes(blob) for blob in (y_blob, cb_blob, cr_blob))
+    nb_images = _check_planes(None, image_size, blobs)
+    head = _COLOUR_HEADER.pack(COLOUR_MAGIC, COLOUR_VERSION, 0, nb_images, image_size[0], image_size[1], SUBSAMPLING_420, b'\0\0\0',
+                               *(len(blob) for blob in blobs))
+    return head + b''.join(blobs)
+
+
+def read_colour_header(blob):
+    """The 48 bytes in front of the plane blobs of an EAC1 blob -> {'nb_images', 'image_height', 'image_width', 'subsampling',
+    'plane_bytes' (three), 'plane_offsets' (three)}. Raises ValueError on anything but a whole, well-formed EAC1 header whose three
+    lengths add up to the blob's."""
+    if len(blob) < _COLOUR_HEADER.size:
+        raise ValueError('The colour container is truncated.')
+    (magic, version, flags, nb_images, height, width, subsampling, reserved, *plane_bytes) = _COLOUR_HEADER.unpack_from(blob, 0)
+    if magic != COLOUR_MAGIC:
+        raise ValueError('The colour container does not start with the magic bytes.')
+    if version != COLOUR_VERSION:
+        raise ValueError('The colour container version {} is not supported.'.format(version))
+    if flags != 0 or reserved != b'\0\0\0':
+        raise ValueError('A reserved field of the colour container is not zero.')
+    if subsampling != SUBSAMPLING_420:
+        raise ValueError('The chroma subsampling {} is not supported: only 4:2:0 (1) is.'.format(subsampling))
+    if nb_images < 1 or height < 1 or width < 1:
+        raise ValueError('The colour container holds no pixel.')
+    if min(plane_bytes) < 1 or _COLOUR_HEADER.size + sum(plane_bytes) != len(blob):
+        raise ValueError('The plane lengths of the colour container do not add up to its length.')
+    offsets = (_COLOUR_HEADER.size, _COLOUR_HEADER.size + plane_bytes[0], _COLOUR_HEADER.size + plane_bytes[0] + plane_bytes[1])
+    return {'nb_images': nb_images, 'image_height': height, 'image_width': width, 'subsampling': subsampling,
+            'plane_bytes': tuple(plane_bytes), 'plane_offsets': offsets}
+
+
+def split_colour_blob(blob):
+    """EAC1 blob -> (header, y_blob, cb_blob, cr_blob): `read_colour_header`, and the three plane blobs, each an ordinary EAE1 / EAT1
+    blob every decoder of this module reads. Raises ValueError when a plane does not belong to the header (image count, real size)."""
+    header = read_colour_header(blob)
+    view = memoryview(blob)
+    planes = tuple(bytes(view[start:start + count]) for (start, count) in zip(header['plane_offsets'], header['plane_bytes']))
+    _check_planes(header['nb_images'], (header['image_height'], header['image_width']), planes)
+    return (header,) + planes
+
+
+def encode_colour_images(rgb_uint8, encoder, bin_widths_test, map_mean, binary_probabilities, idx_map_exception=-1, chroma=None,
+                         coding_tile=None, rdo_lambda=None, tile=None):
+    """uint8 (N, h, w, 3) RGB pictures of any height and width -> (EAC1 blob bytes, info dict).
+
+    The picture is split on the device into Y, Cb and Cr, 4:2:0 (device.colour_split_420: `colour.split_420_numpy`), and each plane
+    goes through `encode_images(plane, encoder, ..., pad=True)`: the three plane blobs inside the EAC1 are those, byte for byte.
+    encoder, bin_widths_test, map_mean, binary_probabilities, idx_map_exception: `encode_images`'s, for the luminance plane.
+    chroma: None (Cb and Cr take the luminance arguments) or (bin_widths_test, map_mean, binary_probabilities, idx_map_exception)
+    for Cb and Cr: a rate point of their own, through the same model.
+    coding_tile, rdo_lambda, tile: passed on to the three `encode_images` calls.
+    info: 'y', 'cb', 'cr': the planes' infos; 'plane_bytes': their blobs' lengths."""
+    rgb = numpy.ascontiguousarray(rgb_uint8)
+    if rgb.dtype != numpy.uint8:
+        raise TypeError('`rgb_uint8.dtype` is not equal to `numpy.uint8`.')
+    if rgb.ndim != 4 or rgb.shape[3] != 3 or 0 in rgb.shape:
+        raise ValueError('`rgb_uint8` must be (N, h, w, 3) and hold a pixel.')
+    luma_point = (bin_widths_test, map_mean, binary_probabilities, idx_map_exception)
+    chroma_point = luma_point if chroma is None else tuple(chroma)
+    if len(chroma_point) != 4:
+        raise ValueError('`chroma` must be (bin_widths_test, map_mean, binary_probabilities, idx_map_exception).')
+    more = {'tile': tile, 'rdo_lambda': rdo_lambda, 'pad': True}
+    if coding_tile is not None:
+        more['coding_tile'] = coding_tile
+    planes = dev.colour_split_420(torch.from_numpy(rgb).to(encoder.device))
+    blobs = []
+    info = {}
+    for (name, plane, point) in zip(_PLANE_NAMES, planes, (luma_point, chroma_point, chroma_point)):
+        (blob, info[name]) = encode_images(plane.cpu().numpy(), encoder, *point, **more)
+        blobs.append(blob)
+    info['plane_bytes'] = tuple(len(blob) for blob in blobs)
+    return (assemble_colour_blob(rgb.shape[1:3], *blobs), info)
+
+
+def decode_colour_images(blob, decoder, tile=None):
+    """EAC1 blob + pipeline.DeviceDecoder of the model -> uint8 (N, h, w, 3) RGB: `decode_images` of each plane, merged on the device
+    (device.colour_merge_420: `colour.merge_420_numpy` of the three reconstructions)."""
+    (header, *plane_blobs) = split_colour_blob(blob)
+    planes = [torch.from_numpy(decode_images(plane_blob, decoder, tile=tile)).to(decoder.device) for plane_blob in plane_blobs]
+    (rgb, _) = dev.colour_merge_420(*planes, (header['image_height'], header['image_width']))
+    return rgb.cpu().numpy()

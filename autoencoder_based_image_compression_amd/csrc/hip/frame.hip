@@ -4,23 +4,12 @@
 //     dst[i][y][x] = src[i][min(y, h - 1)][min(x, w - 1)]. A lane forms one 16-byte word of a destination row out of four dwords.
 //   eae_hip_frame_sse_u8: sse[i] += sum over y < h, x < w of (ref[i][y][x] - rec[i][y][x])^2 with rec u8 [n][H][W], ref u8 [n][h][w]:
 //     a lane takes four pixels of a row of both; the pixels of rec outside h x w are never loaded.
-// Both read unaligned runs of four bytes the way publish_crops does (codec_decode.hip): from the two aligned dwords around the run,
-// combined by v_alignbyte_b32, when both lie inside the tensor -- the bounds are those of the tensor's bytes, not of its allocation:
-// an aligned dword that starts in front of the first byte or ends behind the last one is never loaded --, else byte by byte.
+// Both read unaligned runs of four bytes with load_run4 (byte_runs.h): from the two aligned dwords around the run when both lie
+// inside the tensor's bytes, else byte by byte.
+#include "byte_runs.h"
 #include "common.h"
 
 namespace {
-
-// The four bytes at `addr` .. `addr + 3`, all inside [begin, end), little endian.
-__device__ __forceinline__ uint32_t load_run4(const uint8_t* begin, const uint8_t* end, const uint8_t* addr) {
-    const uintptr_t a = (uintptr_t)addr, aligned = a & ~(uintptr_t)3;
-    if (aligned >= (uintptr_t)begin && aligned + 8 <= (uintptr_t)end) {
-        const uint32_t lo = *reinterpret_cast<const uint32_t*>(aligned);
-        const uint32_t hi = *reinterpret_cast<const uint32_t*>(aligned + 4);
-        return __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)(a & 3u));
-    }
-    return (uint32_t)addr[0] | ((uint32_t)addr[1] << 8) | ((uint32_t)addr[2] << 16) | ((uint32_t)addr[3] << 24);
-}
 
 struct FrameShape {
     uint32_t n, h, w, H, W;

@@ -7,6 +7,7 @@
 //   tls.count_nb_deads           tools/tools.py:318-320        (per-map "any non-zero" flags)
 // plus the per-map symbol histograms behind tls.count_symbols / discrete_entropy / rate_3d (tools.py:376-388,
 // 523-537, 977-989) and lossless/stats.py:181-195, as a second kernel over the planar symbols.
+#include "bt601.h"
 #include "common.h"
 
 namespace {
@@ -268,20 +269,17 @@ __global__ __launch_bounds__(256) void floor_hist_kernel(const float* __restrict
 }
 
 // tls.rgb_to_ycbcr (tools.py:1019-1083): ITU-R BT.601 in float64, terms added left to right as numpy evaluates them, clip to
-// [0, 255], round half to even, uint8. The constants are the same IEEE doubles Python forms (65.481/255. etc.).
+// [0, 255], round half to even, uint8 (bt601.h: the expressions colour.hip's split shares).
 __global__ void rgb_to_ycbcr_kernel(const uint8_t* __restrict__ rgb, uint8_t* __restrict__ ycbcr, uint8_t* __restrict__ luma,
                                     long count) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < count; i += (long)gridDim.x * blockDim.x) {
         const double r = (double)rgb[3 * i], g = (double)rgb[3 * i + 1], b = (double)rgb[3 * i + 2];
-        const double y = 16. + (65.481 / 255.) * r + (128.553 / 255.) * g + (24.966 / 255.) * b;
-        const double cb = 128. - (37.797 / 255.) * r - (74.203 / 255.) * g + (112. / 255.) * b;
-        const double cr = 128. + (112. / 255.) * r - (93.786 / 255.) * g - (18.214 / 255.) * b;
-        const uint8_t y8 = (uint8_t)rint(fmin(fmax(y, 0.), 255.));
+        const uint8_t y8 = bt601_y(r, g, b);
         if (luma) luma[i] = y8;
         if (ycbcr) {
             ycbcr[3 * i] = y8;
-            ycbcr[3 * i + 1] = (uint8_t)rint(fmin(fmax(cb, 0.), 255.));
-            ycbcr[3 * i + 2] = (uint8_t)rint(fmin(fmax(cr, 0.), 255.));
+            ycbcr[3 * i + 1] = bt601_cb(r, g, b);
+            ycbcr[3 * i + 2] = bt601_cr(r, g, b);
         }
     }
 }

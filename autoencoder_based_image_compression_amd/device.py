@@ -1555,6 +1555,90 @@ def frame_sse_u8(reconstruction, reference, out=None):
     return out
 
 
+# ---- colour images, 4:2:0 (include/eae_hip.h, csrc/hip/colour.hip; colour.py states both in numpy) --------
+
+def chroma_size(height, width):
+    """The size of the Cb and Cr planes of a height x width picture: both sides halved, rounded up."""
+    return ((int(height) + 1)//2, (int(width) + 1)//2)
+
+
+def _colour_device(*tensors):
+    for t in tensors:
+        if t is not None and t.is_cuda:
+            return t.device
+    return torch.device('cuda', torch.cuda.current_device())
+
+
+def colour_split_420(rgb, out=None):
+    """uint8 [N, h, w, 3], contiguous, in device or pinned host memory -> (y [N, h, w], cb [N, hc, wc], cr [N, hc, wc]), uint8 on the
+    device, (hc, wc) = chroma_size(h, w): `colour.split_420_numpy`, bit for bit. One launch; `out`: the three preallocated planes."""
+    if rgb.dtype != torch.uint8 or rgb.dim() != 4 or rgb.shape[3] != 3 or not rgb.is_contiguous() or not (rgb.is_cuda or rgb.is_pinned()):
+        raise HipError('rgb must be a contiguous uint8 [N, h, w, 3] tensor in device or pinned host memory')
+    (n, h, w, _) = rgb.shape
+    (hc, wc) = chroma_size(h, w)
+    if out is None:
+        device = _colour_device(rgb)
+        out = (torch.empty((n, h, w), dtype=torch.uint8, device=device), torch.empty((n, hc, wc), dtype=torch.uint8, device=device),
+               torch.empty((n, hc, wc), dtype=torch.uint8, device=device))
+    (y, cb, cr) = out
+    if any(t.dtype != torch.uint8 for t in out) or tuple(y.shape) != (n, h, w) or tuple(cb.shape) != (n, hc, wc) or tuple(cr.shape) != (n, hc, wc):
+        raise HipError('`out` must be uint8 (y [N, h, w], cb [N, hc, wc], cr [N, hc, wc])')
+    _check(_native.hip().eae_hip_colour_split_420(rgb.data_ptr(), _p(y), _p(cb), _p(cr), n, h, w, _stream(y)), 'eae_hip_colour_split_420')
+    return (y, cb, cr)
+
+
+def _plane_pitch(t):
+    """(rows, columns) of the contiguous [N, rows, columns] planes `t` is, or is the top-left view of (what `BatchCodec(pad=True)`
+    hands out as a reconstruction: `planes[:, :h, :w]`)."""
+    (image, row, column) = t.stride()
+    if column != 1 or row < t.shape[2] or image % row != 0 or image//row < t.shape[1]:
+        raise HipError('expected contiguous planes [N, rows, columns] or their top-left view [:, :h, :w]')
+    return (image//row, row)
+
+
+def colour_merge_420(y, cb, cr, size, out=None, reference=None, sse=None):
+    """Planes -> RGB: `colour.merge_420_numpy` of the top-left h x w of y and hc x wc of cb and cr, bit for bit, with size = (h, w).
+    y uint8 [N, H, W], cb and cr uint8 [N, Hc, Wc], on the device, H >= h, W >= w, Hc >= hc, Wc >= wc: dense planes, or the coded
+    planes a codec keeps (contiguous, or their top-left view), whose padding is never read. Returns (rgb, sse):
+    rgb uint8 [N, h, w, 3] on the device; `out`: a preallocated one, in device or pinned host memory; out=False: no picture is written
+    (then `reference` is needed) and rgb is None.
+    reference: uint8 [N, h, w, 3] on the device: sse int64 [N] receives the squared error per image over its 3 h w samples; `sse`: int64
+    [N] on the device to ADD into (the caller zeroes it). Without a reference sse is None. One launch."""
+    planes = (y, cb, cr)
+    if any(t.dtype != torch.uint8 or t.dim() != 3 or not t.is_cuda for t in planes):
+        raise HipError('y, cb and cr must be uint8 [N, rows, columns] tensors on the device')
+    (h, w) = (int(size[0]), int(size[1]))
+    (hc, wc) = chroma_size(h, w)
+    n = y.shape[0]
+    (coded_h, coded_w) = _plane_pitch(y)
+    (chroma_h, chroma_w) = _plane_pitch(cb)
+    if h < 1 or w < 1 or y.shape[1] < h or y.shape[2] < w or cb.shape[1] < hc or cb.shape[2] < wc or cb.shape[0] != n or cr.shape != cb.shape \
+            or _plane_pitch(cr) != (chroma_h, chroma_w):
+        raise HipError('the planes do not hold {0} x {1} pictures: y [N, >= h, >= w], cb and cr alike [N, >= hc, >= wc]'.format(h, w))
+    if out is False:
+        out = None
+        if reference is None:
+            raise HipError('neither a picture nor a squared error was asked for')
+    else:
+        if out is None:
+            out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=y.device)
+        if out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w, 3) or not out.is_contiguous() or not (out.is_cuda or out.is_pinned()):
+            raise HipError('`out` must be a contiguous uint8 [N, h, w, 3] tensor in device or pinned host memory')
+    if reference is None:
+        if sse is not None:
+            raise HipError('`sse` comes with a `reference`')
+    else:
+        if reference.dtype != torch.uint8 or tuple(reference.shape) != (n, h, w, 3) or not reference.is_cuda:
+            raise HipError('`reference` must be a uint8 [N, h, w, 3] tensor on the device')
+        if sse is None:
+            sse = torch.zeros(n, dtype=torch.int64, device=y.device)
+        if sse.dtype != torch.int64 or sse.numel() != n:
+            raise HipError('`sse` must hold one int64 per image')
+    _check(_native.hip().eae_hip_colour_merge_420(y.data_ptr(), cb.data_ptr(), cr.data_ptr(), None if out is None else out.data_ptr(), _p(reference), _p(sse), n, h, w,
+                                                  coded_h, coded_w, chroma_h, chroma_w, _stream(y)), 'eae_hip_colour_merge_420')
+    return (out, sse)
+
+
 # ---- SVHN float64 path (include/eae_hip.h, "SVHN path") -------------------------------------------------------------
 
 def svhn_dense(x, w, b, leaky_relu):

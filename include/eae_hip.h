@@ -713,6 +713,35 @@ int eae_hip_publish_crops(const uint8_t* planes, int n, int H, int W, const int3
 int eae_hip_frame_pad_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int H, int W, void* stream);
 int eae_hip_frame_sse_u8(const uint8_t* rec, const uint8_t* ref, uint64_t* sse, int n, int h, int w, int H, int W, void* stream);
 
+/* ---- colour images, 4:2:0 (csrc/hip/colour.hip) -------------------------------------------------------------
+ * An RGB picture of h x w is coded as three planes through the luminance model: Y at h x w, Cb and Cr at hc x wc = ceil(h / 2) x
+ * ceil(w / 2). The two entry points stand in front of and behind the codecs of the planes; autoencoder_based_image_compression_amd/
+ * colour.py states both in numpy and the kernels are held to it bit for bit. Each is one launch, asynchronous on `stream`, with no
+ * argument the host computes from the data (a hipGraph can capture it); images are addressed with 64-bit offsets, the bytes inside
+ * one image with 32 bits: h * w * 3 and H * W must stay below 2^32. Every refusal returns EAE_HIP_BAD_ARGUMENT in front of the launch.
+ *
+ * colour_split_420: rgb u8 [n][h][w][3] dense, in device or pinned, device-mapped host memory, at ANY byte address ->
+ *   y u8 [n][h][w], cb and cr u8 [n][hc][wc], dense, in device memory. Per pixel (Y, Cb, Cr) is tls.rgb_to_ycbcr (float64 BT.601,
+ *   eae_hip_rgb_to_ycbcr's expressions); the Cb and Cr of a picture are extended to even sides by edge replication and every chroma
+ *   sample is (a + b + c + d + 2) >> 2 over its 2 x 2 block. Chroma is not clamped: up to 240 goes in, and the model's cast
+ *   (eae_hip_cast_bt601) returns 235 at most. A lane owns one chroma sample. Every load lies inside the n * h * w * 3 bytes of rgb (no
+ *   aligned word that begins in front of them or ends behind them is touched), every store inside the three outputs.
+ *   Refused: a NULL pointer, a non-positive size, an image of 2^32 bytes or more, more than 2^31 - 1 blocks.
+ * colour_merge_420: y u8 [n][H][W], cb and cr u8 [n][Hc][Wc] in device memory -- the coded planes a codec keeps, of which the
+ *   top-left h x w and hc x wc are read and NOTHING else (H = h, W = w, Hc = hc, Wc = wc: dense planes) -> rgb_out u8 [n][h][w][3]
+ *   dense, in device or pinned host memory, nullable. Chroma is upsampled centre-sited with weights 3:1 both ways, the neighbour
+ *   clamped at the REAL chroma size: for pixel (r, c), i = r >> 1, i2 = clip(i + (r & 1 ? 1 : -1), 0, hc - 1), j and j2 alike,
+ *   C = (9 P[i][j] + 3 P[i][j2] + 3 P[i2][j] + P[i2][j2] + 8) >> 4; then in int32, with Y' = 298 (Y - 16), U = Cb - 128, V = Cr - 128:
+ *   R = clip((Y' + 409 V + 128) >> 8), G = clip((Y' - 100 U - 208 V + 128) >> 8), B = clip((Y' + 516 U + 128) >> 8), clip to [0, 255],
+ *   `>>` an arithmetic shift (a floor). ref_rgb u8 [n][h][w][3] dense in device memory with sse u64 [n], 8-byte aligned, both or
+ *   neither: sse[i] += the exact squared error of image i over its 3 h w samples (the caller zeroes sse); one 64-bit atomic per block,
+ *   and with sse at most 64 blocks per image, which then loop over the image (without it: one chroma sample per lane, no cap).
+ *   Refused: y, cb or cr NULL, neither rgb_out nor ref_rgb, ref_rgb without sse or sse without ref_rgb, a misaligned sse, a
+ *   non-positive size, H < h, W < w, Hc < hc, Wc < wc, a plane or image of 2^32 bytes or more, more than 2^31 - 1 blocks. */
+int eae_hip_colour_split_420(const uint8_t* rgb, uint8_t* y, uint8_t* cb, uint8_t* cr, int n, int h, int w, void* stream);
+int eae_hip_colour_merge_420(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint8_t* rgb_out, const uint8_t* ref_rgb,
+                             uint64_t* sse, int n, int h, int w, int H, int W, int Hc, int Wc, void* stream);
+
 /* ==== TEST HOOKS (-DEAE_TEST_HOOKS): NOT exported by the product library lib/libeae_hip.so ====================================
  * Five entry points the test-suite needs and a deployment must not have (they change what later launches do, or only
  * exist to prove something about the kernels). Compiled into lib/libeae_hip_test.so only; tests/test_abi.py checks that
