@@ -1791,7 +1791,8 @@ class BatchDecoder(object):
     (pad, image_size) = (False, None)      # `BatchDecoder(pad=True)`; a `RegionDecoder` never crops to a real size
 
     def __init__(self, variables, are_bin_widths_learned, batch_size, h_in, w_in, truncated_unary_length, device='cuda', nb_in_flight=None,
-                 nb_streams=None, use_graphs=False, payload_capacity_bytes=None, fetch_reconstruction=True, coding_tile=None, pad=False):
+                 nb_streams=None, use_graphs=False, payload_capacity_bytes=None, fetch_reconstruction=True, coding_tile=None, pad=False,
+                 keep_reconstruction=False):
         """nb_streams: consecutive steps go round that many private streams, so that one step's serial decoder core runs beside
         another step's synthesis transform. nb_in_flight: steps that may be pending at once (= slots: pinned buffers and planes).
         None: `DECODER_STREAMS` streams, or as many of them as the process's hardware queues allow (`stream_budget`; streams asked
@@ -1809,7 +1810,11 @@ class BatchDecoder(object):
         whose coded size is that size rounded up to multiples of 16 and whose `crop` byte gives exactly it -- what
         `container.encode_images(..., pad=True)` and `BatchCodec(..., pad=True)` write --, refuses every other (`plan_decode_step`), and
         `result()` is uint8 (n, h_in, w_in), the top-left of the coded planes, cut by `device.publish_crops` at the end of the step
-        (into pinned memory with `fetch_reconstruction`). A decoder without `pad` refuses a blob whose `crop` is not 0."""
+        (into pinned memory with `fetch_reconstruction`). A decoder without `pad` refuses a blob whose `crop` is not 0.
+        keep_reconstruction: as `BatchCodec`'s: every ticket gets, at submit time, `decoded_event`, recorded on the slot's stream
+        behind the step, and `reconstruction_uint8`, the slot's planes on the device -- `planes[:n, :h_in, :w_in]` with `pad`, the
+        top-left view of the coded planes, `planes[:n]` without --, valid until the slot comes round again: another stream waits for
+        the event and reads them there (`ColourDecoder`). False: neither attribute exists and no event is made."""
         (self.pad, self.image_size) = (bool(pad), None)
         if self.pad:
             self.image_size = (container_format._positive_int(h_in, '`h_in`'), container_format._positive_int(w_in, '`w_in`'))
@@ -1817,7 +1822,7 @@ class BatchDecoder(object):
         self._lay_out(batch_size, h_in, w_in, truncated_unary_length, payload_capacity_bytes, coding_tile)
         if self.pad:
             self.region = self.image_size          # what a slot cuts out of its planes for the ticket (`_DecodeSlot`), at the origin
-        self._build(variables, are_bin_widths_learned, device, nb_in_flight, nb_streams, use_graphs, fetch_reconstruction)
+        self._build(variables, are_bin_widths_learned, device, nb_in_flight, nb_streams, use_graphs, fetch_reconstruction, keep_reconstruction)
 
     def _lay_out(self, batch_size, h_in, w_in, truncated_unary_length, payload_capacity_bytes, coding_tile):
         """The first half of construction: refuses what no decoder can be built for, then lays a step out -- everything `_build`,
@@ -1857,13 +1862,15 @@ class BatchDecoder(object):
         self.nb_maps = csts.NB_MAPS_3
         self.truncated_unary_length = int(truncated_unary_length)
 
-    def _build(self, variables, are_bin_widths_learned, device, nb_in_flight, nb_streams, use_graphs, fetch_reconstruction):
+    def _build(self, variables, are_bin_widths_learned, device, nb_in_flight, nb_streams, use_graphs, fetch_reconstruction,
+               keep_reconstruction=False):
         """The second half of construction, of a decoder `_lay_out` has accepted: the device, the model, the streams, the static
         tables, the slots, the worker."""
         self.device = _decoder_device(device)
         self.learned = bool(are_bin_widths_learned)
         self.decoder = pipeline.DeviceDecoder(variables, are_bin_widths_learned, self.device)
         self.fetch_reconstruction = bool(fetch_reconstruction)
+        self.keep_reconstruction = bool(keep_reconstruction)
         self.use_graphs = bool(use_graphs)
         self.nb_streams = nb_streams = _decoder_streams(nb_streams, type(self).__name__)
         self.nb_in_flight = max(1, int(nb_in_flight)) if nb_in_flight is not None else nb_streams + 2
@@ -1933,6 +1940,12 @@ class BatchDecoder(object):
                     slot.graph.replay()
                 else:
                     self._launch_step(slot)
+                if self.keep_reconstruction:
+                    # behind the step on the slot's stream, never inside `_launch_step`, which is what a graph captures
+                    ticket.decoded_event = torch.cuda.Event()
+                    ticket.decoded_event.record(slot.lane.stream)
+                    ticket.reconstruction_uint8 = slot.planes[:nb_images, :self.image_size[0], :self.image_size[1]] if self.pad \
+                        else slot.planes[:nb_images]
             finally:
                 torch.cuda.set_stream(caller)
             job = _DecodeJob(ticket, slot, (slot.seq_host, (expected,)), payload_bytes, detail)
@@ -3207,6 +3220,208 @@ class ColourCodec(object):
 
     def close(self):
         """Waits for the pending batches and closes both inner codecs. Idempotent."""
+        try:
+            self.drain()
+        finally:
+            for inner in (self.luma, self.chroma):
+                if inner is not None:
+                    inner.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, traceback):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:      # interpreter shutdown: nothing left to report to
+            pass
+
+
+# ---- colour pictures out of EAC1 containers, resident and pipelined (DESIGN.md section 27) --------------------------------------------
+
+class ColourDecodeTicket(object):
+    """Handle on one submitted `ColourDecoder` step: the three plane tickets (`tickets`: Y, Cb, Cr), `nb_images`, and `merged_event`,
+    recorded behind the merge: wait for it on another stream before reading the device result there."""
+
+    def __init__(self, tickets, step, image_size):
+        self.nb_images = tickets[0].nb_images
+        self.tickets = tuple(tickets)
+        self.merged_event = None
+        self.errors = None                    # after result(): per picture, None or the first error among its Y, Cb and Cr planes
+        self._step = step
+        self._image_size = image_size
+        self._value = None
+
+    def result(self, raise_errors=True):
+        """Blocks until the three planes and the merge are through; uint8 (nb_images, h, w, 3): a numpy view of the colour slot's pinned
+        buffer (`fetch_reconstruction=True`) or the device tensor, valid until the colour slot comes round `ColourDecoder.depth`
+        submits later. Raises the first picture's error unless `raise_errors` is False: `errors` then says which pictures of the
+        array to leave alone. Only waits: everything was enqueued by `submit`."""
+        if self.errors is None:
+            for ticket in self.tickets:
+                ticket.result(raise_errors=False)
+            self.merged_event.synchronize()
+            self.errors = [next((ticket.errors[i] for ticket in self.tickets if ticket.errors[i] is not None), None)
+                           for i in range(self.nb_images)]
+            (h, w) = self._image_size
+            buffer = self._step.host if self._step.host is not None else self._step.device
+            self._value = buffer[:self.nb_images*h*w*3].reshape(self.nb_images, h, w, 3)
+        if raise_errors:
+            for error in self.errors:
+                if error is not None:
+                    raise error
+        return self._value
+
+
+class _ColourDecodeStep(object):
+    """What one colour step in flight owns beside the inner decoders' slots: the buffer its merge writes, whole 16-byte words of it
+    (`device.colour_merge_420_words`), pinned or on the device; `ColourDecoder` goes round `depth` of them."""
+
+    def __init__(self, decoder):
+        nbytes = dev.colour_words_bytes(decoder.batch_size, decoder.h, decoder.w)
+        (self.pinned, self.host, self.device) = (None, None, None)
+        if decoder.fetch_reconstruction:
+            self.pinned = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+            self.host = self.pinned.numpy()
+        else:
+            self.device = torch.zeros(nbytes, dtype=torch.uint8, device=decoder.device)
+        self.merged = None                    # the event behind the last merge that used this entry
+
+
+class ColourDecoder(object):
+    """`EAC1` containers -> uint8 RGB pictures (n, h, w, 3), resident and pipelined: what `container.decode_colour_images` computes
+    (same bytes), the mirror of `ColourCodec`. Two unmodified `BatchDecoder(pad=True, keep_reconstruction=True,
+    fetch_reconstruction=False)` of batch size `batch_size` -- `luma` at (h, w), `chroma` at (hc, wc) = ceil(h/2) x ceil(w/2) -- and,
+    on a stream of this decoder's own behind the three tickets' `decoded_event`s, ONE `device.colour_merge_420_words` launch over the
+    step's pictures, straight into the colour slot's pinned buffer (`fetch_reconstruction`) or into its device buffer; both hold
+    `batch_size` pictures rounded up to 16 bytes. `merged_event` is recorded behind it.
+
+    A colour step is one step of `luma` and two consecutive steps of `chroma`, Cb then Cr. The ring rule is `ColourCodec`'s, for the
+    same reason: the inner decoders free a slot against their own worker, not against a merge on another stream, so the inner rings
+    hold depth = min(luma.nb_slots, chroma.nb_slots // 2) colour steps, `submit` of step i first waits on the host for the merge event
+    of step i - depth, and the colour ring is `depth` long. A depth of 0 is refused. A `submit` that raises half way drains both
+    inner decoders and the merge stream before it re-raises.
+
+    chroma_options: `nb_in_flight`, `nb_streams`, `payload_capacity_bytes`, `truncated_unary_length` of the chroma decoder, where they
+    differ from the luminance decoder's. `coding_tile` goes to both and each clamps it to its own latent plane, as
+    `container.encode_colour_images(coding_tile=...)` writes them. Unless given, chroma's `nb_in_flight` is 2 * `luma.nb_in_flight`,
+    and the two decoders share what `stream_budget` leaves this process after one stream for the merge (4 + 4 streams at 16 hardware
+    queues, 1 + 1 at 4), quietly, since nobody asked; numbers the caller gives are capped, and warned about, by `BatchDecoder`."""
+    CHROMA_OPTIONS = ('nb_in_flight', 'nb_streams', 'payload_capacity_bytes', 'truncated_unary_length')
+
+    def __init__(self, variables, are_bin_widths_learned, batch_size, h, w, truncated_unary_length, device='cuda', nb_in_flight=None,
+                 nb_streams=None, use_graphs=False, payload_capacity_bytes=None, fetch_reconstruction=True, coding_tile=None,
+                 chroma_options=None):
+        (self.luma, self.chroma, self._merge_stream, self._closed) = (None, None, None, False)
+        chroma_options = dict(chroma_options or {})
+        for name in chroma_options:
+            if name not in self.CHROMA_OPTIONS:
+                raise ValueError('`{0}` is not an option of the chroma decoder alone: `chroma_options` takes {1}.'.format(
+                    name, ', '.join(self.CHROMA_OPTIONS)))
+        self.batch_size = container_format._positive_int(batch_size, '`batch_size`')
+        (self.h, self.w) = (container_format._positive_int(h, '`h`'), container_format._positive_int(w, '`w`'))
+        (self.hc, self.wc) = dev.chroma_size(self.h, self.w)
+        self.fetch_reconstruction = bool(fetch_reconstruction)
+        for_luma = {'nb_in_flight': nb_in_flight, 'nb_streams': nb_streams, 'payload_capacity_bytes': payload_capacity_bytes}
+        for_chroma = dict(for_luma, nb_in_flight=None)      # chroma's slots follow the luminance decoder's unless given
+        for_chroma.update({name: value for (name, value) in chroma_options.items() if name != 'truncated_unary_length'})
+        if os.environ.get('EAE_IGNORE_HW_QUEUES') != '1':
+            # one stream is the merge's; the two decoders share the rest
+            (luma_streams, chroma_streams, _) = stream_budget(DECODER_STREAMS, DECODER_STREAMS, copies=1)
+            if for_luma['nb_streams'] is None:
+                for_luma['nb_streams'] = luma_streams
+            if for_chroma['nb_streams'] is None:
+                for_chroma['nb_streams'] = chroma_streams
+        shared = {'device': device, 'use_graphs': use_graphs, 'fetch_reconstruction': False, 'coding_tile': coding_tile, 'pad': True,
+                  'keep_reconstruction': True}
+        try:
+            self.luma = BatchDecoder(variables, are_bin_widths_learned, self.batch_size, self.h, self.w, truncated_unary_length,
+                                     **shared, **for_luma)
+            if for_chroma['nb_in_flight'] is None:
+                for_chroma['nb_in_flight'] = 2*self.luma.nb_in_flight      # two inner steps per colour step
+            self.chroma = BatchDecoder(variables, are_bin_widths_learned, self.batch_size, self.hc, self.wc,
+                                       chroma_options.get('truncated_unary_length', truncated_unary_length), **shared, **for_chroma)
+            self.device = self.luma.device
+            self.depth = min(self.luma.nb_slots, self.chroma.nb_slots//2)
+            if self.depth < 1:
+                raise ValueError('the chroma decoder has {0} slot(s): it cannot hold the two steps (Cb, Cr) of one colour step.'.format(
+                    self.chroma.nb_slots))
+            self._steps = [_ColourDecodeStep(self) for _ in range(self.depth)]
+            self._merge_stream = torch.cuda.Stream(device=self.device)
+            self._index = 0
+        except BaseException:
+            self.close()
+            raise
+
+    def submit(self, blobs):
+        """One `EAC1` blob of 1..batch_size pictures, or a sequence of `EAC1` blobs holding that many in all -> ColourDecodeTicket.
+        The blobs are split and checked on the host first (`container.split_colour_blob`, then the decoder's own size and batch:
+        ValueError, nothing launched; the inner `plan_decode_step` refuses what does not fit its decoder); then everything is enqueued,
+        and the host waits only for free inner slots and for the merge of the step `depth` submits ago."""
+        if self._closed:
+            raise RuntimeError('this decoder is closed')
+        if isinstance(blobs, (bytes, bytearray, memoryview)):
+            blobs = [blobs]
+        blobs = list(blobs)
+        if not blobs:
+            raise ValueError('A step needs at least one blob.')
+        planes = ([], [], [])
+        nb_images = 0
+        for blob in blobs:
+            (header, *plane_blobs) = container_format.split_colour_blob(blob)
+            if (header['image_height'], header['image_width']) != (self.h, self.w):
+                raise ValueError('The colour container holds {0} x {1} pictures, the decoder was built for {2} x {3}.'.format(
+                    header['image_height'], header['image_width'], self.h, self.w))
+            nb_images += header['nb_images']
+            for (plane, plane_blob) in zip(planes, plane_blobs):
+                plane.append(plane_blob)
+        if nb_images > self.batch_size:
+            raise ValueError('The blobs hold {0} pictures, the decoder takes {1} per step.'.format(nb_images, self.batch_size))
+        step = self._steps[self._index % self.depth]
+        self._index += 1
+        if step.merged is not None:
+            # the merge that wrote this entry, and read the inner reconstructions that come round with this step, is through
+            step.merged.synchronize()
+        try:
+            return self._enqueue(step, planes)
+        except BaseException:
+            # part of the step may be enqueued (an inner submit raised): wait for all of it, so that the next step finds idle rings
+            step.merged = None
+            try:
+                self.drain()
+            except Exception:                 # the device itself is in trouble: the next submit will say so
+                pass
+            raise
+
+    def _enqueue(self, step, planes):
+        """The launches of one colour step on ring entry `step` (class docstring) -> its ticket."""
+        tickets = (self.luma.submit(planes[0]), self.chroma.submit(planes[1]), self.chroma.submit(planes[2]))
+        ticket = ColourDecodeTicket(tickets, step, (self.h, self.w))
+        with torch.cuda.stream(self._merge_stream):
+            for inner in tickets:
+                self._merge_stream.wait_event(inner.decoded_event)
+            dev.colour_merge_420_words(*(inner.reconstruction_uint8 for inner in tickets), (self.h, self.w),
+                                       out=step.pinned if step.pinned is not None else step.device)
+            step.merged = torch.cuda.Event()
+            step.merged.record()
+        ticket.merged_event = step.merged
+        return ticket
+
+    def drain(self):
+        """Waits until every submitted step is through, the merges included."""
+        for inner in (self.luma, self.chroma):
+            if inner is not None:
+                inner.drain()
+        if self._merge_stream is not None:
+            self._merge_stream.synchronize()
+
+    def close(self):
+        """Waits for the pending steps and closes both inner decoders. Idempotent."""
+        self._closed = True
         try:
             self.drain()
         finally:

@@ -6,7 +6,8 @@
 //   eae_hip_colour_merge_420: y u8 [n][H][W], cb, cr u8 [n][Hc][Wc], of which the top-left h x w / hc x wc are read -> rgb u8
 //     [n][h][w][3] and / or sse[i] += the squared error against a reference picture: chroma upsampled 3:1 centre-sited with the
 //     neighbours clamped at the real chroma size, then the integer BT.601 inverse.
-// In both a lane owns one chroma sample, i.e. a 2 x 2 block of pixels: 12 bytes of the picture, six contiguous ones in each of two
+//   eae_hip_colour_merge_420_words: the same picture in whole aligned 16-byte words, for the resident decoder (further down).
+// In the first two a lane owns one chroma sample, i.e. a 2 x 2 block of pixels: 12 bytes of the picture, six contiguous ones in each of two
 // rows, so a wave covers 384 contiguous bytes of a row. A block lies inside one image (blocks_per_image blocks of 256 samples each):
 // the image index is a division of the block index, the offset of the image 64 bits wide, everything inside an image 32 bits. The
 // grids are one chroma sample per lane, whatever the size, with ONE exception: a merge that takes the squared error ends every block
@@ -197,6 +198,140 @@ bool colour_shape(int n, int h, int w, int H, int W, int Hc, int Wc, ColourShape
     return true;
 }
 
+// ---- the merge in whole words ----------------------------------------------------------------------------------
+// The batch's output [n][h][w][3] is one flat run of bytes, cut into aligned 16-byte words. A lane owns 16 consecutive flat pixels: 48
+// bytes, three words; a block 768 consecutive words, which it stages in LDS so that every store instruction of a wave writes 1 KB of
+// consecutive words (lane t stores words t, t + 256 and t + 512 of the block). A lane finds (picture, row, column) of its first pixel
+// by division. When its 16 pixels lie in one row -- every lane of a picture whose width is a multiple of 16, all but the one or two
+// lanes around each row end otherwise -- it takes them in runs of four (`load_run4`, bounded by the ROW: nothing outside the top-left
+// h x w / hc x wc of a plane is loaded) and writes its three words into LDS whole. A lane whose pixels cross a row end, a picture end
+// or the end of the batch goes pixel by pixel with carries and writes bytes into LDS; pixels past n * h * w are zero bytes.
+constexpr uint32_t WORDS_LANE_PIXELS = 16, WORDS_PER_BLOCK = 768;
+
+// Four bytes of one row of a plane, at columns first .. first + 3 clamped to [0, width): a run where all four exist
+__device__ __forceinline__ uint32_t clamped_run4(const uint8_t* line, uint32_t width, int first) {
+    if (first >= 0 && (uint32_t)first + 4u <= width) return load_run4(line, line + width, line + first);
+    uint32_t v = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int column = first + k;
+        v |= (uint32_t)line[column < 0 ? 0 : ((uint32_t)column < width ? (uint32_t)column : width - 1u)] << (8 * k);
+    }
+    return v;
+}
+
+__device__ __forceinline__ int window_byte(const uint32_t (&window)[3], int index) { return (int)((window[index >> 2] >> (8 * (index & 3))) & 255u); }
+
+// One chroma plane over the 16 pixels of row r that start at column c: `near` is chroma row r >> 1, `far` its clamped neighbour, both
+// as the 12 bytes at chroma columns (c >> 1) - 1 .. (c >> 1) + 10, clamped. Position m = 0 .. 16 counts pixels from the even column
+// c & ~1: its sample is byte 1 + (m >> 1) of the window, the neighbour the byte in front (m even) or behind (m odd). value[m] is the
+// upsampled chroma of that pixel; the pixels of the lane are positions (c & 1) .. (c & 1) + 15.
+__device__ __forceinline__ void upsample_row16(const uint32_t (&near)[3], const uint32_t (&far)[3], int (&value)[17]) {
+#pragma unroll
+    for (int m = 0; m < 17; ++m) {
+        const int sample = 1 + (m >> 1), neighbour = (m & 1) ? sample + 1 : sample - 1;
+        const int here = 3 * window_byte(near, sample) + window_byte(near, neighbour);
+        const int there = 3 * window_byte(far, sample) + window_byte(far, neighbour);
+        value[m] = (3 * here + there + 8) >> 4;
+    }
+}
+
+// Pixel (r, c) of a picture from bytes: r | g << 8 | b << 16
+__device__ __forceinline__ uint32_t merge_pixel(const uint8_t* luma, const uint8_t* plane_b, const uint8_t* plane_r, uint32_t r, uint32_t c,
+                                                const ColourShape& s) {
+    const uint32_t i = r >> 1, j = c >> 1;
+    const uint32_t i2 = (r & 1u) ? (i + 1u < s.hc ? i + 1u : s.hc - 1u) : (i > 0u ? i - 1u : 0u);
+    const uint32_t j2 = (c & 1u) ? (j + 1u < s.wc ? j + 1u : s.wc - 1u) : (j > 0u ? j - 1u : 0u);
+    const uint32_t near = i * s.Wc, far = i2 * s.Wc;
+    const int c_b = (9 * (int)plane_b[near + j] + 3 * (int)plane_b[near + j2] + 3 * (int)plane_b[far + j] + (int)plane_b[far + j2] + 8) >> 4;
+    const int c_r = (9 * (int)plane_r[near + j] + 3 * (int)plane_r[near + j2] + 3 * (int)plane_r[far + j] + (int)plane_r[far + j2] + 8) >> 4;
+    return bt601_inverse((int)luma[r * s.W + c], c_b, c_r);
+}
+
+__global__ __launch_bounds__(256) void colour_merge_words_kernel(const uint8_t* __restrict__ y, const uint8_t* __restrict__ cb,
+                                                                 const uint8_t* __restrict__ cr, u32x4* __restrict__ dst, ColourShape s,
+                                                                 uint64_t pixels, uint64_t words) {
+    __shared__ u32x4 tile[WORDS_PER_BLOCK];
+    const uint64_t first = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * WORDS_LANE_PIXELS;
+    u32x4* mine = tile + 3u * threadIdx.x;
+    if (first >= pixels) {                              // behind the batch: zero bytes (stored only where the last word reaches)
+        const u32x4 zero = {0u, 0u, 0u, 0u};
+        mine[0] = zero, mine[1] = zero, mine[2] = zero;
+    } else {
+        const uint32_t picture_pixels = s.h * s.w;
+        uint64_t img = first / picture_pixels;
+        const uint32_t inside = (uint32_t)(first - img * picture_pixels);
+        uint32_t r = inside / s.w, c = inside - r * s.w;
+        const uint8_t* luma = y + img * s.H * s.W;
+        const uint8_t* plane_b = cb + img * s.Hc * s.Wc;
+        const uint8_t* plane_r = cr + img * s.Hc * s.Wc;
+        if (c + WORDS_LANE_PIXELS <= s.w) {             // one row holds all 16
+            const uint32_t i = r >> 1;
+            const uint32_t i2 = (r & 1u) ? (i + 1u < s.hc ? i + 1u : s.hc - 1u) : (i > 0u ? i - 1u : 0u);
+            const int first_column = (int)(c >> 1) - 1;
+            uint32_t near[3], far[3];
+            int c_b[17], c_r[17];
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                near[t] = clamped_run4(plane_b + i * s.Wc, s.wc, first_column + 4 * t);
+                far[t] = clamped_run4(plane_b + i2 * s.Wc, s.wc, first_column + 4 * t);
+            }
+            upsample_row16(near, far, c_b);
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                near[t] = clamped_run4(plane_r + i * s.Wc, s.wc, first_column + 4 * t);
+                far[t] = clamped_run4(plane_r + i2 * s.Wc, s.wc, first_column + 4 * t);
+            }
+            upsample_row16(near, far, c_r);
+            const uint8_t* line = luma + r * s.W;
+            const bool odd = (c & 1u) != 0u;
+            uint32_t out[12];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const uint32_t four = load_run4(line, line + s.w, line + c + 4 * g);
+                uint32_t p[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int m = 4 * g + k;
+                    p[k] = bt601_inverse((int)((four >> (8 * k)) & 255u), odd ? c_b[m + 1] : c_b[m], odd ? c_r[m + 1] : c_r[m]);
+                }
+                out[3 * g] = p[0] | (p[1] << 24);
+                out[3 * g + 1] = (p[1] >> 8) | (p[2] << 16);
+                out[3 * g + 2] = (p[2] >> 16) | (p[3] << 8);
+            }
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                u32x4 word;
+                word.x = out[4 * t], word.y = out[4 * t + 1], word.z = out[4 * t + 2], word.w = out[4 * t + 3];
+                mine[t] = word;
+            }
+        } else {                                        // a row end, a picture end or the end of the batch inside the 16: by pixels
+            uint8_t* bytes = reinterpret_cast<uint8_t*>(mine);
+            for (uint32_t k = 0; k < WORDS_LANE_PIXELS; ++k) {
+                uint32_t p = 0;
+                if (first + k < pixels) {
+                    p = merge_pixel(luma, plane_b, plane_r, r, c, s);
+                    if (++c == s.w) {
+                        c = 0;
+                        if (++r == s.h) {
+                            r = 0, ++img;
+                            luma = y + img * s.H * s.W, plane_b = cb + img * s.Hc * s.Wc, plane_r = cr + img * s.Hc * s.Wc;      // formed, not read, behind the last picture
+                        }
+                    }
+                }
+                bytes[3u * k] = (uint8_t)p, bytes[3u * k + 1u] = (uint8_t)(p >> 8), bytes[3u * k + 2u] = (uint8_t)(p >> 16);
+            }
+        }
+    }
+    __syncthreads();
+    const uint64_t base = (uint64_t)blockIdx.x * WORDS_PER_BLOCK;
+#pragma unroll
+    for (uint32_t t = 0; t < 3; ++t) {
+        const uint64_t word = base + t * 256u + threadIdx.x;
+        if (word < words) dst[word] = tile[t * 256u + threadIdx.x];
+    }
+}
+
 }  // namespace
 
 extern "C" int eae_hip_colour_split_420(const uint8_t* rgb, uint8_t* y, uint8_t* cb, uint8_t* cr, int n, int h, int w, void* stream) {
@@ -217,6 +352,22 @@ extern "C" int eae_hip_colour_merge_420(const uint8_t* y, const uint8_t* cb, con
     if (sse && s.blocks_per_image > (uint32_t)MERGE_SSE_BLOCKS_PER_IMAGE) s.blocks_per_image = MERGE_SSE_BLOCKS_PER_IMAGE;
     hipLaunchKernelGGL(colour_merge_kernel, dim3(s.n * s.blocks_per_image), dim3(256), 0, (hipStream_t)stream, y, cb, cr, rgb_out, ref_rgb,
                        reinterpret_cast<unsigned long long*>(sse), s);
+    EAE_HIP_CHECK_LAUNCH();
+    return EAE_HIP_OK;
+}
+
+extern "C" int eae_hip_colour_merge_420_words(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint8_t* dst, uint64_t dst_bytes,
+                                              int n, int h, int w, int H, int W, int Hc, int Wc, void* stream) {
+    ColourShape s;
+    if (!y || !cb || !cr || !dst || !colour_shape(n, h, w, H, W, Hc, Wc, s)) return EAE_HIP_BAD_ARGUMENT;
+    const uint64_t pixels = (uint64_t)s.n * s.h * s.w;
+    const uint64_t words = (pixels * 3u + 15u) / 16u;
+    // whole aligned words, and room for every one of them: the last word is written whole, pad bytes included
+    if ((((uintptr_t)dst) & 15u) || (dst_bytes & 15u) || dst_bytes / 16u < words) return EAE_HIP_BAD_ARGUMENT;
+    const uint64_t blocks = (words + WORDS_PER_BLOCK - 1u) / WORDS_PER_BLOCK;          // one block per 768 words, whatever the size
+    if (blocks > 0x7FFFFFFFull) return EAE_HIP_BAD_ARGUMENT;
+    hipLaunchKernelGGL(colour_merge_words_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, y, cb, cr,
+                       reinterpret_cast<u32x4*>(dst), s, pixels, words);
     EAE_HIP_CHECK_LAUNCH();
     return EAE_HIP_OK;
 }

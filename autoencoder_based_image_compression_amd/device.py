@@ -1639,6 +1639,41 @@ def colour_merge_420(y, cb, cr, size, out=None, reference=None, sse=None):
     return (out, sse)
 
 
+def colour_words_bytes(nb_images, height, width):
+    """The bytes `colour_merge_420_words` needs of its `out` for that many pictures: 3 h w each, rounded up to whole 16-byte words."""
+    return -(-int(nb_images)*int(height)*int(width)*3//16)*16
+
+
+def colour_merge_420_words(y, cb, cr, size, out):
+    """`colour_merge_420`'s picture of the same planes (same checks, same top-left rule), written in whole aligned 16-byte words
+    (DESIGN.md section 27): `out` is a contiguous uint8 tensor in device or pinned host memory, 16-byte aligned, flat or [N, h, w, 3]
+    over a buffer of a multiple of 16 bytes that is at least `colour_words_bytes(N, h, w)` (the bytes of the tensor itself, or, for
+    a view, of its storage behind its first byte). The first N h w 3 bytes are the pictures, the pad of the last word is zero and
+    nothing behind that word is written. One launch. Returns `out`."""
+    planes = (y, cb, cr)
+    if any(t.dtype != torch.uint8 or t.dim() != 3 or not t.is_cuda for t in planes):
+        raise HipError('y, cb and cr must be uint8 [N, rows, columns] tensors on the device')
+    (h, w) = (int(size[0]), int(size[1]))
+    (hc, wc) = chroma_size(h, w)
+    n = y.shape[0]
+    (coded_h, coded_w) = _plane_pitch(y)
+    (chroma_h, chroma_w) = _plane_pitch(cb)
+    if h < 1 or w < 1 or y.shape[1] < h or y.shape[2] < w or cb.shape[1] < hc or cb.shape[2] < wc or cb.shape[0] != n or cr.shape != cb.shape \
+            or _plane_pitch(cr) != (chroma_h, chroma_w):
+        raise HipError('the planes do not hold {0} x {1} pictures: y [N, >= h, >= w], cb and cr alike [N, >= hc, >= wc]'.format(h, w))
+    if out.dtype != torch.uint8 or not out.is_contiguous() or not (out.is_cuda or out.is_pinned()) \
+            or (out.dim() != 1 and tuple(out.shape) != (n, h, w, 3)):
+        raise HipError('`out` must be a contiguous uint8 tensor, flat or [N, h, w, 3], in device or pinned host memory')
+    # the bytes the launch may write: the tensor's own, or, for a [N, h, w, 3] view of a longer buffer, what its storage holds behind it
+    room = out.numel()
+    if out.dim() != 1:
+        room = out.untyped_storage().nbytes() - out.storage_offset()
+        room -= room % 16
+    _check(_native.hip().eae_hip_colour_merge_420_words(y.data_ptr(), cb.data_ptr(), cr.data_ptr(), out.data_ptr(), room, n, h, w,
+                                                        coded_h, coded_w, chroma_h, chroma_w, _stream(y)), 'eae_hip_colour_merge_420_words')
+    return out
+
+
 # ---- SVHN float64 path (include/eae_hip.h, "SVHN path") -------------------------------------------------------------
 
 def svhn_dense(x, w, b, leaky_relu):

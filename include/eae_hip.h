@@ -742,6 +742,20 @@ int eae_hip_colour_split_420(const uint8_t* rgb, uint8_t* y, uint8_t* cb, uint8_
 int eae_hip_colour_merge_420(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint8_t* rgb_out, const uint8_t* ref_rgb,
                              uint64_t* sse, int n, int h, int w, int H, int W, int Hc, int Wc, void* stream);
 
+/* colour_merge_420_words: the planes, the top-left rule and the picture of colour_merge_420, written as the
+ *   dense [n][h][w][3] batch, flat, into dst in WHOLE aligned 16-byte words -- what a resident decoder publishes, into device or
+ *   pinned, device-mapped host memory. With B = n * h * w * 3 and K = ceil(B / 16): exactly the words 0 .. K - 1 of dst are written,
+ *   each by one 16-byte store (no narrower store reaches dst); bytes B .. 16 K - 1, the pad of the last word, are zero; nothing
+ *   behind word K - 1 is touched, so a longer dst keeps its tail. A lane owns 16 consecutive flat pixels (three words) across row and
+ *   picture ends, a block of 256 lanes 768 consecutive words, staged in LDS so that a wave's store instruction writes 1 KB of
+ *   consecutive words; ceil(K / 768) blocks, whatever the size (no cap, no loop). Every load lies inside the top-left h x w of y and
+ *   hc x wc of cb and cr. One launch, asynchronous on `stream`, no argument computed from data. Picture offsets are 64 bits wide,
+ *   everything inside a picture 32.
+ *   Refused (EAE_HIP_BAD_ARGUMENT, in front of the launch): y, cb, cr or dst NULL, everything colour_merge_420 refuses of the sizes,
+ *   a dst that is not 16-byte aligned, a dst_bytes that is not a multiple of 16 or is less than 16 K, more than 2^31 - 1 blocks. */
+int eae_hip_colour_merge_420_words(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint8_t* dst, uint64_t dst_bytes,
+                                   int n, int h, int w, int H, int W, int Hc, int Wc, void* stream);
+
 /* ==== TEST HOOKS (-DEAE_TEST_HOOKS): NOT exported by the product library lib/libeae_hip.so ====================================
  * Five entry points the test-suite needs and a deployment must not have (they change what later launches do, or only
  * exist to prove something about the kernels). Compiled into lib/libeae_hip_test.so only; tests/test_abi.py checks that
