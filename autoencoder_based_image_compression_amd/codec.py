@@ -30,6 +30,7 @@ import weakref
 import numpy
 import torch
 
+from . import colour as colour_rules
 from . import container as container_format
 from . import device as dev
 from . import pipeline
@@ -1944,8 +1945,7 @@ class BatchDecoder(object):
                     # behind the step on the slot's stream, never inside `_launch_step`, which is what a graph captures
                     ticket.decoded_event = torch.cuda.Event()
                     ticket.decoded_event.record(slot.lane.stream)
-                    ticket.reconstruction_uint8 = slot.planes[:nb_images, :self.image_size[0], :self.image_size[1]] if self.pad \
-                        else slot.planes[:nb_images]
+                    ticket.reconstruction_uint8 = self._kept(slot, nb_images)
             finally:
                 torch.cuda.set_stream(caller)
             job = _DecodeJob(ticket, slot, (slot.seq_host, (expected,)), payload_bytes, detail)
@@ -1962,6 +1962,10 @@ class BatchDecoder(object):
                 pass
             slot.free.set()
             raise
+
+    def _kept(self, slot, nb_images):
+        """`reconstruction_uint8` of a ticket (`keep_reconstruction`): what of the slot another stream reads behind `decoded_event`."""
+        return slot.planes[:nb_images, :self.image_size[0], :self.image_size[1]] if self.pad else slot.planes[:nb_images]
 
     def _plan_step(self, slot, blobs):
         """The host side of a step, into the slot's pinned head and payload -> (images, payload bytes, detail for the worker).
@@ -2068,13 +2072,17 @@ class RegionSource(object):
     """An `EAT1` (or `EAE1`) container a `RegionDecoder` cuts crops out of: a bytes-like blob or a seekable binary file object. The
     header is parsed and checked ONCE, here (`container.read_header`'s checks; of a file only the header is read); what stays is
     `header`, and per (image, tile) entry the byte offset `starts` and the byte length `sizes` of its streams in the source, int64
-    [nb_images, nb_tiles]. `read(entries)` returns the bytes of [(image, tile)] entries."""
+    [nb_images, nb_tiles]. `read(entries)` returns the bytes of [(image, tile)] entries.
+    pad: a source whose header's `crop` byte is not 0 -- images of `image_height` x `image_width` pixels, the top-left of coded planes
+    of `header['height']` x `header['width']` -- is accepted, for a `RegionDecoder(pad=True)` of that real size; False: refused."""
 
-    def __init__(self, source):
+    def __init__(self, source, pad=False):
         (self.header, self._blob) = container_format._source_header(source)
         self._source = source
         header = self.header
-        if (header['image_height'], header['image_width']) != (header['height'], header['width']):
+        self.pad = bool(pad)
+        (self.image_height, self.image_width) = (header['image_height'], header['image_width'])
+        if not self.pad and (header['image_height'], header['image_width']) != (header['height'], header['width']):
             raise ValueError('The source holds images of {0} x {1} pixels inside {2} x {3} planes (the `crop` byte of its header): '
                              '`RegionSource` / `RegionDecoder` do not crop to a real size; `container.decode_region` does.'.format(
                                  header['image_height'], header['image_width'], header['height'], header['width']))
@@ -2208,8 +2216,41 @@ def place_region(layout, y0, x0):
     return (r0, c0), placed
 
 
+def _refuse_region_request(source, image, y0, x0, layout, region, truncated_unary_length, are_bin_widths_learned, image_size=None):
+    """What `plan_region_step` refuses (ValueError) of one request by its source's header alone: nothing is read, nothing written."""
+    (h, w) = (layout['h'], layout['w'])
+    (rh, rw) = region
+    header = source.header
+    if (source.h_map, source.w_map) != (h, w):
+        raise ValueError('The source holds {0} x {1} images, the decoder was built for {2} x {3}.'.format(
+            header['height'], header['width'], 16*h, 16*w))
+    if header.get('format') != 'EAT1':
+        raise ValueError('This decoder takes EAT1 sources of `coding_tile`={0}: this is an EAE1 source, whose maps are coded whole '
+                         '(container.decode_region reads a crop out of it).'.format(layout['coding_tile']))
+    if source.coding_tile != layout['coding_tile']:
+        raise ValueError('The source was coded in tiles of {0} latents, the decoder was built with `coding_tile`={1}.'.format(
+            source.coding_tile, layout['coding_tile']))
+    if header['truncated_unary_length'] != truncated_unary_length:
+        raise ValueError('The source was coded with a truncated unary length of {0}, the decoder was built for {1}.'.format(
+            header['truncated_unary_length'], truncated_unary_length))
+    if header['are_bin_widths_learned'] != bool(are_bin_widths_learned):
+        raise ValueError('The source was written by the other kind of model (learned / fixed bin widths).')
+    if not 0 <= image < header['nb_images']:
+        raise ValueError('The source holds {0} images: there is no image {1}.'.format(header['nb_images'], image))
+    real = (header['image_height'], header['image_width'])
+    if image_size is None:
+        if real != (header['height'], header['width']):
+            raise ValueError('The source holds images of {0} x {1} pixels inside {2} x {3} planes: a decoder built without `pad` '
+                             'does not crop to a real size.'.format(real[0], real[1], header['height'], header['width']))
+    elif real != tuple(image_size):
+        raise ValueError('The source holds images of {0} x {1} pixels, the decoder was built for {2} x {3}.'.format(
+            real[0], real[1], image_size[0], image_size[1]))
+    if y0 < 0 or x0 < 0 or y0 + rh > real[0] or x0 + rw > real[1]:
+        raise ValueError('The region {0} leaves the {1} x {2} image.'.format((int(y0), int(x0), rh, rw), real[0], real[1]))
+
+
 def plan_region_step(requests, layout, head, payload, capacity, region, truncated_unary_length, are_bin_widths_learned,
-                     nb_maps=csts.NB_MAPS_3):
+                     nb_maps=csts.NB_MAPS_3, image_size=None):
     """The host side of one `RegionDecoder` step; numpy only (and the sources' own reads). requests: 1..batch_size of (RegionSource,
     image, y0, x0); layout: `region_layout`; region = (rh, rw) pixels. EVERYTHING is checked -- and every byte range is read -- before
     a byte of `head` (uint8: `region_head_layout`) or `payload` (uint8) is written: a refused step (ValueError) leaves both as they
@@ -2218,11 +2259,12 @@ def plan_region_step(requests, layout, head, payload, capacity, region, truncate
     image; a payload beyond `capacity`. Then the head is filled -- crop k's map m decodes with row k*(nb_maps + 1) + m of the table,
     its exception map with row k*(nb_maps + 1) + nb_maps; absent slots get zero bits, row -1 and crop -1, absent crops zero bin
     widths and means and rows of 0.5 -- and the placed entries' bytes go to `payload` in run order, one behind the other.
+    image_size: None, or the REAL size (h, w) of the images of a `RegionDecoder(pad=True)`, the top-left of the coded plane the
+    layout was made for: a source of another real size is refused, and a region must lie inside the real image. None: a source
+    whose real size is not its coded size (`RegionSource(pad=True)` of a padded container) is refused.
     -> (crops, payload bytes, per crop the run-order slots of its tiles in tile row-major order)."""
     requests = list(requests)
     (batch_size, n_slots) = (layout['batch_size'], layout['n_slots'])
-    (h, w) = (layout['h'], layout['w'])
-    (rh, rw) = region
     if not requests:
         raise ValueError('A step needs at least one request.')
     if len(requests) > batch_size:
@@ -2235,25 +2277,7 @@ def plan_region_step(requests, layout, head, payload, capacity, region, truncate
         for x in (image, y0, x0):
             if isinstance(x, bool) or not isinstance(x, (int, numpy.integer)):
                 raise ValueError('A request is (RegionSource, image, y0, x0) in integers.')
-        header = source.header
-        if (source.h_map, source.w_map) != (h, w):
-            raise ValueError('The source holds {0} x {1} images, the decoder was built for {2} x {3}.'.format(
-                header['height'], header['width'], 16*h, 16*w))
-        if header.get('format') != 'EAT1':
-            raise ValueError('This decoder takes EAT1 sources of `coding_tile`={0}: this is an EAE1 source, whose maps are coded whole '
-                             '(container.decode_region reads a crop out of it).'.format(layout['coding_tile']))
-        if source.coding_tile != layout['coding_tile']:
-            raise ValueError('The source was coded in tiles of {0} latents, the decoder was built with `coding_tile`={1}.'.format(
-                source.coding_tile, layout['coding_tile']))
-        if header['truncated_unary_length'] != truncated_unary_length:
-            raise ValueError('The source was coded with a truncated unary length of {0}, the decoder was built for {1}.'.format(
-                header['truncated_unary_length'], truncated_unary_length))
-        if header['are_bin_widths_learned'] != bool(are_bin_widths_learned):
-            raise ValueError('The source was written by the other kind of model (learned / fixed bin widths).')
-        if not 0 <= image < header['nb_images']:
-            raise ValueError('The source holds {0} images: there is no image {1}.'.format(header['nb_images'], image))
-        if y0 < 0 or x0 < 0 or y0 + rh > 16*h or x0 + rw > 16*w:
-            raise ValueError('The region {0} leaves the {1} x {2} image.'.format((int(y0), int(x0), rh, rw), 16*h, 16*w))
+        _refuse_region_request(source, image, y0, x0, layout, region, truncated_unary_length, are_bin_widths_learned, image_size)
         ((r0, c0), placed) = place_region(layout, int(y0), int(x0))
         payload_bytes += int(sum(source.sizes[image, t] for (t, _, _, _) in placed))
         steps.append((source, int(image), (int(y0) - 16*r0, int(x0) - 16*c0), placed))
@@ -2299,6 +2323,11 @@ def plan_region_step(requests, layout, head, payload, capacity, region, truncate
     return n, payload_bytes, crop_slots
 
 
+class _KeepNeedsDeviceCrops(ValueError, TypeError):
+    """`RegionDecoder(keep_reconstruction=True)` with the crops fetched to the host: a ValueError. Until `RegionDecoder` took the
+    keyword, passing it at all was a TypeError, and whoever caught that still does."""
+
+
 class RegionDecoder(BatchDecoder):
     """(RegionSource, image, y0, x0) requests -> uint8 crops of one fixed size, resident and pipelined: what
     `container.decode_region(source, decoder, (y0, x0, rh, rw), images=[image])[0]` computes (same bytes), with `BatchDecoder`'s
@@ -2310,16 +2339,37 @@ class RegionDecoder(BatchDecoder):
     again. Everything is checked on the host first (`plan_region_step`: ValueError, nothing written, nothing launched)."""
 
     def __init__(self, variables, are_bin_widths_learned, batch_size, h_in, w_in, truncated_unary_length, coding_tile, region,
-                 device='cuda', nb_in_flight=None, nb_streams=None, use_graphs=False, payload_capacity_bytes=None, fetch_reconstruction=True):
+                 device='cuda', nb_in_flight=None, nb_streams=None, use_graphs=False, payload_capacity_bytes=None, fetch_reconstruction=True,
+                 pad=False, keep_reconstruction=False):
         """h_in, w_in: the size of the SOURCE images, fixed for the decoder's lifetime like `coding_tile` = (th, tw) latents
         (clamped to the latent plane) and region = (rh, rw) pixels, the size of every crop. Only the window around a crop is
         synthesised (`region_window`: the region's latents and the decoder's halo), so the source may be larger than the untiled
         synthesis takes; the window must not be. At most 65,535 slots per step (`batch_size` times `region_layout`'s slots per crop).
         payload_capacity_bytes: payload bytes a step may hold (rounded up to 16); None: 16 bits per symbol of the step's slots.
         fetch_reconstruction: the crops reach pinned host memory inside the step and `result()` is a numpy view of them; False:
-        `result()` is a view of the slot's device tensor. The other arguments as `BatchDecoder`'s."""
+        `result()` is a view of the slot's device tensor. The other arguments as `BatchDecoder`'s.
+        pad: h_in x w_in is the REAL size of the source images, any positive integers (DESIGN.md sections 25, 28): the layout is that
+        of the coded size, both sides rounded up to multiples of 16, and the real image is the top-left of the coded plane, so the
+        window and the placement of a crop are what they are without `pad`. The sources are `RegionSource(..., pad=True)` of exactly
+        that real size, a region lies inside the REAL image, and `result()` is `container.decode_region`'s of the padded container.
+        False: a source whose `crop` byte is not 0 is refused.
+        keep_reconstruction: every ticket gets, at submit time, `decoded_event`, recorded on the slot's stream behind the step, and
+        `reconstruction_uint8`, the slot's crops on the device as (n, rh, rw), valid until the slot comes round again: another stream
+        waits for the event and reads them there (`ColourRegionDecoder`). The crops must then stay on the device:
+        `fetch_reconstruction=True` with it is refused (ValueError; the error is a TypeError as well, which passing this keyword was
+        before `RegionDecoder` took it)."""
+        (self.pad, self.image_size) = (bool(pad), None)
+        if keep_reconstruction and fetch_reconstruction:
+            raise _KeepNeedsDeviceCrops('`keep_reconstruction` keeps the crops on the device for another stream: it needs '
+                                        '`fetch_reconstruction=False`.')
+        if self.pad:
+            self.image_size = (container_format._positive_int(h_in, '`h_in`'), container_format._positive_int(w_in, '`w_in`'))
+            region = container_format._positive_pair(region, '`region`')
+            if region[0] > self.image_size[0] or region[1] > self.image_size[1]:
+                raise ValueError('`region` = {0} is larger than the {1} x {2} images.'.format(region, self.image_size[0], self.image_size[1]))
+            (h_in, w_in) = container_format.coded_size(*self.image_size)
         self._lay_out(batch_size, h_in, w_in, truncated_unary_length, payload_capacity_bytes, coding_tile, region)
-        self._build(variables, are_bin_widths_learned, device, nb_in_flight, nb_streams, use_graphs, fetch_reconstruction)
+        self._build(variables, are_bin_widths_learned, device, nb_in_flight, nb_streams, use_graphs, fetch_reconstruction, keep_reconstruction)
 
     def _lay_out(self, batch_size, h_in, w_in, truncated_unary_length, payload_capacity_bytes, coding_tile, region):
         coding_tile = _refuse_shape(batch_size, h_in, w_in, truncated_unary_length, coding_tile)
@@ -2357,9 +2407,13 @@ class RegionDecoder(BatchDecoder):
         """As `BatchDecoder._plan_step`; a crop's streams are those of its tiles' slots, its tiles in row-major order as
         `container.decode_region` meets them, the maps of a tile in order."""
         (crops, payload_bytes, crop_slots) = plan_region_step(requests, self._layout, slot.head_host, slot.payload_host, self.payload_capacity_bytes,
-                                                              self.region, self.truncated_unary_length, self.learned, self.nb_maps)
+                                                              self.region, self.truncated_unary_length, self.learned, self.nb_maps,
+                                                              self.image_size)
         ranges = self._slot_ranges
         return crops, payload_bytes, [[ranges[run] for run in runs] for runs in crop_slots]
+
+    def _kept(self, slot, nb_images):
+        return slot.value(nb_images)          # the crops on the device: `keep_reconstruction` came with `fetch_reconstruction=False`
 
     def _launch_latents(self, slot):
         lane = slot.lane
@@ -3428,6 +3482,228 @@ class ColourDecoder(object):
             for inner in (self.luma, self.chroma):
                 if inner is not None:
                     inner.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, traceback):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:      # interpreter shutdown: nothing left to report to
+            pass
+
+
+# ---- crops of colour pictures out of tile-indexed EAC1 containers, resident and pipelined ------------------------
+
+class ColourRegionSource(object):
+    """An `EAC1` container a `ColourRegionDecoder` cuts RGB crops out of: a bytes-like blob or a seekable binary file object. The
+    48-byte header and the three plane headers are parsed and checked ONCE, here (of a file nothing else is read: every plane is read
+    in place through a view of its byte range); what stays is `header` (`container.read_colour_header`), `nb_images`, `image_height`,
+    `image_width` and `planes`: the three `RegionSource(..., pad=True)` of Y, Cb and Cr."""
+
+    def __init__(self, source):
+        (self.header, plane_sources) = container_format.colour_source(source)
+        self.planes = tuple(RegionSource(plane, pad=True) for plane in plane_sources)
+        container_format.check_colour_planes(self.header, [plane.header for plane in self.planes])
+        (self.nb_images, self.image_height, self.image_width) = (self.header['nb_images'], self.header['image_height'],
+                                                                 self.header['image_width'])
+
+
+class ColourRegionTicket(object):
+    """Handle on one submitted `ColourRegionDecoder` step: the three plane tickets (`tickets`: Y, Cb, Cr), `nb_images` (the crops of the
+    step), and `merged_event`, recorded behind the merge: wait for it on another stream before reading the device result there."""
+
+    def __init__(self, tickets, step, region):
+        self.nb_images = tickets[0].nb_images
+        self.tickets = tuple(tickets)
+        self.merged_event = None
+        self.errors = None                    # after result(): per crop, None or the first error among its Y, Cb and Cr planes
+        self._step = step
+        self._region = region
+        self._value = None
+
+    def result(self, raise_errors=True):
+        """Blocks until the three planes and the merge are through; uint8 (nb_images, rh, rw, 3): a numpy view of the colour slot's
+        pinned buffer (`fetch_reconstruction=True`) or the device tensor, valid until the colour slot comes round
+        `ColourRegionDecoder.depth` submits later. Raises the first crop's error unless `raise_errors` is False: `errors` then says
+        which crops of the array to leave alone. Only waits: everything was enqueued by `submit`."""
+        if self.errors is None:
+            for ticket in self.tickets:
+                ticket.result(raise_errors=False)
+            self.merged_event.synchronize()
+            self.errors = [next((ticket.errors[i] for ticket in self.tickets if ticket.errors[i] is not None), None)
+                           for i in range(self.nb_images)]
+            (rh, rw) = self._region
+            buffer = self._step.host if self._step.host is not None else self._step.device
+            self._value = buffer[:self.nb_images*rh*rw*3].reshape(self.nb_images, rh, rw, 3)
+        if raise_errors:
+            for error in self.errors:
+                if error is not None:
+                    raise error
+        return self._value
+
+
+class _ColourRegionStep(object):
+    """What one colour crop step in flight owns beside the inner decoders' slots: the pinned pixel origins of its crops, int32
+    [batch][2], which the merge reads from memory, and the buffer the merge writes, whole 16-byte words of it
+    (`device.colour_merge_420_crops`), pinned or on the device; `ColourRegionDecoder` goes round `depth` of them."""
+
+    def __init__(self, decoder):
+        nbytes = dev.colour_words_bytes(decoder.batch_size, *decoder.region)
+        self.pinned_origins = torch.zeros((decoder.batch_size, 2), dtype=torch.int32).pin_memory()
+        self.origins_host = self.pinned_origins.numpy()
+        (self.pinned, self.host, self.device) = (None, None, None)
+        if decoder.fetch_reconstruction:
+            self.pinned = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+            self.host = self.pinned.numpy()
+        else:
+            self.device = torch.zeros(nbytes, dtype=torch.uint8, device=decoder.device)
+        self.merged = None                    # the event behind the last merge that used this entry
+
+
+class ColourRegionDecoder(object):
+    """(ColourRegionSource, image, y0, x0) requests -> uint8 RGB crops (n, rh, rw, 3) of one fixed size, resident and pipelined: what
+    `container.decode_colour_region(source, decoder, (y0, x0, rh, rw), images=[image])[0]` computes (same bytes). Built the way
+    `ColourDecoder` is, around two `RegionDecoder(pad=True, keep_reconstruction=True, fetch_reconstruction=False)` of batch size
+    `batch_size`: `luma` at (h, w) with `region`, `chroma` at (hc, wc) with the chroma rectangle `colour.chroma_region` gives every
+    crop of that region, whose size does not depend on where the crop lies. A colour step is one step of `luma` and two consecutive
+    steps of `chroma`, Cb then Cr, each at its crops' chroma origins; then, on a stream of this decoder's own behind the three
+    tickets' `decoded_event`s, ONE `device.colour_merge_420_crops` launch, which reads the crops' pixel origins from the ring entry's
+    pinned block and writes straight into its pinned buffer (`fetch_reconstruction`) or its device buffer. `merged_event` is
+    recorded behind it. The merge is not captured into a graph; `use_graphs` is the inner decoders'.
+
+    The ring rule, `chroma_options`, the stream budget and what a failing `submit` does are `ColourDecoder`'s:
+    depth = min(luma.nb_slots, chroma.nb_slots // 2), `submit` of step i first waits for the merge of step i - depth."""
+    CHROMA_OPTIONS = ColourDecoder.CHROMA_OPTIONS
+
+    def __init__(self, variables, are_bin_widths_learned, batch_size, h, w, truncated_unary_length, coding_tile, region, device='cuda',
+                 nb_in_flight=None, nb_streams=None, use_graphs=False, payload_capacity_bytes=None, fetch_reconstruction=True,
+                 chroma_options=None):
+        (self.luma, self.chroma, self._merge_stream, self._closed) = (None, None, None, False)
+        chroma_options = dict(chroma_options or {})
+        for name in chroma_options:
+            if name not in self.CHROMA_OPTIONS:
+                raise ValueError('`{0}` is not an option of the chroma decoder alone: `chroma_options` takes {1}.'.format(
+                    name, ', '.join(self.CHROMA_OPTIONS)))
+        self.batch_size = container_format._positive_int(batch_size, '`batch_size`')
+        (self.h, self.w) = (container_format._positive_int(h, '`h`'), container_format._positive_int(w, '`w`'))
+        (self.hc, self.wc) = dev.chroma_size(self.h, self.w)
+        self.region = container_format._positive_pair(region, '`region`')
+        if self.region[0] > self.h or self.region[1] > self.w:
+            raise ValueError('`region` = {0} is larger than the {1} x {2} pictures.'.format(self.region, self.h, self.w))
+        self.chroma_region = dev.chroma_region_size((self.h, self.w), self.region)
+        self.fetch_reconstruction = bool(fetch_reconstruction)
+        for_luma = {'nb_in_flight': nb_in_flight, 'nb_streams': nb_streams, 'payload_capacity_bytes': payload_capacity_bytes}
+        for_chroma = dict(for_luma, nb_in_flight=None)      # chroma's slots follow the luminance decoder's unless given
+        for_chroma.update({name: value for (name, value) in chroma_options.items() if name != 'truncated_unary_length'})
+        if os.environ.get('EAE_IGNORE_HW_QUEUES') != '1':
+            # one stream is the merge's; the two decoders share the rest
+            (luma_streams, chroma_streams, _) = stream_budget(DECODER_STREAMS, DECODER_STREAMS, copies=1)
+            if for_luma['nb_streams'] is None:
+                for_luma['nb_streams'] = luma_streams
+            if for_chroma['nb_streams'] is None:
+                for_chroma['nb_streams'] = chroma_streams
+        shared = {'device': device, 'use_graphs': use_graphs, 'fetch_reconstruction': False, 'pad': True, 'keep_reconstruction': True}
+        try:
+            self.luma = RegionDecoder(variables, are_bin_widths_learned, self.batch_size, self.h, self.w, truncated_unary_length,
+                                      coding_tile, self.region, **shared, **for_luma)
+            if for_chroma['nb_in_flight'] is None:
+                for_chroma['nb_in_flight'] = 2*self.luma.nb_in_flight      # two inner steps per colour step
+            self.chroma = RegionDecoder(variables, are_bin_widths_learned, self.batch_size, self.hc, self.wc,
+                                        chroma_options.get('truncated_unary_length', truncated_unary_length), coding_tile,
+                                        self.chroma_region, **shared, **for_chroma)
+            self.device = self.luma.device
+            self.depth = min(self.luma.nb_slots, self.chroma.nb_slots//2)
+            if self.depth < 1:
+                raise ValueError('the chroma decoder has {0} slot(s): it cannot hold the two steps (Cb, Cr) of one colour step.'.format(
+                    self.chroma.nb_slots))
+            self._steps = [_ColourRegionStep(self) for _ in range(self.depth)]
+            self._merge_stream = torch.cuda.Stream(device=self.device)
+            self._index = 0
+        except BaseException:
+            self.close()
+            raise
+
+    def _plan(self, requests):
+        """The host checks of a step -> (pixel origins int32 [n][2], the requests of the Y, Cb and Cr steps). Raises ValueError for
+        what the headers of the sources alone refuse; nothing is read, written or launched."""
+        requests = list(requests)
+        if not requests:
+            raise ValueError('A step needs at least one request.')
+        if len(requests) > self.batch_size:
+            raise ValueError('{0} requests, a step of this decoder takes {1} at most.'.format(len(requests), self.batch_size))
+        origins = numpy.zeros((len(requests), 2), dtype=numpy.int32)
+        planes = ([], [], [])
+        for (k, request) in enumerate(requests):
+            if not isinstance(request, (tuple, list)) or len(request) != 4 or not isinstance(request[0], ColourRegionSource):
+                raise ValueError('A request is (ColourRegionSource, image, y0, x0).')
+            (source, image, y0, x0) = request
+            for x in (image, y0, x0):
+                if isinstance(x, bool) or not isinstance(x, (int, numpy.integer)):
+                    raise ValueError('A request is (ColourRegionSource, image, y0, x0) in integers.')
+            (image, y0, x0) = (int(image), int(y0), int(x0))
+            if (source.image_height, source.image_width) != (self.h, self.w):
+                raise ValueError('The source holds {0} x {1} pictures, the decoder was built for {2} x {3}.'.format(
+                    source.image_height, source.image_width, self.h, self.w))
+            if not 0 <= image < source.nb_images:
+                raise ValueError('The source holds {0} pictures: there is no picture {1}.'.format(source.nb_images, image))
+            if y0 < 0 or x0 < 0 or y0 + self.region[0] > self.h or x0 + self.region[1] > self.w:
+                raise ValueError('The region {0} leaves the {1} x {2} picture.'.format((y0, x0) + self.region, self.h, self.w))
+            (_, (cy0, cx0)) = colour_rules.chroma_region(self.h, self.w, self.region, y0, x0)
+            origins[k] = (y0, x0)
+            for (plane, inner, at, requests_of_plane) in zip(source.planes, (self.luma, self.chroma, self.chroma),
+                                                             ((y0, x0), (cy0, cx0), (cy0, cx0)), planes):
+                _refuse_region_request(plane, image, at[0], at[1], inner._layout, inner.region, inner.truncated_unary_length, inner.learned,
+                                       inner.image_size)
+                requests_of_plane.append((plane, image, at[0], at[1]))
+        return origins, planes
+
+    def submit(self, requests):
+        """1..batch_size requests (ColourRegionSource, image, y0, x0), the sources the same or not -> ColourRegionTicket, whose
+        `result()` is uint8 (n, rh, rw, 3), crop k the pixels [y0, y0 + rh) x [x0, x0 + rw) of its picture. Everything the headers
+        say is checked on the host first (ValueError, nothing launched; a payload beyond an inner decoder's capacity is refused by that
+        decoder's own plan, and `submit` then drains before it re-raises); then everything is enqueued, and the host waits only for
+        free inner slots and for the merge of the step `depth` submits ago."""
+        if self._closed:
+            raise RuntimeError('this decoder is closed')
+        (origins, planes) = self._plan(requests)
+        step = self._steps[self._index % self.depth]
+        self._index += 1
+        if step.merged is not None:
+            # the merge that wrote this entry, read its origins and the inner crops that come round with this step, is through
+            step.merged.synchronize()
+        try:
+            return self._enqueue(step, origins, planes)
+        except BaseException:
+            # part of the step may be enqueued (an inner submit raised): wait for all of it, so that the next step finds idle rings
+            step.merged = None
+            try:
+                self.drain()
+            except Exception:                 # the device itself is in trouble: the next submit will say so
+                pass
+            raise
+
+    def _enqueue(self, step, origins, planes):
+        """The launches of one colour step on ring entry `step` (class docstring) -> its ticket."""
+        n = len(origins)
+        step.origins_host[:n] = origins
+        tickets = (self.luma.submit(planes[0]), self.chroma.submit(planes[1]), self.chroma.submit(planes[2]))
+        ticket = ColourRegionTicket(tickets, step, self.region)
+        with torch.cuda.stream(self._merge_stream):
+            for inner in tickets:
+                self._merge_stream.wait_event(inner.decoded_event)
+            dev.colour_merge_420_crops(*(inner.reconstruction_uint8 for inner in tickets), (self.h, self.w), step.pinned_origins[:n],
+                                       out=step.pinned if step.pinned is not None else step.device)
+            step.merged = torch.cuda.Event()
+            step.merged.record()
+        ticket.merged_event = step.merged
+        return ticket
+
+    (drain, close) = (ColourDecoder.drain, ColourDecoder.close)          # the same two inner decoders and merge stream
 
     def __enter__(self):
         return self

@@ -80,6 +80,57 @@ def merge_420_numpy(y, cb, cr):
     return numpy.clip(rgb, 0, 255).astype(numpy.uint8)
 
 
+def chroma_region(h, w, region, y0, x0):
+    """((rch, rcw), (cy0, cx0)): the chroma rectangle the crop of region = (rh, rw) pixels at pixel (y0, x0) of an h x w picture needs
+    (DESIGN.md section 28). Its SIZE depends on the region and the picture alone -- half the region, the sample a crop that starts at
+    an odd pixel shares with its neighbour, and one sample on either side for the 3:1 neighbours, at most the plane --, so a resident
+    decoder is built for it; its origin is one sample in front of the crop's first, clamped into the plane. Every sample
+    `merge_420_numpy` reads for the crop's pixels, the clamped neighbours included, lies inside."""
+    (rh, rw) = (int(region[0]), int(region[1]))
+    (y0, x0) = (int(y0), int(x0))
+    if rh < 1 or rw < 1 or y0 < 0 or x0 < 0 or y0 + rh > h or x0 + rw > w:
+        raise ValueError('The region {0} is empty or leaves the {1} x {2} picture.'.format((y0, x0, rh, rw), h, w))
+    (hc, wc) = chroma_size(h, w)
+    (rch, rcw) = (min(hc, rh//2 + 3), min(wc, rw//2 + 3))
+    return ((rch, rcw), (min(max((y0 >> 1) - 1, 0), hc - rch), min(max((x0 >> 1) - 1, 0), wc - rcw)))
+
+
+def merge_420_region_numpy(y_crop, cb_crop, cr_crop, image_size, origins):
+    """uint8 y_crop (n, rh, rw), cb_crop and cr_crop (n, rch, rcw), origins int (n, 2) -> uint8 (n, rh, rw, 3): crop k is the pixels
+    [y0, y0 + rh) x [x0, x0 + rw), (y0, x0) = origins[k], of an image_size = (h, w) picture, its chroma crops the rectangle
+    `chroma_region` names. The samples, the parity of the weights and the clamp of the neighbours are those of the pixel's position
+    in the PICTURE (`merge_420_numpy`); every chroma index is then shifted by the crop's chroma origin. Equal to
+    `merge_420_numpy(full planes)[k, y0:y0 + rh, x0:x0 + rw]` for crops cut out of full planes."""
+    (y_crop, cb_crop, cr_crop) = (numpy.asarray(plane) for plane in (y_crop, cb_crop, cr_crop))
+    if y_crop.dtype != numpy.uint8 or cb_crop.dtype != numpy.uint8 or cr_crop.dtype != numpy.uint8:
+        raise TypeError('The planes must be `numpy.uint8`.')
+    if y_crop.ndim != 3 or 0 in y_crop.shape:
+        raise ValueError('`y_crop` must be (n, rh, rw) and hold a pixel.')
+    (n, rh, rw) = y_crop.shape
+    (h, w) = (int(image_size[0]), int(image_size[1]))
+    (hc, wc) = chroma_size(h, w)
+    origins = numpy.asarray(origins)
+    if origins.shape != (n, 2) or origins.dtype.kind not in 'iu':
+        raise ValueError('`origins` must be (n, 2) in integers.')
+    out = numpy.empty((n, rh, rw, 3), dtype=numpy.uint8)
+    for k in range(n):
+        (y0, x0) = (int(origins[k, 0]), int(origins[k, 1]))
+        ((rch, rcw), (cy0, cx0)) = chroma_region(h, w, (rh, rw), y0, x0)
+        if cb_crop.shape != (n, rch, rcw) or cr_crop.shape != cb_crop.shape:
+            raise ValueError('`cb_crop` and `cr_crop` must be (n, {0}, {1}): `chroma_region`.'.format(rch, rcw))
+        (r, c) = (y0 + numpy.arange(rh), x0 + numpy.arange(rw))
+        (i, j) = (r >> 1, c >> 1)
+        i2 = numpy.clip(i + numpy.where(r & 1, 1, -1), 0, hc - 1)
+        j2 = numpy.clip(j + numpy.where(c & 1, 1, -1), 0, wc - 1)
+        (i, i2, j, j2) = ((i - cy0)[:, None], (i2 - cy0)[:, None], (j - cx0)[None, :], (j2 - cx0)[None, :])
+        scaled = 298*(y_crop[k].astype(numpy.int32) - 16)
+        (u, v) = ((9*p[i, j] + 3*p[i, j2] + 3*p[i2, j] + p[i2, j2] + 8 >> 4) - 128
+                  for p in (cb_crop[k].astype(numpy.int32), cr_crop[k].astype(numpy.int32)))
+        rgb = numpy.stack(((scaled + 409*v + 128) >> 8, (scaled - 100*u - 208*v + 128) >> 8, (scaled + 516*u + 128) >> 8), axis=-1)
+        out[k] = numpy.clip(rgb, 0, 255)
+    return out
+
+
 def sse_rgb_numpy(rgb, rec):
     """int64 (N,): the exact squared error of every picture over its 3 h w samples."""
     rgb = _checked_rgb(rgb, 'rgb')

@@ -946,7 +946,11 @@ def decode_region(source, decoder, region, images=None, tile=None, tiles_per_cal
     region's sub-plane are entropy-decoded (for an EAE1 source: the whole maps), and only the sub-plane is synthesised.
     tile=(th, tw): synthesise the sub-plane through windows (pipeline.DeviceDecoder.__call__)."""
     tiles_per_call = _positive_int(tiles_per_call, '`tiles_per_call`')
-    (header, plan, chunks) = fetch_region(source, region, images)
+    return _decode_fetched(*fetch_region(source, region, images), decoder, tile, tiles_per_call)
+
+
+def _decode_fetched(header, plan, chunks, decoder, tile=None, tiles_per_call=TILES_PER_CALL):
+    """The device side of decode_region, of what fetch_region returned."""
     _require_kind(header, decoder)
     device = decoder.device
     (r0, r1, c0, c1) = plan['sub_plane']
@@ -1011,6 +1015,11 @@ def read_colour_header(blob):
     """The 48 bytes in front of the plane blobs of an EAC1 blob -> {'nb_images', 'image_height', 'image_width', 'subsampling',
     'plane_bytes' (three), 'plane_offsets' (three)}. Raises ValueError on anything but a whole, well-formed EAC1 header whose three
     lengths add up to the blob's."""
+    return _colour_header(blob, len(blob))
+
+
+def _colour_header(blob, total_length):
+    """`read_colour_header` of a container of `total_length` bytes of which `blob` holds the first 48 at least."""
     if len(blob) < _COLOUR_HEADER.size:
         raise ValueError('The colour container is truncated.')
     (magic, version, flags, nb_images, height, width, subsampling, reserved, *plane_bytes) = _COLOUR_HEADER.unpack_from(blob, 0)
@@ -1024,7 +1033,7 @@ def read_colour_header(blob):
         raise ValueError('The chroma subsampling {} is not supported: only 4:2:0 (1) is.'.format(subsampling))
     if nb_images < 1 or height < 1 or width < 1:
         raise ValueError('The colour container holds no pixel.')
-    if min(plane_bytes) < 1 or _COLOUR_HEADER.size + sum(plane_bytes) != len(blob):
+    if min(plane_bytes) < 1 or _COLOUR_HEADER.size + sum(plane_bytes) != total_length:
         raise ValueError('The plane lengths of the colour container do not add up to its length.')
     offsets = (_COLOUR_HEADER.size, _COLOUR_HEADER.size + plane_bytes[0], _COLOUR_HEADER.size + plane_bytes[0] + plane_bytes[1])
     return {'nb_images': nb_images, 'image_height': height, 'image_width': width, 'subsampling': subsampling,
@@ -1081,3 +1090,84 @@ def decode_colour_images(blob, decoder, tile=None):
     planes = [torch.from_numpy(decode_images(plane_blob, decoder, tile=tile)).to(decoder.device) for plane_blob in plane_blobs]
     (rgb, _) = dev.colour_merge_420(*planes, (header['image_height'], header['image_width']))
     return rgb.cpu().numpy()
+
+
+# ---- crops of colour pictures ---------------------------------------------------------------------------------
+
+class _FileRange(object):
+    """The bytes [start, start + length) of a seekable binary file as a read-only seekable file of their own: what `_source_header`,
+    `_read_ranges` and `codec.RegionSource` need of a file, so that a plane blob inside an EAC1 file is read in place."""
+
+    def __init__(self, f, start, length):
+        (self._file, self._start, self._length, self._pos) = (f, int(start), int(length), 0)
+
+    def seek(self, offset, whence=0):
+        pos = int(offset) + (0 if whence == 0 else (self._pos if whence == 1 else self._length))
+        if whence not in (0, 1, 2) or pos < 0:
+            raise ValueError('A seek in front of the range, or of an unknown kind.')
+        self._pos = pos
+        return pos
+
+    def tell(self):
+        return self._pos
+
+    def read(self, count=-1):
+        left = max(self._length - self._pos, 0)
+        count = left if count is None or count < 0 else min(int(count), left)
+        self._file.seek(self._start + self._pos)
+        data = self._file.read(count)
+        self._pos += len(data)
+        return data
+
+
+def colour_source(source):
+    """An EAC1 container given as a bytes-like blob or as a seekable binary file object -> (`read_colour_header`'s header, the three
+    plane sources Y, Cb, Cr), each a source `fetch_region`, `decode_region` and `codec.RegionSource` take: a memoryview of the plane's
+    bytes, or a view of its byte range of the file. Of a file only the 48 bytes of the header are read here."""
+    if not hasattr(source, 'read'):
+        blob = memoryview(source).cast('B')
+        header = _colour_header(blob, len(blob))
+        return header, tuple(blob[start:start + count] for (start, count) in zip(header['plane_offsets'], header['plane_bytes']))
+    source.seek(0, 2)
+    total = source.tell()
+    header = _colour_header(_read_at(source, 0, min(_COLOUR_HEADER.size, total)), total)
+    return header, tuple(_FileRange(source, start, count) for (start, count) in zip(header['plane_offsets'], header['plane_bytes']))
+
+
+def check_colour_planes(header, plane_headers):
+    """`_check_planes` on parsed plane headers: every plane of an EAC1 container holds the header's image count at its plane's real
+    size. Raises ValueError."""
+    sizes = _plane_sizes((header['image_height'], header['image_width']))
+    for (name, size, fields) in zip(_PLANE_NAMES, sizes, plane_headers):
+        if fields['nb_images'] != header['nb_images']:
+            raise ValueError('The {0} plane holds {1} images, not {2}.'.format(name, fields['nb_images'], header['nb_images']))
+        if (fields['image_height'], fields['image_width']) != size:
+            raise ValueError('The {0} plane of a {1} x {2} picture is {3} x {4}, not {5} x {6}.'.format(
+                name, header['image_height'], header['image_width'], size[0], size[1], fields['image_height'], fields['image_width']))
+
+
+def decode_colour_region(source, decoder, region, images=None, tile=None):
+    """The pixels region = (y0, x0, height, width) of the pictures `images` (indices, default all) of an EAC1 container -> uint8
+    [N_sel, height, width, 3] RGB, equal to decode_colour_images(blob, decoder)[images, y0:y0 + height, x0:x0 + width].
+    `source`: a bytes-like EAC1 blob, or a seekable binary file object, of which only the 48-byte header, the three plane headers
+    and the byte ranges the three `region_plan`s name are read (an EAE1 plane, whose maps are coded whole, is read whole).
+    `decode_region` on Y at `region` and on Cb and Cr at `colour.chroma_region`'s rectangle, then one
+    `device.colour_merge_420_crops` launch (`colour.merge_420_region_numpy`). Raises ValueError for a region that is empty or leaves
+    the picture. tile: as `decode_region`'s."""
+    (header, planes) = colour_source(source)
+    (h, w) = (header['image_height'], header['image_width'])
+    if not isinstance(region, (tuple, list)) or len(region) != 4 or \
+            any(not isinstance(x, numbers.Integral) or isinstance(x, bool) for x in region):
+        raise ValueError('`region` must be (y0, x0, height, width) in integers.')
+    (y0, x0, rh, rw) = (int(x) for x in region)
+    ((rch, rcw), (cy0, cx0)) = colour_rules.chroma_region(h, w, (rh, rw), y0, x0)
+    chroma = (cy0, cx0, rch, rcw)
+    # everything is read and checked before anything is decoded
+    fetched = [fetch_region(plane, where, images) for (plane, where) in zip(planes, ((y0, x0, rh, rw), chroma, chroma))]
+    check_colour_planes(header, [plane_header for (plane_header, _, _) in fetched])
+    crops = [torch.from_numpy(numpy.ascontiguousarray(_decode_fetched(*plane, decoder, tile))).to(decoder.device) for plane in fetched]
+    n = crops[0].shape[0]
+    origins = torch.tensor([[y0, x0]]*n, dtype=torch.int32, device=decoder.device)
+    out = torch.empty(dev.colour_words_bytes(n, rh, rw), dtype=torch.uint8, device=decoder.device)
+    dev.colour_merge_420_crops(*crops, (h, w), origins, out)
+    return out[:n*rh*rw*3].view(n, rh, rw, 3).cpu().numpy()

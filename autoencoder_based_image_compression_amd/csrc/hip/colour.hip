@@ -332,6 +332,145 @@ __global__ __launch_bounds__(256) void colour_merge_words_kernel(const uint8_t* 
     }
 }
 
+// ---- the merge of crops ----------------------------------------------------------------------------------------
+// colour_merge_words_kernel for crops of a picture: y is dense [n][rh][rw], crop k the pixels at (y0, x0) = origins[k] of an h x w
+// picture, cb and cr dense [n][rch][rcw], the chroma rectangle colour.chroma_region names for it, whose origin (cy0, cx0) the kernel
+// derives from (y0, x0) by the same rule. The samples, the parity of the weights and the clamp of the neighbours are those of the
+// pixel's position in the PICTURE (y0 + r, x0 + c against hc, wc); every chroma index is then shifted by (cy0, cx0). The 12-byte
+// windows of the fast path reach up to three samples further than the 16 pixels need, so a run is loaded as a run only where it lies
+// inside the crop's own chroma row and byte by byte, clamped into that row, elsewhere: nothing outside the three dense inputs is read.
+struct CropShape {
+    uint32_t n, hc, wc;                // crops; the real size of the picture's chroma planes
+    uint32_t rh, rw, rch, rcw;         // the size of a crop and of its chroma rectangle
+    uint32_t last_y0, last_x0;         // h - rh, w - rw: the last origin inside the picture
+};
+
+// colour.chroma_region's origin along one axis: one sample in front of the crop's first, clamped into the plane
+__device__ __forceinline__ uint32_t chroma_origin(uint32_t origin, uint32_t size, uint32_t crop) {
+    const uint32_t first = origin >> 1, start = first > 0u ? first - 1u : 0u;
+    return start < size - crop ? start : size - crop;
+}
+
+// Four bytes of one row of a chroma crop (`width` samples that start at column `origin` of a plane `plane_width` wide), at the PLANE's
+// columns first .. first + 3 clamped to [0, plane_width): a run where all four lie in the crop's row; a column outside the row -- never
+// one the 16 pixels need -- reads the row's nearest sample
+__device__ __forceinline__ uint32_t crop_run4(const uint8_t* line, uint32_t width, uint32_t plane_width, uint32_t origin, int first) {
+    const int local = first - (int)origin;
+    if (local >= 0 && (uint32_t)local + 4u <= width) return load_run4(line, line + width, line + local);
+    uint32_t v = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int column = first + k;
+        const int at = (column < 0 ? 0 : ((uint32_t)column < plane_width ? column : (int)plane_width - 1)) - (int)origin;
+        v |= (uint32_t)line[at < 0 ? 0 : ((uint32_t)at < width ? (uint32_t)at : width - 1u)] << (8 * k);
+    }
+    return v;
+}
+
+// Pixel (r, c) of the crop at (y0, x0), chroma origin (cy0, cx0), from bytes: r | g << 8 | b << 16
+__device__ __forceinline__ uint32_t merge_crop_pixel(const uint8_t* luma, const uint8_t* plane_b, const uint8_t* plane_r, uint32_t r, uint32_t c,
+                                                     uint32_t y0, uint32_t x0, uint32_t cy0, uint32_t cx0, const CropShape& s) {
+    const uint32_t row = y0 + r, column = x0 + c, i = row >> 1, j = column >> 1;
+    const uint32_t i2 = (row & 1u) ? (i + 1u < s.hc ? i + 1u : s.hc - 1u) : (i > 0u ? i - 1u : 0u);
+    const uint32_t j2 = (column & 1u) ? (j + 1u < s.wc ? j + 1u : s.wc - 1u) : (j > 0u ? j - 1u : 0u);
+    const uint32_t near = (i - cy0) * s.rcw, far = (i2 - cy0) * s.rcw, here = j - cx0, there = j2 - cx0;
+    const int c_b = (9 * (int)plane_b[near + here] + 3 * (int)plane_b[near + there] + 3 * (int)plane_b[far + here] + (int)plane_b[far + there] + 8) >> 4;
+    const int c_r = (9 * (int)plane_r[near + here] + 3 * (int)plane_r[near + there] + 3 * (int)plane_r[far + here] + (int)plane_r[far + there] + 8) >> 4;
+    return bt601_inverse((int)luma[r * s.rw + c], c_b, c_r);
+}
+
+__global__ __launch_bounds__(256) void colour_merge_crops_kernel(const uint8_t* __restrict__ y, const uint8_t* __restrict__ cb,
+                                                                 const uint8_t* __restrict__ cr, const int32_t* __restrict__ origins,
+                                                                 u32x4* __restrict__ dst, CropShape s, uint64_t pixels, uint64_t words) {
+    __shared__ u32x4 tile[WORDS_PER_BLOCK];
+    const uint64_t first = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * WORDS_LANE_PIXELS;
+    u32x4* mine = tile + 3u * threadIdx.x;
+    if (first >= pixels) {                              // behind the batch: zero bytes (stored only where the last word reaches)
+        const u32x4 zero = {0u, 0u, 0u, 0u};
+        mine[0] = zero, mine[1] = zero, mine[2] = zero;
+    } else {
+        const uint32_t crop_pixels = s.rh * s.rw, chroma_pixels = s.rch * s.rcw;
+        uint64_t img = first / crop_pixels;
+        const uint32_t inside = (uint32_t)(first - img * crop_pixels);
+        uint32_t r = inside / s.rw, c = inside - r * s.rw;
+        // (an origin outside the picture is the host's to refuse; clamped here, so that even then no load leaves the inputs)
+        uint32_t y0 = min((uint32_t)origins[2u * img], s.last_y0), x0 = min((uint32_t)origins[2u * img + 1u], s.last_x0);
+        uint32_t cy0 = chroma_origin(y0, s.hc, s.rch), cx0 = chroma_origin(x0, s.wc, s.rcw);
+        const uint8_t* luma = y + img * crop_pixels;
+        const uint8_t* plane_b = cb + img * chroma_pixels;
+        const uint8_t* plane_r = cr + img * chroma_pixels;
+        if (c + WORDS_LANE_PIXELS <= s.rw) {            // one row of the crop holds all 16
+            const uint32_t row = y0 + r, column = x0 + c, i = row >> 1;
+            const uint32_t i2 = (row & 1u) ? (i + 1u < s.hc ? i + 1u : s.hc - 1u) : (i > 0u ? i - 1u : 0u);
+            const uint32_t near_row = (i - cy0) * s.rcw, far_row = (i2 - cy0) * s.rcw;
+            const int first_column = (int)(column >> 1) - 1;
+            uint32_t near[3], far[3];
+            int c_b[17], c_r[17];
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                near[t] = crop_run4(plane_b + near_row, s.rcw, s.wc, cx0, first_column + 4 * t);
+                far[t] = crop_run4(plane_b + far_row, s.rcw, s.wc, cx0, first_column + 4 * t);
+            }
+            upsample_row16(near, far, c_b);
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                near[t] = crop_run4(plane_r + near_row, s.rcw, s.wc, cx0, first_column + 4 * t);
+                far[t] = crop_run4(plane_r + far_row, s.rcw, s.wc, cx0, first_column + 4 * t);
+            }
+            upsample_row16(near, far, c_r);
+            const uint8_t* line = luma + r * s.rw;
+            const bool odd = (column & 1u) != 0u;
+            uint32_t out[12];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const uint32_t four = load_run4(line, line + s.rw, line + c + 4 * g);
+                uint32_t p[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int m = 4 * g + k;
+                    p[k] = bt601_inverse((int)((four >> (8 * k)) & 255u), odd ? c_b[m + 1] : c_b[m], odd ? c_r[m + 1] : c_r[m]);
+                }
+                out[3 * g] = p[0] | (p[1] << 24);
+                out[3 * g + 1] = (p[1] >> 8) | (p[2] << 16);
+                out[3 * g + 2] = (p[2] >> 16) | (p[3] << 8);
+            }
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                u32x4 word;
+                word.x = out[4 * t], word.y = out[4 * t + 1], word.z = out[4 * t + 2], word.w = out[4 * t + 3];
+                mine[t] = word;
+            }
+        } else {                                        // a row end, a crop end or the end of the batch inside the 16: by pixels
+            uint8_t* bytes = reinterpret_cast<uint8_t*>(mine);
+            for (uint32_t k = 0; k < WORDS_LANE_PIXELS; ++k) {
+                uint32_t p = 0;
+                if (first + k < pixels) {
+                    p = merge_crop_pixel(luma, plane_b, plane_r, r, c, y0, x0, cy0, cx0, s);
+                    if (++c == s.rw) {
+                        c = 0;
+                        if (++r == s.rh) {
+                            r = 0, ++img;
+                            if (img < s.n) {            // the next crop has an origin of its own; behind the last one nothing is read
+                                y0 = min((uint32_t)origins[2u * img], s.last_y0), x0 = min((uint32_t)origins[2u * img + 1u], s.last_x0);
+                                cy0 = chroma_origin(y0, s.hc, s.rch), cx0 = chroma_origin(x0, s.wc, s.rcw);
+                                luma = y + img * crop_pixels, plane_b = cb + img * chroma_pixels, plane_r = cr + img * chroma_pixels;
+                            }
+                        }
+                    }
+                }
+                bytes[3u * k] = (uint8_t)p, bytes[3u * k + 1u] = (uint8_t)(p >> 8), bytes[3u * k + 2u] = (uint8_t)(p >> 16);
+            }
+        }
+    }
+    __syncthreads();
+    const uint64_t base = (uint64_t)blockIdx.x * WORDS_PER_BLOCK;
+#pragma unroll
+    for (uint32_t t = 0; t < 3; ++t) {
+        const uint64_t word = base + t * 256u + threadIdx.x;
+        if (word < words) dst[word] = tile[t * 256u + threadIdx.x];
+    }
+}
+
 }  // namespace
 
 extern "C" int eae_hip_colour_split_420(const uint8_t* rgb, uint8_t* y, uint8_t* cb, uint8_t* cr, int n, int h, int w, void* stream) {
@@ -367,6 +506,31 @@ extern "C" int eae_hip_colour_merge_420_words(const uint8_t* y, const uint8_t* c
     const uint64_t blocks = (words + WORDS_PER_BLOCK - 1u) / WORDS_PER_BLOCK;          // one block per 768 words, whatever the size
     if (blocks > 0x7FFFFFFFull) return EAE_HIP_BAD_ARGUMENT;
     hipLaunchKernelGGL(colour_merge_words_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, y, cb, cr,
+                       reinterpret_cast<u32x4*>(dst), s, pixels, words);
+    EAE_HIP_CHECK_LAUNCH();
+    return EAE_HIP_OK;
+}
+
+extern "C" int eae_hip_colour_merge_420_crops(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, const int32_t* origins, uint8_t* dst,
+                                              uint64_t dst_bytes, int n, int h, int w, int rh, int rw, int rch, int rcw, void* stream) {
+    if (!y || !cb || !cr || !origins || !dst || n <= 0 || h <= 0 || w <= 0 || rh <= 0 || rw <= 0 || rh > h || rw > w) return EAE_HIP_BAD_ARGUMENT;
+    // colour_shape's limits: everything inside a picture, and so inside a crop, is addressed with 32 bits
+    if ((uint64_t)h * (uint64_t)w * 3u > 0xFFFFFFFFull) return EAE_HIP_BAD_ARGUMENT;
+    const int64_t hc = ((int64_t)h + 1) / 2, wc = ((int64_t)w + 1) / 2;
+    // colour.chroma_region's size, which the host cut the chroma crops to
+    const int64_t need_rch = hc < (int64_t)rh / 2 + 3 ? hc : (int64_t)rh / 2 + 3, need_rcw = wc < (int64_t)rw / 2 + 3 ? wc : (int64_t)rw / 2 + 3;
+    if ((int64_t)rch != need_rch || (int64_t)rcw != need_rcw) return EAE_HIP_BAD_ARGUMENT;
+    const uint64_t pixels = (uint64_t)n * (uint64_t)rh * (uint64_t)rw;
+    const uint64_t words = (pixels * 3u + 15u) / 16u;
+    // whole aligned words, and room for every one of them: the last word is written whole, pad bytes included
+    if ((((uintptr_t)dst) & 15u) || (((uintptr_t)origins) & 3u) || (dst_bytes & 15u) || dst_bytes / 16u < words) return EAE_HIP_BAD_ARGUMENT;
+    const uint64_t blocks = (words + WORDS_PER_BLOCK - 1u) / WORDS_PER_BLOCK;          // one block per 768 words, whatever the size
+    if (blocks > 0x7FFFFFFFull) return EAE_HIP_BAD_ARGUMENT;
+    CropShape s;
+    s.n = (uint32_t)n, s.hc = (uint32_t)hc, s.wc = (uint32_t)wc;
+    s.rh = (uint32_t)rh, s.rw = (uint32_t)rw, s.rch = (uint32_t)rch, s.rcw = (uint32_t)rcw;
+    s.last_y0 = (uint32_t)(h - rh), s.last_x0 = (uint32_t)(w - rw);
+    hipLaunchKernelGGL(colour_merge_crops_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, y, cb, cr, origins,
                        reinterpret_cast<u32x4*>(dst), s, pixels, words);
     EAE_HIP_CHECK_LAUNCH();
     return EAE_HIP_OK;

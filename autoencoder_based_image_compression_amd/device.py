@@ -1674,6 +1674,48 @@ def colour_merge_420_words(y, cb, cr, size, out):
     return out
 
 
+def chroma_region_size(size, region):
+    """(rch, rcw): the size of the chroma rectangle `colour.chroma_region` gives a crop of region = (rh, rw) pixels out of a picture
+    of size = (h, w), wherever the crop lies: half the region and three samples, at most the chroma plane."""
+    (hc, wc) = chroma_size(*size)
+    return (min(hc, int(region[0])//2 + 3), min(wc, int(region[1])//2 + 3))
+
+
+def colour_merge_420_crops(y, cb, cr, image_size, origins, out):
+    """Crops of planes -> crops of RGB pictures: `colour.merge_420_region_numpy`, bit for bit. y uint8
+    [N, rh, rw], cb and cr uint8 [N, rch, rcw] with (rch, rcw) = `chroma_region_size(image_size, (rh, rw))`, contiguous, on the
+    device: crop k the pixels at origins[k] = (y0, x0) of a picture of image_size = (h, w), its chroma crops the rectangle
+    `colour.chroma_region` names, whose origin the kernel derives itself. origins: int32 [N, 2], contiguous, on the device or in pinned
+    host memory; the kernel reads it, so a launch's arguments do not depend on the placement. Every crop must lie inside the picture
+    (0 <= y0 <= h - rh, 0 <= x0 <= w - rw): the caller's to ensure, nothing here reads `origins`.
+    `out` as `colour_merge_420_words`': a contiguous uint8 tensor in device or pinned host memory, 16-byte aligned, flat or
+    [N, rh, rw, 3] over a buffer of a multiple of 16 bytes that is at least `colour_words_bytes(N, rh, rw)`; the first N rh rw 3
+    bytes are the crops, the pad of the last word is zero and nothing behind that word is written. One launch. Returns `out`."""
+    planes = (y, cb, cr)
+    if any(t.dtype != torch.uint8 or t.dim() != 3 or not t.is_cuda or not t.is_contiguous() for t in planes):
+        raise HipError('y, cb and cr must be contiguous uint8 [N, rows, columns] tensors on the device')
+    (h, w) = (int(image_size[0]), int(image_size[1]))
+    (n, rh, rw) = y.shape
+    if h < 1 or w < 1 or n < 1 or not (1 <= rh <= h and 1 <= rw <= w):
+        raise HipError('the crops [N, {0}, {1}] are empty or larger than the {2} x {3} picture'.format(rh, rw, h, w))
+    (rch, rcw) = chroma_region_size((h, w), (rh, rw))
+    if tuple(cb.shape) != (n, rch, rcw) or cr.shape != cb.shape:
+        raise HipError('cb and cr must be [N, {0}, {1}]: the chroma rectangle of a {2} x {3} crop of a {4} x {5} picture'.format(
+            rch, rcw, rh, rw, h, w))
+    if origins.dtype != torch.int32 or tuple(origins.shape) != (n, 2) or not origins.is_contiguous() or not (origins.is_cuda or origins.is_pinned()):
+        raise HipError('origins must be a contiguous int32 [N, 2] tensor in device or pinned host memory')
+    if out.dtype != torch.uint8 or not out.is_contiguous() or not (out.is_cuda or out.is_pinned()) \
+            or (out.dim() != 1 and tuple(out.shape) != (n, rh, rw, 3)):
+        raise HipError('`out` must be a contiguous uint8 tensor, flat or [N, rh, rw, 3], in device or pinned host memory')
+    room = out.numel()
+    if out.dim() != 1:
+        room = out.untyped_storage().nbytes() - out.storage_offset()
+        room -= room % 16
+    _check(_native.hip().eae_hip_colour_merge_420_crops(y.data_ptr(), cb.data_ptr(), cr.data_ptr(), origins.data_ptr(), out.data_ptr(), room,
+                                                        n, h, w, rh, rw, rch, rcw, _stream(y)), 'eae_hip_colour_merge_420_crops')
+    return out
+
+
 # ---- SVHN float64 path (include/eae_hip.h, "SVHN path") -------------------------------------------------------------
 
 def svhn_dense(x, w, b, leaky_relu):

@@ -756,6 +756,24 @@ int eae_hip_colour_merge_420(const uint8_t* y, const uint8_t* cb, const uint8_t*
 int eae_hip_colour_merge_420_words(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint8_t* dst, uint64_t dst_bytes,
                                    int n, int h, int w, int H, int W, int Hc, int Wc, void* stream);
 
+/* colour_merge_420_crops: colour_merge_420_words for CROPS of pictures. y u8 [n][rh][rw] dense, crop k the
+ *   pixels [y0, y0 + rh) x [x0, x0 + rw) of an h x w picture, (y0, x0) = origins[k]; cb and cr u8 [n][rch][rcw] dense, the chroma
+ *   rectangle of colour.py's chroma_region: rch = min(hc, rh / 2 + 3), rcw = min(wc, rw / 2 + 3), its origin
+ *   cy0 = min(max((y0 >> 1) - 1, 0), hc - rch), cx0 alike, derived by the kernel. origins i32 [n][2] (row, column) in device or
+ *   pinned, device-mapped host memory: the kernel reads it, so no argument of the launch depends on where the crops lie. Pixel
+ *   (r, c) of crop k is colour_merge_420's pixel (y0 + r, x0 + c) of the picture: i, i2, j, j2 and the parity of the weights from that
+ *   position, the clamp at hc - 1 / wc - 1 of the REAL chroma planes, every chroma index then less (cy0, cx0) -- bit for bit
+ *   colour.merge_420_region_numpy. dst as colour_merge_420_words': with B = n * rh * rw * 3 and K = ceil(B / 16) exactly the words
+ *   0 .. K - 1 are written, each by one 16-byte store, the pad of the last one zero, nothing behind it; a lane owns 16 consecutive flat
+ *   pixels across row and crop ends, a block 768 words staged in LDS, ceil(K / 768) blocks. Every load lies inside the three dense
+ *   inputs and origins. 0 <= y0 <= h - rh and 0 <= x0 <= w - rw are the caller's to ensure (an origin outside is clamped into that
+ *   range, so that no load leaves the inputs; the pixels are then those of the clamped crop). One launch, asynchronous on `stream`.
+ *   Refused (EAE_HIP_BAD_ARGUMENT, in front of the launch): a NULL pointer, a non-positive size, rh > h or rw > w, rch or rcw other
+ *   than chroma_region's, a picture of 2^32 bytes or more, origins not 4-byte aligned, a dst that is not 16-byte aligned, a
+ *   dst_bytes that is not a multiple of 16 or is less than 16 K, more than 2^31 - 1 blocks. */
+int eae_hip_colour_merge_420_crops(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, const int32_t* origins, uint8_t* dst,
+                                   uint64_t dst_bytes, int n, int h, int w, int rh, int rw, int rch, int rcw, void* stream);
+
 /* ==== TEST HOOKS (-DEAE_TEST_HOOKS): NOT exported by the product library lib/libeae_hip.so ====================================
  * Five entry points the test-suite needs and a deployment must not have (they change what later launches do, or only
  * exist to prove something about the kernels). Compiled into lib/libeae_hip_test.so only; tests/test_abi.py checks that
