@@ -2456,7 +2456,7 @@ class BudgetTicket(Ticket):
             blobs.append(container_format.assemble_blob(learned, 1, height, width, exception, ladder.bin_widths_points[k], ladder.map_mean,
                                                         ladder.binary_probabilities_points[k], rows[i:i + 1] if exception >= 0 else rows[:0],
                                                         bits[i*per_image:(i + 1)*per_image], view[int(stops[i] - image_bytes[i]):int(stops[i])],
-                                                        coding_tile=parts['coding_tile'])[0])
+                                                        coding_tile=parts['coding_tile'], image_size=parts.get('image_size'))[0])
         return blobs
 
 
@@ -2558,6 +2558,9 @@ class BudgetCodec(BatchCodec):
     # what the subclasses flip: whether `coding_tile` is taken (and in what words it is refused), and the class of the per-step state
     # beyond `_Slot`
     (_takes_coding_tile, _budget_slot_class) = (False, _BudgetSlot)
+    # `pad` stays refused by every public rate-control codec; `_PlaneBudgetCodec`, a plane of a colour
+    # picture inside `ColourBudgetCodec`, flips this
+    _takes_pad = False
     _no_coding_tile = '`BudgetCodec` does not take `coding_tile`: the bounds are those of whole maps (EAE1).'
 
     def __init__(self, variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, budget_bytes=None, **batch_codec_options):
@@ -2591,7 +2594,7 @@ class BudgetCodec(BatchCodec):
         if options.get('rdo_lambda') is not None:
             raise ValueError('The rate-control codecs do not take `rdo_lambda`: the price of a bit comes with the ladder '
                              '(`ratecontrol.RateLadder(..., rdo_lambda=...)`), a point at a time.')
-        if options.get('pad'):
+        if options.get('pad') and not self._takes_pad:
             raise ValueError('The rate-control codecs do not take `pad`: their bounds and probes are over the coded plane, and a PSNR floor '
                              'would need the real pixel count (DESIGN.md section 25). `BatchCodec(..., pad=True)` pads.')
         if options.get('coder', 'device') != 'device':
@@ -2614,7 +2617,8 @@ class BudgetCodec(BatchCodec):
                                           emit_container=True, **options)
         try:
             to_device = lambda array: torch.from_numpy(numpy.ascontiguousarray(array)).to(self.device)
-            self._header_bytes = ratecontrol.header_bytes(ladder, h_in, w_in, self.coding_tile)
+            # (the coded size, not the arguments: with `pad`, which only `_takes_pad` lets through, they are the real size)
+            self._header_bytes = ratecontrol.header_bytes(ladder, self.h_in, self.w_in, self.coding_tile)
             if self._tile_layout is not None:
                 # `device.ladder_select_tiles`: the image of every (image, tile) entry in the run order the coder takes them in
                 tiled = self._tile_layout
@@ -2630,7 +2634,7 @@ class BudgetCodec(BatchCodec):
             self._fixed_costs = to_device(ratecontrol.fixed_costs(ladder).view(numpy.int32))
             self._log2_tables = to_device(ratecontrol.log2_tables(self.map_size).view(numpy.int32)) if self.idx_map_exception >= 0 else None
             self._budget_slots = {}
-            fixed = (bool(are_bin_widths_learned), 1, h_in, w_in, self.idx_map_exception, ladder)
+            fixed = (bool(are_bin_widths_learned), 1, self.h_in, self.w_in, self.idx_map_exception, ladder)
             for slot in self._slots:
                 budget_slot = self._budget_slot_class(self)
                 self._budget_slots[id(slot)] = budget_slot
@@ -2699,9 +2703,13 @@ class BudgetCodec(BatchCodec):
         if not self.learned:
             y = hook('gdn3', lambda: dev.gdn(y, enc.g[3], v['encoder/beta_3']))
         hook('ladder', lambda: self._launch_ladder(y, budget))
-        dev.fetch_prefix(budget.pinned_budgets, budget.budgets, budget.budgets_nbytes)
+        self._launch_budgets(budget)
         hook('select', lambda: self._launch_select(budget))
         return y
+
+    def _launch_budgets(self, budget):
+        """The step's budgets out of the slot's pinned block into its device block, in front of the selection."""
+        dev.fetch_prefix(budget.pinned_budgets, budget.budgets, budget.budgets_nbytes)
 
     def _launch_quantiser(self, y, slot, budget, hook):
         """`_launch_analysis` from the quantiser on, at `budget.point`; returns the synthesis transform's input."""
@@ -2749,6 +2757,69 @@ class BudgetCodec(BatchCodec):
         budget = self._budget_slots[id(slot)]
         rows = ((budget.exception_rows, budget.pinned_rows),) if self.idx_map_exception >= 0 else ()
         super(BudgetCodec, self)._publish_coder_side(slot, ((budget.select, budget.pinned_select),) + rows)
+
+
+class _PlaneBudgetCodec(BudgetCodec):
+    """`BudgetCodec` as one plane of a colour picture inside `ColourBudgetCodec`; private: the public
+    rate-control codecs go on refusing `pad`. Two things are its own.
+    `pad=True` is taken: h_in x w_in is the plane's REAL size, the step runs at the coded size as `BatchCodec(pad=True)` runs it, the
+    bounds, the header and the blobs are those of the coded plane with the real size in the `crop` byte -- `container.encode_images(...,
+    pad=True)` at the image's point, byte for byte -- and 'sse' is over the real pixels.
+    budgets_on_device=True: `submit(images, budget_bytes)` also takes an int64 device tensor (batch_size,) that was written earlier
+    on the caller's stream. The step copies it into its slot's `budgets` block on the step's own stream, behind that stream's wait for
+    the caller's and in front of the selection, launches no `fetch_prefix` of budgets, and publishes `budgets` into the slot's
+    `pinned_budgets` together with the selection: 'budget_bytes' of `result()` is what the device used. A host array or a scalar goes
+    the same way, through the slot's pinned block. The slot's `budgets` block is free then: `_submit` has waited for the slot, so the
+    step that used it last has published its counters, behind its selection."""
+    _takes_pad = True
+
+    def __init__(self, variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, budget_bytes=None, budgets_on_device=False,
+                 **batch_codec_options):
+        self.budgets_on_device = bool(budgets_on_device)
+        super(_PlaneBudgetCodec, self).__init__(variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, budget_bytes,
+                                                **batch_codec_options)
+
+    def _budgets_for(self, budget_bytes):
+        if not isinstance(budget_bytes, torch.Tensor):
+            return super(_PlaneBudgetCodec, self)._budgets_for(budget_bytes)
+        if not self.budgets_on_device:
+            raise ValueError('`budget_bytes` as a tensor needs `budgets_on_device=True`.')
+        if budget_bytes.dtype != torch.int64 or tuple(budget_bytes.shape) != (self.batch_size,) or not budget_bytes.is_contiguous() \
+                or budget_bytes.device != self.device:
+            raise ValueError('`budget_bytes` as a tensor must be int64 (batch_size,), contiguous, on the codec\'s device.')
+        return budget_bytes
+
+    def _stage(self, slot):
+        """With `budgets_on_device`: the step's budgets into the slot's DEVICE block, on the current stream (the step's own)."""
+        if not self.budgets_on_device:
+            return super(_PlaneBudgetCodec, self)._stage(slot)
+        (budget, staged, n) = (self._budget_slots[id(slot)], self._staged[0], self.batch_size)
+        if isinstance(staged, torch.Tensor):
+            budget.budgets[:n].copy_(staged, non_blocking=True)
+            staged.record_stream(torch.cuda.current_stream())
+        else:
+            budget.budgets_host[:n] = staged
+            budget.budgets[:n].copy_(budget.pinned_budgets[:n], non_blocking=True)
+
+    def _replay_step(self, luminances_uint8, slot, index, ticket, coded):
+        if not self.budgets_on_device:
+            return super(_PlaneBudgetCodec, self)._replay_step(luminances_uint8, slot, index, ticket, coded)
+        # the stream `BatchCodec._replay_step` replays this step's graphs on: the budgets go there in front of them
+        stream = self._transform_streams[index % len(self._transform_streams)]
+        stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(stream):
+            self._stage(slot)
+        return BatchCodec._replay_step(self, luminances_uint8, slot, index, ticket, coded)
+
+    def _launch_budgets(self, budget):
+        if not self.budgets_on_device:                   # (else `_stage` has put them there: nothing is launched, captured or eager)
+            super(_PlaneBudgetCodec, self)._launch_budgets(budget)
+
+    def _publish_coder_side(self, slot):
+        if self.budgets_on_device:
+            budget = self._budget_slots[id(slot)]
+            dev.publish_to_host(budget.budgets, budget.pinned_budgets)
+        super(_PlaneBudgetCodec, self)._publish_coder_side(slot)
 
 
 # ---- the same for tile-indexed containers: counts, bounds and streams per coding tile (DESIGN.md section 20) ------------------------
@@ -3153,8 +3224,24 @@ class ColourCodec(object):
     queues that is 2, and depth = 2. A value the caller gives is budgeted, and warned about, by `BatchCodec` as ever.
     `fetch_reconstruction` is this codec's: the merged pictures in pinned memory as well. `pad` and `keep_reconstruction` are fixed."""
 
+    # what `ColourBudgetCodec` replaces: the ring entry, the ticket and (`_build`'s `make_inner`, `_submit_planes`) the inner codecs
+    (_step_class, _ticket_class) = (_ColourStep, ColourTicket)
+
     def __init__(self, variables, are_bin_widths_learned, bin_widths_test, map_mean, binary_probabilities, idx_map_exception, batch_size,
                  h, w, chroma=None, chroma_options=None, **batch_codec_options):
+        (self.luma, self.chroma) = (None, None)
+        luma_point = (bin_widths_test, map_mean, binary_probabilities, idx_map_exception)
+        chroma_point = luma_point if chroma is None else tuple(chroma)
+        if len(chroma_point) != 4:
+            raise ValueError('`chroma` must be (bin_widths_test, map_mean, binary_probabilities, idx_map_exception).')
+        self._build(batch_size, h, w, chroma_options, batch_codec_options,
+                    lambda is_chroma, height, width, **options: BatchCodec(variables, are_bin_widths_learned, *(chroma_point if is_chroma else luma_point),
+                                                                           self.batch_size, height, width, pad=True, keep_reconstruction=True,
+                                                                           **options))
+
+    def _build(self, batch_size, h, w, chroma_options, batch_codec_options, make_inner):
+        """Everything the constructor does behind its own arguments: the options' refusals, the two inner codecs --
+        make_inner(is_chroma, height, width, **options) -> the luminance codec, then the chroma codec --, the ring and the merge stream."""
         (self.luma, self.chroma) = (None, None)
         options = dict(batch_codec_options)
         chroma_options = dict(chroma_options or {})
@@ -3168,16 +3255,11 @@ class ColourCodec(object):
         self.batch_size = container_format._positive_int(batch_size, '`batch_size`')
         (self.h, self.w) = (container_format._positive_int(h, '`h`'), container_format._positive_int(w, '`w`'))
         (self.hc, self.wc) = dev.chroma_size(self.h, self.w)
-        luma_point = (bin_widths_test, map_mean, binary_probabilities, idx_map_exception)
-        chroma_point = luma_point if chroma is None else tuple(chroma)
-        if len(chroma_point) != 4:
-            raise ValueError('`chroma` must be (bin_widths_test, map_mean, binary_probabilities, idx_map_exception).')
         for_chroma = dict(options)
         for_chroma.update(chroma_options)
         self.emit_container = bool(options.get('emit_container', False))
         try:
-            self.luma = BatchCodec(variables, are_bin_widths_learned, *luma_point, self.batch_size, self.h, self.w, pad=True,
-                                   keep_reconstruction=True, **options)
+            self.luma = make_inner(False, self.h, self.w, **options)
             if chroma_options.get('nb_in_flight') is None:
                 # two inner steps per colour step: as many colour steps as the luminance codec's nb_in_flight + 2 slots hold, as far as
                 # this process's hardware queues go (the condition is `BatchCodec`'s own, so it finds nothing left to cut or to say)
@@ -3186,14 +3268,13 @@ class ColourCodec(object):
                         and os.environ.get('EAE_IGNORE_HW_QUEUES') != '1':
                     (_, wanted, _) = stream_budget(for_chroma.get('nb_transform_streams', 1), wanted)
                 for_chroma['nb_in_flight'] = wanted
-            self.chroma = BatchCodec(variables, are_bin_widths_learned, *chroma_point, self.batch_size, self.hc, self.wc, pad=True,
-                                     keep_reconstruction=True, **for_chroma)
+            self.chroma = make_inner(True, self.hc, self.wc, **for_chroma)
             self.device = self.luma.device
             self.depth = min(self.luma.nb_slots, self.chroma.nb_slots//2)
             if self.depth < 1:
                 raise ValueError('the chroma codec has {0} slot(s): it cannot hold the two steps (Cb, Cr) of one colour step.'.format(
                     self.chroma.nb_slots))
-            self._steps = [_ColourStep(self) for _ in range(self.depth)]
+            self._steps = [self._step_class(self) for _ in range(self.depth)]
             self._merge_stream = torch.cuda.Stream(device=self.device)
             self._feed_stream = None
             self._index = 0
@@ -3244,8 +3325,8 @@ class ColourCodec(object):
         else:
             step.rgb_in.copy_(rgb_uint8, non_blocking=True)
         dev.colour_split_420(step.rgb_in, out=step.planes)
-        tickets = (self.luma.submit(step.planes[0]), self.chroma.submit(step.planes[1]), self.chroma.submit(step.planes[2]))
-        ticket = ColourTicket(tickets, (self.h, self.w), step)
+        tickets = self._submit_planes(step)
+        ticket = self._ticket_class(tickets, (self.h, self.w), step)
         ticket.fed_event = fed
         with torch.cuda.stream(self._merge_stream):
             for inner in tickets:
@@ -3263,6 +3344,10 @@ class ColourCodec(object):
         ticket.reconstruction_rgb = step.rgb_out
         step.ticket = ticket
         return ticket
+
+    def _submit_planes(self, step):
+        """The three inner submits of the step whose planes `step.planes` holds, on the current stream -> the tickets (Y, Cb, Cr)."""
+        return (self.luma.submit(step.planes[0]), self.chroma.submit(step.planes[1]), self.chroma.submit(step.planes[2]))
 
     def drain(self):
         """Waits until every submitted batch is through, the merges included."""
@@ -3293,6 +3378,136 @@ class ColourCodec(object):
             self.close()
         except Exception:      # interpreter shutdown: nothing left to report to
             pass
+
+
+# ---- a byte budget per colour picture ---------------------------------------------------------------------------
+
+class ColourBudgetTicket(ColourTicket):
+    """Handle on one submitted `ColourBudgetCodec` step."""
+    _picture_budgets = None                   # int64 (N,): the step's budgets per picture, the ticket's own copy
+
+    def result(self):
+        """`ColourTicket.result()` over the three `BudgetCodec.result()`s -- every key (N, 3, ...) in the order Y, Cb, Cr, 'budget_bytes'
+        the budgets the planes' selections used, and 'sse_rgb' -- plus, per picture, int64 / bool (N,): 'picture_budget_bytes';
+        'picture_blob_bytes', 48 plus the three 'blob_bytes': the length of `image_containers()[i]`; 'picture_promised': all three
+        planes are promised, and then 48 plus the three bounds taken is within the budget; 'picture_fits': the blob is."""
+        if self._values is None:
+            values = super(ColourBudgetTicket, self).result()
+            values['picture_budget_bytes'] = self._picture_budgets
+            values['picture_blob_bytes'] = container_format.COLOUR_HEADER_BYTES + values['blob_bytes'].sum(axis=1)
+            values['picture_promised'] = values['promised'].all(axis=1)
+            values['picture_fits'] = values['picture_blob_bytes'] <= self._picture_budgets
+        return self._values
+
+    def container(self):
+        """Always raises, as `BudgetTicket.container()`: every picture of the step has rate points of its own."""
+        raise RuntimeError('a ColourBudgetCodec step has rate points per picture and one EAC1 blob holds one per plane: use `image_containers()`')
+
+
+class _ColourBudgetStep(_ColourStep):
+    """`_ColourStep` with the step's budgets: the pictures' in a pinned block and on the device, the luminance planes' on the device."""
+
+    def __init__(self, codec):
+        super(_ColourBudgetStep, self).__init__(codec)
+        n = codec.batch_size
+        self.pinned_budgets = torch.zeros(n, dtype=torch.int64).pin_memory()
+        self.budgets_host = self.pinned_budgets.numpy()
+        self.budgets = torch.zeros(n, dtype=torch.int64, device=codec.device)
+        self.luma_budgets = torch.zeros(n, dtype=torch.int64, device=codec.device)      # written by `device.colour_budget_rest`
+
+
+class ColourBudgetCodec(ColourCodec):
+    """`ColourCodec` with ONE byte budget per picture: that of the picture's single-picture `EAC1` blob, shared between its three
+    planes on the device inside the step (the rule is `ratecontrol.colour_chroma_budgets` /
+    `colour_luma_budgets`, its synchronous sibling `container.encode_colour_images_to_budget`). The inner codecs are two
+    `_PlaneBudgetCodec(pad=True, keep_reconstruction=True)`, `luma` with `budgets_on_device=True`; the ring depth, the drain when a
+    submit raises, `close`, `fetch_reconstruction` and the merge are `ColourCodec`'s.
+
+    `submit(rgb, budget_bytes)` enqueues, in this order: the batch copy and the split; Cb and Cr into `chroma`, each with the
+    host-computed budget c = (P * share_q16) >> 17; on the caller's stream, behind both chroma steps' `decoded_event`, ONE
+    `device.colour_budget_rest` launch, which reads the picture budgets (uploaded from the step's pinned block) and the `upper` and
+    `point` blocks of the two chroma slots and writes r = max(P - ub_cb - ub_cr, 0) into the step's own buffer; Y into `luma` with that
+    buffer as its budgets; the merge. The luminance budget never visits the host, and no launch argument depends on it.
+    The chroma blocks read stay valid until their slot comes round, which `ColourCodec`'s depth rule puts behind this step's merge,
+    hence behind the launch that read them (DESIGN.md section 29 has the whole argument). The luminance analysis of a colour step
+    runs behind its chroma steps; steps of the ring overlap as in `ColourCodec`.
+
+    ladder, chroma_ladder (None: `ladder`): `ratecontrol.RateLadder`s of the same number of points and the same truncated unary
+    length; chroma_share: the fraction of the payload both chroma planes together may take, in ]0, 1[ (0.25: a starting value, not a
+    measured one). budget_bytes: the budget of a `submit` that names none. Refused: `coding_tile`, the keyword `rdo_lambda` (a ladder
+    with a price is fine), `pad` / `keep_reconstruction` as options, and what `BudgetCodec` refuses."""
+    (_step_class, _ticket_class) = (_ColourBudgetStep, ColourBudgetTicket)
+
+    def __init__(self, variables, are_bin_widths_learned, ladder, batch_size, h, w, budget_bytes=None, chroma_ladder=None, chroma_share=0.25,
+                 chroma_options=None, **batch_codec_options):
+        from . import ratecontrol
+        (self.luma, self.chroma) = (None, None)
+        chroma_ladder = ladder if chroma_ladder is None else chroma_ladder
+        if not isinstance(ladder, ratecontrol.RateLadder) or not isinstance(chroma_ladder, ratecontrol.RateLadder):
+            raise TypeError('`ladder` and `chroma_ladder` must be `ratecontrol.RateLadder`s.')
+        # refused in front of every allocation
+        for options in (batch_codec_options, chroma_options or {}):
+            if options.get('coding_tile') is not None:
+                raise ValueError('`ColourBudgetCodec` does not take `coding_tile`: the bounds are those of whole maps (EAE1 plane blobs).')
+            if options.get('rdo_lambda') is not None:
+                raise ValueError('`ColourBudgetCodec` does not take `rdo_lambda`: the price of a bit comes with the ladder '
+                                 '(`ratecontrol.RateLadder(..., rdo_lambda=...)`).')
+            if 'budgets_on_device' in options:
+                raise ValueError('`budgets_on_device` is not an option of ColourBudgetCodec: its luminance codec runs with it.')
+        if chroma_ladder.nb_points != ladder.nb_points:
+            raise ValueError('`ladder` and `chroma_ladder` hold {0} and {1} rate points: the same number is needed.'.format(
+                ladder.nb_points, chroma_ladder.nb_points))
+        if chroma_ladder.truncated_unary_length != ladder.truncated_unary_length:
+            raise ValueError('`ladder` and `chroma_ladder` have truncated unary lengths {0} and {1}: the same is needed.'.format(
+                ladder.truncated_unary_length, chroma_ladder.truncated_unary_length))
+        ratecontrol.colour_chroma_budgets(0, chroma_share)             # refuses a share outside ]0, 1[
+        self.chroma_share = float(chroma_share)
+        (self.ladder, self.chroma_ladder) = (ladder, chroma_ladder)
+        self._default_budgets = None if budget_bytes is None else BudgetCodec._budgets_of(budget_bytes, container_format._positive_int(batch_size, '`batch_size`'))
+        self._submitting = None
+        self._build(batch_size, h, w, chroma_options, batch_codec_options,
+                    lambda is_chroma, height, width, **options: _PlaneBudgetCodec(
+                        variables, are_bin_widths_learned, chroma_ladder if is_chroma else ladder, self.batch_size, height, width, pad=True,
+                        keep_reconstruction=True, budgets_on_device=not is_chroma, **options))
+        self.emit_container = True
+
+    def submit(self, rgb_uint8, budget_bytes=None):
+        """`ColourCodec.submit` with the step's budgets: a scalar or one value per picture, bytes of the picture's whole single-picture
+        `EAC1` blob (its 48-byte header included); None: the constructor's `budget_bytes`."""
+        from . import ratecontrol
+        budgets = self._default_budgets if budget_bytes is None else BudgetCodec._budgets_of(budget_bytes, self.batch_size)
+        if budgets is None:
+            raise ValueError('no `budget_bytes`, and the codec was built without a default.')
+        self._submitting = (budgets, ratecontrol.colour_chroma_budgets(budgets, self.chroma_share))
+        try:
+            return super(ColourBudgetCodec, self).submit(rgb_uint8)
+        finally:
+            self._submitting = None
+
+    def _submit_planes(self, step):
+        (budgets, chroma_budgets) = self._submitting
+        # the entry is this step's: `submit` has waited for the merge of the step that used it last, which lies behind that step's
+        # `colour_budget_rest` and luminance selection
+        step.budgets_host[:] = budgets
+        step.budgets.copy_(step.pinned_budgets, non_blocking=True)
+        chroma_slots = []
+        chroma_tickets = []
+        for plane in step.planes[1:]:
+            slot = self.chroma._slots[self.chroma._index % self.chroma.nb_slots]       # the slot this inner step takes (`BatchCodec._submit`)
+            chroma_slots.append(self.chroma._budget_slots[id(slot)])
+            chroma_tickets.append(self.chroma.submit(plane, chroma_budgets))
+        caller = torch.cuda.current_stream()
+        for inner in chroma_tickets:
+            caller.wait_event(inner.decoded_event)
+        (of_cb, of_cr) = chroma_slots
+        dev.colour_budget_rest(step.budgets, of_cb.upper, of_cb.point, of_cr.upper, of_cr.point, step.luma_budgets)
+        luma_ticket = self.luma.submit(step.planes[0], step.luma_budgets)
+        return (luma_ticket,) + tuple(chroma_tickets)
+
+    def _enqueue(self, step, rgb_uint8, host):
+        ticket = super(ColourBudgetCodec, self)._enqueue(step, rgb_uint8, host)
+        ticket._picture_budgets = self._submitting[0].copy()
+        return ticket
 
 
 # ---- colour pictures out of EAC1 containers, resident and pipelined (DESIGN.md section 27) --------------------------------------------

@@ -975,6 +975,7 @@ COLOUR_MAGIC = b'EAC1'
 COLOUR_VERSION = 1
 SUBSAMPLING_420 = 1            # the only value written and read; the others are reserved for 4:4:4 / 4:2:2 and refused
 _COLOUR_HEADER = struct.Struct('<4sHHIIIB3s3Q')
+COLOUR_HEADER_BYTES = _COLOUR_HEADER.size          # 48: what a picture's byte budget pays in front of its plane blobs (ratecontrol.py)
 _PLANE_NAMES = ('y', 'cb', 'cr')
 
 
@@ -1081,6 +1082,82 @@ def encode_colour_images(rgb_uint8, encoder, bin_widths_test, map_mean, binary_p
         blobs.append(blob)
     info['plane_bytes'] = tuple(len(blob) for blob in blobs)
     return (assemble_colour_blob(rgb.shape[1:3], *blobs), info)
+
+
+def encode_colour_images_to_budget(rgb_uint8, encoder, ladder, budget_bytes, chroma_ladder=None, chroma_share=0.25):
+    """uint8 (N, h, w, 3) RGB pictures of any height and width -> (blobs, info): every picture as a single-picture EAC1 blob of at
+    most `budget_bytes` bytes (a scalar, or one value per picture) where the bounds promise it. The synchronous sibling of
+    `codec.ColourBudgetCodec` and the statement of its rule (ratecontrol.py, "the rule of `codec.ColourBudgetCodec`"; DESIGN.md section
+    29): a point is taken on `ratecontrol.upper_bounds_fixed` alone, as `codec.BudgetCodec` takes it, and nothing is coded to find out
+    -- this is not `encode_images_to_budget`'s trial-coding loop.
+
+    The pictures are split 4:2:0 on the device (device.colour_split_420); every plane is padded (device.frame_pad_u8) and gets one
+    analysis transform and one pass of counts at the K points of its ladder -- `ladder` for Y, `chroma_ladder` (None: `ladder`) for
+    Cb and Cr, both of the same K. Cb and Cr take `select_by_upper_bound`'s point for `ratecontrol.colour_chroma_budgets(budget_bytes,
+    chroma_share)`, Y the point for `ratecontrol.colour_luma_budgets`: the payload less the bounds of the points chroma took. Every
+    plane is then coded with `encode_images(plane[i:i + 1], ..., pad=True)` at its point (`rdo_lambda=ladder.rdo_lambdas[k]` for a
+    ladder with a price) and the three blobs are assembled with `assemble_colour_blob`: `decode_colour_images` and
+    `codec.ColourDecoder` read the blobs unchanged.
+    info: 'rate_point' int64 (N, 3) in the order Y, Cb, Cr; 'upper_bound_bytes' int64 (N, 3, K); 'plane_budget_bytes' int64 (N, 3);
+    'valid_points' bool (N, 3, K): the points whose symbols fit int16; 'plane_promised' bool (N, 3); 'plane_blob_bytes' int64 (N, 3);
+    'budget_bytes', 'blob_bytes' int64 (N,); 'promised' bool (N,): all
+    three planes' bounds are within their budgets, and then 48 + the three bounds <= budget; 'fits' bool (N,): the blob is."""
+    from . import ratecontrol
+    rgb = numpy.ascontiguousarray(rgb_uint8)
+    if rgb.dtype != numpy.uint8:
+        raise TypeError('`rgb_uint8.dtype` is not equal to `numpy.uint8`.')
+    if rgb.ndim != 4 or rgb.shape[3] != 3 or 0 in rgb.shape:
+        raise ValueError('`rgb_uint8` must be (N, h, w, 3) and hold a pixel.')
+    chroma_ladder = ladder if chroma_ladder is None else chroma_ladder
+    if not isinstance(ladder, ratecontrol.RateLadder) or not isinstance(chroma_ladder, ratecontrol.RateLadder):
+        raise TypeError('`ladder` and `chroma_ladder` must be `ratecontrol.RateLadder`s.')
+    if chroma_ladder.nb_points != ladder.nb_points:
+        raise ValueError('`ladder` and `chroma_ladder` hold {0} and {1} rate points: the same number is needed.'.format(
+            ladder.nb_points, chroma_ladder.nb_points))
+    nb_images = rgb.shape[0]
+    budgets = numpy.asarray(budget_bytes)
+    if budgets.ndim > 1 or (budgets.ndim == 1 and budgets.shape[0] != nb_images) or budgets.dtype.kind not in 'iuf':
+        raise ValueError('`budget_bytes` must be a number or one number per picture.')
+    budgets = numpy.ascontiguousarray(numpy.broadcast_to(budgets.astype(numpy.int64), (nb_images,)))
+    chroma_budgets = ratecontrol.colour_chroma_budgets(budgets, chroma_share)
+    device = encoder.device
+    planes = dev.colour_split_420(torch.from_numpy(rgb).to(device))
+    ladders = (ladder, chroma_ladder, chroma_ladder)
+
+    def bounds(plane, plane_ladder):
+        padded = dev.frame_pad_u8(plane)
+        map_size = (padded.shape[1]//csts.STRIDE_PROD)*(padded.shape[2]//csts.STRIDE_PROD)
+        (hist, bypass_bits) = _LadderOnDevice(plane_ladder, device).histograms(encoder(padded))
+        return ratecontrol.upper_bounds_fixed(hist, bypass_bits, plane_ladder, map_size), ratecontrol.valid_points(hist, map_size)
+
+    (upper_y, valid_y) = bounds(planes[0], ladder)
+    (upper_cb, valid_cb) = bounds(planes[1], chroma_ladder)
+    (upper_cr, valid_cr) = bounds(planes[2], chroma_ladder)
+    (point_cb, promised_cb) = ratecontrol.select_by_upper_bound(upper_cb, valid_cb, chroma_budgets)
+    (point_cr, promised_cr) = ratecontrol.select_by_upper_bound(upper_cr, valid_cr, chroma_budgets)
+    luma_budgets = ratecontrol.colour_luma_budgets(budgets, upper_cb, point_cb, upper_cr, point_cr)
+    (point_y, promised_y) = ratecontrol.select_by_upper_bound(upper_y, valid_y, luma_budgets)
+    info = {'rate_point': numpy.stack([point_y, point_cb, point_cr], axis=1),
+            'upper_bound_bytes': numpy.stack([upper_y, upper_cb, upper_cr], axis=1),
+            'plane_budget_bytes': numpy.stack([luma_budgets, chroma_budgets, chroma_budgets], axis=1),
+            'valid_points': numpy.stack([valid_y, valid_cb, valid_cr], axis=1),
+            'plane_promised': numpy.stack([promised_y, promised_cb, promised_cr], axis=1),
+            'plane_blob_bytes': numpy.zeros((nb_images, 3), dtype=numpy.int64), 'budget_bytes': budgets}
+    host_planes = [plane.cpu().numpy() for plane in planes]
+    blobs = []
+    for i in range(nb_images):
+        plane_blobs = []
+        for (which, (plane, plane_ladder)) in enumerate(zip(host_planes, ladders)):
+            k = int(info['rate_point'][i, which])
+            more = {} if plane_ladder.rdo_lambdas is None else {'rdo_lambda': plane_ladder.rdo_lambdas[k]}
+            plane_blobs.append(encode_images(plane[i:i + 1], encoder, plane_ladder.bin_widths_points[k], plane_ladder.map_mean,
+                                             plane_ladder.binary_probabilities_points[k], plane_ladder.idx_map_exception, pad=True, **more)[0])
+            info['plane_blob_bytes'][i, which] = len(plane_blobs[which])
+        blobs.append(assemble_colour_blob(rgb.shape[1:3], *plane_blobs))
+    info['blob_bytes'] = numpy.array([len(blob) for blob in blobs], dtype=numpy.int64)
+    info['promised'] = info['plane_promised'].all(axis=1)
+    info['fits'] = info['blob_bytes'] <= budgets
+    return blobs, info
 
 
 def decode_colour_images(blob, decoder, tile=None):

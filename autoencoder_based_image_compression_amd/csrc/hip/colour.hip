@@ -7,6 +7,8 @@
 //     [n][h][w][3] and / or sse[i] += the squared error against a reference picture: chroma upsampled 3:1 centre-sited with the
 //     neighbours clamped at the real chroma size, then the integer BT.601 inverse.
 //   eae_hip_colour_merge_420_words: the same picture in whole aligned 16-byte words, for the resident decoder (further down).
+//   eae_hip_colour_budget_rest: the byte budget of a picture's luminance plane from what its chroma planes took (at
+//     the end of the file): no pixel work, one lane per picture.
 // In the first two a lane owns one chroma sample, i.e. a 2 x 2 block of pixels: 12 bytes of the picture, six contiguous ones in each of two
 // rows, so a wave covers 384 contiguous bytes of a row. A block lies inside one image (blocks_per_image blocks of 256 samples each):
 // the image index is a division of the block index, the offset of the image 64 bits wide, everything inside an image 32 bits. The
@@ -471,6 +473,30 @@ __global__ __launch_bounds__(256) void colour_merge_crops_kernel(const uint8_t* 
     }
 }
 
+// ---- the luminance budget of a colour picture -------------------------------------------------------------------
+// ratecontrol.colour_luma_budgets on the device, so that the budget of Y never visits the host: a lane owns one picture. With P =
+// max(B - header_bytes, 0) the payload of its EAC1 blob (header_bytes: the size of container.py's colour header), out = max(max(P - upper_cb[point_cb], 0) - upper_cr[point_cr], 0): for the byte counts
+// the bounds are (never negative) that is max(P - ub_cb - ub_cr, 0), and no difference leaves int64 for any B up to 2^62. A point
+// outside [0, K) gives 0 and loads nothing from the tables.
+constexpr int BUDGET_REST_LANES = 256;
+__global__ __launch_bounds__(BUDGET_REST_LANES) void colour_budget_rest_kernel(const int64_t* __restrict__ budgets, const int64_t* __restrict__ upper_cb,
+                                                                               const int32_t* __restrict__ point_cb, const int64_t* __restrict__ upper_cr,
+                                                                               const int32_t* __restrict__ point_cr, int64_t* __restrict__ out,
+                                                                               uint32_t n, uint32_t k_points, int64_t header_bytes) {
+    const uint32_t i = blockIdx.x * (uint32_t)BUDGET_REST_LANES + threadIdx.x;
+    if (i >= n) return;
+    const int32_t pb = point_cb[i], pr = point_cr[i];
+    int64_t rest = 0;
+    if (pb >= 0 && (uint32_t)pb < k_points && pr >= 0 && (uint32_t)pr < k_points) {
+        const int64_t budget = budgets[i];
+        rest = budget > header_bytes ? budget - header_bytes : 0;
+        const int64_t ub_cb = upper_cb[(uint64_t)i * k_points + (uint32_t)pb], ub_cr = upper_cr[(uint64_t)i * k_points + (uint32_t)pr];
+        rest = rest > ub_cb ? rest - ub_cb : 0;
+        rest = rest > ub_cr ? rest - ub_cr : 0;
+    }
+    out[i] = rest;
+}
+
 }  // namespace
 
 extern "C" int eae_hip_colour_split_420(const uint8_t* rgb, uint8_t* y, uint8_t* cb, uint8_t* cr, int n, int h, int w, void* stream) {
@@ -532,6 +558,18 @@ extern "C" int eae_hip_colour_merge_420_crops(const uint8_t* y, const uint8_t* c
     s.last_y0 = (uint32_t)(h - rh), s.last_x0 = (uint32_t)(w - rw);
     hipLaunchKernelGGL(colour_merge_crops_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, y, cb, cr, origins,
                        reinterpret_cast<u32x4*>(dst), s, pixels, words);
+    EAE_HIP_CHECK_LAUNCH();
+    return EAE_HIP_OK;
+}
+
+extern "C" int eae_hip_colour_budget_rest(const int64_t* budgets, const int64_t* upper_cb, const int32_t* point_cb, const int64_t* upper_cr,
+                                          const int32_t* point_cr, int64_t* out, int n, int k_points, int64_t header_bytes, void* stream) {
+    if (!budgets || !upper_cb || !point_cb || !upper_cr || !point_cr || !out || n <= 0 || k_points <= 0 || header_bytes < 0) return EAE_HIP_BAD_ARGUMENT;
+    if ((((uintptr_t)budgets | (uintptr_t)upper_cb | (uintptr_t)upper_cr | (uintptr_t)out) & 7u) || (((uintptr_t)point_cb | (uintptr_t)point_cr) & 3u))
+        return EAE_HIP_BAD_ARGUMENT;
+    const uint32_t blocks = ((uint32_t)n + (uint32_t)BUDGET_REST_LANES - 1u) / (uint32_t)BUDGET_REST_LANES;      // one lane per picture, whatever n
+    hipLaunchKernelGGL(colour_budget_rest_kernel, dim3(blocks), dim3(BUDGET_REST_LANES), 0, (hipStream_t)stream, budgets, upper_cb, point_cb,
+                       upper_cr, point_cr, out, (uint32_t)n, (uint32_t)k_points, header_bytes);
     EAE_HIP_CHECK_LAUNCH();
     return EAE_HIP_OK;
 }

@@ -1716,6 +1716,31 @@ def colour_merge_420_crops(y, cb, cr, image_size, origins, out):
     return out
 
 
+def colour_budget_rest(budgets, upper_cb, point_cb, upper_cr, point_cr, out):
+    """The byte budget of the luminance plane of N colour pictures from what their chroma planes took:
+    `ratecontrol.colour_luma_budgets`, element for element, without a visit to the host. budgets int64 [N]: the budget of every
+    picture's single-picture EAC1 blob; upper_cb, upper_cr int64 [N, K]: the upper bounds of the chroma planes at every point (byte
+    counts, never negative); point_cb, point_cr int32 [N]: the points they took; out int64 [N]. All contiguous, in device or pinned
+    host memory. out[i] = max(P - upper_cb[i, point_cb[i]] - upper_cr[i, point_cr[i]], 0) with P = max(budgets[i] - 48, 0), the 48
+    `container`'s colour header; a picture with a point outside [0, K) gets 0. One launch on the current stream. Returns `out`."""
+    from . import container                       # (it imports this module; both are loaded by the time anything is called)
+    wide = (budgets, upper_cb, upper_cr, out)
+    points = (point_cb, point_cr)
+    if any(t.dtype != torch.int64 for t in wide) or any(t.dtype != torch.int32 for t in points):
+        raise HipError('budgets, upper_cb, upper_cr and out must be int64, point_cb and point_cr int32')
+    if any(not t.is_contiguous() or not (t.is_cuda or t.is_pinned()) for t in wide + points):
+        raise HipError('every argument must be contiguous, in device or pinned host memory')
+    if upper_cb.dim() != 2 or upper_cb.shape[0] < 1 or upper_cb.shape[1] < 1 or upper_cr.shape != upper_cb.shape:
+        raise HipError('upper_cb and upper_cr must be alike [N, K] with N, K >= 1')
+    (n, k_points) = upper_cb.shape
+    if any(tuple(t.shape) != (n,) for t in (budgets, point_cb, point_cr, out)):
+        raise HipError('budgets, point_cb, point_cr and out must be [N]')
+    _check(_native.hip().eae_hip_colour_budget_rest(budgets.data_ptr(), upper_cb.data_ptr(), point_cb.data_ptr(), upper_cr.data_ptr(),
+                                                    point_cr.data_ptr(), out.data_ptr(), n, k_points, container.COLOUR_HEADER_BYTES,
+                                                    _stream(next((t for t in wide + points if t.is_cuda), None))), 'eae_hip_colour_budget_rest')
+    return out
+
+
 # ---- SVHN float64 path (include/eae_hip.h, "SVHN path") -------------------------------------------------------------
 
 def svhn_dense(x, w, b, leaky_relu):

@@ -4,7 +4,8 @@
 as numpy arrays. The second half of the file is the rule of `codec.BudgetCodec`: the same upper bound in integer
 arithmetic, which `eae_hip_ladder_select` restates on the device element for element, and the choice on that bound alone. The end of
 the file is the rule of `codec.QualityCodec`: a PSNR floor as an integer bound on the squared error, and the
-bisection of the ladder for the coarsest point that keeps it, which `eae_hip_quality_search` restates round by round.
+bisection of the ladder for the coarsest point that keeps it, which `eae_hip_quality_search` restates round by round. Between the two
+stands the rule of `codec.ColourBudgetCodec`: how one byte budget is shared between the planes of a picture.
 
 A rate point is a pair: 128 bin widths and a table of binary probabilities (the reference walks nine, `multipliers` of
 reconstructing_eae_kodak.py, and learns a point's cost by quantising and coding at it). The coder's cost is a function of the
@@ -409,6 +410,76 @@ def select_by_upper_bound(upper, valid, budgets):
         promised[i] = fitting.size != 0
         rate_point[i] = fitting[0] if fitting.size else candidates[-1]
     return rate_point, promised
+
+
+# ---- the rule of `codec.ColourBudgetCodec`: one byte budget for the three planes of a colour picture ----------
+# A picture's budget B is that of its single-picture EAC1 blob: the colour header and three plane blobs. With P = max(B - header, 0):
+#   1. Cb and Cr each get c = (P * share_q16) >> 17, share_q16 = round(chroma_share * 65536), and take `select_by_upper_bound`'s point
+#      for c on their own `upper_bounds_fixed`;
+#   2. Y gets r = max(P - ub_cb - ub_cr, 0), ub_x the bound of the point the chroma plane TOOK, promised or not: what chroma did not
+#      need goes to the luminance. The device restates this line (`eae_hip_colour_budget_rest`), so that r never visits the host;
+#   3. if all three planes are promised, header + ub_y + ub_cb + ub_cr <= B: ub_y <= r = P - ub_cb - ub_cr, and r > 0 or ub_y > 0 = r
+#      would not be promised, so P = B - header.
+COLOUR_SHARE_SHIFT = 16
+
+
+def colour_header_bytes():
+    """The bytes in front of the three plane blobs of an EAC1 blob: the size of `container`'s colour header struct."""
+    from . import container
+    return container.COLOUR_HEADER_BYTES
+
+
+def _colour_payloads(budget_bytes):
+    """budget_bytes, a scalar or one value per picture -> P = max(B - header, 0), int64 (N,) (a scalar: (1,))."""
+    budgets = numpy.asarray(budget_bytes)
+    if budgets.ndim > 1 or budgets.dtype.kind not in 'iuf' or (budgets.dtype.kind == 'f' and not numpy.isfinite(budgets).all()):
+        raise ValueError('`budget_bytes` must be a number or one number per picture.')
+    if budgets.size and (budgets.max() > (1 << 62) or budgets.min() < -(1 << 62)):
+        raise ValueError('`budget_bytes` does not belong to [-2^62, 2^62].')
+    return numpy.maximum(numpy.atleast_1d(budgets).astype(numpy.int64) - colour_header_bytes(), 0)
+
+
+def colour_chroma_budgets(budget_bytes, chroma_share):
+    """-> int64 (N,): c, the byte budget of the Cb blob and of the Cr blob of every picture (rule 1 above). budget_bytes: a scalar
+    (N = 1) or one value per picture, up to 2^62; chroma_share: the fraction of the payload both chroma planes together may take,
+    0 < chroma_share < 1, else ValueError. The product is formed in two halves, so nothing leaves int64."""
+    try:
+        share = float(chroma_share)
+    except (TypeError, ValueError):
+        raise ValueError('`chroma_share` must be a number.')
+    if isinstance(chroma_share, (bool, numpy.bool_)) or not 0. < share < 1.:
+        raise ValueError('`chroma_share` does not belong to ]0, 1[.')
+    share_q16 = int(round(share*(1 << COLOUR_SHARE_SHIFT)))
+    payload = _colour_payloads(budget_bytes)
+    shift = COLOUR_SHARE_SHIFT + 1
+    # (P * q) >> 17 with P = high * 2^17 + low: high * q + ((low * q) >> 17), high * q < 2^45 * 2^16
+    return (payload >> shift)*share_q16 + (((payload & ((1 << shift) - 1))*share_q16) >> shift)
+
+
+def colour_luma_budgets(budget_bytes, upper_cb, point_cb, upper_cr, point_cr):
+    """-> int64 (N,): r, the byte budget of the Y blob of every picture (rule 2 above): max(P - upper_cb[i, point_cb[i]] -
+    upper_cr[i, point_cr[i]], 0). budget_bytes: a scalar or one value per picture, up to 2^62; upper_cb, upper_cr int (N, K), the
+    chroma planes' `upper_bounds_fixed`, not negative; point_cb, point_cr int (N,), the points they took. A picture with a point
+    outside [0, K) gets 0, as on the device (`device.colour_budget_rest` is this function element for element)."""
+    (upper_cb, upper_cr) = (numpy.asarray(upper_cb), numpy.asarray(upper_cr))
+    (point_cb, point_cr) = (numpy.asarray(point_cb), numpy.asarray(point_cr))
+    if upper_cb.ndim != 2 or upper_cb.shape[1] < 1 or upper_cr.shape != upper_cb.shape or upper_cb.dtype.kind not in 'iu' or upper_cr.dtype.kind not in 'iu':
+        raise ValueError('`upper_cb` and `upper_cr` must be integer arrays (N, K) with K >= 1.')
+    (nb_images, nb_points) = upper_cb.shape
+    if point_cb.shape != (nb_images,) or point_cr.shape != (nb_images,) or point_cb.dtype.kind not in 'iu' or point_cr.dtype.kind not in 'iu':
+        raise ValueError('`point_cb` and `point_cr` must be integer arrays (N,).')
+    if nb_images and (upper_cb.min() < 0 or upper_cr.min() < 0 or max(int(upper_cb.max()), int(upper_cr.max())) >= (1 << 63)):
+        raise ValueError('An upper bound is negative or does not fit int64.')
+    payload = _colour_payloads(budget_bytes)
+    if payload.shape[0] not in (1, nb_images):
+        raise ValueError('`budget_bytes` must be a number or one number per picture.')
+    rest = numpy.broadcast_to(payload, (nb_images,)).copy()
+    inside = (point_cb >= 0) & (point_cb < nb_points) & (point_cr >= 0) & (point_cr < nb_points)
+    rows = numpy.arange(nb_images)
+    for (upper, point) in ((upper_cb, point_cb), (upper_cr, point_cr)):
+        taken = upper.astype(numpy.int64)[rows, numpy.where(inside, point, 0)]
+        rest = numpy.where(rest > taken, rest - taken, 0)          # never below -2^63: both operands are in [0, 2^63)
+    return numpy.where(inside, rest, 0).astype(numpy.int64)
 
 
 # ---- the rule of `codec.QualityCodec`: the coarsest point per image that keeps a PSNR floor, in integers (DESIGN.md section 21) -----

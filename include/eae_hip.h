@@ -774,6 +774,22 @@ int eae_hip_colour_merge_420_words(const uint8_t* y, const uint8_t* cb, const ui
 int eae_hip_colour_merge_420_crops(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, const int32_t* origins, uint8_t* dst,
                                    uint64_t dst_bytes, int n, int h, int w, int rh, int rw, int rch, int rcw, void* stream);
 
+/* colour_budget_rest: the byte budget of the luminance plane of n colour pictures, from what their chroma planes
+ *   took -- ratecontrol.colour_luma_budgets, integers only, so that the number never visits the host between the chroma steps and the
+ *   luminance step of a colour codec. budgets i64 [n]: B, the budget of each picture's single-picture EAC1 blob; header_bytes: the
+ *   bytes of the EAC1 header in front of the three plane blobs (container.py's colour header struct, 48); upper_cb, upper_cr i64
+ *   [n][k_points]: the upper bounds of the chroma planes at every point (eae_hip_ladder_select's `upper`, byte counts, never
+ *   negative); point_cb, point_cr i32 [n]: the points they took. With P = max(B - header_bytes, 0):
+ *     out[i] = max(max(P - upper_cb[i][point_cb[i]], 0) - upper_cr[i][point_cr[i]], 0)
+ *   which for bounds that are not negative is max(P - ub_cb - ub_cr, 0), and in which no difference leaves int64 for any B in
+ *   [-2^63 + header_bytes, 2^63). A picture with a point outside [0, k_points) gets out[i] = 0 and nothing of its rows is loaded.
+ *   All six in device or pinned, device-mapped host memory. One lane per picture, ceil(n / 256) blocks of 256, any n; one launch,
+ *   asynchronous on `stream`, no argument computed from data.
+ *   Refused (EAE_HIP_BAD_ARGUMENT, in front of the launch): a NULL pointer, n or k_points not positive, header_bytes negative, a 64-bit
+ *   array that is not 8-byte aligned, a point array that is not 4-byte aligned. */
+int eae_hip_colour_budget_rest(const int64_t* budgets, const int64_t* upper_cb, const int32_t* point_cb, const int64_t* upper_cr,
+                               const int32_t* point_cr, int64_t* out, int n, int k_points, int64_t header_bytes, void* stream);
+
 /* ==== TEST HOOKS (-DEAE_TEST_HOOKS): NOT exported by the product library lib/libeae_hip.so ====================================
  * Five entry points the test-suite needs and a deployment must not have (they change what later launches do, or only
  * exist to prove something about the kernels). Compiled into lib/libeae_hip_test.so only; tests/test_abi.py checks that
