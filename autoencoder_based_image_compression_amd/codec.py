@@ -3040,7 +3040,7 @@ class QualityCodec(BudgetCodec):
         and arguments are the same every step: the rounds differ by a scalar, the step's contents travel through device memory."""
         quality = self._budget_slots[id(slot)]
         y = self._launch_selection(luminances_uint8, slot, quality, hook)
-        dev.fetch_prefix(quality.pinned_max_sse, quality.max_sse, quality.max_sse_nbytes)
+        self._launch_thresholds(quality)
         hook('search', lambda: self._launch_round(quality, 0))
         dec = self.decoder
         d = dec.v
@@ -3054,10 +3054,90 @@ class QualityCodec(BudgetCodec):
                                                                   d['decoder/beta_5'], workspace=ws))
             t = hook('probe_tconv2_igdn6', lambda: dev.tconv5x5s2(t, dec.w5, d['decoder/biases_5'], dev.NORM_IGDN, dec.g[6], d['decoder/beta_6'],
                                                                   workspace=ws))
-            hook('probe_tconv3', lambda: dev.tconv9x9s4_luma(t, dec.w6, want_f32=False, want_u8=False, ref_u8=luminances_uint8,
-                                                             sse=quality.probe_acc))
+            hook('probe_tconv3', lambda: self._launch_probe_error(t, luminances_uint8, quality))
             hook('search', lambda: self._launch_round(quality, r))
         return self._launch_quantiser(y, slot, quality, hook)
+
+    def _launch_thresholds(self, quality):
+        """The step's thresholds out of the slot's pinned block into its device block, in front of round 0."""
+        dev.fetch_prefix(quality.pinned_max_sse, quality.max_sse, quality.max_sse_nbytes)
+
+    def _launch_probe_error(self, t, luminances_uint8, quality):
+        """A probe's transpose_conv_3 without a plane: its squared error against the step's input, added into `probe_acc`."""
+        return dev.tconv9x9s4_luma(t, self.decoder.w6, want_f32=False, want_u8=False, ref_u8=luminances_uint8, sse=quality.probe_acc)
+
+
+class _PlaneQualityCodec(QualityCodec):
+    """`QualityCodec` as one plane of a colour picture inside `ColourQualityCodec`; private: the public
+    rate-control codecs go on refusing `pad`. Two things are its own, as two are `_PlaneBudgetCodec`'s.
+    `pad=True` is taken: h_in x w_in is the plane's REAL size, the step runs at the coded size as `BatchCodec(pad=True)` runs it, and
+    EVERY squared error of the step is over the real pixels: the final one as `BatchCodec(pad=True)` takes it, a probe's out of the
+    epilogue of its own transpose_conv_3 (`device.tconv9x9s4_luma_frame`) against the padded frame the analysis side was given, so
+    that 'probe_sse' at the point taken IS 'sse' and `sse <= max_sse` stands on the count `max_sse_for_psnr(T, h_in*w_in)` assumes.
+    The bounds, the header and the blobs are those of the coded plane with the real size in the `crop` byte.
+    thresholds_on_device=True: `submit(images, max_sse=...)` also takes an int64 device tensor (batch_size,) that was written earlier
+    on the caller's stream. The step copies it into its slot's `max_sse` block on the step's own stream, behind that stream's wait for
+    the caller's and in front of round 0, launches no `fetch_prefix` of thresholds, eager or replayed, and publishes `max_sse` into
+    the slot's `pinned_max_sse` together with the selection: 'max_sse' of `result()` is what the device used. A host array or a scalar
+    goes the same way, through the slot's pinned block. The slot's `max_sse` block is free then: `_submit` has waited for the slot."""
+    _takes_pad = True
+
+    def __init__(self, variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, target_psnr=None, max_sse=None, budget_bytes=None,
+                 thresholds_on_device=False, **batch_codec_options):
+        self.thresholds_on_device = bool(thresholds_on_device)
+        super(_PlaneQualityCodec, self).__init__(variables, are_bin_widths_learned, ladder, batch_size, h_in, w_in, target_psnr=target_psnr,
+                                                 max_sse=max_sse, budget_bytes=budget_bytes, **batch_codec_options)
+
+    def _max_sse_of(self, target_psnr, max_sse, batch_size):
+        if not isinstance(max_sse, torch.Tensor):
+            return super(_PlaneQualityCodec, self)._max_sse_of(target_psnr, max_sse, batch_size)
+        if target_psnr is not None:
+            raise ValueError('give `target_psnr` or `max_sse`, not both.')
+        if not self.thresholds_on_device:
+            raise ValueError('`max_sse` as a tensor needs `thresholds_on_device=True`.')
+        if max_sse.dtype != torch.int64 or tuple(max_sse.shape) != (batch_size,) or not max_sse.is_contiguous() or max_sse.device != self.device:
+            raise ValueError('`max_sse` as a tensor must be int64 (batch_size,), contiguous, on the codec\'s device.')
+        return max_sse
+
+    def _stage(self, slot):
+        """With `thresholds_on_device`: the step's thresholds into the slot's DEVICE block, on the current stream (the step's own);
+        its budgets as ever."""
+        if not self.thresholds_on_device:
+            return super(_PlaneQualityCodec, self)._stage(slot)
+        BudgetCodec._stage(self, slot)
+        (quality, staged, n) = (self._budget_slots[id(slot)], self._staged[1], self.batch_size)
+        if isinstance(staged, torch.Tensor):
+            quality.max_sse[:n].copy_(staged, non_blocking=True)
+            staged.record_stream(torch.cuda.current_stream())
+        else:
+            quality.max_sse_host[:n] = staged
+            quality.max_sse[:n].copy_(quality.pinned_max_sse[:n], non_blocking=True)
+
+    def _replay_step(self, luminances_uint8, slot, index, ticket, coded):
+        if not self.thresholds_on_device:
+            return super(_PlaneQualityCodec, self)._replay_step(luminances_uint8, slot, index, ticket, coded)
+        # the stream `BatchCodec._replay_step` replays this step's graphs on: the thresholds go there in front of them
+        stream = self._transform_streams[index % len(self._transform_streams)]
+        stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(stream):
+            self._stage(slot)
+        return BatchCodec._replay_step(self, luminances_uint8, slot, index, ticket, coded)
+
+    def _launch_thresholds(self, quality):
+        if not self.thresholds_on_device:                # (else `_stage` has put them there: nothing is launched, captured or eager)
+            super(_PlaneQualityCodec, self)._launch_thresholds(quality)
+
+    def _launch_probe_error(self, t, luminances_uint8, quality):
+        """The probe's error over the plane's real pixels, out of the transposed conv's own epilogue: `luminances_uint8` is the padded
+        frame here (`BatchCodec._launch_step` / the graph's static input)."""
+        return dev.tconv9x9s4_luma_frame(t, self.decoder.w6, (self.h_image, self.w_image), want_f32=False, want_u8=False,
+                                         ref_u8=luminances_uint8, sse=quality.probe_acc)
+
+    def _publish_coder_side(self, slot):
+        if self.thresholds_on_device:
+            quality = self._budget_slots[id(slot)]
+            dev.publish_to_host(quality.max_sse, quality.pinned_max_sse)
+        super(_PlaneQualityCodec, self)._publish_coder_side(slot)
 
 
 # ---- the same for tile-indexed containers: the search's rows per stream, in the coder's run order (DESIGN.md section 22) -----------
@@ -3507,6 +3587,165 @@ class ColourBudgetCodec(ColourCodec):
     def _enqueue(self, step, rgb_uint8, host):
         ticket = super(ColourBudgetCodec, self)._enqueue(step, rgb_uint8, host)
         ticket._picture_budgets = self._submitting[0].copy()
+        return ticket
+
+
+# ---- a PSNR floor per colour picture ----------------------------------------------------------------------------
+
+class ColourQualityTicket(ColourTicket):
+    """Handle on one submitted `ColourQualityCodec` step."""
+    _picture_max_sse = None                   # int64 (N,): the step's thresholds per picture, the ticket's own copy
+
+    def result(self):
+        """`ColourTicket.result()` over the three `QualityCodec.result()`s -- every key (N, 3, ...) in the order Y, Cb, Cr, 'max_sse'
+        the thresholds the planes' searches used, and 'sse_rgb' (information: the rule does not read it) -- plus, per picture, int64 /
+        bool (N,): 'picture_max_sse', M; 'picture_sse', the three 'sse' summed: the squared error over all samples of the 4:2:0 form;
+        'picture_met': picture_sse <= M; 'picture_blob_bytes', 48 plus the three 'blob_bytes': the length of `image_containers()[i]`."""
+        if self._values is None:
+            values = super(ColourQualityTicket, self).result()
+            values['picture_max_sse'] = self._picture_max_sse
+            values['picture_sse'] = values['sse'].astype(numpy.int64).sum(axis=1)
+            values['picture_met'] = values['picture_sse'] <= self._picture_max_sse
+            values['picture_blob_bytes'] = container_format.COLOUR_HEADER_BYTES + values['blob_bytes'].sum(axis=1)
+        return self._values
+
+    def container(self):
+        """Always raises, as `BudgetTicket.container()`: every picture of the step has rate points of its own."""
+        raise RuntimeError('a ColourQualityCodec step has rate points per picture and one EAC1 blob holds one per plane: use `image_containers()`')
+
+
+class _ColourQualityStep(_ColourStep):
+    """`_ColourStep` with the step's thresholds: the pictures' in a pinned block and on the device, the luminance planes' on the device."""
+
+    def __init__(self, codec):
+        super(_ColourQualityStep, self).__init__(codec)
+        n = codec.batch_size
+        self.pinned_max_sse = torch.zeros(n, dtype=torch.int64).pin_memory()
+        self.max_sse_host = self.pinned_max_sse.numpy()
+        self.max_sse = torch.zeros(n, dtype=torch.int64, device=codec.device)
+        self.luma_max_sse = torch.zeros(n, dtype=torch.int64, device=codec.device)      # written by `device.colour_quality_rest`
+
+
+class ColourQualityCodec(ColourCodec):
+    """`ColourCodec` with ONE PSNR floor per picture: over all S = h w + 2 hc wc samples of its 4:2:0 form, shared between its three
+    planes on the device inside the step (the rule is `ratecontrol.colour_chroma_max_sse` /
+    `colour_luma_max_sse`, its synchronous sibling `container.encode_colour_images_to_quality`). The inner codecs are two
+    `_PlaneQualityCodec(pad=True, keep_reconstruction=True)`, `luma` with `thresholds_on_device=True`; the ring depth, the drain when a
+    submit raises, `close`, `fetch_reconstruction` and the merge are `ColourCodec`'s.
+
+    `submit(rgb, target_psnr=None, max_sse=None)` enqueues, in this order: the batch copy and the split; Cb and Cr into `chroma`, each
+    with the host-computed threshold a = (M * share_q16) >> 17; on the caller's stream, behind both chroma steps' `decoded_event`, ONE
+    `device.colour_quality_rest` launch, which reads the picture thresholds (uploaded from the step's pinned block) and the two chroma
+    slots' published 'sse' -- the real squared errors of the points taken, which the synthesis side's `publish_step` writes into the
+    slot's pinned words in front of that event (the device's own words are cleared by the same launch) -- and writes max(M - sse_cb -
+    sse_cr, 0) into the step's own buffer; Y into `luma` with that buffer as its thresholds; the merge. The luminance threshold never
+    visits the host, and no launch argument depends on it. The words read stay valid until their slot comes round, which
+    `ColourCodec`'s depth rule puts behind this step's merge, hence behind the launch that read them. The luminance analysis of a
+    colour step runs behind its chroma steps; steps of the ring overlap as in `ColourCodec`.
+
+    ladder, chroma_ladder (None: `ladder`): `ratecontrol.RateLadder`s of the same number of points and the same truncated unary
+    length; chroma_share: the fraction of the picture's squared error both chroma planes together may take, in ]0, 1[ (1/3, the
+    chroma planes' share of the samples: a starting value nobody has measured on a trained model). target_psnr (dB, over the S
+    samples: `ratecontrol.max_sse_for_psnr(T, colour_nb_samples(h, w))`) or max_sse (an integer in [0, 2^62]): the threshold of a
+    `submit` that names none, a scalar or one value per picture, at most one of the two. Refused in front of every allocation:
+    `budget_bytes` (a budget under a floor is out of scope), `coding_tile`, the keyword `rdo_lambda` (a ladder with a price is
+    fine), `pad` / `keep_reconstruction` / `thresholds_on_device` as options, and what `QualityCodec` refuses.
+    MONOTONICITY IS ASSUMED AND NOT CHECKED, per plane, as in `ratecontrol.select_by_quality`."""
+    (_step_class, _ticket_class) = (_ColourQualityStep, ColourQualityTicket)
+
+    def __init__(self, variables, are_bin_widths_learned, ladder, batch_size, h, w, target_psnr=None, max_sse=None, chroma_ladder=None,
+                 chroma_share=1./3., chroma_options=None, **batch_codec_options):
+        from . import ratecontrol
+        (self.luma, self.chroma) = (None, None)
+        chroma_ladder = ladder if chroma_ladder is None else chroma_ladder
+        if not isinstance(ladder, ratecontrol.RateLadder) or not isinstance(chroma_ladder, ratecontrol.RateLadder):
+            raise TypeError('`ladder` and `chroma_ladder` must be `ratecontrol.RateLadder`s.')
+        # refused in front of every allocation
+        for options in (batch_codec_options, chroma_options or {}):
+            if 'budget_bytes' in options:
+                raise ValueError('`ColourQualityCodec` does not take `budget_bytes`: a byte budget under a quality floor is out of scope.')
+            if options.get('coding_tile') is not None:
+                raise ValueError('`ColourQualityCodec` does not take `coding_tile`: the plane blobs are those of whole maps (EAE1).')
+            if options.get('rdo_lambda') is not None:
+                raise ValueError('`ColourQualityCodec` does not take `rdo_lambda`: the price of a bit comes with the ladder '
+                                 '(`ratecontrol.RateLadder(..., rdo_lambda=...)`).')
+            if 'thresholds_on_device' in options:
+                raise ValueError('`thresholds_on_device` is not an option of ColourQualityCodec: its luminance codec runs with it.')
+        if chroma_ladder.nb_points != ladder.nb_points:
+            raise ValueError('`ladder` and `chroma_ladder` hold {0} and {1} rate points: the same number is needed.'.format(
+                ladder.nb_points, chroma_ladder.nb_points))
+        if chroma_ladder.truncated_unary_length != ladder.truncated_unary_length:
+            raise ValueError('`ladder` and `chroma_ladder` have truncated unary lengths {0} and {1}: the same is needed.'.format(
+                ladder.truncated_unary_length, chroma_ladder.truncated_unary_length))
+        ratecontrol.colour_chroma_max_sse(0, chroma_share)             # refuses a share outside ]0, 1[
+        self.chroma_share = float(chroma_share)
+        (self.ladder, self.chroma_ladder) = (ladder, chroma_ladder)
+        self.batch_size = container_format._positive_int(batch_size, '`batch_size`')
+        self._nb_samples = ratecontrol.colour_nb_samples(container_format._positive_int(h, '`h`'), container_format._positive_int(w, '`w`'))
+        self._default_max_sse = self._max_sse_of(target_psnr, max_sse)
+        self._submitting = None
+        self._build(batch_size, h, w, chroma_options, batch_codec_options,
+                    lambda is_chroma, height, width, **options: _PlaneQualityCodec(
+                        variables, are_bin_widths_learned, chroma_ladder if is_chroma else ladder, self.batch_size, height, width, pad=True,
+                        keep_reconstruction=True, thresholds_on_device=not is_chroma, **options))
+        self.emit_container = True
+
+    def _max_sse_of(self, target_psnr, max_sse):
+        """The thresholds of a step as int64 (batch_size,), from one of the two ways to name them; None when neither is given."""
+        from . import ratecontrol
+        if target_psnr is not None and max_sse is not None:
+            raise ValueError('give `target_psnr` or `max_sse`, not both.')
+        if target_psnr is not None:
+            targets = numpy.asarray(target_psnr, dtype=numpy.float64)
+            if targets.ndim > 1 or (targets.ndim == 1 and targets.shape[0] != self.batch_size):
+                raise ValueError('`target_psnr` must be a number or one number per picture.')
+            max_sse = ratecontrol.max_sse_for_psnr(targets, self._nb_samples)
+        if max_sse is None:
+            return None
+        thresholds = ratecontrol._colour_max_sse(max_sse)              # refuses what is no integer in [0, 2^62]
+        if numpy.ndim(max_sse) == 1 and thresholds.shape[0] != self.batch_size:
+            raise ValueError('`max_sse` must be an integer or one integer per picture.')
+        return numpy.ascontiguousarray(numpy.broadcast_to(thresholds, (self.batch_size,)))
+
+    def submit(self, rgb_uint8, target_psnr=None, max_sse=None):
+        """`ColourCodec.submit` with the step's thresholds: `target_psnr` (dB over the picture's S samples) or `max_sse` (the largest
+        sse_Y + sse_Cb + sse_Cr), a scalar or one value per picture; neither: the constructor's."""
+        from . import ratecontrol
+        if target_psnr is None and max_sse is None:
+            thresholds = self._default_max_sse
+            if thresholds is None:
+                raise ValueError('neither `target_psnr` nor `max_sse`, and the codec was built without a default.')
+        else:
+            thresholds = self._max_sse_of(target_psnr, max_sse)
+        self._submitting = (thresholds, ratecontrol.colour_chroma_max_sse(thresholds, self.chroma_share))
+        try:
+            return super(ColourQualityCodec, self).submit(rgb_uint8)
+        finally:
+            self._submitting = None
+
+    def _submit_planes(self, step):
+        (thresholds, chroma_thresholds) = self._submitting
+        # the entry is this step's: `submit` has waited for the merge of the step that used it last, which lies behind that step's
+        # `colour_quality_rest` and luminance search
+        step.max_sse_host[:] = thresholds
+        step.max_sse.copy_(step.pinned_max_sse, non_blocking=True)
+        n = self.batch_size
+        chroma_slots = []
+        chroma_tickets = []
+        for plane in step.planes[1:]:
+            chroma_slots.append(self.chroma._slots[self.chroma._index % self.chroma.nb_slots])     # the slot this inner step takes (`BatchCodec._submit`)
+            chroma_tickets.append(self.chroma.submit(plane, max_sse=chroma_thresholds))
+        caller = torch.cuda.current_stream()
+        for inner in chroma_tickets:
+            caller.wait_event(inner.decoded_event)
+        (of_cb, of_cr) = chroma_slots
+        dev.colour_quality_rest(step.max_sse, of_cb.pinned_sse[:n], of_cr.pinned_sse[:n], step.luma_max_sse)
+        luma_ticket = self.luma.submit(step.planes[0], max_sse=step.luma_max_sse)
+        return (luma_ticket,) + tuple(chroma_tickets)
+
+    def _enqueue(self, step, rgb_uint8, host):
+        ticket = super(ColourQualityCodec, self)._enqueue(step, rgb_uint8, host)
+        ticket._picture_max_sse = self._submitting[0].copy()
         return ticket
 
 

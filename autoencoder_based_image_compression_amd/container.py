@@ -1160,6 +1160,107 @@ def encode_colour_images_to_budget(rgb_uint8, encoder, ladder, budget_bytes, chr
     return blobs, info
 
 
+def encode_colour_images_to_quality(rgb_uint8, encoder, decoder, ladder, target_psnr=None, max_sse=None, chroma_ladder=None,
+                                    chroma_share=1./3.):
+    """uint8 (N, h, w, 3) RGB pictures of any height and width -> (blobs, info): every picture as a single-picture EAC1 blob, as small
+    as the ladders allow while its PSNR over all S = h w + 2 hc wc samples of its 4:2:0 form is `target_psnr` dB or better -- its
+    squared error sse_Y + sse_Cb + sse_Cr against the split input within `max_sse`; give one of the two, a scalar or one value per
+    picture. The synchronous sibling of `codec.ColourQualityCodec` and the statement of its rule (ratecontrol.py, "the rule of
+    `codec.ColourQualityCodec`").
+
+    The pictures are split 4:2:0 on the device (device.colour_split_420); every plane is padded (device.frame_pad_u8) and gets one
+    analysis transform and one pass of counts at the K points of its ladder -- `ladder` for Y, `chroma_ladder` (None: `ladder`) for
+    Cb and Cr, both of the same K --, from which its search starts at the first point whose symbols fit int16. A probe quantises the
+    padded plane at its point, decodes it with `decoder` and takes the squared error over the REAL samples (`device.frame_sse_u8`
+    against the real plane). Cb and Cr run `ratecontrol.bisect_by_quality` for `ratecontrol.colour_chroma_max_sse(max_sse,
+    chroma_share)`, Y for `ratecontrol.colour_luma_max_sse`: the threshold less the real squared errors of the points chroma took.
+    Every plane is then coded with `encode_images(plane[i:i + 1], ..., pad=True)` at its point (`rdo_lambda=ladder.rdo_lambdas[k]` for
+    a ladder with a price) and the three blobs are assembled with `assemble_colour_blob`: `decode_colour_images` and
+    `codec.ColourDecoder` read the blobs unchanged. The squared error of a plane is assumed not to decrease along its ladder
+    (`ratecontrol.select_by_quality`); the default share is a starting value nobody has measured on a trained model.
+    info: 'rate_point', 'first_point', 'sse', 'plane_max_sse', 'plane_blob_bytes' int64 (N, 3) in the order Y, Cb, Cr;
+    'plane_met' bool (N, 3); 'probe_points', 'probe_sse' int64 (N, 3, R); 'max_sse', 'picture_sse', 'blob_bytes' int64 (N,); 'met'
+    bool (N,): picture_sse <= max_sse."""
+    from . import ratecontrol
+    rgb = numpy.ascontiguousarray(rgb_uint8)
+    if rgb.dtype != numpy.uint8:
+        raise TypeError('`rgb_uint8.dtype` is not equal to `numpy.uint8`.')
+    if rgb.ndim != 4 or rgb.shape[3] != 3 or 0 in rgb.shape:
+        raise ValueError('`rgb_uint8` must be (N, h, w, 3) and hold a pixel.')
+    chroma_ladder = ladder if chroma_ladder is None else chroma_ladder
+    if not isinstance(ladder, ratecontrol.RateLadder) or not isinstance(chroma_ladder, ratecontrol.RateLadder):
+        raise TypeError('`ladder` and `chroma_ladder` must be `ratecontrol.RateLadder`s.')
+    if chroma_ladder.nb_points != ladder.nb_points:
+        raise ValueError('`ladder` and `chroma_ladder` hold {0} and {1} rate points: the same number is needed.'.format(
+            ladder.nb_points, chroma_ladder.nb_points))
+    if (target_psnr is None) == (max_sse is None):
+        raise ValueError('give `target_psnr` or `max_sse`, one of the two.')
+    (nb_images, height, width) = rgb.shape[:3]
+    if target_psnr is not None:
+        targets = numpy.asarray(target_psnr, dtype=numpy.float64)
+        if targets.ndim > 1 or (targets.ndim == 1 and targets.shape[0] != nb_images):
+            raise ValueError('`target_psnr` must be a number or one number per picture.')
+        max_sse = ratecontrol.max_sse_for_psnr(targets, ratecontrol.colour_nb_samples(height, width))
+    if numpy.ndim(max_sse) > 1 or (numpy.ndim(max_sse) == 1 and numpy.shape(max_sse)[0] != nb_images):
+        raise ValueError('`max_sse` must be an integer or one integer per picture.')
+    thresholds = numpy.ascontiguousarray(numpy.broadcast_to(ratecontrol._colour_max_sse(max_sse), (nb_images,)))
+    chroma_thresholds = ratecontrol.colour_chroma_max_sse(thresholds, chroma_share)
+    device = encoder.device
+    planes = dev.colour_split_420(torch.from_numpy(rgb).to(device))
+    (nb_points, rounds) = (ladder.nb_points, ratecontrol.quality_rounds(ladder.nb_points))
+
+    def search(plane, plane_ladder, plane_thresholds):
+        """One plane of every picture -> (point, met, probe_points, probe_sse, first, sse of the point taken)."""
+        padded = dev.frame_pad_u8(plane)
+        map_size = (padded.shape[1]//csts.STRIDE_PROD)*(padded.shape[2]//csts.STRIDE_PROD)
+        y = encoder(padded)
+        points = _LadderOnDevice(plane_ladder, device)
+        (hist, bypass_bits) = points.histograms(y)
+        upper = ratecontrol.upper_bounds_fixed(hist, bypass_bits, plane_ladder, map_size)
+        (first, _) = ratecontrol.select_by_upper_bound(upper, ratecontrol.valid_points(hist, map_size), 1 << 62)
+        found = (numpy.zeros(nb_images, dtype=numpy.int64), numpy.zeros(nb_images, dtype=bool), numpy.zeros((nb_images, rounds), dtype=numpy.int64),
+                 numpy.zeros((nb_images, rounds), dtype=numpy.int64), first, numpy.zeros(nb_images, dtype=numpy.int64))
+        for i in range(nb_images):
+            known = {}
+
+            def sse_of(k):
+                if k not in known:
+                    q = points.quantize(y[i:i + 1], k, want_shifted=True)
+                    (_, decoded, _) = decoder(q['shifted'])
+                    known[k] = int(dev.frame_sse_u8(decoded, plane[i:i + 1]).item())
+                return known[k]
+
+            (found[0][i], found[1][i], found[2][i], found[3][i]) = ratecontrol.bisect_by_quality(sse_of, nb_points, int(first[i]),
+                                                                                                 int(plane_thresholds[i]))
+            found[5][i] = sse_of(int(found[0][i]))
+        return found
+
+    of_cb = search(planes[1], chroma_ladder, chroma_thresholds)
+    of_cr = search(planes[2], chroma_ladder, chroma_thresholds)
+    luma_thresholds = ratecontrol.colour_luma_max_sse(thresholds, of_cb[5], of_cr[5])
+    of_y = search(planes[0], ladder, luma_thresholds)
+    every = (of_y, of_cb, of_cr)
+    info = {key: numpy.stack([found[at] for found in every], axis=1)
+            for (at, key) in enumerate(('rate_point', 'plane_met', 'probe_points', 'probe_sse', 'first_point', 'sse'))}
+    info.update({'plane_max_sse': numpy.stack([luma_thresholds, chroma_thresholds, chroma_thresholds], axis=1), 'max_sse': thresholds,
+                 'plane_blob_bytes': numpy.zeros((nb_images, 3), dtype=numpy.int64)})
+    host_planes = [plane.cpu().numpy() for plane in planes]
+    blobs = []
+    for i in range(nb_images):
+        plane_blobs = []
+        for (which, (plane, plane_ladder)) in enumerate(zip(host_planes, (ladder, chroma_ladder, chroma_ladder))):
+            k = int(info['rate_point'][i, which])
+            more = {} if plane_ladder.rdo_lambdas is None else {'rdo_lambda': plane_ladder.rdo_lambdas[k]}
+            plane_blobs.append(encode_images(plane[i:i + 1], encoder, plane_ladder.bin_widths_points[k], plane_ladder.map_mean,
+                                             plane_ladder.binary_probabilities_points[k], plane_ladder.idx_map_exception, pad=True, **more)[0])
+            info['plane_blob_bytes'][i, which] = len(plane_blobs[which])
+        blobs.append(assemble_colour_blob(rgb.shape[1:3], *plane_blobs))
+    info['blob_bytes'] = numpy.array([len(blob) for blob in blobs], dtype=numpy.int64)
+    info['picture_sse'] = info['sse'].sum(axis=1)
+    info['met'] = info['picture_sse'] <= thresholds
+    return blobs, info
+
+
 def decode_colour_images(blob, decoder, tile=None):
     """EAC1 blob + pipeline.DeviceDecoder of the model -> uint8 (N, h, w, 3) RGB: `decode_images` of each plane, merged on the device
     (device.colour_merge_420: `colour.merge_420_numpy` of the three reconstructions)."""

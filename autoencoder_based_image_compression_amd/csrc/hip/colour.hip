@@ -9,6 +9,8 @@
 //   eae_hip_colour_merge_420_words: the same picture in whole aligned 16-byte words, for the resident decoder (further down).
 //   eae_hip_colour_budget_rest: the byte budget of a picture's luminance plane from what its chroma planes took (at
 //     the end of the file): no pixel work, one lane per picture.
+//   eae_hip_colour_quality_rest: the squared-error threshold of a picture's luminance plane from what its chroma planes spent (DESIGN.md
+//     section 30; behind it): the same shape of launch.
 // In the first two a lane owns one chroma sample, i.e. a 2 x 2 block of pixels: 12 bytes of the picture, six contiguous ones in each of two
 // rows, so a wave covers 384 contiguous bytes of a row. A block lies inside one image (blocks_per_image blocks of 256 samples each):
 // the image index is a division of the block index, the offset of the image 64 bits wide, everything inside an image 32 bits. The
@@ -497,6 +499,22 @@ __global__ __launch_bounds__(BUDGET_REST_LANES) void colour_budget_rest_kernel(c
     out[i] = rest;
 }
 
+// ---- the luminance threshold of a colour picture ----------------------------------------------------------------
+// ratecontrol.colour_luma_max_sse on the device, so that the threshold of Y never visits the host: a lane owns one picture.
+// out = max(max(M - sse_cb, 0) - sse_cr, 0): for the squared errors they are (never negative) that is max(M - sse_cb - sse_cr, 0), and
+// every difference is taken between two values in [0, 2^63), so nothing leaves int64 for any M up to 2^62. A negative M gives 0.
+__global__ __launch_bounds__(BUDGET_REST_LANES) void colour_quality_rest_kernel(const int64_t* __restrict__ max_sse, const int64_t* __restrict__ sse_cb,
+                                                                                const int64_t* __restrict__ sse_cr, int64_t* __restrict__ out, uint32_t n) {
+    const uint32_t i = blockIdx.x * (uint32_t)BUDGET_REST_LANES + threadIdx.x;
+    if (i >= n) return;
+    int64_t rest = max_sse[i];
+    const int64_t of_cb = sse_cb[i], of_cr = sse_cr[i];
+    rest = rest > 0 ? rest : 0;
+    rest = rest > of_cb ? rest - of_cb : 0;
+    rest = rest > of_cr ? rest - of_cr : 0;
+    out[i] = rest;
+}
+
 }  // namespace
 
 extern "C" int eae_hip_colour_split_420(const uint8_t* rgb, uint8_t* y, uint8_t* cb, uint8_t* cr, int n, int h, int w, void* stream) {
@@ -570,6 +588,16 @@ extern "C" int eae_hip_colour_budget_rest(const int64_t* budgets, const int64_t*
     const uint32_t blocks = ((uint32_t)n + (uint32_t)BUDGET_REST_LANES - 1u) / (uint32_t)BUDGET_REST_LANES;      // one lane per picture, whatever n
     hipLaunchKernelGGL(colour_budget_rest_kernel, dim3(blocks), dim3(BUDGET_REST_LANES), 0, (hipStream_t)stream, budgets, upper_cb, point_cb,
                        upper_cr, point_cr, out, (uint32_t)n, (uint32_t)k_points, header_bytes);
+    EAE_HIP_CHECK_LAUNCH();
+    return EAE_HIP_OK;
+}
+
+extern "C" int eae_hip_colour_quality_rest(const int64_t* max_sse, const int64_t* sse_cb, const int64_t* sse_cr, int64_t* out, int n, void* stream) {
+    if (!max_sse || !sse_cb || !sse_cr || !out || n <= 0) return EAE_HIP_BAD_ARGUMENT;
+    if (((uintptr_t)max_sse | (uintptr_t)sse_cb | (uintptr_t)sse_cr | (uintptr_t)out) & 7u) return EAE_HIP_BAD_ARGUMENT;
+    const uint32_t blocks = ((uint32_t)n + (uint32_t)BUDGET_REST_LANES - 1u) / (uint32_t)BUDGET_REST_LANES;      // one lane per picture, whatever n
+    hipLaunchKernelGGL(colour_quality_rest_kernel, dim3(blocks), dim3(BUDGET_REST_LANES), 0, (hipStream_t)stream, max_sse, sse_cb, sse_cr, out,
+                       (uint32_t)n);
     EAE_HIP_CHECK_LAUNCH();
     return EAE_HIP_OK;
 }

@@ -71,10 +71,21 @@ __device__ __forceinline__ Tile tile_of(int t, int tiles_r, int tiles_c) {
 // MFMAs of one pass run, the input sites of the next pass -- the next channels of this tile, or the first ones of the block's
 // next tile -- are already on their way into registers, and so are the tile's reference pixels for the epilogue: the only
 // staging time left on the critical path is the LDS write between two barriers.
+//
+// FRAME (eae_hip_tconv9x9s4_luma_frame): the squared error is that of the pixels y < real_h, x < real_w
+// of every plane only -- the real picture inside a padded coded plane. Everything up to the epilogue's differences is the same code; there
+// a four-pixel group keeps the differences of its first real_w - x pixels (none on a row >= real_h) and zeroes the others: one
+// subtraction, five selects and four compares per group on values that live for those instructions only, real_h and real_w in
+// SGPRs. `ref` bytes outside the rectangle are loaded (they lie inside the coded frame) and never reach the sum. Without FRAME the
+// pack is empty: the kernel it was, argument for argument.
+template <bool FRAME, typename... Real>
 __global__ __launch_bounds__(NT, WAVES_PER_SIMD) void tconv3_kernel(const float* __restrict__ x, const float* __restrict__ wq,
                                                                      float* __restrict__ out_f32, uint8_t* __restrict__ out_u8,
                                                                      const uint8_t* __restrict__ ref, unsigned long long* sse,
-                                                                     int n_tiles, int h, int win, int tiles_r, int tiles_c) {
+                                                                     int n_tiles, int h, int win, int tiles_r, int tiles_c, Real... real) {
+    static_assert(sizeof...(Real) == (FRAME ? 2 : 0), "FRAME takes (int real_h, int real_w) behind the arguments, the other form nothing");
+    const int real_hw[] = {real..., 0, 0};
+    const int real_h = real_hw[0], real_w = real_hw[1];
     __shared__ __attribute__((aligned(16))) float patch[PATCH_FLOATS];
     __shared__ unsigned int red[WAVES];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -240,8 +251,13 @@ __global__ __launch_bounds__(NT, WAVES_PER_SIMD) void tconv3_kernel(const float*
                     if (out_u8) *reinterpret_cast<unsigned int*>(out_u8 + o) = q0 | (q1 << 8) | (q2 << 16) | (q3 << 24);
                     if (ref) {
                         const unsigned int rv = ref_px[half];
-                        const int d0 = (int)(rv & 0xFF) - (int)q0, d1 = (int)((rv >> 8) & 0xFF) - (int)q1;
-                        const int d2 = (int)((rv >> 16) & 0xFF) - (int)q2, d3 = (int)(rv >> 24) - (int)q3;
+                        int d0 = (int)(rv & 0xFF) - (int)q0, d1 = (int)((rv >> 8) & 0xFF) - (int)q1;
+                        int d2 = (int)((rv >> 16) & 0xFF) - (int)q2, d3 = (int)(rv >> 24) - (int)q3;
+                        if (FRAME) {           // a mask per pixel: real_w is any value in [1, wo]
+                            const int inside = gr < real_h ? real_w - gcc : 0;     // <= 0: none of the four, >= 4: all
+                            d0 = inside > 0 ? d0 : 0; d1 = inside > 1 ? d1 : 0;
+                            d2 = inside > 2 ? d2 : 0; d3 = inside > 3 ? d3 : 0;
+                        }
                         se += (unsigned int)(d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3);
                     }
                 }
@@ -308,8 +324,32 @@ extern "C" int eae_hip_tconv9x9s4_luma(const float* x, const float* w_phase, flo
     long grid = (long)cus * BLOCKS_PER_CU;
     if (grid > n_tiles) grid = n_tiles;
     grid = (grid + 7) / 8 * 8;
-    hipLaunchKernelGGL(tconv3_kernel, dim3((unsigned)grid), dim3(NT), 0, (hipStream_t)stream, x, w_phase, out_f32,
+    hipLaunchKernelGGL(tconv3_kernel<false>, dim3((unsigned)grid), dim3(NT), 0, (hipStream_t)stream, x, w_phase, out_f32,
                        out_u8, ref_u8, reinterpret_cast<unsigned long long*>(sse), (int)n_tiles, h, w_in, tiles_r, tiles_c);
+    EAE_HIP_CHECK_LAUNCH();
+    return EAE_HIP_OK;
+}
+
+// The same launch -- the tiling, the persistent grid and its cap are those above, restated, so that the entry point above stays the
+// code it was -- of the FRAME instantiation: the squared error over the top-left real_h x real_w of every coded plane.
+extern "C" int eae_hip_tconv9x9s4_luma_frame(const float* x, const float* w_phase, float* out_f32, uint8_t* out_u8,
+                                             const uint8_t* ref_u8, uint64_t* sse, int n, int h, int w_in, int real_h, int real_w,
+                                             void* stream) {
+    if (!x || !w_phase || n <= 0 || h <= 0 || w_in <= 0) return EAE_HIP_BAD_ARGUMENT;
+    if (!out_f32 && !out_u8 && !ref_u8) return EAE_HIP_BAD_ARGUMENT;
+    if ((ref_u8 != nullptr) != (sse != nullptr)) return EAE_HIP_BAD_ARGUMENT;
+    if ((long)h * w_in * EAE_C * (long)sizeof(float) > 0x7FFFFFFFL) return EAE_HIP_BAD_SHAPE;       // 32-bit offsets inside an image
+    if (real_h < 1 || real_w < 1 || real_h > 4L * h || real_w > 4L * w_in) return EAE_HIP_BAD_ARGUMENT;   // inside the coded plane
+    const int tiles_r = (h + TH - 1) / TH, tiles_c = (w_in + TW - 1) / TW;
+    const long n_tiles = (long)n * tiles_r * tiles_c;
+    if (n_tiles > 0x7FFFFFFFL) return EAE_HIP_BAD_ARGUMENT;
+    const int cus = eae_compute_units();
+    if (cus <= 0) return (int)hipErrorInvalidDevice;
+    long grid = (long)cus * BLOCKS_PER_CU;
+    if (grid > n_tiles) grid = n_tiles;
+    grid = (grid + 7) / 8 * 8;
+    hipLaunchKernelGGL((tconv3_kernel<true, int, int>), dim3((unsigned)grid), dim3(NT), 0, (hipStream_t)stream, x, w_phase, out_f32,
+                       out_u8, ref_u8, reinterpret_cast<unsigned long long*>(sse), (int)n_tiles, h, w_in, tiles_r, tiles_c, real_h, real_w);
     EAE_HIP_CHECK_LAUNCH();
     return EAE_HIP_OK;
 }

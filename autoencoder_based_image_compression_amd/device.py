@@ -306,6 +306,24 @@ def tconv9x9s4_luma(x, w_phase, want_f32=False, want_u8=True, ref_u8=None, sse=N
     return out_f32, out_u8, sse
 
 
+def tconv9x9s4_luma_frame(x, w_phase, image_size, want_f32=False, want_u8=True, ref_u8=None, sse=None):
+    """`tconv9x9s4_luma` whose squared error is over the REAL pixels of padded planes: image_size = (real_h,
+    real_w), anywhere in [1, 4h] x [1, 4w]; ref_u8 is the CODED frame [N, 4h, 4w] (`frame_pad_u8`'s output), of which the bytes outside
+    the real rectangle never reach the sum; the outputs requested are of the whole coded plane, bit for bit `tconv9x9s4_luma`'s.
+    sse[i] is added into. Returns (f32 or None, u8 or None, sse or None)."""
+    (n, h, wd, c) = x.shape
+    (real_h, real_w) = (int(image_size[0]), int(image_size[1]))
+    if ref_u8 is not None and (ref_u8.dtype != torch.uint8 or tuple(ref_u8.shape) != (n, 4*h, 4*wd) or not ref_u8.is_contiguous()):
+        raise HipError('ref_u8 must be the coded frame: uint8 [N, 4h, 4w], contiguous')
+    out_f32 = torch.empty((n, 4*h, 4*wd), dtype=torch.float32, device=x.device) if want_f32 else None
+    out_u8 = torch.empty((n, 4*h, 4*wd), dtype=torch.uint8, device=x.device) if want_u8 else None
+    if ref_u8 is not None and sse is None:
+        sse = torch.zeros(n, dtype=torch.int64, device=x.device)
+    _check(_native.hip().eae_hip_tconv9x9s4_luma_frame(_p(x), _p(w_phase), _p(out_f32), _p(out_u8), _p(ref_u8), _p(sse), n, h, wd, real_h,
+                                                       real_w, _stream(x)), 'eae_hip_tconv9x9s4_luma_frame')
+    return out_f32, out_u8, sse
+
+
 def pack_conv_weights(w_hwio):
     """HWIO [k,k,128,128] -> kernel layout [k*k,128,packed out] (include/eae_hip.h)."""
     (k, k2, ci, co) = w_hwio.shape
@@ -1738,6 +1756,24 @@ def colour_budget_rest(budgets, upper_cb, point_cb, upper_cr, point_cr, out):
     _check(_native.hip().eae_hip_colour_budget_rest(budgets.data_ptr(), upper_cb.data_ptr(), point_cb.data_ptr(), upper_cr.data_ptr(),
                                                     point_cr.data_ptr(), out.data_ptr(), n, k_points, container.COLOUR_HEADER_BYTES,
                                                     _stream(next((t for t in wide + points if t.is_cuda), None))), 'eae_hip_colour_budget_rest')
+    return out
+
+
+def colour_quality_rest(max_sse, sse_cb, sse_cr, out):
+    """The squared-error threshold of the luminance plane of N colour pictures from what their chroma planes spent (DESIGN.md section
+    30): `ratecontrol.colour_luma_max_sse`, element for element, without a visit to the host. max_sse int64 [N]: the threshold of
+    every picture over all samples of its 4:2:0 form, up to 2^62; sse_cb, sse_cr int64 [N]: the squared errors of the points the
+    chroma planes took, never negative; out int64 [N]. All contiguous, in device or pinned host memory. out[i] = max(max_sse[i] -
+    sse_cb[i] - sse_cr[i], 0). One launch on the current stream. Returns `out`."""
+    every = (max_sse, sse_cb, sse_cr, out)
+    if any(t.dtype != torch.int64 for t in every):
+        raise HipError('max_sse, sse_cb, sse_cr and out must be int64')
+    if any(not t.is_contiguous() or not (t.is_cuda or t.is_pinned()) for t in every):
+        raise HipError('every argument must be contiguous, in device or pinned host memory')
+    if max_sse.dim() != 1 or max_sse.shape[0] < 1 or any(t.shape != max_sse.shape for t in every):
+        raise HipError('max_sse, sse_cb, sse_cr and out must be alike [N] with N >= 1')
+    _check(_native.hip().eae_hip_colour_quality_rest(max_sse.data_ptr(), sse_cb.data_ptr(), sse_cr.data_ptr(), out.data_ptr(), max_sse.shape[0],
+                                                     _stream(next((t for t in every if t.is_cuda), None))), 'eae_hip_colour_quality_rest')
     return out
 
 

@@ -5,7 +5,8 @@ as numpy arrays. The second half of the file is the rule of `codec.BudgetCodec` 
 arithmetic, which `eae_hip_ladder_select` restates on the device element for element, and the choice on that bound alone. The end of
 the file is the rule of `codec.QualityCodec`: a PSNR floor as an integer bound on the squared error, and the
 bisection of the ladder for the coarsest point that keeps it, which `eae_hip_quality_search` restates round by round. Between the two
-stands the rule of `codec.ColourBudgetCodec`: how one byte budget is shared between the planes of a picture.
+stands the rule of `codec.ColourBudgetCodec` (DESIGN.md section 29): how one byte budget is shared between the planes of a picture;
+behind `QualityCodec`'s the rule of `codec.ColourQualityCodec`: how one PSNR floor is.
 
 A rate point is a pair: 128 bin widths and a table of binary probabilities (the reference walks nine, `multipliers` of
 reconstructing_eae_kodak.py, and learns a point's cost by quantising and coding at it). The coder's cost is a function of the
@@ -577,6 +578,78 @@ def bisect_by_quality(sse_of, nb_points, first, max_sse):
             else:
                 high = probed
     return (low, True, points, values) if low >= first else (first, False, points, values)
+
+
+# ---- the rule of `codec.ColourQualityCodec`: one PSNR floor for the three planes of a colour picture ----------
+# A picture's quality is the PSNR over all S = h w + 2 hc wc samples of its 4:2:0 form, (hc, wc) the chroma size: its error is E = sse_Y +
+# sse_Cb + sse_Cr, each over its plane's REAL samples against the split input (for even sides the 4:1:1-weighted YUV PSNR). The
+# threshold is M = `max_sse_for_psnr(T, S)`, or a given integer. Then:
+#   1. Cb and Cr each get a = (M * share_q16) >> 17, share_q16 = round(chroma_share * 65536), and take `select_by_quality`'s point for
+#      a on their own squared errors;
+#   2. Y gets max(M - sse_cb - sse_cr, 0), sse_x the REAL squared error of the point the chroma plane TOOK, met or not: the error
+#      chroma does not spend goes to the luminance, as unspent bytes do above. The device restates this line
+#      (`eae_hip_colour_quality_rest`), so that it never visits the host; Y takes `select_by_quality`'s point for it;
+#   3. the picture is met when sse_y + sse_cb + sse_cr <= M, on the three squared errors of the points taken. If all three planes are
+#      met it is: sse_y <= M - sse_cb - sse_cr. The converse does not hold (chroma may miss a and Y make up for it).
+# `select_by_quality`'s caveat is this rule's: MONOTONICITY IS ASSUMED AND NOT CHECKED. Where a plane's squared error is not
+# non-decreasing along its ladder, its point is the bisection's own outcome, not necessarily the coarsest that keeps its threshold.
+# The rule is not a joint search: 'sse_rgb' is not separable over the planes, and a coarser triple that keeps M may exist.
+
+def colour_nb_samples(h, w):
+    """S = h w + 2 hc wc: the samples of the 4:2:0 form of an h x w picture, (hc, wc) = (ceil(h / 2), ceil(w / 2))
+    (`device.chroma_size`)."""
+    (h, w) = (int(h), int(w))
+    if h < 1 or w < 1:
+        raise ValueError('`h` and `w` must be positive.')
+    return h*w + 2*((h + 1)//2)*((w + 1)//2)
+
+
+def _colour_max_sse(max_sse):
+    """max_sse, a scalar or one value per picture -> int64 (N,) (a scalar: (1,)), in [0, 2^62]."""
+    thresholds = numpy.asarray(max_sse)
+    if thresholds.ndim > 1 or thresholds.dtype.kind not in 'iu':
+        raise ValueError('`max_sse` must be an integer or one integer per picture.')
+    if thresholds.size and (int(thresholds.max()) > MAX_SSE_SATURATION or int(thresholds.min()) < 0):
+        raise ValueError('`max_sse` does not belong to [0, 2^62].')
+    return numpy.atleast_1d(thresholds).astype(numpy.int64)
+
+
+def colour_chroma_max_sse(max_sse, chroma_share):
+    """-> int64 (N,): a, the squared-error threshold of the Cb plane and of the Cr plane of every picture (rule 1 above). max_sse: a
+    scalar (N = 1) or one value per picture, in [0, 2^62]; chroma_share: the fraction of the picture's error both chroma planes
+    together may take, 0 < chroma_share < 1, else ValueError (1/3, `codec.ColourQualityCodec`'s default, is the chroma planes' share
+    of the samples: a starting value nobody has measured on a trained model). The product is formed in two halves, as in
+    `colour_chroma_budgets`, so nothing leaves int64."""
+    try:
+        share = float(chroma_share)
+    except (TypeError, ValueError):
+        raise ValueError('`chroma_share` must be a number.')
+    if isinstance(chroma_share, (bool, numpy.bool_)) or not 0. < share < 1.:
+        raise ValueError('`chroma_share` does not belong to ]0, 1[.')
+    share_q16 = int(round(share*(1 << COLOUR_SHARE_SHIFT)))
+    thresholds = _colour_max_sse(max_sse)
+    shift = COLOUR_SHARE_SHIFT + 1
+    # (M * q) >> 17 with M = high * 2^17 + low: high * q + ((low * q) >> 17), high * q <= 2^45 * 2^16
+    return (thresholds >> shift)*share_q16 + (((thresholds & ((1 << shift) - 1))*share_q16) >> shift)
+
+
+def colour_luma_max_sse(max_sse, sse_cb, sse_cr):
+    """-> int64 (N,): the squared-error threshold of the Y plane of every picture (rule 2 above): max(M - sse_cb[i] - sse_cr[i], 0).
+    max_sse: a scalar or one value per picture, in [0, 2^62]; sse_cb, sse_cr int (N,): the real squared errors of the points the
+    chroma planes took, not negative (`device.colour_quality_rest` is this function element for element)."""
+    (sse_cb, sse_cr) = (numpy.asarray(sse_cb), numpy.asarray(sse_cr))
+    if sse_cb.ndim != 1 or sse_cr.shape != sse_cb.shape or sse_cb.dtype.kind not in 'iu' or sse_cr.dtype.kind not in 'iu':
+        raise ValueError('`sse_cb` and `sse_cr` must be integer arrays (N,).')
+    nb_images = sse_cb.shape[0]
+    if nb_images and (sse_cb.min() < 0 or sse_cr.min() < 0 or max(int(sse_cb.max()), int(sse_cr.max())) >= (1 << 63)):
+        raise ValueError('A squared error is negative or does not fit int64.')
+    thresholds = _colour_max_sse(max_sse)
+    if thresholds.shape[0] not in (1, nb_images):
+        raise ValueError('`max_sse` must be an integer or one integer per picture.')
+    rest = numpy.broadcast_to(thresholds, (nb_images,)).copy()
+    for spent in (sse_cb.astype(numpy.int64), sse_cr.astype(numpy.int64)):
+        rest = numpy.where(rest > spent, rest - spent, 0)          # never below -2^63: both operands are in [0, 2^63)
+    return rest.astype(numpy.int64)
 
 
 # ---- the rule of the rate-distortion optimised quantiser (DESIGN.md section 23) --------------------------------------------------------

@@ -239,6 +239,17 @@ int eae_hip_tconv5x5s2_ws(const float* x, const float* w_packed, const float* bi
 int eae_hip_tconv9x9s4_luma(const float* x, const float* w_phase, float* out_f32, uint8_t* out_u8,
                             const uint8_t* ref_u8, uint64_t* sse, int n, int h, int w_in, void* stream);
 
+/* The same launch with the squared error over the REAL pixels of padded planes: the contraction, the tiling,
+ * the persistent grid and the BT.601 cast are eae_hip_tconv9x9s4_luma's, and out_f32 / out_u8, where requested, are written over the
+ * whole coded plane [N][4h][4w]. ref_u8 is the CODED frame, rows of 4 w_in bytes (what eae_hip_frame_pad_u8 writes);
+ * sse[i] += the sum over y < real_h and x < real_w only, exact uint64, masked per pixel: real_w is any value in [1, 4 w_in]. Bytes
+ * of ref_u8 outside the rectangle may be loaded -- they lie inside the buffer -- and never reach the sum. At real_h = 4 h,
+ * real_w = 4 w_in it adds what eae_hip_tconv9x9s4_luma adds. Refused (EAE_HIP_BAD_ARGUMENT) beyond what that entry point
+ * refuses: real_h or real_w below 1 or outside the coded plane. */
+int eae_hip_tconv9x9s4_luma_frame(const float* x, const float* w_phase, float* out_f32, uint8_t* out_u8,
+                                  const uint8_t* ref_u8, uint64_t* sse, int n, int h, int w_in, int real_h, int real_w,
+                                  void* stream);
+
 /* TF filter [9][9][1][128] -> per-lane MFMA fragments [4 channel blocks][9 neighbours][64 lanes][8] (zeros where an
  * output phase has no tap). */
 int eae_hip_pack_tconv9x9s4_weights(const float* w_tf, float* w_phase, void* stream);
@@ -789,6 +800,18 @@ int eae_hip_colour_merge_420_crops(const uint8_t* y, const uint8_t* cb, const ui
  *   array that is not 8-byte aligned, a point array that is not 4-byte aligned. */
 int eae_hip_colour_budget_rest(const int64_t* budgets, const int64_t* upper_cb, const int32_t* point_cb, const int64_t* upper_cr,
                                const int32_t* point_cr, int64_t* out, int n, int k_points, int64_t header_bytes, void* stream);
+
+/* colour_quality_rest: the squared-error threshold of the luminance plane of n colour pictures, from what their
+ *   chroma planes spent -- ratecontrol.colour_luma_max_sse, integers only, so that the number never visits the host between the
+ *   chroma steps and the luminance step of a colour codec. max_sse i64 [n]: M, the threshold of each picture over all samples of
+ *   its 4:2:0 form, in [0, 2^62]; sse_cb, sse_cr i64 [n]: the squared errors of the points the chroma planes took, over their real
+ *   samples, never negative.
+ *     out[i] = max(max(M - sse_cb[i], 0) - sse_cr[i], 0)
+ *   which for errors that are not negative is max(M - sse_cb - sse_cr, 0); no difference leaves int64. All four in device or
+ *   pinned, device-mapped host memory. One lane per picture, ceil(n / 256) blocks of 256, any n; one launch, asynchronous on
+ *   `stream`, no argument computed from data.
+ *   Refused (EAE_HIP_BAD_ARGUMENT, in front of the launch): a NULL pointer, n not positive, an array that is not 8-byte aligned. */
+int eae_hip_colour_quality_rest(const int64_t* max_sse, const int64_t* sse_cb, const int64_t* sse_cr, int64_t* out, int n, void* stream);
 
 /* ==== TEST HOOKS (-DEAE_TEST_HOOKS): NOT exported by the product library lib/libeae_hip.so ====================================
  * Five entry points the test-suite needs and a deployment must not have (they change what later launches do, or only
